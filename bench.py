@@ -3,10 +3,23 @@
 optim.rmsprop, main.lua:133) on vgg_small with synthetic 800x450 frames, one image per GPU per
 step, data-parallel over N GPUs of one node (gradient all-reduce on RCCL).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), carrying
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (every pooled image once, then W steps), times K steps and
+prints the headline: "value" (images/sec over the K steps), "ms_per_step" (milliseconds per timed step), "metric", "unit",
+"higher_is_better", "dtype", and the workload's description ("arithmetic", "config").  The timed steps bracket nothing.
+
+The last timed step starts from the seeded state a fresh run starts from (weights of seed 42, no RMSprop history, initial
+batch-norm statistics; the restore is queued before it, once per run), so the inputs of that step -- weights, frame, examples,
+dropout masks -- depend on the arguments alone.  --dump-outputs DIR writes what it computed, as DIR/<name>.npy (float32 /
+float64, < 64 MB): "loss" (the value optim.rmsprop returns), "losses" (pcls, preg, dcls, dreg of the stats table),
+"bn_running", and a fixed sample of the updated "weights" and of the "gradient" at the flat indices in "sample_index".  Two
+runs differ by rounding only: the kernels' float reductions land in run-dependent order (with the library's option
+deterministic, FRCNN_DETERMINISTIC=1, they write identical files).
+
+--full measures everything else, in the same process after the headline (the conv classes are then bracketed with HIP
+events on every 4th timed step, so `value` carries that sampling), and adds to the line:
   "roofline"     -- achieved TFLOP/s of the dominant kernel (conv_x3: forward + input-gradient of the convolutions
                     in the split operand form; conv_igemm 3x3, fp32 MFMA, with the option off)
                     = algorithmic FLOPs of its launches / their HIP-event durations, measured live over the timed
@@ -438,6 +451,65 @@ def dtype_text(F):
     return "f32 (conv operands as 3 x bf16 split planes: 24 significand bits, 6 MFMA partial products; fp32 accumulate)"
 
 
+def arithmetic_text(nprod, split_on):
+    """`arithmetic` of the JSON line: which products take which form."""
+    if not split_on:
+        return "fp32 tensors, fp32 products (v_mfma_f32_32x32x2_f32 / VALU), fp32 accumulation"
+    if nprod != F16_PRODUCTS:
+        return ("fp32 tensors, fp32 accumulation; the 3x3 convolutions (forward, input gradient, weight gradient) form every fp32 "
+                "product from six exact bf16 x bf16 partial products of three-way split operands (24 significand bits, "
+                "v_mfma_f32_32x32x16_bf16); every other product is a plain fp32 product (v_mfma_f32_32x32x2_f32 / VALU)")
+    gemm_f16 = os.environ.get("FRCNN_GEMM_F16", "1") != "0"
+    return ("fp32 tensors, fp32 accumulation; the 3x3 / 5x5 / 7x7 convolutions (forward, input gradient, 3x3 weight gradient) scale "
+            "each operand tensor by a power of two chosen from its largest magnitude, split it into two fp16 planes (22 significand "
+            "bits) and form every product from three exact fp16 x fp16 partial products (v_mfma_f32_32x32x16_f16); measured "
+            "error against fp64 at the level of the fp32 matrix-core kernel (tools/x3_f16_check.py); the classification net's "
+            "Linear(13824,1024) forward / input-gradient products " + ("take the same two-plane form" if gemm_f16
+                                                                      else "use three bf16 planes / six partial products (FRCNN_GEMM_F16=0)") +
+            (", its weight-gradient product two fp16 planes of both operands" if os.environ.get("FRCNN_GEMM_WGRAD_F16", "1") != "0" and gemm_f16
+             else ", its weight-gradient product three bf16 planes / six partial products") + "; every other product is a plain fp32 product")
+
+
+DUMP_SAMPLE = 1 << 20          # flat weight / gradient elements drawn for --dump-outputs (seeded), beside every small tensor whole
+DUMP_SMALL_TENSOR = 65536      # parameter tensors up to this many elements are dumped whole
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, weights, gradient, last, stats):
+    """--dump-outputs: what the caller of the timed path (optim.rmsprop over lossAndGradient, main.lua:133) holds after the last
+    timed step -- the loss it returned, the four losses the objective appended to the stats table (objective.lua:211-214), the
+    batch-norm running statistics of the classification net, and the updated weights and the gradient, as a fixed sample
+    (every element of the tensors up to DUMP_SMALL_TENSOR elements, DUMP_SAMPLE seeded draws over the whole vector) whose flat
+    indices are written beside them.  The step starts from the seeded state (main: restart), so the same arguments give the same
+    inputs and two builds compare output for output."""
+    import torch
+    nat = model["native"]
+    n = weights.numel()
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        parts = [np.random.RandomState(0).randint(0, n, DUMP_SAMPLE).astype(np.int64)]
+        for off, cnt, _kind, _aux in nat.param_table:
+            if cnt <= DUMP_SMALL_TENSOR:
+                parts.append(np.arange(int(off), int(off) + int(cnt), dtype=np.int64))
+        idx = np.unique(np.concatenate(parts))
+    torch.cuda.synchronize()
+    di = torch.from_numpy(idx).to(weights.device)
+    arrays = dict(loss=np.array([last[1][0]], np.float64),
+                  losses=np.array([stats[k][-1] for k in ("pcls", "preg", "dcls", "dreg")], np.float64),
+                  weights=weights[di].cpu().numpy().astype(np.float32),
+                  gradient=gradient[di].cpu().numpy().astype(np.float32),
+                  sample_index=idx.astype(np.float64))
+    if getattr(nat, "bn_running", None) is not None:
+        arrays["bn_running"] = nat.bn_running.cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        _fail("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def dropout_text(F):
     """What the pass does with the channels nn.SpatialDropout(0.4) drops (option drop_compact, include/frcnn_hip.h)."""
     v = C.c_int(0)
@@ -660,10 +732,18 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--model", default="vgg_small", choices=["vgg_small", "vgg_large"],
                     help="vgg_large = SURVEY 8d config 5 (config/imagenet.lua, use --height 600 --width 1000); not the bench line")
-    ap.add_argument("--profile-all", action="store_true", help="HIP-event profile of every kernel class (adds overhead)")
-    ap.add_argument("--no-other-legs", action="store_true", help="skip the inference / nms legs")
-    ap.add_argument("--no-upload-leg", action="store_true", help="skip the PCIe-inclusive pass (frames uploaded every step)")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the %.0f-second sustained pass" % SUSTAINED_SECONDS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the live roofline and kernel classes (conv classes bracketed on "
+                         "every 4th timed step), host times, the sustained, HBM, serial and upload passes, the exchange schedule, "
+                         "and at N = 1 the CPU baseline, the parity check and the other legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (loss, the four losses of "
+                         "the stats table, the batch-norm running statistics, and a fixed sample of the updated weights and "
+                         "of the gradient with the sample's indices)")
+    ap.add_argument("--profile-all", action="store_true", help="HIP-event profile of every kernel class (adds overhead; implies --full)")
+    ap.add_argument("--no-other-legs", action="store_true", help="with --full: skip the inference / nms legs")
+    ap.add_argument("--no-upload-leg", action="store_true", help="with --full: skip the PCIe-inclusive pass (frames uploaded every step)")
+    ap.add_argument("--no-sustained", action="store_true", help="with --full: skip the %.0f-second sustained pass" % SUSTAINED_SECONDS)
     ap.add_argument("--comm", default=os.environ.get("FRCNN_COMM", "torch"), choices=["torch", "native"],
                     help="exchange back end at N > 1: torch.distributed ('nccl' = RCCL; the default -- the multi-rank path the "
                          "world-size-2 tests cover) or the C ABI's own frcnn_comm_* (RCCL bound by the library; what a LuaJIT "
@@ -671,6 +751,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         _fail("--gpus must be >= 1")
+    if args.steps < 1:
+        _fail("--steps must be >= 1")
+    full = args.full or args.profile_all
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args)     # no launcher: this process becomes the launcher of N ranks
 
@@ -738,6 +821,22 @@ def main():
     stats = dict(pcls=[], preg=[], dcls=[], dreg=[])
     f = F.create_objective(model, weights, gradient, it, stats)
     state = dict(learningRate=1e-4, alpha=0.9)  # main.lua:122
+    # The last timed step starts again from this seeded state (weights of seed 42, no RMSprop history, the initial batch-norm
+    # statistics): its inputs are then fixed by the arguments alone.  Without that they would be the product of every step
+    # before it, whose float reductions land in run-dependent order (the library's default; option deterministic) and whose
+    # RMSprop updates amplify those rounding differences step by step -- --dump-outputs would not be reproducible.
+    nat = model["native"]
+    w_init = weights.clone()
+    bn_init = nat.bn_running.clone() if getattr(nat, "bn_running", None) is not None else None
+
+    def restart():
+        """Seeded state back in place, queued on the current stream (one weight-sized copy and one fill; the next pass measures
+        the weights' magnitudes itself, as after any host write of the weights)."""
+        weights.copy_(w_init)
+        if "m" in state:
+            state["m"].zero_()
+        if bn_init is not None:
+            nat.bn_running.copy_(bn_init)
 
     # (experiments: FRCNN_BENCH_STREAM=1 a stream of the caller's own instead of the NULL stream, =hi the same with high priority)
     user_stream = (torch.cuda.Stream(priority=-1) if os.environ.get("FRCNN_BENCH_STREAM") == "hi"
@@ -746,9 +845,8 @@ def main():
     def step():
         if user_stream is not None:
             with torch.cuda.stream(user_stream):
-                F.rmsprop(f, weights, state)
-            return
-        F.rmsprop(f, weights, state)  # main.lua:133
+                return F.rmsprop(f, weights, state)
+        return F.rmsprop(f, weights, state)  # main.lua:133
 
     def barrier():
         if native_comm is not None:
@@ -762,23 +860,28 @@ def main():
     for _ in range(args.warmup):
         step()
     # Live HIP-event bracketing puts two event packets around every bracketed launch of the dependent chain (~3 % of
-    # the step when every step is bracketed): the conv classes are bracketed on every 4th step of the timed region
-    # (a sample of the same launches), --profile-all brackets every class on every step.
+    # the step when every step is bracketed): with --full the conv classes are bracketed on every 4th step of the timed
+    # region (a sample of the same launches), --profile-all brackets every class on every step.  A plain run brackets nothing.
     conv_mask = sum(1 << F._lib.KC_NAMES.index(n) for n in CONV_CLASSES)
     mask = (1 << len(F._lib.KC_NAMES)) - 1 if args.profile_all else conv_mask
     every = 1 if args.profile_all else 4
     sampled = 0
+    if args.steps == 1:
+        restart()       # (the only timed step is the last one: the restart stays outside the timed region)
     barrier()
-    if native_comm is not None:
-        native_comm.timing = []       # per-bucket all-reduce durations of the timed region (config.exchange.buckets)
-    state["_timing"] = dict(enqueue=0.0, wait=0.0, steps=0)   # utilities.rmsprop fills it: host time per step
+    if full:
+        if native_comm is not None:
+            native_comm.timing = []       # per-bucket all-reduce durations of the timed region (config.exchange.buckets)
+        state["_timing"] = dict(enqueue=0.0, wait=0.0, steps=0)   # utilities.rmsprop fills it: host time per step
     t0 = time.perf_counter()
     for i in range(args.steps):
-        on = (i % every) == 0
+        if i == args.steps - 1 and i > 0:
+            restart()   # (asynchronous: ~0.1 ms of device time once per run)
+        on = full and (i % every) == 0
         if on:
             F._lib.call("frcnn_prof_enable", mask)
             sampled += 1
-        step()
+        last = step()
         if on:
             F._lib.call("frcnn_prof_enable", 0)
     barrier()
@@ -789,9 +892,11 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    host_t = state.pop("_timing")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, weights, gradient, last, stats)
+    host_t = state.pop("_timing", None)
     bucket_times = None
-    if native_comm is not None:
+    if full and native_comm is not None:
         bucket_times = native_comm.bucket_times()
         native_comm.timing = None
     nk = len(F._lib.KC_NAMES)
@@ -800,7 +905,7 @@ def main():
     # The same metric over SUSTAINED_SECONDS of back-to-back steps (nothing bracketed): clocks and
     # thermals are steady by then and an external SMI sampler sees the device busy.  `value` stays the K timed steps above.
     sustained = None
-    if not args.no_sustained:
+    if full and not args.no_sustained:
         # (SUSTAINED_SECONDS of steps at the speed just measured -- about 5 000 of them; a debug back end that takes hundreds of
         # milliseconds per step gets the same seconds, not the same count)
         n_sus = max(20, min(SUSTAINED_STEPS_MAX, int(SUSTAINED_SECONDS / max(dt / args.steps, 1e-4))))
@@ -820,7 +925,7 @@ def main():
                          ms_per_step=round(1e3 * ts / n_sus, 3), seconds=round(ts, 2))
     # HBM-bound kernels of the live step: four more steps with those classes bracketed
     hbm = None
-    if world == 1:
+    if full and world == 1:
         hbm_names = ("optim", "roi", "elemwise")
         F._lib.call("frcnn_prof_enable", sum(1 << F._lib.KC_NAMES.index(n) for n in hbm_names))
         for _ in range(4):
@@ -831,7 +936,7 @@ def main():
         F._lib.call("frcnn_prof_collect", lh, mh, fh, bh)
         hbm = hbm_rows(F, lh, mh, bh, hbm_names, 4)
     sched = None
-    if world == 1:
+    if full and world == 1:
         try:
             sched = exchange_schedule(F, step)
         except Exception as e:    # (a probe: never fails the bench line)
@@ -841,7 +946,7 @@ def main():
     # (roofline.achieved, as prescribed) is longer than the kernel needs when it has the GPU to itself.
     iso = None
     iso_classes = None
-    if world == 1:   # (a lone rank cannot step: the objective all-reduces)
+    if full and world == 1:   # (a lone rank cannot step: the objective all-reduces)
         F._lib.call("frcnn_set_option", b"side_stream", 0)
         step()
         barrier_local = torch.cuda.synchronize
@@ -871,7 +976,7 @@ def main():
     # The PCIe-inclusive rate is measured here, outside the timed region: the same step fed by an iterator whose frames
     # live in page-locked host memory and cross PCIe every step (copy stream + ring of device buffers, one step ahead).
     upload_leg = None
-    if world == 1 and not args.no_upload_leg:
+    if full and world == 1 and not args.no_upload_leg:
         it_up = F.SyntheticBatchIterator(model, H=H, W=W, images_per_batch=1, rank=rank, world_size=world, pool=4, upload=True)
         f_up = F.create_objective(model, weights, gradient, it_up, dict(pcls=[], preg=[], dcls=[], dreg=[]))
         for _ in range(4 + args.warmup):
@@ -888,110 +993,107 @@ def main():
                                "x.img:cuda()), asynchronously on a copy stream one step ahead; not the headline value")
     if rank == 0:
         fwd_flops, train_flops = conv_flops_per_image(model, H, W)
-        split_on = launches[F._lib.KC_NAMES.index("conv_x3")] > 0
-        k = F._lib.KC_NAMES.index("conv_x3" if split_on else "conv_igemm_k3")
         nprod = split_products(F)
-        peak = BF16_MFMA_PEAK_TFLOPS / nprod if split_on else FP32_MFMA_PEAK_TFLOPS
-        ach = (fl[k] / 1e12) / (ms[k] / 1e3) if ms[k] > 0 else 0.0
-        traffic = None
-        traffic_taken = None
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get("%s_bytes_per_launch" % F._lib.KC_NAMES[k])
-                traffic_taken = tj.get("taken")    # {git, date, csrc_sha256}: which tree the PMC passes measured
-                # a table taken from other kernel sources than the ones that just ran is not evidence about them: refuse it
-                if not traffic_taken or traffic_taken.get("csrc_sha256") != csrc_sha256():
-                    traffic_taken = dict(traffic_taken or {}, stale="the PMC table was taken from other kernel sources (csrc hash %s now): "
-                                                                    "roofline.traffic withheld; tools/refresh_round.sh renews it" % csrc_sha256())
-                    traffic = None
-            except Exception:
-                traffic = None
-        classes = {}
-        for i, name in enumerate(F._lib.KC_NAMES):
-            if launches[i]:
-                classes[name] = dict(launches_per_step=launches[i] / sampled, ms_per_step=round(ms[i] / sampled, 4),
-                                     tflops=round((fl[i] / 1e12) / (ms[i] / 1e3), 2) if fl[i] > 0 and ms[i] > 0 else None)
-        conv_ms = sum(ms[F._lib.KC_NAMES.index(n)] for n in CONV_CLASSES) / sampled
+        if full:    # the form that ran, from the live launches
+            split_on = launches[F._lib.KC_NAMES.index("conv_x3")] > 0
+        else:       # nothing was bracketed: the option that selects it (conv_x3 takes the 3x3 layers whenever split_bf16 is on)
+            v = C.c_int(0)
+            F._lib.call("frcnn_get_option", b"split_bf16", C.byref(v))
+            split_on = bool(v.value)
         out = dict(
             metric="images/sec (%s %dx%d fwd+bwd)" % (args.model, W, H), value=round(world * args.steps / dt, 3), unit="images/sec",
             n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(1e3 * dt / args.steps, 3),
             higher_is_better=True, scaling="weak", vs_baseline=None, dtype=dtype_text(F), data="synthetic",
-            arithmetic=(("fp32 tensors, fp32 accumulation; the 3x3 / 5x5 / 7x7 convolutions (forward, input gradient, 3x3 weight gradient) scale "
-                         "each operand tensor by a power of two chosen from its largest magnitude, split it into two fp16 planes (22 significand "
-                         "bits) and form every product from three exact fp16 x fp16 partial products (v_mfma_f32_32x32x16_f16); measured "
-                         "error against fp64 at the level of the fp32 matrix-core kernel (tools/x3_f16_check.py); the classification net's "
-                         "Linear(13824,1024) forward / input-gradient products " + ("take the same two-plane form" if os.environ.get("FRCNN_GEMM_F16", "1") != "0"
-                                                                                   else "use three bf16 planes / six partial products (FRCNN_GEMM_F16=0)") +
-                         (", its weight-gradient product two fp16 planes of both operands" if os.environ.get("FRCNN_GEMM_WGRAD_F16", "1") != "0" and os.environ.get("FRCNN_GEMM_F16", "1") != "0"
-                          else ", its weight-gradient product three bf16 planes / six partial products") + "; every other product is a plain fp32 product"
-                         if nprod == F16_PRODUCTS else
-                         "fp32 tensors, fp32 accumulation; the 3x3 convolutions (forward, input gradient, weight gradient) form every fp32 "
-                         "product from six exact bf16 x bf16 partial products of three-way split operands (24 significand bits, "
-                         "v_mfma_f32_32x32x16_bf16); every other product is a plain fp32 product (v_mfma_f32_32x32x2_f32 / VALU)")
-                        if split_on else "fp32 tensors, fp32 products (v_mfma_f32_32x32x2_f32 / VALU), fp32 accumulation"),
+            arithmetic=arithmetic_text(nprod, split_on),
             config=dict(workload=args.model + " %dx%d train step: lossAndGradient (pnet fwd, sparse RPN loss, ROI pool, cnet fwd/bwd, "
                                  "ROI-pool bwd, pnet bwd) + gradient all-reduce + rmsprop; config/%s.lua values; frames resident in HBM when the timed "
                                  "region starts (the per-image upload of objective.lua:66 is not in `value`: see with_h2d_upload)"
                                  % (W, H, "duplo" if args.model == "vgg_small" else "imagenet"),
-                        with_h2d_upload=upload_leg,
                         images_per_gpu_per_step=1,
                         dropout=dropout_text(F),
                         examples_per_image=[len(b["positive"]) + len(b["negative"]) for b in it.pool], global_batch=world, parallelism="dp%d" % world,
                         conv_gflop_per_image=round(train_flops / 1e9, 2),   # (the dense algorithm: every channel multiplied out)
-                        conv_gflop_per_image_as_run=round(sum(fl[F._lib.KC_NAMES.index(n)] for n in CONV_CLASSES) / 1e9 / sampled, 2),
-                        whole_step_conv_tflops=round(sum(fl[F._lib.KC_NAMES.index(n)] for n in CONV_CLASSES) / 1e12 / sampled / (dt / args.steps), 2),
-                        conv_kernel_ms_per_step=round(conv_ms, 3), kernel_classes=classes,
-                        kernel_classes_serial_pass=iso_classes,
                         last_loss=stats["pcls"][-1] + stats["preg"][-1] if stats["pcls"] else None),
-            host=dict(enqueue_ms_per_step=round(1e3 * host_t["enqueue"] / max(host_t["steps"], 1), 3),
-                      wait_ms_per_step=round(1e3 * host_t["wait"] / max(host_t["steps"], 1), 3),
-                      note="rank 0, timed region: time the host needs to queue one step through the C ABI (batch draw, example tables, "
-                           "every launch, the update) and the time it then waits for the step's 64-byte statistics; while wait > 0 the "
-                           "host is ahead of the device and does not bound `value`"),
-            roofline=dict(bound="mfma",
-                          kernel=(("conv_x3_kernel (conv forward + input-gradient, two fp16 planes per operand: 3 fp16 MFMA partial products "
-                                   "per fp32 product)" if nprod == F16_PRODUCTS else
-                                   "conv_x3_kernel (3x3 conv forward + input-gradient, split-bf16 operands: 6 bf16 MFMA partial products "
-                                   "per fp32 product)") if split_on else
-                                  "conv_igemm_kernel<3,8,*> (3x3 conv forward + input-gradient, fp32 MFMA)"),
-                          achieved=round(ach, 2), peak=round(peak, 1), unit="TFLOP/s",
-                          frac=round(ach / peak, 4), traffic=traffic,
-                          traffic_source=("profiles/pmc_traffic.json: HBM bytes per launch from separate rocprofv3 --pmc FETCH_SIZE / "
-                                          "--pmc WRITE_SIZE passes of this command (FETCH x2, the gfx950 correction; tools/pmc_traffic.py), "
-                                          "taken when the profile was made -- not counted in this run" if traffic is not None else None),
-                          traffic_taken=traffic_taken,
-                          peak_note=("algorithmic (fp32-product) TFLOP/s against the dense fp16 / bf16 matrix-core peak 2516.6 / %d partial "
-                                     "products; executed MFMA rate = %d x achieved = %.0f TFLOP/s (%.3f of the dense peak); the fp32 matrix-core "
-                                     "peak is 157.3 TFLOP/s" % (nprod, nprod, nprod * ach, nprod * ach / BF16_MFMA_PEAK_TFLOPS)
-                                     if split_on else "fp32 matrix-core peak"),
-                          executed=(dict(partial_products_per_fp32_product=nprod, tflops=round(nprod * ach, 1),
-                                         frac_of_dense_16bit_peak=round(nprod * ach / BF16_MFMA_PEAK_TFLOPS, 4),
-                                         note="matrix-core FLOPs actually issued (the MFMA-utilisation figure); the two-plane fp16 form "
-                                              "issues half of what the three-plane bf16 form does for the same algorithmic work")
-                                    if split_on else None),
-                          sampled_steps=sampled, launches_per_step=launches[k] / sampled, avg_launch_ms=round(ms[k] / max(launches[k], 1), 4),
-                          algorithmic_bytes_per_launch=round(by[k] / max(launches[k], 1)),
-                          algorithmic_gflop_per_launch=round(fl[k] / 1e9 / max(launches[k], 1), 3), isolated=iso,
-                          dense_equivalent=(dict(gflop_per_step=round(backbone_x3_dense_flops(model, H, W) / 1e9, 2),
-                                                 tflops=round(backbone_x3_dense_flops(model, H, W) / 1e12 / (ms[k] / 1e3 / sampled), 2),
-                                                 frac=round(backbone_x3_dense_flops(model, H, W) / 1e12 / (ms[k] / 1e3 / sampled) / peak, 4),
-                                                 note="the same launches priced by the DENSE algorithm's FLOP formula (SURVEY 8d): what option "
-                                                      "drop_compact leaves out -- products with the zeros of nn.SpatialDropout -- counted as if "
-                                                      "computed.  Not a matrix-core utilisation: `frac` above counts the launches as run")
-                                            if split_on and launches[k] / sampled == 12.0 else None)),
-            roofline_hbm=hbm,
-            sustained=sustained,
         )
         out["config"]["exchange"] = dict(
             backend=("frcnn_comm (RCCL through the C ABI: frcnn_comm_init_rank_file / frcnn_allreduce_f32 / _f64)" if native_comm is not None
                      else ("torch.distributed nccl (RCCL)" if backend == "nccl" else "torch.distributed %s (debug: ranks may share a device)" % backend)
                      if world > 1 else "none (single process)"),
-            ranks=world, buckets=bucket_times, schedule=sched, **(exchange_info or {}))
+            ranks=world, **(exchange_info or {}))
+        if full:
+            k = F._lib.KC_NAMES.index("conv_x3" if split_on else "conv_igemm_k3")
+            peak = BF16_MFMA_PEAK_TFLOPS / nprod if split_on else FP32_MFMA_PEAK_TFLOPS
+            ach = (fl[k] / 1e12) / (ms[k] / 1e3) if ms[k] > 0 else 0.0
+            traffic = None
+            traffic_taken = None
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    traffic = tj.get("%s_bytes_per_launch" % F._lib.KC_NAMES[k])
+                    traffic_taken = tj.get("taken")    # {git, date, csrc_sha256}: which tree the PMC passes measured
+                    # a table taken from other kernel sources than the ones that just ran is not evidence about them: refuse it
+                    if not traffic_taken or traffic_taken.get("csrc_sha256") != csrc_sha256():
+                        traffic_taken = dict(traffic_taken or {}, stale="the PMC table was taken from other kernel sources (csrc hash %s now): "
+                                                                        "roofline.traffic withheld; tools/refresh_round.sh renews it" % csrc_sha256())
+                        traffic = None
+                except Exception:
+                    traffic = None
+            classes = {}
+            for i, name in enumerate(F._lib.KC_NAMES):
+                if launches[i]:
+                    classes[name] = dict(launches_per_step=launches[i] / sampled, ms_per_step=round(ms[i] / sampled, 4),
+                                         tflops=round((fl[i] / 1e12) / (ms[i] / 1e3), 2) if fl[i] > 0 and ms[i] > 0 else None)
+            conv_ms = sum(ms[F._lib.KC_NAMES.index(n)] for n in CONV_CLASSES) / sampled
+            out["config"].update(
+                with_h2d_upload=upload_leg,
+                conv_gflop_per_image_as_run=round(sum(fl[F._lib.KC_NAMES.index(n)] for n in CONV_CLASSES) / 1e9 / sampled, 2),
+                whole_step_conv_tflops=round(sum(fl[F._lib.KC_NAMES.index(n)] for n in CONV_CLASSES) / 1e12 / sampled / (dt / args.steps), 2),
+                conv_kernel_ms_per_step=round(conv_ms, 3), kernel_classes=classes,
+                kernel_classes_serial_pass=iso_classes)
+            out["config"]["exchange"].update(buckets=bucket_times, schedule=sched)
+            out.update(
+                host=dict(enqueue_ms_per_step=round(1e3 * host_t["enqueue"] / max(host_t["steps"], 1), 3),
+                          wait_ms_per_step=round(1e3 * host_t["wait"] / max(host_t["steps"], 1), 3),
+                          note="rank 0, timed region: time the host needs to queue one step through the C ABI (batch draw, example tables, "
+                               "every launch, the update) and the time it then waits for the step's 64-byte statistics; while wait > 0 the "
+                               "host is ahead of the device and does not bound `value`"),
+                roofline=dict(bound="mfma",
+                              kernel=(("conv_x3_kernel (conv forward + input-gradient, two fp16 planes per operand: 3 fp16 MFMA partial products "
+                                       "per fp32 product)" if nprod == F16_PRODUCTS else
+                                       "conv_x3_kernel (3x3 conv forward + input-gradient, split-bf16 operands: 6 bf16 MFMA partial products "
+                                       "per fp32 product)") if split_on else
+                                      "conv_igemm_kernel<3,8,*> (3x3 conv forward + input-gradient, fp32 MFMA)"),
+                              achieved=round(ach, 2), peak=round(peak, 1), unit="TFLOP/s",
+                              frac=round(ach / peak, 4), traffic=traffic,
+                              traffic_source=("profiles/pmc_traffic.json: HBM bytes per launch from separate rocprofv3 --pmc FETCH_SIZE / "
+                                              "--pmc WRITE_SIZE passes of this command (FETCH x2, the gfx950 correction; tools/pmc_traffic.py), "
+                                              "taken when the profile was made -- not counted in this run" if traffic is not None else None),
+                              traffic_taken=traffic_taken,
+                              peak_note=("algorithmic (fp32-product) TFLOP/s against the dense fp16 / bf16 matrix-core peak 2516.6 / %d partial "
+                                         "products; executed MFMA rate = %d x achieved = %.0f TFLOP/s (%.3f of the dense peak); the fp32 matrix-core "
+                                         "peak is 157.3 TFLOP/s" % (nprod, nprod, nprod * ach, nprod * ach / BF16_MFMA_PEAK_TFLOPS)
+                                         if split_on else "fp32 matrix-core peak"),
+                              executed=(dict(partial_products_per_fp32_product=nprod, tflops=round(nprod * ach, 1),
+                                             frac_of_dense_16bit_peak=round(nprod * ach / BF16_MFMA_PEAK_TFLOPS, 4),
+                                             note="matrix-core FLOPs actually issued (the MFMA-utilisation figure); the two-plane fp16 form "
+                                                  "issues half of what the three-plane bf16 form does for the same algorithmic work")
+                                        if split_on else None),
+                              sampled_steps=sampled, launches_per_step=launches[k] / sampled, avg_launch_ms=round(ms[k] / max(launches[k], 1), 4),
+                              algorithmic_bytes_per_launch=round(by[k] / max(launches[k], 1)),
+                              algorithmic_gflop_per_launch=round(fl[k] / 1e9 / max(launches[k], 1), 3), isolated=iso,
+                              dense_equivalent=(dict(gflop_per_step=round(backbone_x3_dense_flops(model, H, W) / 1e9, 2),
+                                                     tflops=round(backbone_x3_dense_flops(model, H, W) / 1e12 / (ms[k] / 1e3 / sampled), 2),
+                                                     frac=round(backbone_x3_dense_flops(model, H, W) / 1e12 / (ms[k] / 1e3 / sampled) / peak, 4),
+                                                     note="the same launches priced by the DENSE algorithm's FLOP formula (SURVEY 8d): what option "
+                                                          "drop_compact leaves out -- products with the zeros of nn.SpatialDropout -- counted as if "
+                                                          "computed.  Not a matrix-core utilisation: `frac` above counts the launches as run")
+                                                if split_on and launches[k] / sampled == 12.0 else None)),
+                roofline_hbm=hbm,
+                sustained=sustained)
         ok = True
-        full = args.model == "vgg_small" and (H, W) == (FULL_H, FULL_W)
-        if world == 1 and not args.no_cpu_baseline and full:
+        full_frame = args.model == "vgg_small" and (H, W) == (FULL_H, FULL_W)
+        if full and world == 1 and not args.no_cpu_baseline and full_frame:
             nat = model["native"]
             w0 = nat.init_parameters(42)
             bn0 = np.concatenate([np.zeros(1024, np.float32), np.ones(1024, np.float32)])

@@ -144,13 +144,13 @@ def test_lua_drop_in_files_are_consistent_with_the_abi():
     assert "require 'frcnn_hip'" in B("cunn.lua") and "require 'frcnn_nn'" in B("cunn.lua")
     assert re.search(r"^nms = hip\.nms", B("nms.lua"), re.M)
     assert "return require 'objective_hip'" in B("objective.lua") and "return require 'Detector_hip'" in B("Detector.lua")
-    main = os.path.join("/root/reference", "main.lua")
-    if os.path.exists(main):   # (build container only) every `require` of the hot path is served without touching main.lua
-        req = re.findall(r"^require '([A-Za-z_]+)'", open(main).read(), re.M)
-        assert req[:14] == ["torch", "pl", "optim", "image", "nngraph", "cunn", "nms", "gnuplot", "utilities", "Anchors", "BatchIterator",
-                            "objective", "Detector"][:len(req[:14])]
-        for name in ("cunn", "nms", "objective", "Detector"):
-            assert os.path.exists(os.path.join(ROOT, "bindings", name + ".lua")), name
+    # every `require` of the hot path is served without touching main.lua (its require list: tests/golden/main_lua_requires.json)
+    import json
+    req = json.load(open(os.path.join(ROOT, "tests", "golden", "main_lua_requires.json")))["requires"]
+    assert req[:14] == ["torch", "pl", "optim", "image", "nngraph", "cunn", "nms", "gnuplot", "utilities", "Anchors", "BatchIterator",
+                        "objective", "Detector"][:len(req[:14])]
+    for name in ("cunn", "nms", "objective", "Detector"):
+        assert os.path.exists(os.path.join(ROOT, "bindings", name + ".lua")), name
     # the stand-alone nn modules of SURVEY 8b (the reference's own objective.lua:24-30 / Detector.lua:13-14 construct them)
     nnl = B("frcnn_nn.lua")
     for cls in ("nn.SpatialAdaptiveMaxPooling", "nn.LogSoftMax", "nn.CrossEntropyCriterion", "nn.ClassNLLCriterion", "nn.SmoothL1Criterion"):

@@ -18,7 +18,7 @@ def collect(d, counter):
 
 fetch = collect(sys.argv[1], "FETCH_SIZE")
 write = collect(sys.argv[2], "WRITE_SIZE")
-out = {"method": __doc__.split("usage")[0].strip() + " Passes ran over `python bench.py --steps 3 --warmup 1 --no-cpu-baseline`.",
+out = {"method": __doc__.split("usage")[0].strip() + " Passes ran over `python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`.",
        "kernels": {}}
 for k in sorted(set(fetch) | set(write)):
     fv, wv = fetch.get(k, []), write.get(k, [])

@@ -5,7 +5,7 @@ R=${ROUNDS:-2}
 for r in $(seq $R); do
 for cfg in "$@"; do
   echo -n "[$cfg] run $r: "
-  env $cfg python bench.py --steps ${STEPS:-80} --warmup 20 --no-sustained --no-cpu-baseline --no-upload-leg --no-other-legs 2>/dev/null | python -c "
+  env $cfg python bench.py --full --steps ${STEPS:-80} --warmup 20 --no-sustained --no-cpu-baseline --no-upload-leg --no-other-legs 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; O=gpurun_out/exp3; mkdir -p $O
 for e in "FRCNN_X3_F16=1" "FRCNN_X3_F16=0" "FRCNN_SPLIT_BF16=0"; do
-  echo -n "$e: "; env $e python bench.py --no-cpu-baseline --no-sustained --no-upload-leg --steps 40 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'images/s', d['ms_per_step'], 'ms/step', d['roofline']['frac'])"
+  echo -n "$e: "; env $e python bench.py --full --no-cpu-baseline --no-sustained --no-upload-leg --steps 40 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'images/s', d['ms_per_step'], 'ms/step', d['roofline']['frac'])"
 done | tee $O/env.txt
 python - <<'PY' 2>&1 | grep -v amdgpu.ids | tee $O/legs.txt
 import bench, sys

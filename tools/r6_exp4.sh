@@ -17,7 +17,7 @@ echo "== A/B step time" | tee $O/ab.txt
 for r in 1 2 3; do
   for v in base $V; do
     if [ $v = base ]; then unset FRCNN_LIB_PATH; else export FRCNN_LIB_PATH=$A/libfrcnn_$v.so; fi
-    python bench.py --steps 60 --warmup 15 --no-sustained --no-cpu-baseline --no-upload-leg 2>/dev/null | python -c "
+    python bench.py --full --steps 60 --warmup 15 --no-sustained --no-cpu-baseline --no-upload-leg 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: kernel stats of the bench command under rocprofv3 (summary only), into gpurun_out/<tag>/
 TAG=${1:-stats}; R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-upload-leg --no-sustained --no-other-legs > $O/bench_under_rocprof.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-upload-leg --no-sustained --no-other-legs > $O/bench_under_rocprof.json 2> $O/stats.log
 cd $R; cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv; python tools/timeline.py $O/stats 12 > $O/step_timeline.txt 2>&1; rm -rf $O/stats
 python - "$O/kernel_stats.csv" <<'PY'
 import csv, sys

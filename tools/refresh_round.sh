@@ -4,7 +4,7 @@
 TAG=${1:-r04}
 export FRCNN_GIT_HASH=${2:-${FRCNN_GIT_HASH:-unknown}}   # the tree the measurements belong to (the GPU box has no .git): pass `git rev-parse --short HEAD`
 R=/root/repo; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-upload-leg --no-sustained"
+B="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-upload-leg --no-sustained"
 # 1. PMC passes (separate runs, --kernel-trace only, as MI355X_MICROARCH.md prescribes)
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $B > $O/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -- $B > $O/write.log 2>&1
@@ -32,14 +32,14 @@ if [ -n "$PMC_ONLY" ]; then   # only the traffic table (after a change under csr
 fi
 # 2. kernel stats of the bench command (rocprofv3 --kernel-trace --stats) and the step timeline of the same trace
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --no-cpu-baseline --no-upload-leg --no-sustained > $O/${TAG}_bench_under_rocprof.json 2> $O/stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --no-cpu-baseline --no-upload-leg --no-sustained > $O/${TAG}_bench_under_rocprof.json 2> $O/stats.log
 cd $R
 cp $O/stats/*/*kernel_stats.csv $O/${TAG}_bench_kernel_stats.csv 2>/dev/null
 python tools/timeline.py $O/stats 12 > $O/${TAG}_step_timeline.txt 2>&1
 # 3. the bench line itself (un-profiled), with the CPU baseline, the parity object and the other legs (roofline.traffic is
 #    read from profiles/pmc_traffic.json: the table of pass 1 goes there first)
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-python bench.py > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err
 # 4. the other configurations and options
 {
   echo "# MI355X, $TAG: configurations and options beside the bench line (commands as run on the GPU box)"
@@ -53,13 +53,13 @@ python bench.py > $O/${TAG}_bench.json 2> $O/bench.err
   echo "# what an LDS-DMA / register load stream delivers per CU (L2-resident, shared, gathered, HBM) -- tools/bin/lds_dma_probe"
   [ -x tools/bin/lds_dma_probe ] || hipcc --offload-arch=gfx950 -O3 tools/lds_dma_probe.hip -o tools/bin/lds_dma_probe >/dev/null 2>&1
   timeout 60 tools/bin/lds_dma_probe 2>/dev/null
-  echo "# training step with options -- python bench.py --no-cpu-baseline --steps 40 (images/s, ms/step, roofline.frac live)"
+  echo "# training step with options -- python bench.py --full --no-cpu-baseline --steps 40 (images/s, ms/step, roofline.frac live)"
   for e in "FRCNN_SPLIT_BF16=1" "FRCNN_DROP_COMPACT=0" "FRCNN_SPARSE_HEADS=0" "FRCNN_DROP_COMPACT=0 FRCNN_SPARSE_HEADS=0" "FRCNN_EAGER_UPDATE=1" "FRCNN_X3_F16=0" "FRCNN_SPLIT_BF16=0" "FRCNN_GEMM_X=0" "FRCNN_DETERMINISTIC=1" "FRCNN_SIDE_STREAM=0" "FRCNN_HEAD_STREAMS=0" "FRCNN_CNET_WGRAD_ASYNC=0" "FRCNN_FUSE_ACT=0" "FRCNN_FIRST_POOLED=0"; do
-    echo -n "$e: "; env $e python bench.py --no-cpu-baseline --no-sustained --steps 40 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'images/s', d['ms_per_step'], 'ms/step', d['roofline']['frac'])"
+    echo -n "$e: "; env $e python bench.py --full --no-cpu-baseline --no-sustained --steps 40 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'images/s', d['ms_per_step'], 'ms/step', d['roofline']['frac'])"
   done
-  echo "# config 5 shapes on one GPU -- python bench.py --model vgg_large --height 600 --width 1000 --steps 10 --no-cpu-baseline"
+  echo "# config 5 shapes on one GPU -- python bench.py --full --model vgg_large --height 600 --width 1000 --steps 10 --no-cpu-baseline"
   for e in "FRCNN_SPLIT_BF16=1" "FRCNN_SPLIT_BF16=0"; do
-    echo -n "$e: "; env $e python bench.py --model vgg_large --height 600 --width 1000 --steps 10 --no-cpu-baseline --no-sustained 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], 'images/s', d['ms_per_step'], 'ms/step; conv_igemm 3x3', r['achieved'], 'TFLOP/s live,', r['isolated']['achieved'], 'alone')"
+    echo -n "$e: "; env $e python bench.py --full --model vgg_large --height 600 --width 1000 --steps 10 --no-cpu-baseline --no-sustained 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], 'images/s', d['ms_per_step'], 'ms/step; conv_igemm 3x3', r['achieved'], 'TFLOP/s live,', r['isolated']['achieved'], 'alone')"
   done
   echo "# the cnet's Linear(13824,1024) in its three roles, split-bf16 form and (FRCNN_GEMM_X=0) fp32 matrix-core kernels -- python tools/bench_gemm.py"
   python tools/bench_gemm.py 2>/dev/null | grep "I=13824"; FRCNN_GEMM_X=0 python tools/bench_gemm.py 2>/dev/null | grep "I=13824"
@@ -73,7 +73,7 @@ cd $R
 cp $O/detect/*/*kernel_stats.csv $O/${TAG}_detect_kernel_stats.csv 2>/dev/null
 # 5b. BASELINE config 5's one-GPU workload (vgg_large 3x600x1000) under rocprofv3: kernel stats of its training step
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/large -- python $R/bench.py --model vgg_large --height 600 --width 1000 --steps 10 --no-cpu-baseline --no-upload-leg --no-sustained > $O/large.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/large -- python $R/bench.py --full --model vgg_large --height 600 --width 1000 --steps 10 --no-cpu-baseline --no-upload-leg --no-sustained > $O/large.log 2>&1
 cd $R
 cp $O/large/*/*kernel_stats.csv $O/${TAG}_vgg_large_kernel_stats.csv 2>/dev/null
 # 6. the weight-gradient kernel by itself: per-launch durations of kernel and fold, and the PMC groups behind the LDS / matrix-pipe figures
