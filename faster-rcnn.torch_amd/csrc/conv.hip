@@ -618,10 +618,6 @@ static void choose_tile(int Ho, int Wo, int k, int maxNT, int* TH, int* TW) {
     }
   }
   *TH = bth; *TW = btw;
-  if (const char* e = getenv("FRCNN_IG_TW")) {
-    int tw = atoi(e);
-    if (tw >= 1 && tw <= Wo && tw <= maxNT) { *TW = tw; *TH = std::max(1, std::min(maxNT / tw, Ho)); }
-  }
 }
 
 template <int KS, int CC, int BM, int MODE, int NIT>
@@ -667,22 +663,20 @@ int conv_igemm(const float* in, int Cin, int H, int W, const float* in_slope, co
   // each).  A CU serves its oldest block first, so blocks retire one after the other and the last one runs
   // alone with its staging exposed; smaller blocks make that tail shorter (measured on every vgg_small layer:
   // 64-row tiles are 0-14% faster than 128-row tiles).  1x1 keeps 128 rows (large K chunks, LDS double buffer).
-  static const int ig_bm128 = getenv("FRCNN_IG_BM128") ? atoi(getenv("FRCNN_IG_BM128")) : 0;
-  const int BM = (a.Mpad == 64 || (k > 1 && !ig_bm128)) ? 64 : 128;
+  const int BM = (a.Mpad == 64 || k > 1) ? 64 : 128;
   const int cc = conv_cc(k);
   a.nChunks = cdiv(Cin, cc);
   a.mTiles = a.Mpad / BM;
   // split K until one wave of blocks fills the resident slots, keeping >= ~200 K rows per split
-  const long slots = BM == 64 && k > 1 ? 256 * IG_BPC : 768;
+  const long slots = k > 1 ? 256 * IG_BPC : 768;
   const int minChunks = k == 1 ? 2 : std::max(1, cdiv(200, cc * k * k));
   auto splits_for = [&](long blocks) {
     return (int)std::min<long>(std::min<long>(std::max<long>(1, slots / blocks), 24), std::max(1, a.nChunks / minChunks));
   };
   // fused max pool: needs the 4 x 32 tile (two rows per wave, neighbours in lane^1), 64-row M tiles, a plain store and
   // a single K split (the pooled map is a function of the complete sum)
-  static const int ig_pool = getenv("FRCNN_IG_POOL") ? atoi(getenv("FRCNN_IG_POOL")) : 1;
   bool fuse = false;
-  if (pool && ig_pool && k == 3 && BM == 64 && IG_NTW == 2 && out_mode == OUT_STORE && !getenv("FRCNN_IG_SPLITK")) {
+  if (pool && k == 3 && IG_NTW == 2 && out_mode == OUT_STORE) {
     const long blocks = (long)cdiv(a.Wo, 32) * cdiv(a.Ho, 4) * a.mTiles;
     fuse = (Cin <= 4 ? 1 : splits_for(blocks)) == 1;
     // ... and the fixed tile must not cost a round of blocks: 200x113 in 4x32 tiles is 812 blocks = up to 4 per CU where the
@@ -703,7 +697,6 @@ int conv_igemm(const float* in, int Cin, int H, int W, const float* in_slope, co
   a.tilesX = cdiv(a.Wo, a.TW); a.tilesY = cdiv(a.Ho, a.TH);
   long blocks = (long)a.tilesX * a.tilesY * a.mTiles;
   int splitK = splits_for(blocks);
-  if (const char* e = getenv("FRCNN_IG_SPLITK")) splitK = std::max(1, std::min(a.nChunks, atoi(e)));
   a.chunksPerSplit = cdiv(a.nChunks, splitK);
   a.splitK = cdiv(a.nChunks, a.chunksPerSplit);
   a.out_mode = out_mode;
@@ -716,27 +709,22 @@ int conv_igemm(const float* in, int Cin, int H, int W, const float* in_slope, co
     FR_TRY(ig_workspace((size_t)a.splitK * M * a.Ho * a.Wo * 4, &ws, ws_slot & 7));
     a.out = ws; a.out_mode = 3; a.bias = nullptr; slab = true;
   }
-  static const int ig_dma = getenv("FRCNN_IG_DMA") ? atoi(getenv("FRCNN_IG_DMA")) : 1;
-  a.dma_patch = ig_dma && k > 1 && !in_slope && !in_scale && (double)Cin * H * W * 4.0 < 2147483647.0 ? 1 : 0;
+  a.dma_patch = k > 1 && !in_slope && !in_scale && (double)Cin * H * W * 4.0 < 2147483647.0 ? 1 : 0;
   if (algo_flops <= 0) algo_flops = 2.0 * M * Cin * k * k * (double)a.Ho * a.Wo;
   int klass = k == 3 ? KC_CONV_IGEMM_K3 : KC_CONV_IGEMM_OTHER;
   int rc;
   if (k == 3 && Cin <= 4) {  // first layer: a 4-channel chunk (the packed rows are ordered by channel pair)
     a.nChunks = 1; a.chunksPerSplit = 1; a.splitK = 1; a.out_mode = out_mode; a.bias = bias; a.out = out;
-    rc = BM == 64 ? launch_igemm<3, 4, 64, 0>(a, klass, algo_flops, s)
-                  : launch_igemm<3, 4, 128, 0>(a, klass, algo_flops, s);
+    rc = launch_igemm<3, 4, 64, 0>(a, klass, algo_flops, s);
   } else if (k == 3) {
-    rc = BM == 64 ? launch_igemm<3, 8, 64, 0>(a, klass, algo_flops, s)
-                  : launch_igemm<3, 8, 128, 0>(a, klass, algo_flops, s);
+    rc = launch_igemm<3, 8, 64, 0>(a, klass, algo_flops, s);
   } else if (k == 1) {
     rc = BM == 64 ? launch_igemm<1, 32, 64, 1>(a, klass, algo_flops, s)
                   : launch_igemm<1, 32, 128, 1>(a, klass, algo_flops, s);
   } else if (k == 5) {
-    rc = BM == 64 ? launch_igemm<5, 2, 64, 0>(a, klass, algo_flops, s)
-                  : launch_igemm<5, 2, 128, 0>(a, klass, algo_flops, s);
+    rc = launch_igemm<5, 2, 64, 0>(a, klass, algo_flops, s);
   } else {
-    rc = BM == 64 ? launch_igemm<7, 2, 64, 0>(a, klass, algo_flops, s)
-                  : launch_igemm<7, 2, 128, 0>(a, klass, algo_flops, s);
+    rc = launch_igemm<7, 2, 64, 0>(a, klass, algo_flops, s);
   }
   FR_TRY(rc);
   if (slab) {
@@ -770,7 +758,6 @@ struct WgradArgs {
   int Cin, H, W, O, Ho, Wo, pad;
   int TH, TW, tilesX, tilesY;
   int oTiles, cTiles, kyGroups, nSplit;
-  int dbg;  // tuning knobs (tools/bench_conv.py): bit0 skip epilogue, bit1 skip MFMA loop, bit2 skip staging
 };
 
 #define WG_NT 64     // staged gradient pixels per tile (TH*TW <= 64)
@@ -888,15 +875,13 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p) {
 
   const int nPix = p.tilesX * p.tilesY;
   for (int t = split; t < nPix; t += p.nSplit) {
-    if (!(p.dbg & 4)) {
-      if (has_slope) {
-        if (has_scale) stage_tile(t, std::true_type{}, std::true_type{}); else stage_tile(t, std::true_type{}, std::false_type{});
-      } else {
-        if (has_scale) stage_tile(t, std::false_type{}, std::true_type{}); else stage_tile(t, std::false_type{}, std::false_type{});
-      }
+    if (has_slope) {
+      if (has_scale) stage_tile(t, std::true_type{}, std::true_type{}); else stage_tile(t, std::true_type{}, std::false_type{});
+    } else {
+      if (has_scale) stage_tile(t, std::false_type{}, std::true_type{}); else stage_tile(t, std::false_type{}, std::false_type{});
     }
     __syncthreads();
-    if (wave_active && !(p.dbg & 2)) {
+    if (wave_active) {
       // K = pixels: lane half h walks rows [h*halfrows, (h+1)*halfrows).  Along a row the KS taps of one
       // patch row are a sliding window: per pixel ONE new patch value per tap row (+ one gradient value)
       // is read from LDS for TYS*KS MFMAs; the gradient value of the next pixel is fetched a step ahead and
@@ -937,7 +922,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p) {
     __syncthreads();
   }
   // ---- epilogue: D col = lane&31 -> c (contiguous in the slab), row -> o
-  if (wave_active && !(p.dbg & 1)) {
+  if (wave_active) {
     const int c = c0 + wc * 32 + li;
     const size_t OC = (size_t)p.O * p.Cin;
     float* sl = p.slab + (size_t)split * KS * KS * OC;
@@ -1147,51 +1132,46 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_first_kernel(WgradArgs p, W
     }
   };
   if (FUSED && tid < W1_TW) ps[NPATCH * 256 + tid] = 1.f;   // (visible after the first barrier; nothing else writes there)
-  const bool dbg_dead = p.dbg & 8;
-  load(blockIdx.x, (int)blockIdx.x < nPix && !dbg_dead);
+  load(blockIdx.x, (int)blockIdx.x < nPix);
   for (int t = blockIdx.x; t < nPix; t += gridDim.x) {
     // ---- gradient tile: 64 rows (o) x 256 pixels (4 rows of 64)
-    if (!(p.dbg & 4)) {
-      float* gw = gs + (2 * wy) * W1_TW + 2 * wx;
+    float* gw = gs + (2 * wy) * W1_TW + 2 * wx;
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int o = o0 + j;
-        const bool oko = o < p.O;
-        float v[4] = {shifted ? r0[j].y : r0[j].x, r0[j].y, shifted ? r1[j].y : r1[j].x, r1[j].y};
-        const bool ok[4] = {oko && oky0 && okx0, oko && oky0 && okx1, oko && oky1 && okx0, oko && oky1 && okx1};
+    for (int j = 0; j < 16; ++j) {
+      const int o = o0 + j;
+      const bool oko = o < p.O;
+      float v[4] = {shifted ? r0[j].y : r0[j].x, r0[j].y, shifted ? r1[j].y : r1[j].x, r1[j].y};
+      const bool ok[4] = {oko && oky0 && okx0, oko && oky0 && okx1, oko && oky1 && okx0, oko && oky1 && okx1};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float g;
-          if (FUSED) {
-            g = (ok[e] && ib[j] == e) ? gp[j] : 0.f;
-            const bool pos = v[e] > 0.f;
-            sa = fmaf(pos ? 0.f : v[e], g, sa);
-            g = pos ? g : pa * g;
-          } else {
-            g = ok[e] ? v[e] : 0.f;
-          }
-          gw[o * W1_GP + (e >> 1) * W1_TW + (e & 1)] = g;
+      for (int e = 0; e < 4; ++e) {
+        float g;
+        if (FUSED) {
+          g = (ok[e] && ib[j] == e) ? gp[j] : 0.f;
+          const bool pos = v[e] > 0.f;
+          sa = fmaf(pos ? 0.f : v[e], g, sa);
+          g = pos ? g : pa * g;
+        } else {
+          g = ok[e] ? v[e] : 0.f;
         }
-        // one channel at a time: left alone, the scheduler does all 64 stores first and the slope sums last, with every
-        // value, gradient and comparison mask of the tile alive in between (256 registers, masks spilled lane by lane)
-        if (FUSED) asm volatile("" : "+v"(sa)::"memory");   // (and the slope sums HERE: they were moved behind the barrier)
-        __builtin_amdgcn_sched_barrier(0);
+        gw[o * W1_GP + (e >> 1) * W1_TW + (e & 1)] = g;
       }
-#pragma unroll
-      for (int i = 0; i < NPATCH; ++i) ps[tid + 256 * i] = pv[i];   // (NPATCH * 256 floats are there; zeros behind the patch)
+      // one channel at a time: left alone, the scheduler does all 64 stores first and the slope sums last, with every
+      // value, gradient and comparison mask of the tile alive in between (256 registers, masks spilled lane by lane)
+      if (FUSED) asm volatile("" : "+v"(sa)::"memory");   // (and the slope sums HERE: they were moved behind the barrier)
+      __builtin_amdgcn_sched_barrier(0);
     }
+#pragma unroll
+    for (int i = 0; i < NPATCH; ++i) ps[tid + 256 * i] = pv[i];   // (NPATCH * 256 floats are there; zeros behind the patch)
     __syncthreads();
-    load(t + gridDim.x, t + (int)gridDim.x < nPix && !dbg_dead);   // in flight under the MFMA phase
-    if (!(p.dbg & 2)) {
-      const float* ga = gs + li * W1_GP + wave * W1_TW + h;          // pixel pair (x, x+1): h selects
-      const float* pb = ones ? ps + NPATCH * 256 : ps + tapoff + wave * PW + h;
+    load(t + gridDim.x, t + (int)gridDim.x < nPix);   // in flight under the MFMA phase
+    const float* ga = gs + li * W1_GP + wave * W1_TW + h;          // pixel pair (x, x+1): h selects
+    const float* pb = ones ? ps + NPATCH * 256 : ps + tapoff + wave * PW + h;
 #pragma unroll 4
-      for (int x = 0; x < W1_TW; x += 2) {
-        const float b = pb[x];
-        const float a0 = ga[x], a1 = ga[32 * W1_GP + x];
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc[1], 0, 0, 0);
-      }
+    for (int x = 0; x < W1_TW; x += 2) {
+      const float b = pb[x];
+      const float a0 = ga[x], a1 = ga[32 * W1_GP + x];
+      acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc[1], 0, 0, 0);
     }
     __syncthreads();
   }
@@ -1255,9 +1235,6 @@ static void wgrad_plan(WgradArgs& a, int k) {
     a.tilesX = cdiv(a.Wo, W1_TW); a.tilesY = cdiv(a.Ho, W1_TH);
     a.oTiles = a.cTiles = a.kyGroups = 1;
     a.nSplit = std::min(512, a.tilesX * a.tilesY);   // one slab slice per block
-    a.dbg = 0;
-    if (const char* e = getenv("FRCNN_WG_DBG")) a.dbg = atoi(e);
-    if (const char* e = getenv("FRCNN_W1_SPLIT")) a.nSplit = std::min(atoi(e), a.tilesX * a.tilesY);
     return;
   }
   const int tys = k == 3 ? 3 : 1;
@@ -1269,9 +1246,6 @@ static void wgrad_plan(WgradArgs& a, int k) {
   long npix = (long)a.tilesX * a.tilesY;
   // two blocks per CU: aim for ~512 blocks
   a.nSplit = (int)std::max<long>(1, std::min<long>(npix, (512 + base / 2) / base));
-  a.dbg = 0;
-  if (const char* e = getenv("FRCNN_WG_DBG")) a.dbg = atoi(e);
-  if (const char* e = getenv("FRCNN_WG_NSPLIT")) a.nSplit = (int)std::max<long>(1, std::min<long>(npix, atoi(e)));
 }
 
 // the same with four consecutive (o, c) pairs of one tap per thread: 16-byte slab loads, four of them in flight (needs 4 | OC)
@@ -1406,8 +1380,7 @@ static int launch_wgrad_pm(WgradArgs& a, int klass, double flops, float* gw, hip
   const int OC = a.O * a.Cin;
   long total = (long)KS * KS * OC;
   int rgrid = (int)std::min<long>(cdivl(total, 64), 4096);
-  if (!(a.dbg & 1))
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rgrid), dim3(256), 0, s, (const float*)a.slab, a.nSplit, KS * KS, OC, gw);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rgrid), dim3(256), 0, s, (const float*)a.slab, a.nSplit, KS * KS, OC, gw);
   if (frcnn::prof_enabled(klass)) frcnn::prof_after(klass, flops, bytes, s);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
@@ -1479,8 +1452,6 @@ int conv_wgrad_first_pooled(const float* in, int Cin, int H, int W, const float*
   a.tilesX = cdiv(a.Wo, W1_TW); a.tilesY = cdiv(a.Ho, W1_TH);
   a.oTiles = a.cTiles = a.kyGroups = 1;
   a.nSplit = std::min(512, a.tilesX * a.tilesY);
-  a.dbg = 0;
-  if (const char* e = getenv("FRCNN_WG_DBG")) a.dbg = atoi(e);
   const size_t need = (size_t)a.nSplit * (9 * O * Cin + O + 1) * 4 + 256;
   FR_CHECK(ws && ws_bytes >= need, "conv_wgrad_first_pooled: workspace too small (%zu < %zu)", ws_bytes, need);
   a.slab = (float*)(((uintptr_t)ws + 255) / 256 * 256);

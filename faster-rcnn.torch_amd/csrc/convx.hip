@@ -86,10 +86,8 @@ static void x3_choose_tile(int Ho, int Wo, int k, int* TH, int* TW);
 // launch behind them (42 us each, on the dependent chain) go away -- 96 vs 114 us and 171 vs 182 us for the two layers.
 // The weight pack depends on the choice, so the launch and the pack job both ask this function with the same shape.
 int conv_x3_bm(int M, int Ho, int Wo, int k) {
-  static const int force = getenv("FRCNN_X3_BM") ? atoi(getenv("FRCNN_X3_BM")) : 0;
-  if (force == 64) return 64;
   if (M % 128 != 0) return 64;
-  if (force == 128 || k != 3 || Ho <= 0) return 128;
+  if (k != 3 || Ho <= 0) return 128;
   int TH, TW;
   x3_choose_tile(Ho, Wo, k, &TH, &TW);
   const long tiles = (long)cdiv(Ho, TH) * cdiv(Wo, TW);
@@ -1074,24 +1072,9 @@ static int x3_workspace(size_t need, float** out, int slot) {
 }
 
 // output tile TH x TW <= 128 pixels with a patch plane <= CX_PP that wastes the least work
-// FRCNN_X3_WIDE=0: the scalar epilogue everywhere (and tile widths of any size)
-static int x3_wide_enabled() {
-  static const int on = getenv("FRCNN_X3_WIDE") ? atoi(getenv("FRCNN_X3_WIDE")) : 1;
-  return on;
-}
 static void x3_choose_tile(int Ho, int Wo, int k, int* TH, int* TW) {
-  static int fth = 0, ftw = 0;   // FRCNN_X3_TILE=THxTW (experiments)
-  static bool parsed = false;
-  if (!parsed) {
-    parsed = true;
-    if (const char* e = getenv("FRCNN_X3_TILE")) sscanf(e, "%dx%d", &fth, &ftw);
-  }
-  if (fth > 0 && ftw > 0 && k == 3 && fth * ftw <= CX_NTMAX && (fth + k - 1) * (ftw + k - 1) <= cx_pp(k)) {
-    *TH = std::min(fth, Ho); *TW = std::min(ftw, Wo);
-    return;
-  }
   // the wide epilogue stores groups of four pixels: tile widths that are multiples of 4 where the map's width is one
-  const int mult = (x3_wide_enabled() && Wo % 4 == 0) ? 4 : 1;
+  const int mult = Wo % 4 == 0 ? 4 : 1;
   long best = -1;
   int bth = 1, btw = 1;
   for (int tw = 1; tw <= std::min(Wo, CX_NTMAX); ++tw) {
@@ -1126,8 +1109,7 @@ static int launch_x3(CxArgs& a, double flops, hipStream_t s) {
 #endif
   double bytes = 4.0 * ((double)a.Cin * a.H * a.W + (double)a.M * a.Ho * a.Wo);
   // (the wide epilogue turns four 64 x 32 fp32 tiles over in LDS: 32 KB)
-  static const size_t lds_min = getenv("FRCNN_X3_LDS_MIN") ? (size_t)atol(getenv("FRCNN_X3_LDS_MIN")) : 0;   // (experiments: fewer blocks per CU)
-  const size_t lds = std::max(lds_min, std::max<size_t>((size_t)cx_ring(NP) * (2 * NP * 64 * WM * 16) + (size_t)CX_NB * (2 * NP * cx_pp(KS) * 16), a.wide ? 4 * 64 * 32 * 4 : 0));
+  const size_t lds = std::max<size_t>((size_t)cx_ring(NP) * (2 * NP * 64 * WM * 16) + (size_t)CX_NB * (2 * NP * cx_pp(KS) * 16), a.wide ? 4 * 64 * 32 * 4 : 0);
   FR_LAUNCH(KC_CONV_X3, flops, bytes, s, (conv_x3_kernel<KS, WM, SLOPE, SCALE, EPI, NP>), dim3(grid), dim3(256), lds, a);
   FR_LAUNCH_CHECK();
 #ifdef CX_TRACE
@@ -1173,7 +1155,6 @@ int conv_x3(const float* in, int Cin, int H, int W, const float* in_slope, const
   // (the 5x5 / 7x7 kernels hold two blocks per CU and have 25 / 49 stages per chunk: up to 24 splits of one chunk each)
   const long slots = 256 * (k == 3 ? CX_OCC : 2);
   int splitK = (int)std::min<long>(std::min<long>(std::max<long>(1, slots / blocks), k == 3 ? 16 : 24), std::max(1, a.nChunks / min_chunks));
-  if (const char* e = getenv("FRCNN_X3_SPLITK")) splitK = std::max(1, std::min(a.nChunks, atoi(e)));
   a.chunksPerSplit = cdiv(a.nChunks, splitK);
   a.splitK = cdiv(a.nChunks, a.chunksPerSplit);
   a.out_mode = out_mode;
@@ -1191,7 +1172,7 @@ int conv_x3(const float* in, int Cin, int H, int W, const float* in_slope, const
     a.out = ws; a.out_mode = 3; a.bias = nullptr; slab = true;
     a.amax_out = nullptr;   // (the fold sees the final values)
   }
-  a.wide = x3_wide_enabled() && a.Wo % 4 == 0 && a.TW % 4 == 0 && ((uintptr_t)a.out & 15) == 0 &&
+  a.wide = a.Wo % 4 == 0 && a.TW % 4 == 0 && ((uintptr_t)a.out & 15) == 0 &&
            (!post || ((uintptr_t)post->x & 15) == 0);
   if (algo_flops <= 0) algo_flops = 2.0 * M * Cin * k * k * (double)a.Ho * a.Wo;
   int rc;

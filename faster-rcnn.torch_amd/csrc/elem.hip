@@ -660,8 +660,7 @@ int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, floa
   if (lo == hi) return FRCNN_OK;
   const long n = hi - lo;
   // half the wave slots at most: a slice update runs BESIDE other launches (the backward pass) and must not keep them waiting for slots
-  static const int max_grid = getenv("FRCNN_SLICE_GRID") ? atoi(getenv("FRCNN_SLICE_GRID")) : 1024;
-  int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), max_grid);
+  int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 1024);
   if (scale_first)
     FR_LAUNCH(KC_OPTIM, 0, n * 24.0, s, rmsprop_slice_kernel<true>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, gscale);
   else

@@ -380,15 +380,12 @@ int gemm_f32(const float* A, long sAm, long sAk, const float* B, long sBk, long 
   p.bias = bias_n; p.M = M; p.N = N; p.K = K;
   // 64-row tiles (more, shorter-lived blocks per CU: same finding as for the convolution tiles); 128 columns
   // when N is long.  Split K until one wave of blocks fills the resident slots, >= 256 K values per split, <= 16 splits.
-  int TMs = 64;
-  int TNs = (N >= 2048 && K >= 512) ? 128 : 64;
-  if (const char* e = getenv("FRCNN_GEMM_TM")) TMs = atoi(e);
-  if (const char* e = getenv("FRCNN_GEMM_TN")) TNs = atoi(e);
+  constexpr int TMs = 64;
+  const int TNs = (N >= 2048 && K >= 512) ? 128 : 64;
   int tm = cdiv(M, TMs), tn = cdiv(N, TNs);
   long tiles = (long)tm * tn;
   const long slots = TNs == 128 ? 1280 : 2048;
   int splitK = (int)std::max<long>(1, std::min<long>(std::min<long>(K / 256, 16), slots / tiles));
-  if (const char* e = getenv("FRCNN_GEMM_SPLITK")) splitK = std::max(1, atoi(e));
   p.kPerSplit = cdiv(cdiv(K, splitK), GBK) * GBK;
   splitK = cdiv(K, p.kPerSplit);
   p.out_mode = out_mode;
@@ -416,13 +413,11 @@ int gemm_f32(const float* A, long sAm, long sAk, const float* B, long sBk, long 
     if (kc) return sK == 1 && (Kdim % 4) == 0 && (kPer % 4) == 0;
     return sRow == 1 && (nRows % 4) == 0;
   };
-  static const bool dma_unaligned = !(getenv("FRCNN_GEMM_DMA_UNALIGNED") && atoi(getenv("FRCNN_GEMM_DMA_UNALIGNED")) == 0);
-  const bool ad = dma_unaligned ? chunk_ok(A, ak, sAm, sAk, M, K, p.kPerSplit) : av;
-  const bool bd = dma_unaligned ? chunk_ok(B, bk, sBn, sBk, N, K, p.kPerSplit) : bv;
+  const bool ad = chunk_ok(A, ak, sAm, sAk, M, K, p.kPerSplit);
+  const bool bd = chunk_ok(B, bk, sBn, sBk, N, K, p.kPerSplit);
   // DMA kernel: every operand 16-byte addressable (k-contiguous: K and the row stride multiples of 4;
   // row-contiguous: row count and k stride multiples of 4), split boundaries on whole K blocks
-  static const bool dma_on = !(getenv("FRCNN_GEMM_DMA") && atoi(getenv("FRCNN_GEMM_DMA")) == 0);
-  const bool dma_ok = dma_on && ad && bd && (p.kPerSplit % GD_BK == 0 || splitK == 1) && K >= 64 &&
+  const bool dma_ok = ad && bd && (p.kPerSplit % GD_BK == 0 || splitK == 1) && K >= 64 &&
                       (ak ? true : (M % 4 == 0 && M >= 4)) && (bk ? true : (N % 4 == 0 && N >= 4));
   if (dma_ok) {
     const size_t lds = (size_t)GD_STAGES * (TMs + TNs) * GD_BK * 4;
@@ -443,10 +438,8 @@ int gemm_f32(const float* A, long sAm, long sAk, const float* B, long sBk, long 
     else if (bk) GEMM_DMA(TMv, TNv, false, true);                                  \
     else GEMM_DMA(TMv, TNv, false, false);                                         \
   } while (0)
-    if (TMs == 128 && TNs == 128) GEMM_DMA_T(128, 128);
-    else if (TMs == 128) GEMM_DMA_T(128, 64);
-    else if (TNs == 128) GEMM_DMA_T(64, 128);
-    else GEMM_DMA_T(64, 64);
+    if (TNs == 128) GEMM_DMA_T(TMs, 128);
+    else GEMM_DMA_T(TMs, 64);
 #undef GEMM_DMA_T
 #undef GEMM_DMA
   } else {
@@ -455,10 +448,8 @@ int gemm_f32(const float* A, long sAm, long sAk, const float* B, long sBk, long 
   FR_LAUNCH(KC_GEMM, flops, bytes, s, (gemm_kernel<TMv, TNv, AKv, BKv, AVv, BVv>), grid, dim3(256), 0, p)
 #define GEMM_CASE(AKv, BKv, AVv, BVv)                                                                        \
   case ((AKv ? 8 : 0) | (BKv ? 4 : 0) | (AVv ? 2 : 0) | (BVv ? 1 : 0)):                                      \
-    if (TMs == 128 && TNs == 128) GEMM_LAUNCH(128, 128, AKv, BKv, AVv, BVv);                                 \
-    else if (TMs == 128) GEMM_LAUNCH(128, 64, AKv, BKv, AVv, BVv);                                           \
-    else if (TNs == 128) GEMM_LAUNCH(64, 128, AKv, BKv, AVv, BVv);                                           \
-    else GEMM_LAUNCH(64, 64, AKv, BKv, AVv, BVv);                                                            \
+    if (TNs == 128) GEMM_LAUNCH(TMs, 128, AKv, BKv, AVv, BVv);                                               \
+    else GEMM_LAUNCH(TMs, 64, AKv, BKv, AVv, BVv);                                                           \
     break;
   switch (sel) {
     GEMM_CASE(true, true, true, true) GEMM_CASE(true, true, true, false) GEMM_CASE(true, true, false, true)

@@ -484,7 +484,6 @@ static void gx_plan(int M, int N, int K, int bmode, int splitK_max, int* TM, int
       if (cost < best) { best = cost; *TM = tmv; *splitK = sk_eff; }
     }
   }
-  if (const char* e = getenv("FRCNN_GX_SPLITK")) *splitK = std::max(1, atoi(e));
 }
 
 // wave layout by operand form: planes x planes -> 2 x 4 waves of TM / 2 rows x 64 columns (fewest fragment reads per MFMA);

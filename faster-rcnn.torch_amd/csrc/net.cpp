@@ -324,9 +324,8 @@ static int ensure_conv(Conv& c, int H, int W, bool need_dgrad) {
   // layers since round 2; the 5x5 / 7x7 anchor nets since round 5: rounds 2 and 3 had measured them slower in that form (8x10-pixel
   // tiles under the 204-position patch limit; then 8x16 tiles but a stage loop that needed three resident blocks to hide its LDS
   // round trips: 3.14 against 3.11 ms/step).  With the stage pipelined inside the wave (convx.hip) two blocks per CU suffice: the 7x7
-  // net 118.8 -> 63.8 us alone, the 5x5 net 67.4 -> 56.8, the step 2.918 -> 2.834 ms.  FRCNN_X3_ANCHOR_K=3 restores the fp32 kernels.
-  static const int x3_anchor_k = getenv("FRCNN_X3_ANCHOR_K") ? atoi(getenv("FRCNN_X3_ANCHOR_K")) : 7;
-  c.x_f = (c.k == 3 || (c.block < 0 && c.k <= x3_anchor_k)) && conv_x3_eligible(c.Cin, c.Cout, c.k);
+  // net 118.8 -> 63.8 us alone, the 5x5 net 67.4 -> 56.8, the step 2.918 -> 2.834 ms.
+  c.x_f = (c.k == 3 || c.block < 0) && conv_x3_eligible(c.Cin, c.Cout, c.k);
   c.x_d = c.block >= 0 && need_dgrad && conv_x3_eligible(c.Cout, c.Cin, c.k);
   if (c.x_f) FR_TRY(c.wx.ensure(conv_x3_pack_bytes(c.Cin, c.Cout, c.k)));
   if (c.x_d) FR_TRY(c.wxd.ensure(conv_x3_pack_bytes(c.Cout, c.Cin, c.k)));
@@ -1012,8 +1011,7 @@ static int pnet_forward_impl(frcnn_model* m, const float* w, const float* img, i
   m->fresh_mask = 0;
   if (!reuse && !fresh) {
     // (a training pass that leaves the anchor nets to the sparse path packs nothing of theirs: frcnn_model::head_x3_fresh)
-    static const bool skip_on = !(getenv("FRCNN_HEAD_PACK_SKIP") && atoi(getenv("FRCNN_HEAD_PACK_SKIP")) == 0);
-    const bool skip_heads = skip_on && training && m->heads_deferred && any_compact(m) && m->am_bb_n > 0;
+    const bool skip_heads = training && m->heads_deferred && any_compact(m) && m->am_bb_n > 0;
     m->head_x3_fresh = !skip_heads;
     if (training && skip_heads) {
       if (m->pk_bb_n) FR_TRY(conv_pack_weights_multi(w, (const PackJob*)m->pack_jobs.p + m->pk_bb_off, m->pk_bb_n, m->pk_bb_grid, s));
@@ -1607,14 +1605,13 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
     if (!m->heads_joined) {
       // What the backbone's pass needs from an anchor net is its contribution to the pooled map's gradient; a net on a stream
       // of its own marks that point (Head::gin_done) and goes on with its parameter gradients beside the backbone's pass.
-      static const bool partial = !(getenv("FRCNN_HEADS_PARTIAL_JOIN") && atoi(getenv("FRCNN_HEADS_PARTIAL_JOIN")) == 0);
-      if (partial && m->heads_gin) {   // the sparse path's one chain on the side stream: its input-gradient part, the rest at the end
+      if (m->heads_gin) {   // the sparse path's one chain on the side stream: its input-gradient part, the rest at the end
         FR_HIP(hipStreamWaitEvent(s, m->heads_gin_ev, 0));
         heads_tail = true;
       }
       for (auto& h : m->heads) {
         if (!h.stream || m->heads_gin) continue;
-        if (partial && h.gin_recorded) {
+        if (h.gin_recorded) {
           FR_HIP(hipStreamWaitEvent(s, h.gin_done, 0));
           heads_tail = true;
         } else {
@@ -1622,7 +1619,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
           FR_HIP(hipStreamWaitEvent(s, h.done, 0));
         }
       }
-      if (!(partial && m->heads_gin)) {
+      if (!m->heads_gin) {
         FR_HIP(hipEventRecord(m->join_ev, m->side));
         FR_HIP(hipStreamWaitEvent(s, m->join_ev, 0));
       }

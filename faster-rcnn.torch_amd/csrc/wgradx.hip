@@ -516,7 +516,6 @@ static void wgradx_plan(WgradXArgs& a) {
   a.oTiles = a.O / 64; a.cTiles = a.Cin / 64;
   const long base = (long)a.oTiles * a.cTiles, npix = (long)a.tilesX * a.tilesY;
   a.nSplit = (int)std::max<long>(1, std::min<long>(npix, 256 / base));   // one block per CU, one round: <= 256 blocks
-  if (const char* e = getenv("FRCNN_WGX_NSPLIT")) a.nSplit = (int)std::max<long>(1, std::min<long>(npix, atoi(e)));
 }
 
 size_t conv_wgradx_workspace_bytes(int Cin, int H, int W, int O, int pad) {
@@ -526,10 +525,8 @@ size_t conv_wgradx_workspace_bytes(int Cin, int H, int W, int O, int pad) {
   return (size_t)a.nSplit * 9 * O * Cin * 4 + 256;
 }
 
-static const WgradMap* g_wx_map = nullptr;   // (the map of the call being launched: host-side, single-threaded launch path)
-
 template <bool SLOPE, bool SCALE, int VEC, int NP = 3>
-static int launch_wgradx_v(WgradXArgs& a, double flops, float* gw, hipStream_t s) {
+static int launch_wgradx_v(WgradXArgs& a, double flops, float* gw, const WgradMap* map, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
     FR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgradx_kernel<SLOPE, SCALE, VEC, NP>),
@@ -541,7 +538,7 @@ static int launch_wgradx_v(WgradXArgs& a, double flops, float* gw, hipStream_t s
   if (prof_enabled(KC_CONV_WGRADX)) prof_before(KC_CONV_WGRADX, s);
   const size_t lds = 2 * (size_t)NP * (WX_GPLANE + WX_XPLANE);   // two images (> 80 KB: one block per CU)
   hipLaunchKernelGGL((conv_wgradx_kernel<SLOPE, SCALE, VEC, NP>), dim3(grid), dim3(256), lds, s, a);
-  if (g_wx_map) FR_TRY(wgrad_reduce_map(a.slab, a.nSplit, 9, a.O, a.Cin, gw, *g_wx_map, s));
+  if (map) FR_TRY(wgrad_reduce_map(a.slab, a.nSplit, 9, a.O, a.Cin, gw, *map, s));
   else FR_TRY(wgrad_reduce(a.slab, a.nSplit, 9, a.O * a.Cin, gw, s));
   if (prof_enabled(KC_CONV_WGRADX)) prof_after(KC_CONV_WGRADX, flops, bytes, s);
   FR_LAUNCH_CHECK();
@@ -559,14 +556,14 @@ static bool readable_past_end(const void* p, size_t bytes, size_t slack) {
 }
 
 template <bool SLOPE, bool SCALE, int NP = 3>
-static int launch_wgradx(WgradXArgs& a, double flops, float* gw, hipStream_t s) {
+static int launch_wgradx(WgradXArgs& a, double flops, float* gw, const WgradMap* map, hipStream_t s) {
   // one aligned 16-byte load per 4-pixel segment when every segment lies inside a row or outside the image as a whole; one
   // unaligned one when the width is arbitrary and the 12 bytes behind both tensors belong to their allocations
   if (a.pad == 1 && a.W % 4 == 0 && ((uintptr_t)a.in & 15) == 0 && ((uintptr_t)a.g & 15) == 0)
-    return launch_wgradx_v<SLOPE, SCALE, 1, NP>(a, flops, gw, s);
+    return launch_wgradx_v<SLOPE, SCALE, 1, NP>(a, flops, gw, map, s);
   if (a.pad == 1 && readable_past_end(a.in, (size_t)a.Cin * a.H * a.W * 4, 12) && readable_past_end(a.g, (size_t)a.O * a.Ho * a.Wo * 4, 12))
-    return launch_wgradx_v<SLOPE, SCALE, 2, NP>(a, flops, gw, s);
-  return launch_wgradx_v<SLOPE, SCALE, 0, NP>(a, flops, gw, s);
+    return launch_wgradx_v<SLOPE, SCALE, 2, NP>(a, flops, gw, map, s);
+  return launch_wgradx_v<SLOPE, SCALE, 0, NP>(a, flops, gw, map, s);
 }
 
 int conv_wgradx(const float* in, int Cin, int H, int W, const float* in_slope, const float* in_scale, const float* g, int O,
@@ -576,7 +573,7 @@ int conv_wgradx(const float* in, int Cin, int H, int W, const float* in_slope, c
   a.in = in; a.in_slope = in_slope; a.in_scale = in_scale; a.g = g; a.gbias = gbias;
   a.amax_in = amax_in; a.amax_g = amax_g;
   a.omap = map ? map->omap : nullptr;
-  struct MapScope { MapScope(const WgradMap* m) { g_wx_map = (m && (m->omap || m->cmap)) ? m : nullptr; } ~MapScope() { g_wx_map = nullptr; } } scope(map);
+  if (map && !map->omap && !map->cmap) map = nullptr;   // (an empty map: the plain fold)
   FR_CHECK((amax_in != nullptr) == (amax_g != nullptr), "conv_wgradx: the fp16 form needs the magnitude records of both tensors");
   a.Cin = Cin; a.H = H; a.W = W; a.O = O; a.pad = pad; a.Ho = H + 2 * pad - 2; a.Wo = W + 2 * pad - 2;
   FR_CHECK(Cin % 64 == 0 && O % 64 == 0, "conv_wgradx: %d channels x %d filters is not a split-bf16 shape", Cin, O);
@@ -587,11 +584,11 @@ int conv_wgradx(const float* in, int Cin, int H, int W, const float* in_slope, c
   a.slab = (float*)(((uintptr_t)ws + 255) / 256 * 256);
   const double flops = 2.0 * O * Cin * 9 * (double)a.Ho * a.Wo;
   if (amax_in) {
-    if (in_slope) return in_scale ? launch_wgradx<true, true, 2>(a, flops, gw, s) : launch_wgradx<true, false, 2>(a, flops, gw, s);
-    return in_scale ? launch_wgradx<false, true, 2>(a, flops, gw, s) : launch_wgradx<false, false, 2>(a, flops, gw, s);
+    if (in_slope) return in_scale ? launch_wgradx<true, true, 2>(a, flops, gw, map, s) : launch_wgradx<true, false, 2>(a, flops, gw, map, s);
+    return in_scale ? launch_wgradx<false, true, 2>(a, flops, gw, map, s) : launch_wgradx<false, false, 2>(a, flops, gw, map, s);
   }
-  if (in_slope) return in_scale ? launch_wgradx<true, true>(a, flops, gw, s) : launch_wgradx<true, false>(a, flops, gw, s);
-  return in_scale ? launch_wgradx<false, true>(a, flops, gw, s) : launch_wgradx<false, false>(a, flops, gw, s);
+  if (in_slope) return in_scale ? launch_wgradx<true, true>(a, flops, gw, map, s) : launch_wgradx<true, false>(a, flops, gw, map, s);
+  return in_scale ? launch_wgradx<false, true>(a, flops, gw, map, s) : launch_wgradx<false, false>(a, flops, gw, map, s);
 }
 
 }  // namespace frcnn
