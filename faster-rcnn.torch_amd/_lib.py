@@ -80,6 +80,12 @@ _SIGS = {
     "frcnn_scale_rmsprop": ([vp, vp, C.c_float, vp, C.c_longlong, C.c_float, C.c_float, C.c_float, vp], C.c_int),
     "frcnn_scale_rmsprop_dev": ([vp, vp, vp, vp, C.c_longlong, C.c_float, C.c_float, C.c_float, vp], C.c_int),
     "frcnn_scale_rmsprop_slice": ([vp, vp, C.c_float, vp, C.c_longlong, C.c_longlong, C.c_float, C.c_float, C.c_float, vp], C.c_int),
+    "frcnn_sgd": ([vp, vp, vp, C.c_longlong, C.c_float, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, vp], C.c_int),
+    "frcnn_sgd_slice": ([vp, vp, vp, C.c_longlong, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                         vp], C.c_int),
+    "frcnn_nag": ([vp, vp, vp, C.c_longlong, C.c_float, vp, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
+    "frcnn_nag_slice": ([vp, vp, vp, C.c_longlong, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
+    "frcnn_nag_lookahead": ([vp, vp, C.c_longlong, C.c_float, vp], C.c_int),
     "frcnn_model_update_stream": ([vp, C.POINTER(vp)], C.c_int),
     "frcnn_model_update_fork": ([vp, vp], C.c_int),
     "frcnn_model_update_join": ([vp, vp], C.c_int),

@@ -442,6 +442,29 @@ int frcnn_scale_rmsprop_dev(float* x, float* g, const double* gcount_dev, float*
   return rmsprop_step(x, g, m, n, lr, alpha, eps, 1.f, true, S(stream), gcount_dev);
 }
 
+// optim.sgd / optim.nag (main.lua:122-124,134-135)
+int frcnn_sgd(float* x, float* g, float* v, long long n, float gscale, const double* gcount_dev, float clr, float wd, float mom,
+              float one_minus_damp, int nesterov, int first, void* stream) {
+  FR_CHECK(n >= 0, "frcnn_sgd: bad length %lld", n);
+  return sgd_update(x, g, v, 0, n, false, gscale, gcount_dev, clr, wd, mom, one_minus_damp, nesterov != 0, first != 0, S(stream));
+}
+int frcnn_sgd_slice(float* x, float* g, float* v, long long lo, long long hi, float gscale, float clr, float wd, float mom,
+                    float one_minus_damp, int nesterov, int first, void* stream) {
+  return sgd_update(x, g, v, lo, hi, true, gscale, nullptr, clr, wd, mom, one_minus_damp, nesterov != 0, first != 0, S(stream));
+}
+int frcnn_nag(float* x, float* g, float* v, long long n, float gscale, const double* gcount_dev, float clr, float wd, float mom,
+              int first, void* stream) {
+  FR_CHECK(n >= 0, "frcnn_nag: bad length %lld", n);
+  return nag_update(x, g, v, 0, n, false, gscale, gcount_dev, clr, wd, mom, first != 0, S(stream));
+}
+int frcnn_nag_slice(float* x, float* g, float* v, long long lo, long long hi, float gscale, float clr, float wd, float mom,
+                    int first, void* stream) {
+  return nag_update(x, g, v, lo, hi, true, gscale, nullptr, clr, wd, mom, first != 0, S(stream));
+}
+int frcnn_nag_lookahead(float* x, const float* v, long long n, float mom, void* stream) {
+  return nag_lookahead(x, v, n, mom, S(stream));
+}
+
 int frcnn_cnet_losses(float* crout, const float* crtarget, const float* ccout, const float* cctarget, int R,
                       int npos, int ncls, float* crdelta, float* ccdelta, double* loss2, void* stream) {
   return cnet_losses(crout, crtarget, ccout, cctarget, R, npos, ncls, crdelta, ccdelta, loss2, S(stream));

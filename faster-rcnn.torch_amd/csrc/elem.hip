@@ -1,7 +1,7 @@
 // elem.hip -- bandwidth-bound pieces of the proposal network and the optimiser:
 //   nn.PReLU / nn.SpatialDropout / nn.SpatialMaxPooling(2,2,2,2):ceil() forward+backward
 //   (models/model_utilities.lua:9-12,23), bias/slope gradient reductions, flat-buffer ops
-//   (objective.lua:49,200) and optim.rmsprop (main.lua:133).
+//   (objective.lua:49,200) and optim.rmsprop / optim.sgd / optim.nag (main.lua:122-124,133-135).
 // No MFMA here: these are gather / argmax / streaming kernels; the design rule is coalesced
 // 16-byte accesses where the layout allows and one wave-level reduction + one atomic per block.
 #include <algorithm>
@@ -677,6 +677,205 @@ int rmsprop_step(float* x, float* g, float* m, long n, float lr, float alpha, fl
     FR_LAUNCH(KC_OPTIM, 0, n * 24.0, s, rmsprop_kernel<true>, dim3(grid), dim3(256), 0, x, g, m, n, lr, alpha, eps, gscale, gcount_dev);
   else
     FR_LAUNCH(KC_OPTIM, 0, n * 20.0, s, rmsprop_kernel<false>, dim3(grid), dim3(256), 0, x, g, m, n, lr, alpha, eps, 1.f, (const double*)nullptr);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// ---------------------------------------------------------------- optim.sgd / optim.nag
+// The two optimisers main.lua:122-124,134-135 keeps one comment away from optim.rmsprop, one element of each as one inline
+// function shared by the whole-vector kernel and the slice kernel (the same bit-for-bit contract as rmsprop_one), every Lua
+// statement one separately rounded fp32 operation.  x = weights, g = the gradient the objective returned, v = state.dfdx.
+// The variants are template parameters, not per-element branches; the gradient is written back only where Torch leaves
+// something else in it than it was handed (the scale of gradient:div, weight decay, Nesterov's look-ahead term).
+//
+// optim.sgd:  g *= gscale ; g += wd*x ; v = g (first step) | v = v*mom + (1-damp)*g ; g += mom*v (nesterov) ; x += -clr*dir
+// MOM: 0 = no momentum (v untouched, may be NULL), 1 = the first step (v = copy(g)), 2 = later steps
+template <bool SCALE, bool WD, int MOM, bool NEST>
+struct SgdOp {
+  static constexpr bool kScale = SCALE, kReadV = MOM == 2, kWriteV = MOM != 0, kWriteG = SCALE || WD || NEST;
+  static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV;   // fp32 streams moved per element
+  float gscale, clr, wd, mom, omd;   // omd = 1 - dampening
+  __device__ __forceinline__ void operator()(float& x, float& g, float& v) const {
+#pragma clang fp contract(off)   // every operation rounded by itself: the same bits from every kernel that calls this
+    if (SCALE) g *= gscale;                      // gradient:div(n) (objective.lua:200)
+    if (WD) g = g + wd * x;                      // dfdx:add(wd, x)
+    float d = g;
+    if (MOM == 1) v = g;                         // state.dfdx = torch.Tensor():typeAs(dfdx):resizeAs(dfdx):copy(dfdx)
+    if (MOM == 2) v = v * mom + omd * g;         // state.dfdx:mul(mom):add(1-damp, dfdx)
+    if (MOM != 0) {
+      if (NEST) { g = g + mom * v; d = g; }      // dfdx:add(mom, state.dfdx)
+      else d = v;                                // dfdx = state.dfdx
+    }
+    x = x + (-clr) * d;                          // x:add(-clr, dfdx)
+  }
+};
+
+// optim.nag (after its look-ahead x += mom*v, nag_lookahead below):  g *= gscale ; g += wd*x ; v = 0 (first step) | v = v*mom ;
+// v += -clr*g ; x += v.  The first step adds to a literal 0 (0 + -0 = +0, as fill(0):add(-clr, dfdx) leaves it).
+template <bool SCALE, bool WD, bool FIRST>
+struct NagOp {
+  static constexpr bool kScale = SCALE, kReadV = !FIRST, kWriteV = true, kWriteG = SCALE || WD;
+  static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV;
+  float gscale, clr, wd, mom;
+  __device__ __forceinline__ void operator()(float& x, float& g, float& v) const {
+#pragma clang fp contract(off)
+    if (SCALE) g *= gscale;                      // gradient:div(n) (objective.lua:200)
+    if (WD) g = g + wd * x;                      // dfdx:add(wd, x)
+    const float u = (-clr) * g;
+    v = (FIRST ? 0.0f : v * mom) + u;            // state.dfdx:fill(0) | :mul(mom), then :add(-clr, dfdx)
+    x = x + v;                                   // x:add(state.dfdx)
+  }
+};
+
+template <class Op>
+__device__ __forceinline__ void optim_four(float4* x4, float4* g4, float4* v4, long i, const Op& op) {
+  float4 xv = x4[i], gv = g4[i], vv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (Op::kReadV) vv = v4[i];
+  op(xv.x, gv.x, vv.x);
+  op(xv.y, gv.y, vv.y);
+  op(xv.z, gv.z, vv.z);
+  op(xv.w, gv.w, vv.w);
+  if (Op::kWriteG) g4[i] = gv;
+  if (Op::kWriteV) v4[i] = vv;
+  x4[i] = xv;
+}
+template <class Op>
+__device__ __forceinline__ void optim_scalar(float* x, float* g, float* v, long i, const Op& op) {
+  float xi = x[i], gi = g[i], vi = 0.f;
+  if (Op::kReadV) vi = v[i];
+  op(xi, gi, vi);
+  if (Op::kWriteG) g[i] = gi;
+  if (Op::kWriteV) v[i] = vi;
+  x[i] = xi;
+}
+
+// the whole vector: 16-byte groups grid-stride, then the up to three tail elements; gcount as in rmsprop_kernel
+template <class Op>
+__global__ void optim_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long n, Op op,
+                             const double* __restrict__ gcount) {
+  if (Op::kScale && gcount) { const double c = *gcount; op.gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }
+  const long n4 = n >> 2;
+  float4* x4 = reinterpret_cast<float4*>(x);
+  float4* g4 = reinterpret_cast<float4*>(g);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+    optim_four(x4, g4, v4, i, op);
+  for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    optim_scalar(x, g, v, i, op);
+}
+
+// elements [lo, hi): the split of rmsprop_slice_kernel (whole 16-byte groups grid-stride, ragged ends by block 0)
+template <class Op>
+__global__ void optim_slice_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long lo, long hi, Op op) {
+  const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);
+  const long n4 = (b - a) >> 2;
+  float4* x4 = reinterpret_cast<float4*>(x + a);
+  float4* g4 = reinterpret_cast<float4*>(g + a);
+  float4* v4 = reinterpret_cast<float4*>(Op::kReadV || Op::kWriteV ? v + a : v);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+    optim_four(x4, g4, v4, i, op);
+  if (blockIdx.x == 0 && threadIdx.x < 8) {
+    const int t = threadIdx.x;
+    const long i = t < 4 ? lo + t : b + (t - 4);
+    if (t < 4 ? i < a : i < hi) optim_scalar(x, g, v, i, op);
+  }
+}
+
+namespace {
+struct OptimRange {
+  float* x; float* g; float* v;
+  long lo, hi;
+  bool slice;             // slice kernel (grid capped: it runs beside the backward pass) or the whole vector [0, hi)
+  const double* gcount;   // whole vector only: the divisor on the device
+  hipStream_t s;
+};
+
+template <class Op>
+int optim_launch(const Op& op, const OptimRange& r) {
+  const long n = r.hi - r.lo;
+  if (n == 0) return FRCNN_OK;
+  const double bytes = 4.0 * Op::kStreams * n;
+  if (r.slice) {
+    int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 1024);   // half the wave slots, as rmsprop_slice
+    FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_slice_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op);
+  } else {
+    int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 2048);
+    FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, n, op, r.gcount);
+  }
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+template <bool SCALE, bool WD, int MOM, bool NEST>
+int sgd_go(const OptimRange& r, float gscale, float clr, float wd, float mom, float omd) {
+  return optim_launch(SgdOp<SCALE, WD, MOM, NEST>{gscale, clr, wd, mom, omd}, r);
+}
+template <bool SCALE, bool WD>
+int sgd_mom(const OptimRange& r, float gscale, float clr, float wd, float mom, float omd, bool nesterov, bool first) {
+  if (mom == 0.f) return sgd_go<SCALE, WD, 0, false>(r, gscale, clr, wd, mom, omd);
+  if (first)
+    return nesterov ? sgd_go<SCALE, WD, 1, true>(r, gscale, clr, wd, mom, omd) : sgd_go<SCALE, WD, 1, false>(r, gscale, clr, wd, mom, omd);
+  return nesterov ? sgd_go<SCALE, WD, 2, true>(r, gscale, clr, wd, mom, omd) : sgd_go<SCALE, WD, 2, false>(r, gscale, clr, wd, mom, omd);
+}
+template <bool SCALE, bool WD>
+int nag_go(const OptimRange& r, float gscale, float clr, float wd, float mom, bool first) {
+  return first ? optim_launch(NagOp<SCALE, WD, true>{gscale, clr, wd, mom}, r)
+               : optim_launch(NagOp<SCALE, WD, false>{gscale, clr, wd, mom}, r);
+}
+
+int optim_check(const char* what, const OptimRange& r, bool uses_v) {
+  FR_CHECK(r.x && r.g && (r.v || !uses_v), "%s: NULL vector", what);
+  FR_CHECK((((uintptr_t)r.x | (uintptr_t)r.g | (uintptr_t)r.v) & 15) == 0, "%s: the vectors must be 16-byte aligned", what);
+  FR_CHECK(r.lo >= 0 && r.lo <= r.hi, "%s: bad range [%ld, %ld)", what, r.lo, r.hi);
+  return FRCNN_OK;
+}
+}  // namespace
+
+int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
+               float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s) {
+  const OptimRange r{x, g, mom != 0.f ? v : nullptr, lo, hi, slice, slice ? nullptr : gcount_dev, s};
+  FR_TRY(optim_check("sgd", r, mom != 0.f));
+  FR_CHECK(!nesterov || (mom > 0.f && one_minus_damp == 1.f), "sgd: Nesterov momentum requires a momentum and zero dampening");
+  const bool scale = r.gcount || gscale != 1.f;
+  if (scale)
+    return wd != 0.f ? sgd_mom<true, true>(r, gscale, clr, wd, mom, one_minus_damp, nesterov, first)
+                     : sgd_mom<true, false>(r, gscale, clr, wd, mom, one_minus_damp, nesterov, first);
+  return wd != 0.f ? sgd_mom<false, true>(r, 1.f, clr, wd, mom, one_minus_damp, nesterov, first)
+                   : sgd_mom<false, false>(r, 1.f, clr, wd, mom, one_minus_damp, nesterov, first);
+}
+
+int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
+               float wd, float mom, bool first, hipStream_t s) {
+  const OptimRange r{x, g, v, lo, hi, slice, slice ? nullptr : gcount_dev, s};
+  FR_TRY(optim_check("nag", r, true));
+  FR_CHECK(mom > 0.f, "nag: momentum must be positive for Nesterov Accelerated Gradient");
+  const bool scale = r.gcount || gscale != 1.f;
+  if (scale) return wd != 0.f ? nag_go<true, true>(r, gscale, clr, wd, mom, first) : nag_go<true, false>(r, gscale, clr, wd, mom, first);
+  return wd != 0.f ? nag_go<false, true>(r, 1.f, clr, wd, mom, first) : nag_go<false, false>(r, 1.f, clr, wd, mom, first);
+}
+
+// optim.nag's look-ahead before opfunc: x:add(mom, state.dfdx).  3 streams.
+__global__ void nag_lookahead_kernel(float* __restrict__ x, const float* __restrict__ v, long n, float mom) {
+#pragma clang fp contract(off)
+  const long n4 = n >> 2;
+  float4* x4 = reinterpret_cast<float4*>(x);
+  const float4* v4 = reinterpret_cast<const float4*>(v);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    float4 xv = x4[i];
+    const float4 vv = v4[i];
+    xv.x = xv.x + mom * vv.x; xv.y = xv.y + mom * vv.y; xv.z = xv.z + mom * vv.z; xv.w = xv.w + mom * vv.w;
+    x4[i] = xv;
+  }
+  for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    x[i] = x[i] + mom * v[i];
+}
+int nag_lookahead(float* x, const float* v, long n, float mom, hipStream_t s) {
+  FR_CHECK(x && v, "nag_lookahead: NULL vector");
+  FR_CHECK((((uintptr_t)x | (uintptr_t)v) & 15) == 0, "nag_lookahead: the vectors must be 16-byte aligned");
+  FR_CHECK(n >= 0, "nag_lookahead: bad length %ld", n);
+  if (n == 0) return FRCNN_OK;
+  int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 2048);
+  FR_LAUNCH(KC_OPTIM, 0, n * 12.0, s, nag_lookahead_kernel, dim3(grid), dim3(256), 0, x, v, n, mom);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }

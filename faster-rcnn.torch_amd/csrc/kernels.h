@@ -158,6 +158,13 @@ int rmsprop_step(float* x, float* g, float* m, long n, float lr, float alpha, fl
 // leaves in those elements
 int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, float alpha, float eps, float gscale, bool scale_first,
                   hipStream_t s);
+// optim.sgd / optim.nag (main.lua:122-124,134-135) on elements [lo, hi) (slice: the slice kernel, any bounds) or on the whole
+// vector [0, hi) (lo = 0; gcount_dev: the divisor of gradient:div read on the device).  gscale = 1 and no gcount_dev: g unscaled.
+int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
+               float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s);
+int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
+               float wd, float mom, bool first, hipStream_t s);
+int nag_lookahead(float* x, const float* v, long n, float mom, hipStream_t s);
 
 // ---------------------------------------------------------------- anchor nets, sampled positions only (heads.hip)
 #define FRCNN_HEAD_OUT 18   // 3 * (2 + 4) planes of an anchor net's 1 x 1 convolution (model_utilities.lua:33)

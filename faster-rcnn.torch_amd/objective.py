@@ -109,7 +109,7 @@ class _PinnedRing(object):
 
 class DeviceDivisor(object):
     """gradient:div(n) (objective.lua:200) with n on the device: the address of an fp64 count (plus what keeps it alive).
-    utilities.rmsprop hands it to frcnn_scale_rmsprop_dev."""
+    The optimisers of utilities hand it to frcnn_scale_rmsprop_dev / frcnn_sgd / frcnn_nag."""
 
     def __init__(self, p, owner):
         self.ptr = int(p)
@@ -316,7 +316,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         pending = []
         early_copy = False
         # The update beside the backward pass (include/frcnn_hip.h): single process, one image per step, the side streams on.
-        # eager = {m, lr, alpha, eps} from utilities.rmsprop; eager["done"] collects the slices updated on the update stream.
+        # eager = {update} from the optimiser (utilities.rmsprop / sgd / nag): update(weights, gradient, lo, hi, gscale, stream)
+        # queues its step on elements [lo, hi); eager["done"] collects the slices updated on the update stream.
         if eager is not None:
             side = C.c_int(0)
             _lib.call("frcnn_get_option", b"side_stream", C.byref(side))
@@ -339,8 +340,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             nblk = int(native.desc.nblocks)
 
             def eager_slice(lo, hi, on, group=None):
-                _lib.call("frcnn_scale_rmsprop_slice", ptr(weights), ptr(gradient), eager["gscale"], ptr(eager["m"]), lo, hi,
-                          eager["lr"], eager["alpha"], eager["eps"], on)
+                eager["update"](weights, gradient, lo, hi, eager["gscale"], on)
                 eager["done"].append((int(lo), int(hi)))
                 if group is not None:
                     _lib.call("frcnn_pnet_refresh_packs", native.h, ptr(weights), group, on)
@@ -581,13 +581,14 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     def lossAndGradient(w):
         return run(w, False)()
 
-    # private protocol with utilities.rmsprop: begin(w) queues the pass and returns (finish, gradient); the
+    # private protocol with the optimisers of utilities: begin(w) queues the pass and returns (finish, gradient); the
     # optimiser queues its update and only then calls finish() for the loss (no device idle during the read-back)
     lossAndGradient.begin = lambda w: (run(w, True), gradient)
     # begin_fold(w) -> (finish, gradient, gscale): gradient:div(cls_count) (:200) is left to the caller, who folds it
-    # into the first pass of its update (frcnn_scale_rmsprop); gscale is None when there is nothing to scale
+    # into the first pass of its update (frcnn_scale_rmsprop, frcnn_sgd, frcnn_nag); gscale is None when there is nothing to scale
     def begin_fold(w, eager=None):
-        """eager = dict(m=, lr=, alpha=, eps=) (utilities.rmsprop): the pass may apply the optimiser's step to slices of the
+        """eager = dict(update=) (utilities.rmsprop / sgd / nag; update(weights, gradient, lo, hi, gscale, stream) queues the
+        optimiser's step on elements [lo, hi), gscale = 1 meaning unscaled): the pass may apply that step to slices of the
         vectors as they become final (the update beside the backward pass, include/frcnn_hip.h); eager["done"] then lists the
         slices it has updated, eager["slice"](lo, hi, stream, group) updates another one, eager["groups"] the pack groups
         already renewed, and the caller finishes with eager["complete"]()."""

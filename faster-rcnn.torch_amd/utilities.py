@@ -1,5 +1,5 @@
-"""combine_and_flatten_parameters (utilities.lua:136-147) and the optimiser step of
-main.lua:122,133 (optim.rmsprop).  The flat weight / gradient vectors are torch CUDA tensors so that
+"""combine_and_flatten_parameters (utilities.lua:136-147) and the optimiser steps of
+main.lua:122-124,133-135 (optim.rmsprop, optim.sgd, optim.nag).  The flat weight / gradient vectors are torch CUDA tensors so that
 `torch.distributed` (RCCL) can all-reduce the gradient in place."""
 import numpy as np
 
@@ -37,14 +37,12 @@ import os
 EAGER_DEFAULT = os.environ.get("FRCNN_EAGER_UPDATE", "0") == "1"
 
 
-def rmsprop(opfunc, x, state):
-    """optim.rmsprop(opfunc, x, state) [ext]: state.learningRate (1e-2), state.alpha (0.99),
-    state.epsilon (1e-8); m = alpha*m + (1-alpha)*g^2 ; x -= lr * g / (sqrt(m) + eps).
-    Returns x, [f(x)] like the Lua function (main.lua:133)."""
-    import torch
-    lr = state.get("learningRate", 1e-2); alpha = state.get("alpha", 0.99); eps = state.get("epsilon", 1e-8)
-    if "m" not in state:
-        state["m"] = torch.zeros_like(x)
+def _step(opfunc, x, state, whole, update):
+    """One optimiser step around opfunc (main.lua:133-135), the update queued by the optimiser:
+    whole(dfdx, gscale) updates the whole vector, gscale None (nothing to scale), a float (gradient:div(n), objective.lua:200,
+    folded into the update's pass) or a DeviceDivisor (data parallel: the all-reduced count, still on the device);
+    update(w, g, lo, hi, gscale, stream) is the same update on elements [lo, hi) (gscale 1: unscaled).
+    Returns x, [f(x)] like the Lua functions."""
     begin = getattr(opfunc, "begin_fold", None)
     timing = state.get("_timing")     # bench.py: seconds the host spends queueing a step / waiting for its statistics
     if timing is not None:
@@ -54,7 +52,7 @@ def rmsprop(opfunc, x, state):
         # and gradient:div(n) rides on the update's own pass over the vectors.  state["eager"] (default off: measured neutral on
         # one GPU, EXPERIMENTS.md round 6 -- the backward pass has no idle registers for the update to run in): the pass may
         # apply this very step slice by slice, beside its own backward half, as slices of the gradient become final
-        eager = dict(m=state["m"], lr=lr, alpha=alpha, eps=eps) if state.get("eager", EAGER_DEFAULT) else None
+        eager = dict(update=update) if state.get("eager", EAGER_DEFAULT) else None
         finish, dfdx, gscale = begin(x, eager) if eager is not None else begin(x)
         if eager is not None and "done" in eager:
             # what the pass has not updated (the shallowest block: its gradients end the pass; everything, for an image without
@@ -70,14 +68,8 @@ def rmsprop(opfunc, x, state):
             for lo, hi in rest:
                 eager["slice"](lo, hi, stream_ptr())
             eager["complete"]()
-        elif hasattr(gscale, "ptr"):   # data parallel: the divisor is the all-reduced count, still on the device
-            _lib.call("frcnn_scale_rmsprop_dev", ptr(x), ptr(dfdx), ptr(gscale.ptr), ptr(state["m"]), x.numel(), lr, alpha,
-                      eps, stream_ptr())
-        elif gscale is None:
-            _lib.call("frcnn_rmsprop", ptr(x), ptr(dfdx), ptr(state["m"]), x.numel(), lr, alpha, eps, stream_ptr())
         else:
-            _lib.call("frcnn_scale_rmsprop", ptr(x), ptr(dfdx), gscale, ptr(state["m"]), x.numel(), lr, alpha, eps,
-                      stream_ptr())
+            whole(dfdx, gscale)
         if timing is not None:
             t_q = time.perf_counter()
         fx, _ = finish()
@@ -85,8 +77,139 @@ def rmsprop(opfunc, x, state):
             timing["enqueue"] += t_q - t_in; timing["wait"] += time.perf_counter() - t_q; timing["steps"] += 1
         return x, [fx]
     fx, dfdx = opfunc(x)
-    _lib.call("frcnn_rmsprop", ptr(x), ptr(dfdx), ptr(state["m"]), x.numel(), lr, alpha, eps, stream_ptr())
+    whole(dfdx, None)
     return x, [fx]
+
+
+def _fold_args(gscale):
+    """(gscale, gcount_dev) of frcnn_sgd / frcnn_nag for what begin_fold returned as the divisor"""
+    if hasattr(gscale, "ptr"):
+        return 1.0, ptr(gscale.ptr)
+    return (1.0 if gscale is None else gscale), None
+
+
+def rmsprop(opfunc, x, state):
+    """optim.rmsprop(opfunc, x, state) [ext]: state.learningRate (1e-2), state.alpha (0.99),
+    state.epsilon (1e-8); m = alpha*m + (1-alpha)*g^2 ; x -= lr * g / (sqrt(m) + eps).
+    Returns x, [f(x)] like the Lua function (main.lua:133)."""
+    import torch
+    lr = state.get("learningRate", 1e-2); alpha = state.get("alpha", 0.99); eps = state.get("epsilon", 1e-8)
+    if "m" not in state:
+        state["m"] = torch.zeros_like(x)
+    m = state["m"]
+
+    def whole(dfdx, gscale):
+        if hasattr(gscale, "ptr"):
+            _lib.call("frcnn_scale_rmsprop_dev", ptr(x), ptr(dfdx), ptr(gscale.ptr), ptr(m), x.numel(), lr, alpha, eps, stream_ptr())
+        elif gscale is None:
+            _lib.call("frcnn_rmsprop", ptr(x), ptr(dfdx), ptr(m), x.numel(), lr, alpha, eps, stream_ptr())
+        else:
+            _lib.call("frcnn_scale_rmsprop", ptr(x), ptr(dfdx), gscale, ptr(m), x.numel(), lr, alpha, eps, stream_ptr())
+
+    def update(w, g, lo, hi, gscale, on):
+        _lib.call("frcnn_scale_rmsprop_slice", ptr(w), ptr(g), gscale, ptr(m), lo, hi, lr, alpha, eps, on)
+    return _step(opfunc, x, state, whole, update)
+
+
+def _get(config, key, default):
+    v = config.get(key)      # (Lua: `config.key or default`)
+    return default if v is None else v
+
+
+def _no_per_parameter(config, name):
+    if config.get("learningRates") is not None or config.get("weightDecays") is not None:
+        raise ValueError("optim.%s: per-parameter learningRates / weightDecays are not supported by the device optimiser "
+                         "(give the scalar learningRate / weightDecay)" % name)
+
+
+def sgd(opfunc, x, config, state=None):
+    """optim.sgd(opfunc, x, config[, state]) [ext] (main.lua:122-124 sgd_state, :135): config.learningRate (1e-3),
+    learningRateDecay (0), weightDecay (0), momentum (0), dampening (= momentum), nesterov (false).  g += wd*x;
+    v = g on the first step, else v = v*mom + (1-damp)*g (state["dfdx"]); g += mom*v (nesterov) and x -= clr*g, else x -= clr*v;
+    clr = lr / (1 + evalCounter*lrd).  One pass of frcnn_sgd.  Returns x, [f(x)] like the Lua function."""
+    import torch
+    state = config if state is None else state
+    lr = _get(config, "learningRate", 1e-3); lrd = _get(config, "learningRateDecay", 0)
+    wd = _get(config, "weightDecay", 0); mom = _get(config, "momentum", 0)
+    damp = _get(config, "dampening", mom); nesterov = bool(_get(config, "nesterov", False))
+    _no_per_parameter(config, "sgd")
+    if nesterov and not (mom > 0 and damp == 0):
+        raise ValueError("optim.sgd: Nesterov momentum requires a momentum and zero dampening")
+    nevals = state.get("evalCounter") or 0
+    clr = lr / (1 + nevals * lrd)           # host scalars in double, as Lua computes them
+    first = mom != 0 and "dfdx" not in state
+    if first:
+        state["dfdx"] = torch.empty_like(x)   # (its contents are the kernel's: v = copy(g))
+    v = state["dfdx"] if mom != 0 else None
+    args = (wd, mom, 1 - damp, int(nesterov), int(first))
+
+    def whole(dfdx, gscale):
+        gs, gcount = _fold_args(gscale)
+        _lib.call("frcnn_sgd", ptr(x), ptr(dfdx), ptr(v), x.numel(), gs, gcount, clr, *args, stream_ptr())
+
+    def update(w, g, lo, hi, gscale, on):
+        _lib.call("frcnn_sgd_slice", ptr(w), ptr(g), ptr(v), lo, hi, gscale, clr, *args, on)
+    try:
+        r = _step(opfunc, x, state, whole, update)
+    except BaseException:
+        if first:
+            del state["dfdx"]
+        raise
+    state["evalCounter"] = nevals + 1
+    return r
+
+
+def nag(opfunc, x, config, state=None):
+    """optim.nag(opfunc, x, config[, state]) [ext] (main.lua:124 nag_state, :134): config.learningRate (1e-3),
+    learningRateDecay (0), weightDecay (0), momentum (0.9, must be > 0).  The look-ahead x += mom*v (when state["dfdx"]
+    exists) before opfunc, then g += wd*x; v = 0 on the first step, else v = v*mom; v -= clr*g; x += v.
+    clr = lr / (1 + evalCounter*lrd).  Returns x, [f(x)] like the Lua function."""
+    import torch
+    from torch.autograd.graph import increment_version
+    state = config if state is None else state
+    lr = _get(config, "learningRate", 1e-3); lrd = _get(config, "learningRateDecay", 0)
+    wd = _get(config, "weightDecay", 0); mom = _get(config, "momentum", 0.9)
+    if mom <= 0:
+        raise ValueError("optim.nag: momentum must be positive for Nesterov Accelerated Gradient")
+    _no_per_parameter(config, "nag")
+    nevals = state.get("evalCounter") or 0
+    clr = lr / (1 + nevals * lrd)
+    first = "dfdx" not in state
+    if first:
+        state["dfdx"] = torch.empty_like(x)   # (fill(0) is folded into the first update)
+    else:
+        _lib.call("frcnn_nag_lookahead", ptr(x), ptr(state["dfdx"]), x.numel(), mom, stream_ptr())
+        # torch does not see the library's write: counting it as torch's own makes create_objective withdraw a pack promise
+        # made for the weights before the look-ahead (frcnn_pnet_invalidate_packs) instead of forwarding with stale packs
+        increment_version(x)
+    v = state["dfdx"]
+    args = (wd, mom, int(first))
+
+    def whole(dfdx, gscale):
+        gs, gcount = _fold_args(gscale)
+        _lib.call("frcnn_nag", ptr(x), ptr(dfdx), ptr(v), x.numel(), gs, gcount, clr, *args, stream_ptr())
+
+    def update(w, g, lo, hi, gscale, on):
+        _lib.call("frcnn_nag_slice", ptr(w), ptr(g), ptr(v), lo, hi, gscale, clr, *args, on)
+    try:
+        r = _step(opfunc, x, state, whole, update)
+    except BaseException:
+        if first:
+            del state["dfdx"]
+        raise
+    state["evalCounter"] = nevals + 1
+    return r
+
+
+_OPTIMIZERS = dict(rmsprop=rmsprop, sgd=sgd, nag=nag)
+
+
+def optimizer(name):
+    """The optimiser function for a value of main.lua's -opti (main.lua:35): 'rmsprop' (its default), 'sgd' or 'nag'."""
+    try:
+        return _OPTIMIZERS[name]
+    except KeyError:
+        raise ValueError("unknown optimiser %r (main.lua -opti: %s)" % (name, ", ".join(sorted(_OPTIMIZERS))))
 
 
 def reverse(array):  # utilities.lua:79-87

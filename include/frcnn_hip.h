@@ -265,6 +265,34 @@ int frcnn_scale_rmsprop_dev(float *x, float *g, const double *gcount_dev, float 
 int frcnn_scale_rmsprop_slice(float *x, float *g, float gscale, float *m, long long lo, long long hi, float lr,
                               float alpha, float eps, void *stream);
 
+/* ---- optim.sgd / optim.nag (main.lua:122-124 sgd_state / nag_state, main.lua:134-135 the calls beside optim.rmsprop) ----
+ * One step of Torch's optim function on the flat vectors, every Lua statement one separately rounded fp32 operation.
+ * x = weights, g = the gradient the objective returned, v = state.dfdx (the momentum vector, n floats).  The host keeps
+ * state.evalCounter and computes clr = learningRate / (1 + evalCounter * learningRateDecay) in double.  `first`: state.dfdx
+ * did not exist before this step (the kernel then creates its contents; v need not be initialised).  gradient:div(n)
+ * (objective.lua:200) rides on the same pass as in frcnn_scale_rmsprop: g *= gscale first (gscale = 1: g unscaled), or
+ * gscale = 1 / *gcount_dev read on the device when gcount_dev is not NULL (a count of 0 leaves g unscaled).  g is left holding
+ * what Torch leaves in it.  x, g, v: 16-byte aligned.
+ *
+ * optim.sgd: g += wd*x (wd != 0); with mom != 0: v = g on the first step, else v = v*mom + one_minus_damp*g; then
+ * g += mom*v (nesterov) and x += -clr*g, or x += -clr*v; with mom == 0: x += -clr*g, and v may be NULL.  nesterov needs
+ * mom > 0 and a zero dampening (one_minus_damp == 1). */
+int frcnn_sgd(float *x, float *g, float *v, long long n, float gscale, const double *gcount_dev, float clr, float wd,
+              float mom, float one_minus_damp, int nesterov, int first, void *stream);
+/* frcnn_sgd on elements [lo, hi) of the vectors only (x, g, v = the STARTS of the flat vectors; any bounds): what the
+ * whole-vector call does to that slice, bit for bit -- the update beside the backward pass (below) for optim.sgd. */
+int frcnn_sgd_slice(float *x, float *g, float *v, long long lo, long long hi, float gscale, float clr, float wd, float mom,
+                    float one_minus_damp, int nesterov, int first, void *stream);
+/* optim.nag after its look-ahead (frcnn_nag_lookahead) and opfunc: g += wd*x (wd != 0); v = 0 on the first step, else
+ * v = v*mom; v += -clr*g; x += v.  mom > 0. */
+int frcnn_nag(float *x, float *g, float *v, long long n, float gscale, const double *gcount_dev, float clr, float wd,
+              float mom, int first, void *stream);
+int frcnn_nag_slice(float *x, float *g, float *v, long long lo, long long hi, float gscale, float clr, float wd, float mom,
+                    int first, void *stream);
+/* optim.nag's look-ahead, before opfunc is called (when state.dfdx exists): x += mom*v.  A host that holds a pack promise
+ * (frcnn_pnet_refresh_packs below) withdraws it afterwards with frcnn_pnet_invalidate_packs: the weights have changed. */
+int frcnn_nag_lookahead(float *x, const float *v, long long n, float mom, void *stream);
+
 /* ---- model runtime: models/model_utilities.lua:3-136 --------------------------------- */
 typedef struct {
   int nblocks;                      /* vgg_small.lua:5-10 `layers` */
@@ -373,6 +401,7 @@ int frcnn_pnet_wait_block_gradients(frcnn_model *, int block, void *stream);
  *     frcnn_scale_rmsprop_slice(x, g, 1/cls_count, m, lo, hi, ...)  [+ frcnn_pnet_refresh_packs(model, x, group, ...)]
  * on the UPDATE STREAM as each slice becomes final, and frcnn_model_update_join before anything reads the weights again.  The
  * result is bit-identical to frcnn_scale_rmsprop on the whole vector (same arithmetic per element, tests/test_gpu_eager.py).
+ * frcnn_sgd_slice / frcnn_nag_slice do the same for optim.sgd / optim.nag (tests/test_gpu_optim.py).
  *   frcnn_model_update_stream : the library-owned stream for this work (the one the classification net's weight gradients
  *                               run on: a slice update queued there is ordered behind them by itself).  Call it BEFORE the pass
  *                               whose slices are to be updated: from then on the passes record the events the waits below
