@@ -1349,12 +1349,14 @@ static int heads_jobs(frcnn_model* m, const float* w, float* grad, HeadJobs& g) 
     j.gbias3 = grad ? grad + a.b_off : nullptr; j.gslope = grad ? grad + a.a_off : nullptr; j.gbias1 = grad ? grad + c.b_off : nullptr;
     j.out = c.x.f(); j.delta = h.delta.f();
     j.COL = h.spCol.f(); j.HX = h.spHX.f(); j.HY = h.spHY.f(); j.OUT = h.spOut.f(); j.D = h.spD.f(); j.GH = h.spGH.f(); j.DX = h.spDX.f();
-    // K splits of HX = W COL^T: K = ckk is long, the tile grid (n / 64) x (P / 64) small -- about a thousand blocks in all
+    // K splits of HX = W COL^T: K = ckk is long, the tile grid (n / 64) x (P / 64) small -- about a thousand blocks in all.
+    // The slab holds 4096 positions' partial sums: 256 / tiles keeps splits * P under that only for n >= 256 (four tile rows), so
+    // narrower nets are capped at 4096 / P as well; rounding `per` up afterwards can only lower splits.
     const long tiles = (long)cdiv((int)n, 64) * cdiv(P, 64);
-    int splits = (int)std::max<long>(1, std::min<long>(std::min<long>((long)ckk / 256, 64), 256 / tiles));
+    int splits = (int)std::max<long>(1, std::min<long>(std::min<long>(std::min<long>((long)ckk / 256, 64), 256 / tiles), 4096 / P));
     const int per = cdiv(cdiv((int)ckk, splits), 32) * 32;
     splits = cdiv((int)ckk, per);
-    FR_TRY(h.spSlab.ensure(n * 4096 * 4));   // (splits * P <= 64 * 64 whatever P: allocated once)
+    FR_TRY(h.spSlab.ensure(n * 4096 * 4));   // (splits * P <= 4096 whatever P and n: allocated once)
     FR_CHECK((size_t)splits * P <= 4096, "heads_jobs: %d K splits of %d positions", splits, P);
     j.hx_slab = h.spSlab.f(); j.hx_splits = splits;
   }

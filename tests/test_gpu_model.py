@@ -148,24 +148,31 @@ class _OneBatch(object):
         return self.batch
 
 
-def check_loss_and_gradient(F, O, s, H, W, nimages=2, nrois=3, negatives=8, heads_lo=None):
+def check_loss_and_gradient(F, O, s, H, W, nimages=2, nrois=3, negatives=8, heads_lo=None, examples=None, pmasks=None):
     """objective.lua:45-218 on `nimages` images: losses within 1e-5 relative, gradient per SURVEY 8d.  `s`: dict with
-    cfg, model, weights, gradient, om (oracle model), w (host copy of the weights)."""
+    cfg, model, weights, gradient, om (oracle model), w (host copy of the weights).  `examples`: explicit images
+    [(img, rois, positive, negative)], cleaned lists, in place of the sampled ones; `pmasks`: explicit SpatialDropout
+    keep vectors of the proposal net in place of random ones."""
     model, cfg = s["model"], s["cfg"]
     anchors = F.Anchors(model["pnet"], cfg["scales"])
     rng_m = np.random.RandomState(3)
     mt = F.MT19937(7)
     batch, oracle_in = [], []
-    for k in range(nimages):
-        rois = F.synthetic_rois(cfg, W, H, nrois, 7, k)
-        pos, neg = F.assemble_examples(anchors, cfg, rois, W, H, mt, negatives=negatives)
-        sizes = F.output_map_sizes(model, H, W)
-        pos, neg = F.clean_examples(pos, sizes), F.clean_examples(neg, sizes)   # cleanAnchors, objective.lua:74-75
-        img = F.synthetic_image(H, W, k)
-        batch.append(dict(img=img, positive=pos, negative=neg))
-        oracle_in.append((img, rois, pos, neg))
+    if examples is not None:
+        oracle_in = list(examples)
+        batch = [dict(img=img, positive=pos, negative=neg) for img, rois, pos, neg in oracle_in]
+        nimages = len(batch)
+    else:
+        for k in range(nimages):
+            rois = F.synthetic_rois(cfg, W, H, nrois, 7, k)
+            pos, neg = F.assemble_examples(anchors, cfg, rois, W, H, mt, negatives=negatives)
+            sizes = F.output_map_sizes(model, H, W)
+            pos, neg = F.clean_examples(pos, sizes), F.clean_examples(neg, sizes)   # cleanAnchors, objective.lua:74-75
+            img = F.synthetic_image(H, W, k)
+            batch.append(dict(img=img, positive=pos, negative=neg))
+            oracle_in.append((img, rois, pos, neg))
     assert sum(len(b["positive"]) for b in batch) > 0
-    pm = _masks(rng_m, model)
+    pm = _masks(rng_m, model) if pmasks is None else pmasks
     model["pnet"].drop_masks = pm
     nat = model["native"]
     n1, n2 = [l["n"] for l in model["class_layers"]]
