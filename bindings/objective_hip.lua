@@ -55,7 +55,22 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     end
   end
 
+  -- staged training (cfg.train, read at every call; INTEGRATION.md): the settings as they stand, validated
+  local nblocks = #model.layers
+  local function stage()
+    local fb, proposal, classification = hip.train_settings(model.cfg, nblocks)
+    return fb, proposal, classification, hip.trainable_ranges(model, fb, proposal, classification)
+  end
+  -- the optim overrides (frcnn_hip.lua) update the slices published here, keyed by the weight tensor
+  local published = { ranges = function() return select(4, stage()) end }
+  hip.trainable[weights] = published
+
   local function lossAndGradient(w)
+    -- before anything is queued: a bad cfg.train raises here.  The library skips the frozen parts' work, this pass skips a
+    -- disabled stage, the optimiser updates `ranges` only
+    local frozen_blocks, proposal, classification, ranges = stage()
+    check(C.frcnn_model_set_trainable(native, frozen_blocks, proposal and 1 or 0, classification and 1 or 0))
+    published.pass = ranges
     if w ~= weights then weights:copy(w) end                            -- :46-48
     gradient:zero()                                                     -- :49
     check(C.frcnn_zero(acc.ptr, 64, nil))
@@ -146,6 +161,12 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
                                              ffi.cast('const double*', dblob + o_anchor), ffi.cast('const double*', dblob + o_roi),
                                              ffi.cast('const int*', dblob + o_class), npos, nneg, bgclass, ex_loss, crtarget,
                                              cctarget, ffi.cast('double*', acc.ptr), nil))
+        if not classification then
+          -- staged training without the detector stage: no ROI pooling, no cnet (dcls / dreg are NaN below); its dropout
+          -- stream advances as its forward would advance it
+          cnet.seed = (cnet.seed or 0) + 1
+          check(C.frcnn_pnet_anchor_loss_wait(native, nil))             -- (the accumulators are read on this stream)
+        else
         -- ---- ROI pooling of every example in one launch (:117-119, :137-139) ---------------------------------
         local cinput = hip.view(scratch('cinput', 4 * E * D).ptr, { E, D })
         local pidx = ffi.cast('int*', scratch('pidx', 4 * E * D).ptr)
@@ -160,8 +181,11 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         check(C.frcnn_cnet_losses(crout.ptr, crtarget, ccout.ptr, cctarget, E, npos, ncls, crdelta.ptr, ccdelta.ptr,
                                   ffi.cast('double*', acc.ptr) + 4, nil))               -- :170-177
         local post_roi_delta = cnet:backward(cinput, { crdelta, ccdelta })              -- :179
-        check(C.frcnn_roi_pool_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr, pidx, E,
-                                        kh, kw, nil))                                   -- :182-185
+        if frozen_blocks < nblocks then                 -- (a frozen backbone: the library left the input gradient unwritten)
+          check(C.frcnn_roi_pool_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr, pidx, E,
+                                          kh, kw, nil))                                 -- :182-185
+        end
+        end
       else
         for l = 1, nheads do check(C.frcnn_pnet_set_sparse_deltas(native, l, nil, 0)) end
       end
@@ -179,7 +203,13 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
       local counts = ffi.new('double[4]', cls_count, reg_count, creg_count, ccls_count)
       check(C.frcnn_memcpy_h2d(acc.ptr + 16, counts, 16, nil))          -- slots 2, 3 ...
       check(C.frcnn_memcpy_h2d(acc.ptr + 48, counts + 2, 16, nil))      -- ... and 6, 7 of the 8 accumulators
-      check(C.frcnn_allreduce_f32(hip.comm, gradient.ptr, gradient.n, nil))
+      if ranges then                                    -- staged training: the trainable slices only
+        for _, r in ipairs(ranges) do
+          check(C.frcnn_allreduce_f32(hip.comm, ffi.cast('float*', gradient.ptr) + r[1], r[2] - r[1], nil))
+        end
+      else
+        check(C.frcnn_allreduce_f32(hip.comm, gradient.ptr, gradient.n, nil))
+      end
       check(C.frcnn_allreduce_f64(hip.comm, ffi.cast('double*', acc.ptr), 8, nil))
     end
     check(C.frcnn_memcpy_d2h(acc_host, acc.ptr, 64, nil))
@@ -195,6 +225,7 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     local preg = reg_loss / reg_count
     local dcls = ccls_loss / ccls_count
     local dreg = creg_loss / creg_count
+    if not classification then dcls, dreg = 0 / 0, 0 / 0 end           -- (no detector stage was computed)
     print(string.format('prop: cls: %f (%d), reg: %f (%d); det: cls: %f, reg: %f',
       pcls, cls_count, preg, reg_count, dcls, dreg))                    -- :207-209
     table.insert(stats.pcls, pcls)                                      -- :211-214

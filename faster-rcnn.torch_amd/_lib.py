@@ -86,6 +86,7 @@ _SIGS = {
     "frcnn_nag": ([vp, vp, vp, C.c_longlong, C.c_float, vp, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
     "frcnn_nag_slice": ([vp, vp, vp, C.c_longlong, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
     "frcnn_nag_lookahead": ([vp, vp, C.c_longlong, C.c_float, vp], C.c_int),
+    "frcnn_nag_lookahead_slice": ([vp, vp, C.c_longlong, C.c_longlong, C.c_float, vp], C.c_int),
     "frcnn_model_update_stream": ([vp, C.POINTER(vp)], C.c_int),
     "frcnn_model_update_fork": ([vp, vp], C.c_int),
     "frcnn_model_update_join": ([vp, vp], C.c_int),
@@ -99,6 +100,8 @@ _SIGS = {
     "frcnn_model_param_count": ([vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], C.c_int),
     "frcnn_model_param_table": ([vp, vp, C.c_int, C.POINTER(C.c_int)], C.c_int),
     "frcnn_model_localizer_layers": ([vp, C.c_int, vp, C.c_int, C.POINTER(C.c_int)], C.c_int),
+    "frcnn_model_set_trainable": ([vp, C.c_int, C.c_int, C.c_int], C.c_int),
+    "frcnn_model_get_trainable": ([vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
     "frcnn_model_debug_buffer": ([vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong)], C.c_int),
     "frcnn_pnet_forward": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_ulonglong, vp], C.c_int),
     "frcnn_pnet_forward_async_heads": ([vp, vp, vp, C.c_int, C.c_int, vp, C.c_ulonglong, vp], C.c_int),

@@ -464,6 +464,9 @@ int frcnn_nag_slice(float* x, float* g, float* v, long long lo, long long hi, fl
 int frcnn_nag_lookahead(float* x, const float* v, long long n, float mom, void* stream) {
   return nag_lookahead(x, v, n, mom, S(stream));
 }
+int frcnn_nag_lookahead_slice(float* x, const float* v, long long lo, long long hi, float mom, void* stream) {
+  return nag_lookahead_slice(x, v, lo, hi, mom, S(stream));
+}
 
 int frcnn_cnet_losses(float* crout, const float* crtarget, const float* ccout, const float* cctarget, int R,
                       int npos, int ncls, float* crdelta, float* ccdelta, double* loss2, void* stream) {

@@ -880,4 +880,21 @@ int nag_lookahead(float* x, const float* v, long n, float mom, hipStream_t s) {
   return FRCNN_OK;
 }
 
+// the look-ahead on elements [lo, hi) only (staged training: a frozen slice keeps its weights); the same statement per element
+__global__ void nag_lookahead_slice_kernel(float* __restrict__ x, const float* __restrict__ v, long lo, long hi, float mom) {
+#pragma clang fp contract(off)
+  for (long i = lo + (long)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (long)gridDim.x * blockDim.x)
+    x[i] = x[i] + mom * v[i];
+}
+int nag_lookahead_slice(float* x, const float* v, long lo, long hi, float mom, hipStream_t s) {
+  FR_CHECK(x && v, "nag_lookahead_slice: NULL vector");
+  FR_CHECK(lo >= 0 && lo <= hi, "nag_lookahead_slice: bad range [%ld, %ld)", lo, hi);
+  const long n = hi - lo;
+  if (n == 0) return FRCNN_OK;
+  int grid = (int)std::min<long>(std::max<long>(1, cdivl(n, 256)), 2048);
+  FR_LAUNCH(KC_OPTIM, 0, n * 12.0, s, nag_lookahead_slice_kernel, dim3(grid), dim3(256), 0, x, v, lo, hi, mom);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
 }  // namespace frcnn

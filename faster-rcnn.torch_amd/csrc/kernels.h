@@ -165,6 +165,7 @@ int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float
 int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, bool first, hipStream_t s);
 int nag_lookahead(float* x, const float* v, long n, float mom, hipStream_t s);
+int nag_lookahead_slice(float* x, const float* v, long lo, long hi, float mom, hipStream_t s);
 
 // ---------------------------------------------------------------- anchor nets, sampled positions only (heads.hip)
 #define FRCNN_HEAD_OUT 18   // 3 * (2 + 4) planes of an anchor net's 1 x 1 convolution (model_utilities.lua:33)

@@ -213,6 +213,10 @@ struct frcnn_model {
   DevBuf wg_ws;                // split-K slab workspace of the weight-gradient kernels
   DevBuf wg_ws_first;          // ... of the first layer's, which runs on the caller's stream beside the side stream's last launches
   DevBuf img;                  // copy of the input image (needed by the first conv's accGradParameters)
+  // staged training (frcnn_model_set_trainable): backbone blocks 0..frozen_blocks-1, the anchor nets (train_heads = 0) and the
+  // classification net (train_cnet = 0) are held fixed -- the training entry points queue no launch that only serves them
+  int frozen_blocks = 0;
+  int train_heads = 1, train_cnet = 1;
   // cnet state
   int R = 0, D = 0;
   const float* cnet_x = nullptr;
@@ -640,6 +644,24 @@ int frcnn_model_param_table(const frcnn_model* m, long long* table, int cap, int
   *n = (int)m->table.size();
   for (int i = 0; i < *n && i < cap; ++i)
     for (int j = 0; j < 4; ++j) table[4 * i + j] = m->table[i][j];
+  return FRCNN_OK;
+}
+
+int frcnn_model_set_trainable(frcnn_model* m, int frozen_blocks, int heads, int cnet) {
+  const int nb = (int)m->blocks.size();
+  FR_CHECK(frozen_blocks >= 0 && frozen_blocks <= nb, "model_set_trainable: frozen_blocks %d outside 0..%d", frozen_blocks, nb);
+  // (with a stage on, something is trainable: its own net)
+  FR_CHECK(heads || cnet, "model_set_trainable: both stages are off (no loss is back-propagated, no parameter to train)");
+  m->frozen_blocks = frozen_blocks;
+  m->train_heads = heads != 0;
+  m->train_cnet = cnet != 0;
+  return FRCNN_OK;
+}
+
+int frcnn_model_get_trainable(const frcnn_model* m, int* frozen_blocks, int* heads, int* cnet) {
+  if (frozen_blocks) *frozen_blocks = m->frozen_blocks;
+  if (heads) *heads = m->train_heads;
+  if (cnet) *cnet = m->train_cnet;
   return FRCNN_OK;
 }
 
@@ -1209,6 +1231,10 @@ int frcnn_pnet_zero_deltas(frcnn_model* m, void* stream) {
 // buffer (nngraph fan-out; atomic adds -- several anchor nets feed the same map).  Runs on stream s with split-K workspace
 // slot ws_slot.  *dense is set when the dense fallback was taken (no usable sparse hint).
 static bool head_is_sparse(const Head& h) { return h.sp_count >= 0 && h.sp_count <= SPARSE_MAX_POS; }
+// staged training: the anchor net's contribution to its input map's gradient is needed only while that block is trained
+static bool head_needs_gin(const frcnn_model* m, const Head& h) { return h.input >= m->frozen_blocks; }
+// ... and the pooled maps' gradient buffers (which the anchor nets add into) only while some block is
+static bool backbone_trained(const frcnn_model* m) { return m->frozen_blocks < (int)m->blocks.size(); }
 
 static int backward_head(frcnn_model* m, Head& h, const float* w, float* grad, hipStream_t s, int ws_slot) {
   Block& in = m->blocks[h.input];
@@ -1234,9 +1260,11 @@ static int backward_head(frcnn_model* m, Head& h, const float* w, float* grad, h
     // GH[n][P] = W1^T[n][18] * D[18][P], then PReLU backward (+ bias / slope gradients of the k x k conv)
     FR_TRY(gemm_f32(w + c.w_off, 1, n, D, P, 1, GH, P, n, P, HEAD_OUT, OUT_STORE, nullptr, s, ws_slot));
     FR_TRY(act_backward(GH, HX, n, P, w + a.a_off, nullptr, GH, grad + a.b_off, grad + a.a_off, s));
-    // DX[P][ckk] = GH^T[P][n] * W[n][ckk], scattered back into the pooled-map gradient
-    FR_TRY(gemm_f32(GH, 1, P, w + a.w_off, ckk, 1, DX, ckk, P, ckk, n, OUT_STORE, nullptr, s, ws_slot));
-    FR_TRY(col2im_positions_add(DX, a.Cin, a.H, a.W, a.k, a.Wo, pos, P, in.gpooled.f(), s));
+    if (head_needs_gin(m, h)) {
+      // DX[P][ckk] = GH^T[P][n] * W[n][ckk], scattered back into the pooled-map gradient
+      FR_TRY(gemm_f32(GH, 1, P, w + a.w_off, ckk, 1, DX, ckk, P, ckk, n, OUT_STORE, nullptr, s, ws_slot));
+      FR_TRY(col2im_positions_add(DX, a.Cin, a.H, a.W, a.k, a.Wo, pos, P, in.gpooled.f(), s));
+    }
     if (h.stream && s == h.stream) {   // (on its own stream: see Head::gin_done)
       if (!h.gin_done) FR_HIP(hipEventCreateWithFlags(&h.gin_done, hipEventDisableTiming));
       FR_HIP(hipEventRecord(h.gin_done, s));
@@ -1266,6 +1294,7 @@ static int backward_head(frcnn_model* m, Head& h, const float* w, float* grad, h
   FR_TRY(act_backward(a.gx.f(), a.x.f(), a.Cout, (long)a.Ho * a.Wo, w + a.a_off, nullptr, a.gx.f(),
                       grad + a.b_off, grad + a.a_off, s));
   FR_TRY(conv_wgrad(in.pooled.f(), a.Cin, a.H, a.W, nullptr, nullptr, a.gx.f(), a.Cout, a.k, 0, grad + a.w_off, m->wg_ws.p, m->wg_ws.bytes, s));
+  if (!head_needs_gin(m, h)) return FRCNN_OK;
   double f3 = 2.0 * a.Cout * a.Cin * a.k * a.k * (double)a.Ho * a.Wo;
   FR_TRY(conv_igemm(a.gx.f(), a.Cout, a.Ho, a.Wo, nullptr, nullptr, a.wd.f(), nullptr, a.Cin, a.k, a.k - 1,
                     in.gpooled.f(), OUT_ADD, f3, s, ws_slot));  // nngraph fan-out: gradients add up
@@ -1283,7 +1312,7 @@ static int backward_heads(frcnn_model* m, const float* w, float* grad, hipStream
 // fallback (shared weight-gradient workspace) stays on the side stream.
 static int backward_heads_fanout(frcnn_model* m, const float* w, float* grad) {
   FR_TRY(ensure_head_streams(m));
-  FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
+  if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
   FR_HIP(hipEventRecord(m->chain_ev, m->side));
   for (auto& h : m->heads) h.gin_recorded = false;
   std::vector<char> own(m->heads.size(), 0);   // (the hint is consumed by backward_head: decide before calling it)
@@ -1406,13 +1435,19 @@ static int heads_sparse_backward(frcnn_model* m, const float* w, float* grad, co
   }
   FR_TRY(gemm_f32_group(q, g.n, s));
   FR_TRY(heads_act_backward(g, s));                    // PReLU backward, gb3, gslope
-  for (int i = 0; i < g.n; ++i) {                      // DX[P][ckk] = GH^T[P][n] W[n][ckk]
-    const HeadJob& j = g.j[i]; const Head* hd = head_of(j);
+  HeadJobs gi;                                         // (staged training: the nets whose input block is trained)
+  gi.n = 0;
+  for (int i = 0; i < g.n; ++i)
+    if (head_needs_gin(m, *head_of(g.j[i]))) gi.j[gi.n++] = g.j[i];
+  for (int i = 0; i < gi.n; ++i) {                     // DX[P][ckk] = GH^T[P][n] W[n][ckk]
+    const HeadJob& j = gi.j[i]; const Head* hd = head_of(j);
     const int ckk = j.Cin * j.k * j.k;
     q[i] = GemmJob{j.GH, 1, (long)j.P, w + hd->c3.w_off, (long)ckk, 1, j.DX, (long)ckk, j.P, ckk, j.n, OUT_STORE, 1};
   }
-  FR_TRY(gemm_f32_group(q, g.n, s));
-  FR_TRY(heads_col2im(g, s));                          // the pooled maps' gradients
+  if (gi.n) {
+    FR_TRY(gemm_f32_group(q, gi.n, s));
+    FR_TRY(heads_col2im(gi, s));                       // the pooled maps' gradients
+  }
   if (!m->heads_gin_ev) FR_HIP(hipEventCreateWithFlags(&m->heads_gin_ev, hipEventDisableTiming));
   FR_HIP(hipEventRecord(m->heads_gin_ev, s));          // what the backbone's backward pass waits for; the parameter gradients follow
   m->heads_gin = true;
@@ -1434,11 +1469,20 @@ static int heads_sparse_backward(frcnn_model* m, const float* w, float* grad, co
 int frcnn_pnet_backward_heads_begin(frcnn_model* m, const float* w, float* grad, void* stream) {
   hipStream_t s = S(stream);
   FR_CHECK(m->H > 0 && m->training, "pnet_backward_heads_begin: needs a preceding training-mode forward");
-  if (!side_enabled() || m->heads_begun) return FRCNN_OK;   // frcnn_pnet_backward does everything
+  if (!side_enabled() || m->heads_begun || !m->train_heads) return FRCNN_OK;   // frcnn_pnet_backward does everything
   if (m->heads_deferred) FR_TRY(heads_forward_dense(m, w, s));   // (this entry point has no sparse forward: the outputs were the caller's to read)
   FR_TRY(fork_side(m, s, m->blocks.size() + 1));             // delta_outputs[1..nheads] are final on s
   FR_TRY(join_heads(m, m->side));                            // (anchor nets of an asynchronous forward still in flight)
   FR_TRY(backward_heads_fanout(m, w, grad));
+  m->heads_begun = true;
+  return FRCNN_OK;
+}
+
+// Staged training with the anchor nets frozen: the losses are queued, nothing of the anchor nets' backward pass is.  The pass counts
+// as begun (frcnn_pnet_backward joins the side stream, which holds the losses) with no input-gradient contribution recorded.
+static int heads_frozen_begun(frcnn_model* m) {
+  for (auto& h : m->heads) { h.sp_count = -1; h.sp_pos = nullptr; h.gin_recorded = false; }   // (one-shot hints, unused)
+  m->heads_gin = false;
   m->heads_begun = true;
   return FRCNN_OK;
 }
@@ -1476,7 +1520,8 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
     FR_TRY(loss_accumulate(ex_loss, E, acc, m->side));
     FR_HIP(hipEventRecord(m->loss_ev, m->side));
     m->loss_pending = true;
-    FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
+    if (!m->train_heads) return heads_frozen_begun(m);   // staged training: the chain stops after the losses
+    if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
     FR_TRY(heads_sparse_backward(m, w, grad, g, m->side));
     m->heads_begun = true;
     return FRCNN_OK;
@@ -1488,6 +1533,7 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
   FR_TRY(loss_accumulate(ex_loss, E, acc, m->side));
   FR_HIP(hipEventRecord(m->loss_ev, m->side));
   m->loss_pending = true;
+  if (!m->train_heads) return heads_frozen_begun(m);
   FR_TRY(backward_heads_fanout(m, w, grad));
   m->heads_begun = true;
   return FRCNN_OK;
@@ -1627,6 +1673,10 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
       }
     }
     m->heads_begun = false; m->heads_joined = false; m->side_busy = false;
+  } else if (!m->train_heads) {   // staged training, anchor nets frozen: their deltas are not back-propagated
+    for (auto& h : m->heads) { h.sp_count = -1; h.sp_pos = nullptr; }
+    m->heads_deferred = false;
+    FR_TRY(join_side(m, s));
   } else {
     if (m->heads_deferred) {   // nobody asked for the anchor nets' outputs; their backward part below needs the forward part unless no net has a position
       bool any = false;
@@ -1635,10 +1685,15 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
       m->heads_deferred = false;
     }
     FR_TRY(join_side(m, s));   // anchor nets of frcnn_pnet_forward_async_heads still in flight (image without examples)
-    FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, s));
+    if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, s));
     FR_TRY(backward_heads(m, w, grad, s, 0));
   }
-  {  // output nheads+1 is the last pooled map itself (model_utilities.lua:55)
+  // staged training (frcnn_model_set_trainable): blocks 0..fb-1 are frozen; the chain stops at block fb, whose first convolution
+  // computes its weight gradient and no input gradient
+  const int fb = m->frozen_blocks;
+  if (fb < nb) {  // output nheads+1 is the last pooled map itself (model_utilities.lua:55)
+    // (nobody has zeroed the pooled maps' gradients when the anchor nets are frozen: the chain below adds into them)
+    if (!m->train_heads) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, s));
     Block& last = m->blocks.back();
     FR_TRY(add_inplace(last.gpooled.f(), m->delta_last.f(), (long)m->d.filters[nb - 1] * last.Hp * last.Wp, s));
   }
@@ -1646,6 +1701,16 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
   if (m->update_armed) {
     if (!m->bwd_ev) FR_HIP(hipEventCreateWithFlags(&m->bwd_ev, hipEventDisableTiming));
     FR_HIP(hipEventRecord(m->bwd_ev, s));
+  }
+  // a frozen block's gradients are final and its weights free at once: its events mark this point of the caller's stream
+  for (int b = 0; b < fb; ++b) {
+    while (m->block_ev.size() < (size_t)nb) {
+      hipEvent_t e;
+      FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      m->block_ev.push_back(e);
+    }
+    FR_HIP(hipEventRecord(m->block_ev[b], s));
+    FR_TRY(record_block_read(m, b, s));
   }
   // The weight gradient of a layer and the input gradient that feeds the next act_backward are independent:
   // accGradParameters goes to a side stream, so its blocks fill the CUs that the tail of the updateGradInput
@@ -1662,7 +1727,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
   // mode: the sums leave through atomics.)
   const bool fuse_act = !deterministic() && !(getenv("FRCNN_FUSE_ACT") && atoi(getenv("FRCNN_FUSE_ACT")) == 0);
   bool act_done = false;   // the gradient tensor of the convolution being visited already went through its activation
-  for (int b = nb - 1; b >= 0; --b) {
+  for (int b = nb - 1; b >= fb; --b) {
     Block& blk = m->blocks[b];
     for (int st = blk.nconv - 1; st >= 0; --st) {
       Conv& c = m->convs[blk.first_conv + st];
@@ -1748,7 +1813,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
         }
         FR_HIP(hipEventRecord(m->block_ev[b], on_caller ? s : ws));
       }
-      if (b == 0 && st == 0) {   // gradInput of the first conv is unused (objective.lua:189)
+      if (b == fb && st == 0) {   // gradInput of the first conv is unused (objective.lua:189), so is a frozen block's
         FR_TRY(record_block_read(m, b, s));
         break;
       }
@@ -1922,6 +1987,9 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
   const int nf = m->cls.empty() ? m->D : m->cls.back().n;
   const int nc = m->d.class_count + 1;
   const float* feat = m->cls.empty() ? m->cnet_x : m->cls.back().post.f();
+  // staged training with the whole backbone frozen: nobody reads the input gradient -- the chain's last product (and its magnitude
+  // and split passes) is not queued, gx stays unwritten
+  if (m->frozen_blocks >= (int)m->blocks.size()) gx = nullptr;
   // `s` carries the input-gradient chain (what roi_pool_backward and the backbone wait for); the weight-gradient products and
   // bias sums go to `ws`: a stream of their own (see g_cnet_wgrad_async), or `s` itself
   FR_TRY(cw_join(m, s));

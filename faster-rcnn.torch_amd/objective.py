@@ -156,28 +156,43 @@ def allreduce_begin(gradient, lo, hi):
     return (lo, hi, dist.all_reduce(gradient[lo:hi], async_op=True))
 
 
-def allreduce_begin_rest(gradient, pending):
-    """Start the all-reduce of every part of `gradient` that no handle in `pending` covers yet (the whole vector
-    is final).  Returns the extended list; lets the exchange run while the host still reads the accumulators."""
+def uncovered(done, ranges):
+    """The parts of `ranges` (sorted, disjoint [lo, hi) pairs) that no pair of `done` covers, in order."""
+    done = sorted(done)
+    out = []
+    for lo, hi in ranges:
+        pos = lo
+        for dlo, dhi in done:
+            if dhi <= pos or dlo >= hi:
+                continue
+            if dlo > pos:
+                out.append((pos, dlo))
+            pos = max(pos, dhi)
+        if pos < hi:
+            out.append((pos, hi))
+    return out
+
+
+def allreduce_begin_rest(gradient, pending, ranges=None):
+    """Start the all-reduce of every part of `gradient` (of `ranges`, the trainable slices of a staged pass) that no
+    handle in `pending` covers yet (the vector is final).  Returns the extended list; lets the exchange run while the
+    host still reads the accumulators."""
     if _dist() is None:
         return list(pending)
     done = sorted((p[0], p[1]) for p in pending if p is not None)
     out = [p for p in pending if p is not None]
-    pos = 0
-    for lo, hi in done + [(gradient.numel(), gradient.numel())]:
-        if lo > pos:
-            out.append(allreduce_begin(gradient, pos, lo))
-        pos = max(pos, hi)
+    for lo, hi in uncovered(done, ranges if ranges is not None else [(0, gradient.numel())]):
+        out.append(allreduce_begin(gradient, lo, hi))
     return out
 
 
-def allreduce_gradient_and_stats(gradient, tot, pending=()):
+def allreduce_gradient_and_stats(gradient, tot, pending=(), ranges=None):
     """Data-parallel exchange step: sum the flat gradient (in place) and the 8 fp64
     accumulators {cls_loss, reg_loss, cls_count, reg_count, creg_loss, creg_count, ccls_loss,
     ccls_count} (objective.lua:52-58) over all ranks.  `gradient` is a torch tensor (CUDA: RCCL over
     xGMI through torch.distributed's "nccl" backend; CPU: gloo, used by the tests).  Buckets already started
-    with allreduce_begin() (`pending`) are only waited for; the rest of the vector is reduced here.  No-op
-    without an initialised process group."""
+    with allreduce_begin() (`pending`) are only waited for; the rest of the vector (of `ranges`, the trainable slices of
+    a staged pass) is reduced here.  No-op without an initialised process group."""
     dist = _dist()
     if dist is None:
         return tot
@@ -185,15 +200,60 @@ def allreduce_gradient_and_stats(gradient, tot, pending=()):
     t = torch.from_numpy(np.asarray(tot, dtype=np.float64)).to(gradient.device)
     done = sorted((lo, hi) for lo, hi, _ in [p for p in pending if p is not None])
     works = [w for _, _, w in [p for p in pending if p is not None]]
-    pos = 0
-    for lo, hi in done + [(gradient.numel(), gradient.numel())]:
-        if lo > pos:
-            works.append(dist.all_reduce(gradient[pos:lo], async_op=True))
-        pos = max(pos, hi)
+    for lo, hi in uncovered(done, ranges if ranges is not None else [(0, gradient.numel())]):
+        works.append(dist.all_reduce(gradient[lo:hi], async_op=True))
     works.append(dist.all_reduce(t, async_op=True))
     for w in works:
         w.wait()
     return t.cpu().numpy()
+
+
+TRAIN_DEFAULTS = dict(proposal=True, classification=True, frozen_blocks=0)
+
+
+def train_settings(cfg, nblocks):
+    """cfg["train"] (staged training, Faster R-CNN's 4-step alternating training) -> (frozen_blocks, proposal, classification).
+    proposal: the anchor nets are trained and the RPN losses back-propagated; classification: the fine-tuning +
+    classification stage (objective.lua:146-186) runs and is trained; frozen_blocks: the leading backbone blocks whose
+    parameters stay fixed.  Missing keys take TRAIN_DEFAULTS (everything trained).  Raises FrcnnError on a bad setting."""
+    t = cfg.get("train")
+    if t is None:
+        t = {}
+    if not isinstance(t, dict):
+        raise _lib.FrcnnError("cfg.train must be a table of {proposal, classification, frozen_blocks}")
+    unknown = sorted(set(t) - set(TRAIN_DEFAULTS))
+    if unknown:
+        raise _lib.FrcnnError("cfg.train: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    proposal = t.get("proposal", True)
+    classification = t.get("classification", True)
+    fb = t.get("frozen_blocks", 0)
+    if not isinstance(proposal, bool) or not isinstance(classification, bool):
+        raise _lib.FrcnnError("cfg.train: proposal and classification must be booleans")
+    if isinstance(fb, bool) or not isinstance(fb, (int, np.integer)) or not 0 <= fb <= nblocks:
+        raise _lib.FrcnnError("cfg.train.frozen_blocks = %r outside 0..%d (the backbone's blocks)" % (fb, nblocks))
+    if not proposal and not classification:
+        raise _lib.FrcnnError("cfg.train: proposal and classification are both off (no loss to back-propagate)")
+    return int(fb), proposal, classification
+
+
+def trainable_ranges(block_ranges, heads_range, cnet_range, frozen_blocks, proposal, classification):
+    """The trainable slices of the flat vector, sorted and merged: the backbone blocks from frozen_blocks on (block_ranges:
+    [lo, hi) per block, in order), the anchor nets' heads_range when proposal, the classification net's cnet_range when
+    classification.  Raises FrcnnError when nothing is trainable."""
+    parts = [tuple(block_ranges[b]) for b in range(frozen_blocks, len(block_ranges))]
+    if proposal:
+        parts.append(tuple(heads_range))
+    if classification:
+        parts.append(tuple(cnet_range))
+    out = []
+    for lo, hi in sorted(p for p in parts if p[1] > p[0]):
+        if out and lo <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], hi))
+        else:
+            out.append((lo, hi))
+    if not out:
+        raise _lib.FrcnnError("cfg.train: no trainable parameter left")
+    return out
 
 
 def create_objective(model, weights, gradient, batch_iterator, stats):  # objective.lua:15
@@ -292,10 +352,25 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         prep.update(ex_anchor=ex_anchor, ex_roi=ex_roi, ex_idx=ex_idx, ex_class=ex_class, wins=wins, sp=sp, blob=blob)
         return prep
 
+    nblk_all = int(native.desc.nblocks)
+
+    def stage_ranges():
+        """cfg["train"] as it stands -> (frozen_blocks, proposal, classification, trainable ranges, or None for the whole vector)"""
+        fb, prop, clsf = train_settings(model["cfg"], nblk_all)
+        ranges = trainable_ranges([pnet.block_param_range(b) for b in range(nblk_all)], pnet.heads_param_range(),
+                                  (native.pnet_params, gradient.numel()), fb, prop, clsf)
+        return fb, prop, clsf, (None if ranges == [(0, gradient.numel())] else ranges)
+
     def run(w, defer, eager=None):
         """Queues the whole pass.  Returns finish() -> (loss, gradient); with defer=True (single process) the
         accumulators travel to pinned host memory asynchronously and finish() only waits for that copy, so the
         caller may queue more work (the optimiser step) before it looks at the loss."""
+        # staged training (cfg.train, read at every call; validated before anything is queued): the library skips the frozen
+        # parts' work (frcnn_model_set_trainable), this pass skips a disabled stage, and the optimiser updates `ranges` only
+        frozen_blocks, proposal, classification, ranges = stage_ranges()
+        _lib.call("frcnn_model_set_trainable", native.h, frozen_blocks, int(proposal), int(classification))
+        stage[0] = ranges
+        trunk_frozen = frozen_blocks == nblk_all
         if w is not weights:  # :46-48
             weights.copy_(w)
         if packs_promise[0] is not None and packs_promise[0] != getattr(weights, "_version", None):
@@ -335,6 +410,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 n_ex = len(clean_examples(x0["positive"], sizes0)) + len(clean_examples(x0["negative"], sizes0))
             eager["gscale"] = (1.0 / n_ex) if n_ex > 0 else 1.0   # gradient:div(cls_count), :200 (nothing to scale without examples)
             eager["done"] = []
+            eager["ranges"] = ranges   # (staged training: the trainable slices, None = the whole vector)
             us = C.c_void_p()
             _lib.call("frcnn_model_update_stream", native.h, C.byref(us))
             nblk = int(native.desc.nblocks)
@@ -347,7 +423,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                     eager["groups"].add(group)
             eager["groups"] = set()
             eager["slice"] = eager_slice
-        dev_tail = (dev_tail_ok and defer == "fold" and _dist() is not None and getattr(gradient, "is_cuda", False))
+        dev_tail = (dev_tail_ok and defer == "fold" and _dist() is not None and getattr(gradient, "is_cuda", False)
+                    and ranges is None)   # (a staged pass: the optimisers' slice forms take a host divisor)
         c4 = None
         if dev_tail:
             from .synthetic import clean_examples, output_map_sizes
@@ -404,6 +481,13 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 cctarget = scratch.get("cctarget", (E,))
                 pnet.anchor_loss_begin(d_idx, d_anchor, d_roi, d_class, npos, nneg, bgclass, ex_loss, crtarget,
                                        cctarget, acc_dev)
+            if E > 0 and not classification:
+                # staged training without the detector stage: no ROI pooling, no cnet; dcls / dreg are reported as NaN (finish).
+                # The cnet's dropout draw is skipped too: the seed advances as its forward would advance it, so that every
+                # later pass draws what it would draw unstaged
+                native.seed += 1
+                pnet.anchor_loss_wait()   # (the accumulators are read on this stream)
+            elif E > 0:
                 # ---- ROI pooling of every example in one launch (:117-119, :137-139) ---------
                 cinput = scratch.get("cinput", (E, D))
                 pidx = scratch.get("pidx", (E, D), np.int32)
@@ -418,8 +502,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), E, npos, ncls,
                           ptr(crdelta), ptr(ccdelta), C.c_void_p(acc_dev.ptr + 4 * 8), s)  # :170-177
                 post_roi_delta = cnet.backward(cinput, [crdelta, ccdelta])  # :179
-                _lib.call("frcnn_roi_pool_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),
-                          ptr(pidx), E, kh, kw, s)  # :182-185
+                if not trunk_frozen:   # (a frozen backbone: the library left the input gradient unwritten)
+                    _lib.call("frcnn_roi_pool_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),
+                              ptr(pidx), E, kh, kw, s)  # :182-185
             if E == 0:
                 for l in range(4):
                     _lib.call("frcnn_pnet_set_sparse_deltas", native.h, l + 1, None, 0)
@@ -428,14 +513,15 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 # nets' slice once the side stream's part is joined: their all-reduces run beside the backbone's
                 # backward pass; only the backbone's 3.3 M elements remain for the end
                 _lib.call("frcnn_cnet_backward_join", native.h, stream_ptr())   # its weight gradients ride on a stream of their own
-                pending.append(allreduce_begin(gradient, native.pnet_params, gradient.numel()))
+                if classification:
+                    pending.append(allreduce_begin(gradient, native.pnet_params, gradient.numel()))
                 # The decision must not depend on this rank's data (every rank issues the same collectives): with the
                 # side stream on and one image per batch the slice is final here on every rank -- either the
                 # anchor nets' backward was started early and is joined now, or the image had no example and
                 # contributes nothing to that slice.
                 side = C.c_int(0)
                 _lib.call("frcnn_get_option", b"side_stream", C.byref(side))
-                if len(batch) == 1 and side.value:
+                if len(batch) == 1 and side.value and proposal:
                     pnet.backward_heads_join()
                     lo, hi = pnet.heads_param_range()
                     pending.append(allreduce_begin(gradient, lo, hi))
@@ -465,11 +551,13 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 # had their last reader -- also for an image without examples; the anchor nets may still be adding up their
                 # parameter gradients)
                 _lib.call("frcnn_pnet_wait_backward_begun", native.h, us)
-                eager_slice(native.pnet_params, gradient.numel(), us)
+                if classification:
+                    eager_slice(native.pnet_params, gradient.numel(), us)
                 _lib.call("frcnn_pnet_wait_heads_done", native.h, us)
                 lo, hi = pnet.heads_param_range()
-                eager_slice(lo, hi, us, nblk)
-                for b in range(nblk, 1, -1):   # deepest block first: the order in which the pass leaves them; block 1 ends the pass
+                if proposal:
+                    eager_slice(lo, hi, us, nblk)
+                for b in range(nblk, max(frozen_blocks, 1), -1):   # deepest block first: the order in which the pass leaves them; block 1 ends the pass
                     _lib.call("frcnn_pnet_wait_block_done", native.h, b, us)
                     lo, hi = pnet.block_param_range(b - 1)
                     eager_slice(lo, hi, us, b - 1)
@@ -477,7 +565,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             if last and _dist() is not None and early_blocks and getattr(gradient, "is_cuda", False):
                 if aux_stream[0] is None:
                     aux_stream[0] = torch.cuda.Stream()
-                for b in early_blocks:   # deepest first: the order in which their gradients become final
+                for b in [b for b in early_blocks if b >= frozen_blocks]:   # deepest first: the order in which their gradients become final
                     lo, hi = pnet.block_param_range(b)
                     with torch.cuda.stream(aux_stream[0]):
                         pnet.wait_block_gradients(b)
@@ -509,7 +597,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             _lib.call("frcnn_scale", ptr(gradient), gradient.numel(), 1.0 / cls_count, stream_ptr())  # :200
         counts = (cls_count, reg_count, creg_count, ccls_count)
         if not single:   # the rest of the gradient is final too: its exchange starts before the host read-back below
-            pending[:] = allreduce_begin_rest(gradient, pending)
+            pending[:] = allreduce_begin_rest(gradient, pending, ranges)
         if dev_tail:
             # asynchronous data-parallel tail: loss sums AND counts reduced on the device in one 8-element all-reduce
             assert [float(v) for v in (cls_count, reg_count, creg_count, ccls_count)] == c4, "count bookkeeping diverged"
@@ -525,16 +613,16 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             if not early_copy:
                 acc_pin.copy_(acc_t, non_blocking=True)
                 acc_event.record()
-            fin = lambda: finish(None, counts, pending, single)
+            fin = lambda: finish(None, counts, pending, single, staged=(classification, ranges))
             if eager is not None:
                 assert cls_count == 0 or eager["gscale"] == 1.0 / cls_count, "example count bookkeeping diverged"
                 return (fin, eager["gscale"] if cls_count > 0 else None)
             return (fin, 1.0 / cls_count) if fold else fin
         if defer == "fold" and not single:   # the all-reduced count is known after finish(): scaling left to the caller
-            res = finish(acc_dev.numpy(), counts, pending, single, fold=True)
+            res = finish(acc_dev.numpy(), counts, pending, single, fold=True, staged=(classification, ranges))
             gs = dp_gscale[0]
             return ((lambda: res), gs) if gs is not None else (lambda: res)
-        return (lambda r: (lambda: r))(finish(acc_dev.numpy(), counts, pending, single))
+        return (lambda r: (lambda: r))(finish(acc_dev.numpy(), counts, pending, single, staged=(classification, ranges)))
 
     dp_gscale = [None]
     packs_promise = [None]   # weights._version at the moment every pack group had been renewed beside a pass (else None)
@@ -542,7 +630,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     next_batch = [None]
     prefetch_batches = os.environ.get("FRCNN_PREFETCH_BATCH", "1") != "0"
 
-    def finish(a, counts, pending, single, fold=False, reduced=False):
+    stage = [None]   # the trainable ranges of the last pass queued (None: the whole vector)
+
+    def finish(a, counts, pending, single, fold=False, reduced=False, staged=(True, None)):
         if a is None:
             # deferred read-back: the whole step is queued, the device is busy -- the next batch (image decoding hand-over,
             # processImage launches, example assembly: host work of the loader) is drawn now instead of at the start of
@@ -559,7 +649,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         cls_count, reg_count, creg_count, ccls_count = counts
         tot = np.array([a[0], a[1], cls_count, reg_count, a[4], creg_count, a[5], ccls_count], dtype=np.float64)
         if not reduced:   # (asynchronous data-parallel tail: gradient, accumulators and counts are already summed)
-            tot = allreduce_gradient_and_stats(gradient, tot, pending)  # DP: no-op for a single process
+            tot = allreduce_gradient_and_stats(gradient, tot, pending, staged[1])  # DP: no-op for a single process
         cls_loss, reg_loss, cls_count, reg_count, creg_loss, creg_count, ccls_loss, ccls_count = tot
         dp_gscale[0] = None
         if not single and cls_count > 0:
@@ -572,6 +662,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             preg = float(np.float64(reg_loss) / reg_count)
             dcls = float(np.float64(ccls_loss) / ccls_count)
             dreg = float(np.float64(creg_loss) / creg_count)
+        if not staged[0]:   # staged training without the detector stage: nothing was computed for it
+            dcls = dreg = float("nan")
         if stats.get("verbose"):
             print("prop: cls: %f (%d), reg: %f (%d); det: cls: %f, reg: %f" % (pcls, cls_count, preg, reg_count, dcls, dreg))
         stats["pcls"].append(pcls); stats["preg"].append(preg)  # :211-214
@@ -607,6 +699,11 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             eager["complete"] = complete
         return (r[0], gradient, r[1]) if isinstance(r, tuple) else (r, gradient, None)
     lossAndGradient.begin_fold = begin_fold
+    # staged training (cfg["train"]): trainable_ranges() validates the configuration as it stands and returns the slices a
+    # pass would train (None: the whole vector) -- what optim.nag's look-ahead needs before the pass; pass_ranges() returns
+    # those of the last pass queued.  The optimisers of utilities update these slices only.
+    lossAndGradient.trainable_ranges = lambda: stage_ranges()[3]
+    lossAndGradient.pass_ranges = lambda: stage[0]
     lossAndGradient.debug = debug   # (tests: the scratch buffers and the example count of the image being processed)
     return lossAndGradient
 

@@ -37,11 +37,27 @@ import os
 EAGER_DEFAULT = os.environ.get("FRCNN_EAGER_UPDATE", "0") == "1"
 
 
+def staged_ranges(opfunc):
+    """The trainable slices the next pass of opfunc would train (create_objective's cfg["train"], validated now), or None:
+    the whole vector (no staged training, or an opfunc that does not publish ranges)."""
+    f = getattr(opfunc, "trainable_ranges", None)
+    return f() if f is not None else None
+
+
+def _state_vector(x, opfunc):
+    """A fresh optimiser state vector whose first update writes every element it covers: zeros when the coming pass is
+    staged, so that a frozen slice starts from 0 whenever it is trained later (it was never handed to the optimiser)."""
+    import torch
+    return torch.zeros_like(x) if staged_ranges(opfunc) is not None else torch.empty_like(x)
+
+
 def _step(opfunc, x, state, whole, update):
     """One optimiser step around opfunc (main.lua:133-135), the update queued by the optimiser:
     whole(dfdx, gscale) updates the whole vector, gscale None (nothing to scale), a float (gradient:div(n), objective.lua:200,
     folded into the update's pass) or a DeviceDivisor (data parallel: the all-reduced count, still on the device);
     update(w, g, lo, hi, gscale, stream) is the same update on elements [lo, hi) (gscale 1: unscaled).
+    Staged training (create_objective's cfg["train"]): only the slices the pass published (pass_ranges) are updated; a frozen
+    slice keeps its weights and its optimiser state bit for bit, as if it had never been handed to the optimiser.
     Returns x, [f(x)] like the Lua functions."""
     begin = getattr(opfunc, "begin_fold", None)
     timing = state.get("_timing")     # bench.py: seconds the host spends queueing a step / waiting for its statistics
@@ -54,20 +70,20 @@ def _step(opfunc, x, state, whole, update):
         # apply this very step slice by slice, beside its own backward half, as slices of the gradient become final
         eager = dict(update=update) if state.get("eager", EAGER_DEFAULT) else None
         finish, dfdx, gscale = begin(x, eager) if eager is not None else begin(x)
+        pass_ranges = getattr(opfunc, "pass_ranges", None)
+        ranges = pass_ranges() if pass_ranges is not None else None
         if eager is not None and "done" in eager:
             # what the pass has not updated (the shallowest block: its gradients end the pass; everything, for an image without
-            # examples), on the caller's stream, followed by the packs made from it
-            done = sorted(eager["done"])
-            rest, at = [], 0
-            for lo, hi in done:
-                if lo > at:
-                    rest.append((at, lo))
-                at = max(at, hi)
-            if at < x.numel():
-                rest.append((at, x.numel()))
-            for lo, hi in rest:
+            # examples) -- of the trainable slices -- on the caller's stream, followed by the packs made from it
+            from .objective import uncovered
+            for lo, hi in uncovered(eager["done"], eager.get("ranges") or [(0, x.numel())]):
                 eager["slice"](lo, hi, stream_ptr())
             eager["complete"]()
+        elif ranges is not None:
+            if hasattr(gscale, "ptr"):
+                raise _lib.FrcnnError("staged training: the slice updates take a host divisor")
+            for lo, hi in ranges:
+                update(x, dfdx, lo, hi, 1.0 if gscale is None else gscale, stream_ptr())
         else:
             whole(dfdx, gscale)
         if timing is not None:
@@ -139,7 +155,7 @@ def sgd(opfunc, x, config, state=None):
     clr = lr / (1 + nevals * lrd)           # host scalars in double, as Lua computes them
     first = mom != 0 and "dfdx" not in state
     if first:
-        state["dfdx"] = torch.empty_like(x)   # (its contents are the kernel's: v = copy(g))
+        state["dfdx"] = _state_vector(x, opfunc)   # (its contents are the kernel's: v = copy(g))
     v = state["dfdx"] if mom != 0 else None
     args = (wd, mom, 1 - damp, int(nesterov), int(first))
 
@@ -176,9 +192,14 @@ def nag(opfunc, x, config, state=None):
     clr = lr / (1 + nevals * lrd)
     first = "dfdx" not in state
     if first:
-        state["dfdx"] = torch.empty_like(x)   # (fill(0) is folded into the first update)
+        state["dfdx"] = _state_vector(x, opfunc)   # (fill(0) is folded into the first update)
     else:
-        _lib.call("frcnn_nag_lookahead", ptr(x), ptr(state["dfdx"]), x.numel(), mom, stream_ptr())
+        ranges = staged_ranges(opfunc)
+        if ranges is None:
+            _lib.call("frcnn_nag_lookahead", ptr(x), ptr(state["dfdx"]), x.numel(), mom, stream_ptr())
+        else:   # staged training: a frozen slice keeps its weights
+            for lo, hi in ranges:
+                _lib.call("frcnn_nag_lookahead_slice", ptr(x), ptr(state["dfdx"]), lo, hi, mom, stream_ptr())
         # torch does not see the library's write: counting it as torch's own makes create_objective withdraw a pack promise
         # made for the weights before the look-ahead (frcnn_pnet_invalidate_packs) instead of forwarding with stale packs
         increment_version(x)

@@ -292,6 +292,9 @@ int frcnn_nag_slice(float *x, float *g, float *v, long long lo, long long hi, fl
 /* optim.nag's look-ahead, before opfunc is called (when state.dfdx exists): x += mom*v.  A host that holds a pack promise
  * (frcnn_pnet_refresh_packs below) withdraws it afterwards with frcnn_pnet_invalidate_packs: the weights have changed. */
 int frcnn_nag_lookahead(float *x, const float *v, long long n, float mom, void *stream);
+/* frcnn_nag_lookahead on elements [lo, hi) only (x, v = the STARTS of the vectors; any bounds): staged training
+ * (frcnn_model_set_trainable) looks ahead on the trainable slices, a frozen slice keeps its weights. */
+int frcnn_nag_lookahead_slice(float *x, const float *v, long long lo, long long hi, float mom, void *stream);
 
 /* ---- model runtime: models/model_utilities.lua:3-136 --------------------------------- */
 typedef struct {
@@ -322,6 +325,25 @@ int frcnn_model_param_table(const frcnn_model *, long long *table_host, int cap,
  * int[n][6] = {kW,kH,dW,dH,padW,padH}, input first. */
 int frcnn_model_localizer_layers(const frcnn_model *, int output_index, int *layers_host, int cap,
                                  int *n_host);
+/* Staged training (Faster R-CNN's 4-step alternating training, cfg.train of the objective).  frozen_blocks (0..nblocks): the
+ * leading backbone blocks whose parameters stay fixed; heads = 0: the anchor nets are frozen AND the RPN losses' deltas are not
+ * back-propagated; cnet = 0: the classification net is frozen (its stage is the host's to skip: the library is not called for
+ * it).  Default 0, 1, 1: everything trainable, every entry point launch for launch as without the call.  Errors: frozen_blocks
+ * out of range, heads = cnet = 0, no trainable parameter.  The training entry points honour it as follows, and never write a
+ * frozen slice of `grad` (the caller zeroes the vector before the pass):
+ *   frcnn_pnet_anchor_loss_begin  : heads = 0: the losses, crtarget, cctarget and acc as always; no anchor-net backward
+ *   frcnn_pnet_backward_heads_begin: heads = 0: starts nothing
+ *   frcnn_pnet_backward           : no anchor-net launch when heads = 0; otherwise an anchor net's parameter gradients, and its
+ *                                   input gradient only when its input block is trainable.  The backbone chain stops at block
+ *                                   frozen_blocks + 1, whose first convolution computes its weight gradient and no input
+ *                                   gradient; no launch at all for the backbone when every block is frozen.  The waits below
+ *                                   (frcnn_pnet_wait_block_gradients, _wait_block_done, _wait_heads_done, _wait_backward_begun)
+ *                                   stay valid: a frozen block's events mark the start of the backbone's part of the pass.
+ *   frcnn_cnet_backward           : every block frozen: the input-gradient chain's last product is not queued and gx is left
+ *                                   unwritten (frcnn_roi_pool_backward has nothing to do then).
+ * The optimiser entry points take ranges: a host restricts its update to the trainable slices itself. */
+int frcnn_model_set_trainable(frcnn_model *, int frozen_blocks, int heads, int cnet);
+int frcnn_model_get_trainable(const frcnn_model *, int *frozen_blocks_host, int *heads_host, int *cnet_host);
 
 /* pnet:forward(img) (objective.lua:71, Detector.lua:33).  training!=0: SpatialDropout masks are
  * drop_masks_host[b] (device float[filters_b] of 0/1, for parity runs) or, when NULL, drawn on
@@ -382,7 +404,8 @@ int frcnn_pnet_anchor_loss_wait(frcnn_model *, void *stream);
  * the remaining backward pass); 0: nothing had been started, frcnn_pnet_backward will compute that part. */
 int frcnn_pnet_backward_heads_join(frcnn_model *, void *stream, int *joined_host);
 /* pnet:backward(img, delta_outputs) (objective.lua:189): accumulates into the flat gradient.
- * The (unused) input gradient of the first convolution is not computed. */
+ * The (unused) input gradient of the first convolution is not computed (nor anything for frozen parts of the model:
+ * frcnn_model_set_trainable). */
 int frcnn_pnet_backward(frcnn_model *, const float *weights, float *grad, void *stream);
 
 /* After frcnn_pnet_backward has been queued: makes `stream` (any stream) wait until every gradient of backbone
@@ -439,7 +462,8 @@ int frcnn_pnet_invalidate_packs(frcnn_model *);
 int frcnn_cnet_forward(frcnn_model *, const float *weights, const float *x, int R, int training,
                        const float *const *drop_masks_host, unsigned long long seed,
                        float *bn_running, float *bbox_out, float *cls_out, void *stream);
-/* cnet:backward(cinput, {crdelta, ccdelta}) (objective.lua:179) -> gx [R][D] */
+/* cnet:backward(cinput, {crdelta, ccdelta}) (objective.lua:179) -> gx [R][D]; gx is not written when every backbone block is
+ * frozen (frcnn_model_set_trainable) */
 /* cnet:backward.  The input gradient gx is final on `stream` in stream order; the weight gradients and bias sums it adds to
  * `grad` are queued on a library-owned stream beside that chain (option "cnet_wgrad_async", default 1) and are final on
  * `stream` after frcnn_pnet_backward, the next frcnn_cnet_forward, or frcnn_cnet_backward_join -- or after a device-wide
