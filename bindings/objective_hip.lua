@@ -62,7 +62,8 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     return fb, proposal, classification, hip.trainable_ranges(model, fb, proposal, classification)
   end
   -- the optim overrides (frcnn_hip.lua) update the slices published here, keyed by the weight tensor
-  local published = { ranges = function() return select(4, stage()) end }
+  -- ... and fill stats.gnorm / stats.skipped when config.clipNorm / config.skipNonFinite turn the gradient guard on
+  local published = { ranges = function() return select(4, stage()) end, stats = stats }
   hip.trainable[weights] = published
 
   local function lossAndGradient(w)

@@ -85,6 +85,12 @@ _SIGS = {
                          vp], C.c_int),
     "frcnn_nag": ([vp, vp, vp, C.c_longlong, C.c_float, vp, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
     "frcnn_nag_slice": ([vp, vp, vp, C.c_longlong, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
+    "frcnn_scale_rmsprop_slice_dev": ([vp, vp, vp, vp, C.c_longlong, C.c_longlong, C.c_float, C.c_float, C.c_float, vp], C.c_int),
+    "frcnn_sgd_slice_dev": ([vp, vp, vp, C.c_longlong, C.c_longlong, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                            vp], C.c_int),
+    "frcnn_nag_slice_dev": ([vp, vp, vp, C.c_longlong, C.c_longlong, vp, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
+    "frcnn_grad_clip_workspace_bytes": ([C.c_longlong], C.c_size_t),
+    "frcnn_grad_clip": ([vp, C.c_longlong, vp, C.c_int, C.c_double, vp, C.c_double, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_nag_lookahead": ([vp, vp, C.c_longlong, C.c_float, vp], C.c_int),
     "frcnn_nag_lookahead_slice": ([vp, vp, C.c_longlong, C.c_longlong, C.c_float, vp], C.c_int),
     "frcnn_model_update_stream": ([vp, C.POINTER(vp)], C.c_int),

@@ -461,6 +461,27 @@ int frcnn_nag_slice(float* x, float* g, float* v, long long lo, long long hi, fl
                     int first, void* stream) {
   return nag_update(x, g, v, lo, hi, true, gscale, nullptr, clr, wd, mom, first != 0, S(stream));
 }
+// the device-divisor forms of the slice updates, and the gradient guard in front of them
+int frcnn_scale_rmsprop_slice_dev(float* x, float* g, const double* gcount_dev, float* m, long long lo, long long hi, float lr,
+                                  float alpha, float eps, void* stream) {
+  FR_CHECK(gcount_dev, "frcnn_scale_rmsprop_slice_dev: NULL divisor");
+  return rmsprop_slice(x, g, m, lo, hi, lr, alpha, eps, 1.f, true, S(stream), gcount_dev);
+}
+int frcnn_sgd_slice_dev(float* x, float* g, float* v, long long lo, long long hi, const double* gcount_dev, float clr, float wd,
+                        float mom, float one_minus_damp, int nesterov, int first, void* stream) {
+  FR_CHECK(gcount_dev, "frcnn_sgd_slice_dev: NULL divisor");
+  return sgd_update(x, g, v, lo, hi, true, 1.f, gcount_dev, clr, wd, mom, one_minus_damp, nesterov != 0, first != 0, S(stream));
+}
+int frcnn_nag_slice_dev(float* x, float* g, float* v, long long lo, long long hi, const double* gcount_dev, float clr, float wd,
+                        float mom, int first, void* stream) {
+  FR_CHECK(gcount_dev, "frcnn_nag_slice_dev: NULL divisor");
+  return nag_update(x, g, v, lo, hi, true, 1.f, gcount_dev, clr, wd, mom, first != 0, S(stream));
+}
+size_t frcnn_grad_clip_workspace_bytes(long long n) { return grad_clip_workspace_bytes(n); }
+int frcnn_grad_clip(float* g, long long n, const long long* ranges_host, int nranges, double divisor, const double* divisor_dev,
+                    double clip_norm, double* record_dev, void* workspace, size_t workspace_bytes, void* stream) {
+  return grad_clip(g, n, ranges_host, nranges, divisor, divisor_dev, clip_norm, record_dev, workspace, workspace_bytes, S(stream));
+}
 int frcnn_nag_lookahead(float* x, const float* v, long long n, float mom, void* stream) {
   return nag_lookahead(x, v, n, mom, S(stream));
 }

@@ -638,7 +638,8 @@ __global__ void rmsprop_kernel(float* __restrict__ x, float* __restrict__ g, flo
 // in front of the first and behind the last such group one by one (thread t < 8 of block 0)
 template <bool SCALE>
 __global__ void rmsprop_slice_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ m, long lo, long hi,
-                                     float lr, float alpha, float eps, float gscale) {
+                                     float lr, float alpha, float eps, float gscale, const double* __restrict__ gcount) {
+  if (SCALE && gcount) { const double c = *gcount; gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }   // as rmsprop_kernel
   const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);   // [lo, a) ragged | [a, b) whole groups | [b, hi) ragged
   const long n4 = (b - a) >> 2;
   float4* x4 = reinterpret_cast<float4*>(x + a);
@@ -654,7 +655,7 @@ __global__ void rmsprop_slice_kernel(float* __restrict__ x, float* __restrict__ 
   }
 }
 int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, float alpha, float eps, float gscale, bool scale_first,
-                  hipStream_t s) {
+                  hipStream_t s, const double* gcount_dev) {
   FR_CHECK((((uintptr_t)x | (uintptr_t)g | (uintptr_t)m) & 15) == 0, "rmsprop_slice: the vectors must be 16-byte aligned");
   FR_CHECK(lo >= 0 && lo <= hi, "rmsprop_slice: bad range [%ld, %ld)", lo, hi);
   if (lo == hi) return FRCNN_OK;
@@ -662,9 +663,9 @@ int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, floa
   // half the wave slots at most: a slice update runs BESIDE other launches (the backward pass) and must not keep them waiting for slots
   int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 1024);
   if (scale_first)
-    FR_LAUNCH(KC_OPTIM, 0, n * 24.0, s, rmsprop_slice_kernel<true>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, gscale);
+    FR_LAUNCH(KC_OPTIM, 0, n * 24.0, s, rmsprop_slice_kernel<true>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, gscale, gcount_dev);
   else
-    FR_LAUNCH(KC_OPTIM, 0, n * 20.0, s, rmsprop_slice_kernel<false>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, 1.f);
+    FR_LAUNCH(KC_OPTIM, 0, n * 20.0, s, rmsprop_slice_kernel<false>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, 1.f, (const double*)nullptr);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
@@ -766,7 +767,9 @@ __global__ void optim_kernel(float* __restrict__ x, float* __restrict__ g, float
 
 // elements [lo, hi): the split of rmsprop_slice_kernel (whole 16-byte groups grid-stride, ragged ends by block 0)
 template <class Op>
-__global__ void optim_slice_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long lo, long hi, Op op) {
+__global__ void optim_slice_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long lo, long hi, Op op,
+                                   const double* __restrict__ gcount) {
+  if (Op::kScale && gcount) { const double c = *gcount; op.gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }   // as optim_kernel
   const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);
   const long n4 = (b - a) >> 2;
   float4* x4 = reinterpret_cast<float4*>(x + a);
@@ -786,7 +789,7 @@ struct OptimRange {
   float* x; float* g; float* v;
   long lo, hi;
   bool slice;             // slice kernel (grid capped: it runs beside the backward pass) or the whole vector [0, hi)
-  const double* gcount;   // whole vector only: the divisor on the device
+  const double* gcount;   // the divisor on the device (NULL: the host's gscale)
   hipStream_t s;
 };
 
@@ -797,7 +800,7 @@ int optim_launch(const Op& op, const OptimRange& r) {
   const double bytes = 4.0 * Op::kStreams * n;
   if (r.slice) {
     int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 1024);   // half the wave slots, as rmsprop_slice
-    FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_slice_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op);
+    FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_slice_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op, r.gcount);
   } else {
     int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 2048);
     FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, n, op, r.gcount);
@@ -833,7 +836,7 @@ int optim_check(const char* what, const OptimRange& r, bool uses_v) {
 
 int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s) {
-  const OptimRange r{x, g, mom != 0.f ? v : nullptr, lo, hi, slice, slice ? nullptr : gcount_dev, s};
+  const OptimRange r{x, g, mom != 0.f ? v : nullptr, lo, hi, slice, gcount_dev, s};
   FR_TRY(optim_check("sgd", r, mom != 0.f));
   FR_CHECK(!nesterov || (mom > 0.f && one_minus_damp == 1.f), "sgd: Nesterov momentum requires a momentum and zero dampening");
   const bool scale = r.gcount || gscale != 1.f;
@@ -846,7 +849,7 @@ int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float
 
 int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, bool first, hipStream_t s) {
-  const OptimRange r{x, g, v, lo, hi, slice, slice ? nullptr : gcount_dev, s};
+  const OptimRange r{x, g, v, lo, hi, slice, gcount_dev, s};
   FR_TRY(optim_check("nag", r, true));
   FR_CHECK(mom > 0.f, "nag: momentum must be positive for Nesterov Accelerated Gradient");
   const bool scale = r.gcount || gscale != 1.f;
@@ -893,6 +896,151 @@ int nag_lookahead_slice(float* x, const float* v, long lo, long hi, float mom, h
   if (n == 0) return FRCNN_OK;
   int grid = (int)std::min<long>(std::max<long>(1, cdivl(n, 256)), 2048);
   FR_LAUNCH(KC_OPTIM, 0, n * 12.0, s, nag_lookahead_slice_kernel, dim3(grid), dim3(256), 0, x, v, lo, hi, mom);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// ---------------------------------------------------------------- the gradient guard (norm clipping, non-finite steps)
+// include/frcnn_hip.h "gradient-norm clipping" defines what is computed.  S = sum over the trainable slices of (double)g*(double)g:
+// every product is exact in fp64 (24-bit significands), the sum runs in fp64 in an order fixed by n and the slice bounds alone --
+// a thread always adds the same elements in the same order (one fp64 addition per element), a block's 256 sums meet in a fixed
+// tree, and one block folds the per-block partials in a fixed order.  No atomics: two calls on the same data leave the same bits.
+struct ClipRanges {
+  int n;
+  long lo[GRAD_CLIP_MAX_RANGES], hi[GRAD_CLIP_MAX_RANGES];
+};
+
+// acc += (double)e * (double)e for the four elements in index order, one rounding each (the product is exact, so the fused form
+// rounds what a separate add would): a zero element leaves acc as it is, bit for bit
+__device__ __forceinline__ double sumsq_add(double acc, const float4 v) {
+  acc = fma((double)v.x, (double)v.x, acc);
+  acc = fma((double)v.y, (double)v.y, acc);
+  acc = fma((double)v.z, (double)v.z, acc);
+  return fma((double)v.w, (double)v.w, acc);
+}
+
+// 16-byte group q of g (elements [4q, 4q+4)) with everything outside [lo, hi) read as zero: one 16-byte load where the slice
+// covers the group, element by element at a slice's ragged ends
+__device__ __forceinline__ float4 load_group(const float* __restrict__ g, long q, long lo, long hi) {
+  const long base = q << 2;
+  if (base >= lo && base + 4 <= hi) return *reinterpret_cast<const float4*>(g + base);
+  float e[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) e[j] = (base + j >= lo && base + j < hi) ? g[base + j] : 0.f;
+  return make_float4(e[0], e[1], e[2], e[3]);
+}
+
+// The work is dealt out by ABSOLUTE position: group q of the vector always belongs to thread q mod (grid * 256), which adds its
+// groups in ascending order, the even and the odd of its visits into two accumulators (two loads in flight).  Which slices are
+// summed changes what is added, never who adds it or when: the sum over slices whose complement holds exact zeros (the frozen
+// slices of a staged pass) is the sum over the whole vector, bit for bit.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, ClipRanges r, double* __restrict__ partial) {
+  __shared__ double sh[16];
+  double s0 = 0.0, s1 = 0.0;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int k = 0; k < r.n; ++k) {
+    const long lo = r.lo[k], hi = r.hi[k];
+    const long q0 = lo >> 2, q1 = (hi + 3) >> 2;            // the groups the slice touches
+    long visit = q0 > t ? (q0 - t) / stride : 0;            // the thread's last visit at or before q0 ...
+    visit &= ~1L;                                           // ... of even number: the pairing below is that of the whole vector
+    for (long q = t + visit * stride; q < q1; q += 2 * stride) {
+      const long q2 = q + stride;
+      const float4 u = q >= q0 ? load_group(g, q, lo, hi) : zero;
+      const float4 w = (q2 >= q0 && q2 < q1) ? load_group(g, q2, lo, hi) : zero;
+      s0 = sumsq_add(s0, u);
+      s1 = sumsq_add(s1, w);
+    }
+  }
+  const double tot = block_sum_d(s0 + s1, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// record = {S, norm, D', skipped}.  Thread t folds partials [t*per, (t+1)*per) in index order, the 256 sums meet in the fixed tree
+// of block_sum_d.  sqrt, / and * in fp64 are correctly rounded (no contraction, no reciprocal shortcut): a host that repeats the
+// three operations on the recorded S gets the recorded D' bit for bit.
+__global__ __launch_bounds__(256) void grad_clip_finish_kernel(const double* __restrict__ partial, int nparts, double divisor,
+                                                              const double* __restrict__ divisor_dev, double clip_norm,
+                                                              double* __restrict__ record) {
+#pragma clang fp contract(off)
+  __shared__ double sh[16];
+  const int per = (nparts + 255) / 256;
+  double v = 0.0;
+  for (int i = threadIdx.x * per; i < min(nparts, (threadIdx.x + 1) * per); ++i) v += partial[i];
+  const double S = block_sum_d(v, sh);
+  if (threadIdx.x == 0) {
+    double D = divisor_dev ? *divisor_dev : divisor;
+    if (!(D > 0.0)) D = 1.0;                                 // (a count of 0 leaves the gradient as it is: rmsprop_kernel)
+    const double norm = __ddiv_rn(__dsqrt_rn(S), D);
+    const bool finite = S < __builtin_huge_val();            // false for +inf and for NaN (S is a sum of squares: never negative)
+    double Dc = D;
+    if (finite && clip_norm > 0.0) {
+      const double ratio = __ddiv_rn(norm, clip_norm);
+      if (ratio > 1.0) Dc = __dmul_rn(D, ratio);
+    }
+    record[0] = S; record[1] = norm; record[2] = Dc; record[3] = finite ? 0.0 : 1.0;
+  }
+}
+
+// a non-finite step: the gradient counts as zero on the trainable slices (every block reads the flag; 0: nothing to do)
+__global__ __launch_bounds__(256) void grad_zero_if_kernel(float* __restrict__ g, ClipRanges r, const double* __restrict__ record) {
+  if (record[3] == 0.0) return;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (int k = 0; k < r.n; ++k) {
+    const long lo = r.lo[k], hi = r.hi[k];
+    const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);
+    const long n4 = (b - a) >> 2;
+    float4* g4 = reinterpret_cast<float4*>(g + a);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+      const int t = threadIdx.x;
+      const long j = t < 4 ? lo + t : b + (t - 4);
+      if (t < 4 ? j < a : j < hi) g[j] = 0.f;
+    }
+  }
+}
+
+// the grid of the two passes over g, from n alone (the RMSprop pass's sizing): also the number of partials
+static int grad_clip_grid(long n) { return (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 2048); }
+size_t grad_clip_workspace_bytes(long n) { return (size_t)grad_clip_grid(std::max<long>(n, 0)) * sizeof(double); }
+
+int grad_clip(float* g, long n, const long long* ranges_host, int nranges, double divisor, const double* divisor_dev, double clip_norm,
+              double* record, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  FR_CHECK(g && record && workspace, "grad_clip: NULL gradient, record or workspace");
+  FR_CHECK(n >= 0, "grad_clip: bad length %ld", n);
+  FR_CHECK(((uintptr_t)g & 15) == 0, "grad_clip: the gradient must be 16-byte aligned");
+  FR_CHECK((((uintptr_t)record | (uintptr_t)workspace | (uintptr_t)divisor_dev) & 7) == 0,
+           "grad_clip: the record, the workspace and the device divisor must be 8-byte aligned");
+  FR_CHECK(workspace_bytes >= grad_clip_workspace_bytes(n), "grad_clip: workspace of %zu bytes, %zu needed", workspace_bytes,
+           grad_clip_workspace_bytes(n));
+  FR_CHECK(divisor_dev || divisor > 0.0, "grad_clip: the divisor must be positive (1: nothing to scale)");   // (NaN fails too)
+  FR_CHECK(clip_norm == clip_norm && clip_norm < __builtin_huge_val(), "grad_clip: clip_norm must be a finite number (<= 0: no clipping)");
+  FR_CHECK(ranges_host || nranges == 0, "grad_clip: %d ranges without a range list", nranges);
+  FR_CHECK(nranges >= 0 && nranges <= GRAD_CLIP_MAX_RANGES, "grad_clip: %d ranges (at most %d)", nranges, GRAD_CLIP_MAX_RANGES);
+  ClipRanges r;
+  r.n = 0;
+  if (!ranges_host) {
+    r.n = 1; r.lo[0] = 0; r.hi[0] = n;
+  } else {
+    long prev = 0;
+    for (int k = 0; k < nranges; ++k) {
+      const long lo = ranges_host[2 * k], hi = ranges_host[2 * k + 1];
+      FR_CHECK(lo >= 0 && lo <= hi && hi <= n, "grad_clip: bad range [%ld, %ld) of %ld elements", lo, hi, n);
+      FR_CHECK(lo >= prev, "grad_clip: the ranges must be sorted and must not overlap ([%ld, %ld) after an end of %ld)", lo, hi, prev);
+      prev = hi;
+      if (lo < hi) { r.lo[r.n] = lo; r.hi[r.n] = hi; ++r.n; }
+    }
+  }
+  long covered = 0;
+  for (int k = 0; k < r.n; ++k) covered += r.hi[k] - r.lo[k];
+  const int grid = grad_clip_grid(n);
+  double* partial = static_cast<double*>(workspace);
+  FR_LAUNCH(KC_OPTIM, 0, covered * 4.0, s, grad_sumsq_kernel, dim3(grid), dim3(256), 0, g, r, partial);
+  FR_LAUNCH_CHECK();
+  FR_LAUNCH(KC_OPTIM, 0, grid * 8.0, s, grad_clip_finish_kernel, dim3(1), dim3(256), 0, partial, grid, divisor, divisor_dev, clip_norm, record);
+  FR_LAUNCH_CHECK();
+  FR_LAUNCH(KC_OPTIM, 0, 0.0, s, grad_zero_if_kernel, dim3(grid), dim3(256), 0, g, r, record);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }

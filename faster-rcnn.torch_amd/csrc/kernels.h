@@ -157,14 +157,20 @@ int rmsprop_step(float* x, float* g, float* m, long n, float lr, float alpha, fl
 // the same step on elements [lo, hi) only (any bounds; the vectors' bases 16-byte aligned): bit-identical to what rmsprop_step
 // leaves in those elements
 int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, float alpha, float eps, float gscale, bool scale_first,
-                  hipStream_t s);
+                  hipStream_t s, const double* gcount_dev = nullptr);
 // optim.sgd / optim.nag (main.lua:122-124,134-135) on elements [lo, hi) (slice: the slice kernel, any bounds) or on the whole
-// vector [0, hi) (lo = 0; gcount_dev: the divisor of gradient:div read on the device).  gscale = 1 and no gcount_dev: g unscaled.
+// vector [0, hi) (lo = 0); gcount_dev: the divisor of gradient:div read on the device (either form).  gscale = 1 and no gcount_dev: g unscaled.
 int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s);
 int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, bool first, hipStream_t s);
 int nag_lookahead(float* x, const float* v, long n, float mom, hipStream_t s);
+// the gradient guard (include/frcnn_hip.h "gradient-norm clipping"): the sum of squares of g over `ranges`, the clipped divisor
+// and the skip flag into record[4], g zero-filled over `ranges` when the sum is not finite.  Three launches on s.
+constexpr int GRAD_CLIP_MAX_RANGES = 16;
+size_t grad_clip_workspace_bytes(long n);
+int grad_clip(float* g, long n, const long long* ranges_host, int nranges, double divisor, const double* divisor_dev, double clip_norm,
+              double* record, void* workspace, size_t workspace_bytes, hipStream_t s);
 int nag_lookahead_slice(float* x, const float* v, long lo, long hi, float mom, hipStream_t s);
 
 // ---------------------------------------------------------------- anchor nets, sampled positions only (heads.hip)

@@ -271,10 +271,15 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     scratch = _Scratch()
     pinned = _PinnedRing()
     import torch
-    acc_t = torch.zeros(8, dtype=torch.float64, device="cuda")       # the accumulators of objective.lua:52-58
+    # the accumulators of objective.lua:52-58, and behind them the gradient guard's record {S, norm, D', skipped}
+    # (frcnn_grad_clip, queued by the optimisers of utilities when asked for): one device vector, so that a guarded step
+    # reads both back in one copy
+    acc_all = torch.zeros(12, dtype=torch.float64, device="cuda")
+    acc_t = acc_all[:8]
     acc_dev = DeviceTensor(acc_t.data_ptr(), (8,), np.float64, owner=acc_t)
     acc_pin = torch.zeros(8, dtype=torch.float64).pin_memory()
     acc_event = torch.cuda.Event()
+    guard = dict(armed=False, deferred=False, divisor=None, pin=None)
     L = _lib.load()
     # Data parallel, device tail: the four example counts of objective.lua:194-198 are host-side numbers known before
     # any kernel runs.  They are uploaded into the unused slots 2, 3, 6, 7 of the accumulator vector at the start of the
@@ -367,6 +372,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         caller may queue more work (the optimiser step) before it looks at the loss."""
         # staged training (cfg.train, read at every call; validated before anything is queued): the library skips the frozen
         # parts' work (frcnn_model_set_trainable), this pass skips a disabled stage, and the optimiser updates `ranges` only
+        guarded, guard["armed"] = guard["armed"], False   # (the optimiser armed the gradient guard for this very pass)
+        guard["deferred"] = False
+        guard["divisor"] = None
         frozen_blocks, proposal, classification, ranges = stage_ranges()
         _lib.call("frcnn_model_set_trainable", native.h, frozen_blocks, int(proposal), int(classification))
         stage[0] = ranges
@@ -534,7 +542,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                     pnet.backward_heads_join()
                     lo, hi = pnet.heads_param_range()
                     _probe_mark("anchor nets", lo, hi, "frcnn_pnet_backward_heads_join (the anchor nets' streams)")
-            if last and defer and _dist() is None:
+            if last and defer and _dist() is None and not guarded:
+                # (a guarded step reads the accumulators with the guard's record, behind the backward pass: guard_queued)
                 # the eight statistics are final before the backbone's backward pass: their read-back is queued
                 # here, so the caller's wait ends mid-step and the host queues the next step while this one
                 # is still running (the device never drains between steps)
@@ -605,14 +614,19 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             for pnd in pending:
                 pnd[2].wait()           # RCCL: the current stream waits, the host does not
             acc_work.wait()
-            acc_pin.copy_(acc_t, non_blocking=True)
-            acc_event.record()
-            fin = lambda: finish(None, None, (), True, reduced=True)
-            return (fin, DeviceDivisor(acc_dev.ptr + 2 * 8, acc_t))   # slot 2 = the all-reduced cls_count (:200)
-        if single and defer:
-            if not early_copy:
+            if not guarded:
                 acc_pin.copy_(acc_t, non_blocking=True)
                 acc_event.record()
+            fin = lambda: finish(None, None, (), True, reduced=True)
+            guard["deferred"] = guarded
+            guard["divisor"] = DeviceDivisor(acc_dev.ptr + 2 * 8, acc_all)
+            return (fin, DeviceDivisor(acc_dev.ptr + 2 * 8, acc_t))   # slot 2 = the all-reduced cls_count (:200)
+        if single and defer:
+            if not early_copy and not guarded:
+                acc_pin.copy_(acc_t, non_blocking=True)
+                acc_event.record()
+            guard["deferred"] = guarded
+            guard["divisor"] = float(cls_count) if cls_count > 0 else None
             fin = lambda: finish(None, counts, pending, single, staged=(classification, ranges))
             if eager is not None:
                 assert cls_count == 0 or eager["gscale"] == 1.0 / cls_count, "example count bookkeeping diverged"
@@ -621,10 +635,13 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         if defer == "fold" and not single:   # the all-reduced count is known after finish(): scaling left to the caller
             res = finish(acc_dev.numpy(), counts, pending, single, fold=True, staged=(classification, ranges))
             gs = dp_gscale[0]
-            return ((lambda: res), gs) if gs is not None else (lambda: res)
+            guard["divisor"] = dp_count[0]
+            fin = (lambda: (guard_stats(acc_all[8:12].cpu().numpy()), res)[1]) if guarded else (lambda: res)   # (this tail waits anyway)
+            return (fin, gs) if gs is not None else fin
         return (lambda r: (lambda: r))(finish(acc_dev.numpy(), counts, pending, single, staged=(classification, ranges)))
 
     dp_gscale = [None]
+    dp_count = [None]    # the all-reduced cls_count behind dp_gscale, as the gradient guard's divisor
     packs_promise = [None]   # weights._version at the moment every pack group had been renewed beside a pass (else None)
     debug = dict(scratch=scratch, E=0)
     next_batch = [None]
@@ -643,7 +660,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 for xb in next_batch[0]:   # ... and its example tables are packed (host work with no device input)
                     prepared[id(xb)] = (xb, prepare_examples(xb))
             acc_event.synchronize()
-            a = acc_pin.numpy().copy()
+            a = (guard["pin"] if guard["deferred"] else acc_pin).numpy().copy()
         if counts is None:   # device tail: the (all-reduced) counts sit in the slots the kernels leave alone
             counts = (a[2], a[3], a[6], a[7])
         cls_count, reg_count, creg_count, ccls_count = counts
@@ -651,10 +668,11 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         if not reduced:   # (asynchronous data-parallel tail: gradient, accumulators and counts are already summed)
             tot = allreduce_gradient_and_stats(gradient, tot, pending, staged[1])  # DP: no-op for a single process
         cls_loss, reg_loss, cls_count, reg_count, creg_loss, creg_count, ccls_loss, ccls_count = tot
-        dp_gscale[0] = None
+        dp_gscale[0] = dp_count[0] = None
         if not single and cls_count > 0:
             if fold:
                 dp_gscale[0] = 1.0 / cls_count
+                dp_count[0] = float(cls_count)
             else:
                 _lib.call("frcnn_scale", ptr(gradient), gradient.numel(), 1.0 / cls_count, stream_ptr())  # :200
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -668,7 +686,37 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             print("prop: cls: %f (%d), reg: %f (%d); det: cls: %f, reg: %f" % (pcls, cls_count, preg, reg_count, dcls, dreg))
         stats["pcls"].append(pcls); stats["preg"].append(preg)  # :211-214
         stats["dcls"].append(dcls); stats["dreg"].append(dreg)
+        if guard["deferred"]:
+            guard_stats(a[8:12])
         return pcls + preg, gradient  # :216-217
+
+    def guard_stats(rec):
+        """the gradient guard ran in this step: its norm (before clipping) joins the loss series, a skipped step is counted"""
+        stats.setdefault("gnorm", []).append(float(rec[1]))
+        stats["skipped"] = stats.get("skipped", 0) + int(rec[3] != 0)
+
+    class _Guard(object):
+        """What guard_arm() hands the optimiser: ptr = the device address of the record double[4] {S, norm, D', skipped},
+        record = D' as the DeviceDivisor of the update that follows, divisor() = D of the pass just queued (None: nothing to
+        scale, a host count, or a DeviceDivisor), queued() = frcnn_grad_clip has been queued."""
+        ptr = acc_all.data_ptr() + 8 * 8
+        record = DeviceDivisor(acc_all.data_ptr() + 10 * 8, acc_all)
+
+        @staticmethod
+        def divisor():
+            return guard["divisor"]
+
+        @staticmethod
+        def queued():
+            if guard["deferred"]:   # the accumulators and the record travel to the host in one copy; finish() waits for it
+                if guard["pin"] is None:
+                    guard["pin"] = torch.zeros(12, dtype=torch.float64).pin_memory()
+                guard["pin"].copy_(acc_all, non_blocking=True)
+                acc_event.record()
+
+    def guard_arm():
+        guard["armed"] = True
+        return _Guard
 
     def lossAndGradient(w):
         return run(w, False)()
@@ -699,6 +747,10 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             eager["complete"] = complete
         return (r[0], gradient, r[1]) if isinstance(r, tuple) else (r, gradient, None)
     lossAndGradient.begin_fold = begin_fold
+    # the gradient guard (state.clipNorm / state.skipNonFinite of the optimisers): guard_arm() before begin_fold tells the coming
+    # pass to leave the read-back of its accumulators to the optimiser, which queues frcnn_grad_clip behind the pass and then
+    # calls queued(); finish() appends stats["gnorm"] and counts stats["skipped"]
+    lossAndGradient.guard_arm = guard_arm
     # staged training (cfg["train"]): trainable_ranges() validates the configuration as it stands and returns the slices a
     # pass would train (None: the whole vector) -- what optim.nag's look-ahead needs before the pass; pass_ranges() returns
     # those of the last pass queued.  The optimisers of utilities update these slices only.

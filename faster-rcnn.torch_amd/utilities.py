@@ -51,15 +51,72 @@ def _state_vector(x, opfunc):
     return torch.zeros_like(x) if staged_ranges(opfunc) is not None else torch.empty_like(x)
 
 
-def _step(opfunc, x, state, whole, update):
+def _guard_config(config, state, name):
+    """The gradient guard of a step (include/frcnn_hip.h "gradient-norm clipping"): config["clipNorm"] (a positive float: the L2
+    norm the gradient handed to the optimiser may have at most; None or 0: no clipping) and config["skipNonFinite"] (bool; implied
+    by a clipNorm: a step whose gradient holds an inf or a NaN treats it as zero).  Either one turns the guard on.
+    -> None (off: the step queues what it always did) or the clip norm as a float (0.0: record the norm, clip nothing).
+    Bad values raise ValueError, the guard together with state["eager"] FrcnnError, before any device call."""
+    clip = config.get("clipNorm")
+    skip = config.get("skipNonFinite")
+    if clip is not None:
+        if isinstance(clip, bool) or not isinstance(clip, (int, float, np.integer, np.floating)):
+            raise ValueError("optim.%s: clipNorm must be a number, not %r" % (name, clip))
+        clip = float(clip)
+        if clip != clip or clip < 0 or clip == float("inf"):
+            raise ValueError("optim.%s: clipNorm must be a finite number >= 0 (0: no clipping), not %r" % (name, clip))
+    if skip is not None and not isinstance(skip, (bool, np.bool_)):
+        raise ValueError("optim.%s: skipNonFinite must be a boolean, not %r" % (name, skip))
+    if not clip and not skip:
+        return None
+    if state.get("eager", EAGER_DEFAULT):
+        raise _lib.FrcnnError("optim.%s: clipNorm / skipNonFinite cannot be combined with the eager update: its slice-by-slice "
+                              "update starts before the gradient's norm exists" % name)
+    return clip or 0.0
+
+
+def _guard_queue(state, x, dfdx, ranges, divisor, clip, record_ptr):
+    """frcnn_grad_clip over `ranges` of dfdx (None: the whole vector) on the current stream; divisor None, a host count or a
+    DeviceDivisor.  The workspace (and, without an objective that owns one, the record) lives in state["_guard"]."""
+    import ctypes as C
+    import torch
+    n = x.numel()
+    own = state.get("_guard")
+    if own is None or own["n"] != n or own["ws"].device != x.device:
+        nbytes = _lib.load().frcnn_grad_clip_workspace_bytes(n)
+        own = state["_guard"] = dict(n=n, ws=torch.empty(nbytes // 8, dtype=torch.float64, device=x.device),
+                                     record=torch.zeros(4, dtype=torch.float64, device=x.device))
+    if record_ptr is None:
+        record_ptr = own["record"].data_ptr()
+    flat = None
+    if ranges is not None:
+        flat = (C.c_longlong * (2 * len(ranges)))(*[int(b) for r in ranges for b in r])
+    ddev = ptr(divisor.ptr) if hasattr(divisor, "ptr") else None
+    dhost = 1.0 if divisor is None or ddev is not None else float(divisor)
+    _lib.call("frcnn_grad_clip", ptr(dfdx), n, flat, 0 if ranges is None else len(ranges), dhost, ddev, clip,
+              C.c_void_p(record_ptr), ptr(own["ws"]), own["ws"].numel() * 8, stream_ptr())
+    return record_ptr
+
+
+def _step(opfunc, x, state, whole, update, guard=None):
     """One optimiser step around opfunc (main.lua:133-135), the update queued by the optimiser:
     whole(dfdx, gscale) updates the whole vector, gscale None (nothing to scale), a float (gradient:div(n), objective.lua:200,
     folded into the update's pass) or a DeviceDivisor (data parallel: the all-reduced count, still on the device);
     update(w, g, lo, hi, gscale, stream) is the same update on elements [lo, hi) (gscale 1: unscaled).
     Staged training (create_objective's cfg["train"]): only the slices the pass published (pass_ranges) are updated; a frozen
     slice keeps its weights and its optimiser state bit for bit, as if it had never been handed to the optimiser.
+    guard (from _guard_config; None: off): frcnn_grad_clip is queued between the pass and the update, and the update runs with the
+    device divisor D' of the guard's record (update() then receives a DeviceDivisor).  With create_objective's closure the record
+    lives beside its accumulators and finish() reports stats["gnorm"] / stats["skipped"]; with a plain opfunc D = 1 and the
+    record stays on the device in state["_guard"]["record"].
     Returns x, [f(x)] like the Lua functions."""
     begin = getattr(opfunc, "begin_fold", None)
+    armed = None
+    if guard is not None and begin is not None:
+        arm = getattr(opfunc, "guard_arm", None)
+        if arm is None:
+            raise _lib.FrcnnError("clipNorm / skipNonFinite: this objective keeps no record for the gradient guard (no guard_arm)")
+        armed = arm()
     timing = state.get("_timing")     # bench.py: seconds the host spends queueing a step / waiting for its statistics
     if timing is not None:
         import time
@@ -68,10 +125,14 @@ def _step(opfunc, x, state, whole, update):
         # and gradient:div(n) rides on the update's own pass over the vectors.  state["eager"] (default off: measured neutral on
         # one GPU, EXPERIMENTS.md round 6 -- the backward pass has no idle registers for the update to run in): the pass may
         # apply this very step slice by slice, beside its own backward half, as slices of the gradient become final
-        eager = dict(update=update) if state.get("eager", EAGER_DEFAULT) else None
+        eager = dict(update=update) if state.get("eager", EAGER_DEFAULT) else None   # (never with the guard: _guard_config)
         finish, dfdx, gscale = begin(x, eager) if eager is not None else begin(x)
         pass_ranges = getattr(opfunc, "pass_ranges", None)
         ranges = pass_ranges() if pass_ranges is not None else None
+        if armed is not None:
+            _guard_queue(state, x, dfdx, ranges, armed.divisor(), guard, armed.ptr)
+            armed.queued()
+            gscale = armed.record
         if eager is not None and "done" in eager:
             # what the pass has not updated (the shallowest block: its gradients end the pass; everything, for an image without
             # examples) -- of the trainable slices -- on the caller's stream, followed by the packs made from it
@@ -80,9 +141,7 @@ def _step(opfunc, x, state, whole, update):
                 eager["slice"](lo, hi, stream_ptr())
             eager["complete"]()
         elif ranges is not None:
-            if hasattr(gscale, "ptr"):
-                raise _lib.FrcnnError("staged training: the slice updates take a host divisor")
-            for lo, hi in ranges:
+            for lo, hi in ranges:   # (gscale: a host factor, or a DeviceDivisor -> the _slice_dev forms)
                 update(x, dfdx, lo, hi, 1.0 if gscale is None else gscale, stream_ptr())
         else:
             whole(dfdx, gscale)
@@ -93,6 +152,11 @@ def _step(opfunc, x, state, whole, update):
             timing["enqueue"] += t_q - t_in; timing["wait"] += time.perf_counter() - t_q; timing["steps"] += 1
         return x, [fx]
     fx, dfdx = opfunc(x)
+    if guard is not None:
+        from .objective import DeviceDivisor
+        rec = _guard_queue(state, x, dfdx, None, None, guard, None)
+        whole(dfdx, DeviceDivisor(rec + 2 * 8, state["_guard"]["record"]))
+        return x, [fx]
     whole(dfdx, None)
     return x, [fx]
 
@@ -110,6 +174,7 @@ def rmsprop(opfunc, x, state):
     Returns x, [f(x)] like the Lua function (main.lua:133)."""
     import torch
     lr = state.get("learningRate", 1e-2); alpha = state.get("alpha", 0.99); eps = state.get("epsilon", 1e-8)
+    guard = _guard_config(state, state, "rmsprop")
     if "m" not in state:
         state["m"] = torch.zeros_like(x)
     m = state["m"]
@@ -123,8 +188,11 @@ def rmsprop(opfunc, x, state):
             _lib.call("frcnn_scale_rmsprop", ptr(x), ptr(dfdx), gscale, ptr(m), x.numel(), lr, alpha, eps, stream_ptr())
 
     def update(w, g, lo, hi, gscale, on):
-        _lib.call("frcnn_scale_rmsprop_slice", ptr(w), ptr(g), gscale, ptr(m), lo, hi, lr, alpha, eps, on)
-    return _step(opfunc, x, state, whole, update)
+        if hasattr(gscale, "ptr"):
+            _lib.call("frcnn_scale_rmsprop_slice_dev", ptr(w), ptr(g), ptr(gscale.ptr), ptr(m), lo, hi, lr, alpha, eps, on)
+        else:
+            _lib.call("frcnn_scale_rmsprop_slice", ptr(w), ptr(g), gscale, ptr(m), lo, hi, lr, alpha, eps, on)
+    return _step(opfunc, x, state, whole, update, guard)
 
 
 def _get(config, key, default):
@@ -149,6 +217,7 @@ def sgd(opfunc, x, config, state=None):
     wd = _get(config, "weightDecay", 0); mom = _get(config, "momentum", 0)
     damp = _get(config, "dampening", mom); nesterov = bool(_get(config, "nesterov", False))
     _no_per_parameter(config, "sgd")
+    guard = _guard_config(config, state, "sgd")
     if nesterov and not (mom > 0 and damp == 0):
         raise ValueError("optim.sgd: Nesterov momentum requires a momentum and zero dampening")
     nevals = state.get("evalCounter") or 0
@@ -164,9 +233,12 @@ def sgd(opfunc, x, config, state=None):
         _lib.call("frcnn_sgd", ptr(x), ptr(dfdx), ptr(v), x.numel(), gs, gcount, clr, *args, stream_ptr())
 
     def update(w, g, lo, hi, gscale, on):
-        _lib.call("frcnn_sgd_slice", ptr(w), ptr(g), ptr(v), lo, hi, gscale, clr, *args, on)
+        if hasattr(gscale, "ptr"):
+            _lib.call("frcnn_sgd_slice_dev", ptr(w), ptr(g), ptr(v), lo, hi, ptr(gscale.ptr), clr, *args, on)
+        else:
+            _lib.call("frcnn_sgd_slice", ptr(w), ptr(g), ptr(v), lo, hi, gscale, clr, *args, on)
     try:
-        r = _step(opfunc, x, state, whole, update)
+        r = _step(opfunc, x, state, whole, update, guard)
     except BaseException:
         if first:
             del state["dfdx"]
@@ -188,6 +260,7 @@ def nag(opfunc, x, config, state=None):
     if mom <= 0:
         raise ValueError("optim.nag: momentum must be positive for Nesterov Accelerated Gradient")
     _no_per_parameter(config, "nag")
+    guard = _guard_config(config, state, "nag")
     nevals = state.get("evalCounter") or 0
     clr = lr / (1 + nevals * lrd)
     first = "dfdx" not in state
@@ -211,9 +284,12 @@ def nag(opfunc, x, config, state=None):
         _lib.call("frcnn_nag", ptr(x), ptr(dfdx), ptr(v), x.numel(), gs, gcount, clr, *args, stream_ptr())
 
     def update(w, g, lo, hi, gscale, on):
-        _lib.call("frcnn_nag_slice", ptr(w), ptr(g), ptr(v), lo, hi, gscale, clr, *args, on)
+        if hasattr(gscale, "ptr"):
+            _lib.call("frcnn_nag_slice_dev", ptr(w), ptr(g), ptr(v), lo, hi, ptr(gscale.ptr), clr, *args, on)
+        else:
+            _lib.call("frcnn_nag_slice", ptr(w), ptr(g), ptr(v), lo, hi, gscale, clr, *args, on)
     try:
-        r = _step(opfunc, x, state, whole, update)
+        r = _step(opfunc, x, state, whole, update, guard)
     except BaseException:
         if first:
             del state["dfdx"]

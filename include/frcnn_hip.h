@@ -289,6 +289,39 @@ int frcnn_nag(float *x, float *g, float *v, long long n, float gscale, const dou
               float mom, int first, void *stream);
 int frcnn_nag_slice(float *x, float *g, float *v, long long lo, long long hi, float gscale, float clr, float wd, float mom,
                     int first, void *stream);
+/* The slice forms with the divisor read from the device (gscale = 1 / *gcount_dev, a count of 0 leaves g unscaled): what
+ * frcnn_scale_rmsprop_dev / frcnn_sgd / frcnn_nag with that gcount_dev do to elements [lo, hi), bit for bit. */
+int frcnn_scale_rmsprop_slice_dev(float *x, float *g, const double *gcount_dev, float *m, long long lo, long long hi,
+                                  float lr, float alpha, float eps, void *stream);
+int frcnn_sgd_slice_dev(float *x, float *g, float *v, long long lo, long long hi, const double *gcount_dev, float clr,
+                        float wd, float mom, float one_minus_damp, int nesterov, int first, void *stream);
+int frcnn_nag_slice_dev(float *x, float *g, float *v, long long lo, long long hi, const double *gcount_dev, float clr,
+                        float wd, float mom, int first, void *stream);
+
+/* ---- gradient-norm clipping and the non-finite-step guard (not in the reference: main.lua:133-135 applies whatever the pass
+ * produced).  Queued between the pass (and the all-reduce, when data parallel) and the optimiser's update; off unless a host
+ * asks for it.  g = the flat gradient, T = the trainable slices of the pass (ranges_host: nranges sorted, disjoint pairs
+ * {lo, hi}, hi exclusive, any bounds, empty ones allowed, at most 16; NULL: the whole vector), D = the divisor of
+ * gradient:div (objective.lua:200): *divisor_dev when that is not NULL (the all-reduced count), else `divisor` (positive; 1: nothing
+ * to scale); a device count that is not positive counts as 1, as in the optimiser kernels.
+ *   S     = sum over T of (double)g[i] * (double)g[i].  Each product is exact in fp64; the sum is taken in fp64 in a fixed
+ *           order that depends on n and the slice bounds only (per-block partials, then one block folds them; no atomics):
+ *           two calls on the same data give the same bits, and so do the ranks of a data-parallel step.
+ *   norm  = sqrt(S) / D: the L2 norm of the gradient the optimiser is about to see.
+ *   D'    = D * max(1, norm / clip_norm) in fp64, each operation correctly rounded; clip_norm <= 0: D' = D (norm recorded,
+ *           nothing clipped).  A CLIPPED STEP IS the optimiser's existing update with the device divisor D':
+ *           frcnn_scale_rmsprop_dev / frcnn_sgd / frcnn_nag (or their _slice_dev forms) handed record_dev + 2.
+ *   S not finite (inf or NaN; fp32 values as large as 3e38 have finite squares in fp64): the step treats the gradient as zero --
+ *           g is overwritten with zeros on T (untouched elsewhere), D' = D, skipped = 1.  optim.rmsprop then leaves x as it
+ *           is and decays m; optim.sgd / optim.nag continue on their momentum (and weight decay) alone.
+ *   record_dev: double[4] = {S, norm, D', skipped} on the device; a host reads it when it reads its loss sums.
+ * workspace: frcnn_grad_clip_workspace_bytes(n) bytes of device memory (the per-block partials).  Three launches on `stream`;
+ * argument errors are reported before anything is queued. */
+size_t frcnn_grad_clip_workspace_bytes(long long n);
+int frcnn_grad_clip(float *g, long long n, const long long *ranges_host, int nranges, double divisor,
+                    const double *divisor_dev, double clip_norm, double *record_dev, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
 /* optim.nag's look-ahead, before opfunc is called (when state.dfdx exists): x += mom*v.  A host that holds a pack promise
  * (frcnn_pnet_refresh_packs below) withdraws it afterwards with frcnn_pnet_invalidate_packs: the weights have changed. */
 int frcnn_nag_lookahead(float *x, const float *v, long long n, float mom, void *stream);

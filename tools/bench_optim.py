@@ -1,6 +1,8 @@
 """The optimiser passes alone on vgg_small's flat vector (26 784 106 parameters): HIP-event time of each whole-vector form of
 optim.rmsprop / optim.sgd / optim.nag (main.lua:122-124,133-135) and the effective bytes/s of the fp32 streams it moves
-(read x, g[, v]; write x[, g][, v]).  python tools/bench_optim.py [--n N] [--reps R] [--json FILE]"""
+(read x, g[, v]; write x[, g][, v]); the gradient guard (frcnn_grad_clip: one more read of g, two small launches behind it)
+alone and in front of each optimiser's pass, which then takes its divisor from the guard's record.
+python tools/bench_optim.py [--n N] [--reps R] [--json FILE]"""
 import argparse
 import json
 import os
@@ -13,7 +15,15 @@ import frcnn_amd as F
 
 def forms(x, g, v, gc, n, s):
     """(name, fp32 streams per element, launch) -- the streams as the kernels move them"""
+    import torch
     P = F.ptr
+    wsb = F._lib.load().frcnn_grad_clip_workspace_bytes(n)
+    ws = torch.empty(wsb // 8, dtype=torch.float64, device="cuda")
+    rec = torch.zeros(4, dtype=torch.float64, device="cuda")
+    # a clip norm far above the gradient's: D' = D = 1 (the device-divisor forms always run the scaled pass; g keeps its values)
+    clip = lambda: F._lib.call("frcnn_grad_clip", P(g), n, None, 0, 1.0, None, 1e30, P(rec), P(ws), wsb, s)
+    dp = P(rec[2:])
+    guarded = lambda fn: (lambda: (clip(), fn()))
     sc = 1.0 + 2.0 ** -23
     sgd = lambda gs, gcount, wd, mom, omd, nest, first: (
         lambda: F._lib.call("frcnn_sgd", P(x), P(g), P(v) if mom else None, n, gs, gcount, 1e-9, wd, mom, omd, nest, first, s))
@@ -29,6 +39,11 @@ def forms(x, g, v, gc, n, s):
         ("nag nag_state, scaled", 6, nag(sc, 0.0, 0)),
         ("nag nag_state, unscaled", 5, nag(1.0, 0.0, 0)),
         ("nag look-ahead", 3, lambda: F._lib.call("frcnn_nag_lookahead", P(x), P(v), n, 1e-9, s)),
+        ("grad_clip alone", 1, clip),
+        ("rmsprop, device divisor", 6, lambda: F._lib.call("frcnn_scale_rmsprop_dev", P(x), P(g), P(gc), P(v), n, 1e-9, 0.99, 1e-8, s)),
+        ("grad_clip + rmsprop", 7, guarded(lambda: F._lib.call("frcnn_scale_rmsprop_dev", P(x), P(g), dp, P(v), n, 1e-9, 0.99, 1e-8, s))),
+        ("grad_clip + sgd sgd_state", 7, guarded(sgd(1.0, dp, 5e-4, 0.9, 0.1, 0, 0))),
+        ("grad_clip + nag nag_state", 7, guarded(lambda: F._lib.call("frcnn_nag", P(x), P(g), P(v), n, 1.0, dp, 1e-9, 0.0, 0.9, 0, s))),
     ]
 
 
