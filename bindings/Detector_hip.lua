@@ -154,3 +154,201 @@ function Detector:detect(input)                                         -- Detec
 
   return winners
 end
+
+-- Detector:detect_batch(inputs, shared_cnet) -- detect() for a list of frames of ONE size: a list with one entry per frame,
+-- in order, each what detect(frame) returns.  Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
+-- head maps and last feature map are copied to the frame's slot), then ONE scan, ONE segmented NMS, per frame with
+-- candidates the pooling / classification net / class test of detect(), ONE segmented per-class NMS and ONE gather; the
+-- host waits twice per chunk instead of twice per frame.  Bit-identical to detect() frame by frame.
+-- shared_cnet = true: ONE classification-net pass over the candidates of all frames of a chunk (frame b's rows at the prefix
+-- sum of the candidate counts); everything up to the pooled rows stays bit-identical, the net's outputs agree with detect()'s
+-- within the net's own error only (input scale and Linear form depend on the whole tensor / the row count).
+-- 1:1 with Detector.detect_batch of the Python host mirror.
+Detector.BATCH = 8
+
+function Detector:detect_batch(inputs, shared_cnet)
+  local nframes = #inputs
+  for i = 2, nframes do                                                 -- refused before anything is queued
+    local a, b = inputs[1]:size(), inputs[i]:size()
+    if a[1] ~= b[1] or a[2] ~= b[2] or a[3] ~= b[3] then
+      error('Detector:detect_batch: frames of different sizes in one call')
+    end
+  end
+  local results = {}
+  local lo = 1
+  while lo <= nframes do
+    local chunk = {}
+    for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do chunk[#chunk + 1] = inputs[i] end
+    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet)) do results[#results + 1] = winners end
+    lo = lo + Detector.BATCH
+  end
+  return results
+end
+
+function Detector:detect_chunk(frames, shared)
+  local model = self.model
+  local cfg = model.cfg
+  local pnet = model.pnet
+  local cnet = model.cnet
+  local kh, kw = cfg.roi_pooling.kh, cfg.roi_pooling.kw
+  local bgclass = cfg.class_count + 1
+  local ncls = cfg.class_count + 1
+  local D = kh * kw * model.layers[#model.layers].filters
+  local scratch = self.scratch
+  local B = #frames
+
+  -- counts (device int[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
+  local cnt = ffi.cast('int*', scratch('b_counts', 16 * B).ptr)
+  local input_size = frames[1]:size()
+  pnet:evaluate()
+  -- ---- 1. per frame: the proposal net; its outputs are copied to the frame's slot (the net reuses its output buffers)
+  local Hs, Ws, maps, hoff = ffi.new('int[4]'), ffi.new('int[4]'), ffi.new('const float*[4]'), { 0 }
+  local slot, fslot, heads, fms, fs
+  for b = 0, B - 1 do
+    local outputs = pnet:forward(hip.to_device(frames[b + 1]))
+    if b == 0 then
+      for i = 1, 4 do
+        local s = outputs[i]:size()
+        Hs[i - 1], Ws[i - 1] = s[2], s[3]
+        hoff[i + 1] = hoff[i] + math.floor((s[1] * s[2] * s[3] + 63) / 64) * 64
+      end
+      slot = hoff[5]
+      fs = outputs[self.nheads + 1]:size()
+      fslot = math.floor((fs[1] * fs[2] * fs[3] + 63) / 64) * 64
+      heads = ffi.cast('float*', scratch('b_heads', 4 * B * slot).ptr)
+      fms = ffi.cast('float*', scratch('b_fm', 4 * B * fslot).ptr)
+      for i = 0, 3 do maps[i] = heads + hoff[i + 1] end
+    end
+    for i = 1, 4 do
+      check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[i], outputs[i].ptr, 4 * 18 * Hs[i - 1] * Ws[i - 1], nil))
+    end
+    check(C.frcnn_memcpy_d2d(fms + b * fslot, outputs[self.nheads + 1].ptr, 4 * fs[1] * fs[2] * fs[3], nil))
+  end
+  -- ---- 2. ONE scan over the B slots: frame b's matches at rows [b * cap, b * cap + n_b)
+  local cap = 0
+  for i = 0, 3 do cap = cap + ASPECTS * Hs[i] * Ws[i] end
+  local wsb = tonumber(C.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B))
+  local ws = scratch('b_scan_ws', wsb)
+  local mp = ffi.cast('float*', scratch('b_match_p', 4 * B * cap).ptr)
+  local mi = ffi.cast('int*', scratch('b_match_idx', 16 * B * cap).ptr)
+  local mr = ffi.cast('double*', scratch('b_match_rect', 32 * B * cap).ptr)
+  local mb = ffi.cast('float*', scratch('b_match_box', 16 * B * cap).ptr)
+  check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap,
+                               mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
+  -- ---- 3. ONE segmented NMS, the match counts read from device memory, sized for the bound of detect()
+  local ncap = math.min(cap, 16384)
+  local nwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, ncap))
+  local nws = scratch('b_nms_ws', nwsb)
+  local dpick = ffi.cast('long long*', scratch('b_pick', 8 * B * cap).ptr)
+  check(C.frcnn_nms_device_batch(mb, B, cap, ncap, cnt, 4, 0.25, 0, 0, nil, dpick, cnt + B, nws.ptr, nwsb, nil))
+  local count = ffi.new('int[?]', 2 * B)
+  check(C.frcnn_memcpy_d2h(count, cnt, 8 * B, nil))                      -- ---- read-back 1 of 2: B pairs of counts
+  check(C.frcnn_stream_sync(nil))
+  local Rmax = 0
+  for b = 0, B - 1 do
+    if count[b] > cap then
+      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], cap))
+    end
+    if count[b] > ncap then                                             -- the frame repeats its NMS alone, as in detect()
+      local fwsb = tonumber(C.frcnn_nms_workspace_bytes(count[b]))
+      local fws = scratch('nms_ws_full', fwsb)
+      check(C.frcnn_nms_device(mb + 4 * b * cap, count[b], 4, 0.25, 0, 0, dpick + b * cap, cnt + B + b, fws.ptr, fwsb, nil))
+      check(C.frcnn_memcpy_d2h(count + B + b, cnt + B + b, 4, nil))
+      check(C.frcnn_stream_sync(nil))
+    end
+    if count[b] > 0 then Rmax = math.max(Rmax, count[B + b]) end
+  end
+  local results = {}
+  for b = 1, B do results[b] = {} end
+  if Rmax == 0 then return results end                                  -- :71, every frame
+  -- ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into its segment
+  cnet:evaluate()
+  local nl = #self.localizer.layers
+  local layers = ffi.new('int[?]', 6 * nl)
+  for i, l in ipairs(self.localizer.layers) do
+    local o = 6 * (i - 1)
+    layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
+  end
+  local dwins = ffi.cast('int*', scratch('wins', 16 * Rmax).ptr)
+  local dcls = ffi.cast('int*', scratch('cls', 4 * Rmax).ptr)
+  local dconf = ffi.cast('float*', scratch('conf', 4 * Rmax).ptr)
+  local dbb = ffi.cast('float*', scratch('b_bb5', 20 * B * Rmax).ptr)
+  local dkc = ffi.cast('int*', scratch('b_bbcls', 4 * B * Rmax).ptr)
+  local dkeep = ffi.cast('int*', scratch('b_keep_row', 4 * B * Rmax).ptr)
+  local dr2 = ffi.cast('double*', scratch('b_r2', 32 * B * Rmax).ptr)
+  -- first row of frame b in the shared pass's input / output: the prefix sum of the candidate counts
+  local row0, total = {}, 0
+  for b = 0, B - 1 do
+    if count[b] > 0 then
+      row0[b] = total
+      total = total + count[B + b]
+    end
+  end
+  local cbuf = ffi.cast('float*', shared and scratch('b_cinput', 4 * total * D).ptr or scratch('cinput', 4 * Rmax * D).ptr)
+  local function pooled(b)              -- ROI windows and ROI pooling of frame b -> its input rows
+    local R = count[B + b]
+    check(C.frcnn_roi_windows(mr + 4 * b * cap, dpick + b * cap, R, layers, nl, fs[2], fs[3], dwins, nil))
+    local cinput = hip.view(shared and (cbuf + row0[b] * D) or cbuf, { R, D })
+    check(C.frcnn_roi_pool_forward(fms + b * fslot, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
+    return cinput
+  end
+  local all_bbox, all_cls
+  if shared then
+    for b = 0, B - 1 do
+      if count[b] > 0 then pooled(b) end
+    end
+    local coutputs = cnet:forward(hip.view(cbuf, { total, D }))         -- :101, all frames
+    all_bbox, all_cls = ffi.cast('float*', coutputs[1].ptr), ffi.cast('float*', coutputs[2].ptr)
+  end
+  for b = 0, B - 1 do
+    local R = count[B + b]
+    if count[b] > 0 then
+      print(string.format('candidates: %d', R))                         -- :87
+      local bbox_ptr, cls_ptr
+      if shared then
+        bbox_ptr, cls_ptr = all_bbox + 4 * row0[b], all_cls + ncls * row0[b]
+      else
+        local coutputs = cnet:forward(pooled(b))                        -- :101
+        bbox_ptr, cls_ptr = coutputs[1].ptr, coutputs[2].ptr
+      end
+      check(C.frcnn_cnet_decode(cls_ptr, R, ncls, dcls, dconf, nil))
+      check(C.frcnn_detect_post(dcls, dconf, bbox_ptr, mr + 4 * b * cap, dpick + b * cap, R, bgclass, 0.2,
+                                dbb + 5 * b * Rmax, dkc + b * Rmax, dkeep + b * Rmax, dr2 + 4 * b * Rmax, cnt + 2 * B + b, nil))
+    else
+      check(C.frcnn_zero(cnt + 2 * B + b, 4, nil))                      -- no candidates: an empty segment of the per-class NMS
+    end
+  end
+  -- ---- 5. ONE segmented per-class NMS (one segment per frame), ONE gather of every frame's winner records behind a
+  --         header of the frame's four counts
+  local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, Rmax))
+  local cws = scratch('b_nms_ws2', cwsb)
+  local cpick = ffi.cast('long long*', scratch('b_wpick', 8 * B * Rmax).ptr)
+  check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 0.1, 0, 0, dkc, cpick, cnt + 3 * B, cws.ptr, cwsb, nil))
+  local out = ffi.cast('double*', scratch('b_winners', 128 * B * (Rmax + 1)).ptr)
+  check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb, dr2, dpick, cap, mp, mr, mi, out, nil))
+  local h = ffi.new('double[?]', 16 * B * (Rmax + 1))
+  check(C.frcnn_memcpy_d2h(h, out, 128 * B * (Rmax + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table
+  check(C.frcnn_stream_sync(nil))
+  for b = 0, B - 1 do
+    local tab = h + 16 * b * (Rmax + 1)
+    local nwin = ffi.cast('int*', tab)[3]
+    -- classes in ascending order (the reference iterates with pairs(): unspecified), pick order within a class
+    local byclass, classes = {}, {}
+    for q = 1, nwin do
+      local v = tab + 16 * q
+      local l, a, y, x = tonumber(v[12]), tonumber(v[13]), tonumber(v[14]), tonumber(v[15])
+      local det = { p = v[3], a = self.anchors:get(l, a, y, x), l = l, r = Rect.new(v[4], v[5], v[6], v[7]),
+                    r2 = Rect.new(v[8], v[9], v[10], v[11]), class = tonumber(v[0]), confidence = v[2] }
+      if not byclass[det.class] then
+        byclass[det.class] = {}
+        classes[#classes + 1] = det.class
+      end
+      table.insert(byclass[det.class], det)
+    end
+    table.sort(classes)
+    for _, ci in ipairs(classes) do
+      for _, x in ipairs(byclass[ci]) do table.insert(results[b + 1], x) end
+    end
+  end
+  return results
+end

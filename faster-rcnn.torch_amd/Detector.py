@@ -61,6 +61,64 @@ class _Detections(object):
         return len(self) > 0
 
 
+def _frame_shape(x):
+    """(3, H, W) of a frame as detect() accepts it, without touching the device."""
+    shp = tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+    if len(shp) != 3 or shp[0] != 3:
+        raise ValueError("detect_batch: expected 3xHxW frames, got %r" % (shp,))
+    return shp
+
+
+class _BatchRecord(object):
+    """One frame's entry of Detector.last_batch: reads like a dict with the keys n, idx, box, rect, p (the frame's scan rows),
+    pick (1-based candidate rows, pick order), cnet (dict bbox, cls; None for a frame without matches), kept; and pooled --
+    the classification net's input rows, kept only by a shared_cnet pass and only for the last chunk of a call (else None).
+    The arrays stay on the device and are fetched when they are looked at, like last_scan / last_pick / last_cnet of detect()."""
+    _KEYS = ("n", "idx", "box", "rect", "p", "pick", "cnet", "kept", "pooled")
+
+    def __init__(self, n, R, kept, dev):
+        self._v = dict(n=n, R=R, kept=kept)
+        self._dev = dev      # name -> DeviceTensor (views of the chunk's buffers until detach())
+        self._view = True
+
+    def detach(self):
+        """A private device copy of the frame's arrays (one allocation; the copies are queued on the stream, no wait): the
+        chunk's buffers are about to be reused by the next chunk of the same call."""
+        if not self._view:
+            return
+        self._view = False
+        self._dev.pop("pooled", None)     # (R x 13 824 floats a frame: not carried over)
+        off, total = {}, 0
+        for k, t in self._dev.items():
+            off[k] = total
+            total += (t.nbytes + 255) // 256 * 256
+        own = DeviceTensor.empty((max(total, 256),), np.uint8)
+        for k, t in list(self._dev.items()):
+            c = DeviceTensor(own.ptr + off[k], t.shape, t.dtype, owner=own)
+            if t.nbytes:
+                c.copy_(t)
+            self._dev[k] = c
+
+    def keys(self):
+        return list(self._KEYS)
+
+    def __contains__(self, k):
+        return k in self._KEYS
+
+    def __getitem__(self, k):
+        v = self._v
+        if k not in v:
+            if k not in self._KEYS:
+                raise KeyError(k)
+            if k == "pooled":
+                v[k] = self._dev[k].numpy() if k in self._dev else None
+            elif k == "cnet":
+                v[k] = dict(bbox=self._dev["bbox"].numpy(), cls=self._dev["cls"].numpy()) if "bbox" in self._dev else None
+            else:
+                v[k] = self._dev[k].numpy()
+        return v[k]
+
+
 class Detector(object):
     def __init__(self, model, static_weights=False):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
@@ -82,6 +140,7 @@ class Detector(object):
         self.verbose = False
         self.last_scan = None
         self._last = {}
+        self.last_batch = []
 
     def __del__(self):
         if getattr(self, "_host", None):
@@ -237,3 +296,188 @@ class Detector(object):
         # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
         order = np.argsort(rec[:, 0], kind="stable")
         return _Detections(rec[order], self.anchors)
+
+    BATCH = 8   # frames per chunk of detect_batch: bounds the memory of a call
+
+    def detect_batch(self, inputs, shared_cnet=False):
+        """detect() for a sequence of frames of one size: a list with one entry per frame, in order, each exactly what
+        detect(frame) returns.  The frames are processed in chunks of BATCH: the proposal net runs frame by frame, everything
+        between and after those passes once per chunk -- one scan, one segmented NMS, (per frame: pooling, classification net,
+        class test), one segmented per-class NMS, one gather -- and the host waits twice per chunk instead of twice per frame.
+        Results are bit-identical to detect(): every stage of a frame sees the inputs detect() gives it, through the same
+        kernels or through kernels that share their code.  last_batch holds one record per frame (_BatchRecord).
+        shared_cnet=True: ONE classification-net pass over the candidates of all frames of a chunk (frame b's rows at the
+        prefix sum of the candidate counts) instead of one per frame -- the large Linear streams its weights once per chunk.
+        Everything up to the pooled rows stays bit-identical to detect(); the net's outputs do NOT (the two-plane form scales
+        its input by the largest magnitude of the whole tensor, the Linear picks tile shape and arithmetic form by row
+        count): they agree with detect()'s within the net's own error (1e-3 bar), and winners follow from them."""
+        frames = list(inputs)
+        shapes = [_frame_shape(f) for f in frames]
+        if any(shp != shapes[0] for shp in shapes):
+            raise ValueError("detect_batch: frames of different sizes in one call: %s" % sorted(set(shapes)))
+        results, records = [], []
+        step = max(int(self.BATCH), 1)
+        for lo in range(0, len(frames), step):
+            for r in records:     # (the records of the previous chunk view buffers this chunk writes)
+                r.detach()
+            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet))
+            results += res
+            records += rec
+        self.last_batch = records
+        return results
+
+    def _detect_chunk(self, frames, shared):
+        model = self.model
+        cfg = model["cfg"]
+        pnet, cnet = model["pnet"], model["cnet"]
+        kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
+        bgclass = cfg["class_count"] + 1
+        ncls = cfg["class_count"] + 1
+        planes = model["layers"][-1]["filters"]
+        s = stream_ptr()
+        L = _lib.load()
+        B = len(frames)
+        i32 = np.int32
+
+        # counts (device int32[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
+        counts = self._buf("b_counts", (4, B), i32)
+        c_n, c_R, c_K, c_W = [C.c_void_p(counts.ptr + 4 * B * k) for k in range(4)]
+        # ---- 1. per frame: the proposal net; its head maps and last feature map go to the frame's slot (the model owns and
+        #         reuses its output buffers).  A chunk of ONE frame reads the model's buffers where they are, as detect() does.
+        pnet.evaluate()
+        heads = fms = None
+        for b, f in enumerate(frames):
+            inp = to_device(f)
+            _, H, W = inp.shape
+            outputs = pnet.forward(inp)
+            if heads is None:
+                hshape = [o.shape for o in outputs[:4]]
+                hoff = [0]
+                for shp in hshape:
+                    hoff.append(hoff[-1] + (int(np.prod(shp)) + 63) // 64 * 64)
+                slot = hoff[4]
+                fshape = outputs[-1].shape
+                fslot = (int(np.prod(fshape)) + 63) // 64 * 64
+                if B == 1:
+                    heads, fms = outputs, outputs[-1]
+                    break
+                heads = self._buf("b_heads", (B, slot))
+                fms = self._buf("b_fm", (B, fslot))
+            for i in range(4):
+                _lib.call("frcnn_memcpy_d2d", C.c_void_p(heads.ptr + 4 * (b * slot + hoff[i])), ptr(outputs[i]), outputs[i].nbytes, s)
+            _lib.call("frcnn_memcpy_d2d", C.c_void_p(fms.ptr + 4 * b * fslot), ptr(outputs[-1]), outputs[-1].nbytes, s)
+        # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b)
+        Hs = (C.c_int * 4)(*[shp[1] for shp in hshape])
+        Ws = (C.c_int * 4)(*[shp[2] for shp in hshape])
+        maps = (C.c_void_p * 4)(*[heads[i].ptr if B == 1 else heads.ptr + 4 * hoff[i] for i in range(4)])
+        cap = ASPECTS * sum(shp[1] * shp[2] for shp in hshape)
+        wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B)
+        ws = self._buf("b_scan_ws", (wsb,), np.uint8)
+        mp = self._buf("b_match_p", (B, cap)); mi = self._buf("b_match_idx", (B, cap, 4), i32)
+        mr = self._buf("b_match_rect", (B, cap, 4), np.float64); mb = self._buf("b_match_box", (B, cap, 4))
+        threshold = 0.95
+        _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, B, slot, ptr(self._aw), ptr(self._ah), float(W), float(H), threshold, cap,
+                  ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
+        # ---- 3. ONE segmented NMS (:74-85), the match counts read from device memory, sized for the bound of detect()
+        ncap = min(cap, self.NMS_FIRST_CAP)
+        wsb = L.frcnn_nms_batch_workspace_bytes(B, ncap)
+        ws = self._buf("b_nms_ws", (wsb,), np.uint8)
+        pick = self._buf("b_nms_pick", (B, cap), np.int64)
+        _lib.call("frcnn_nms_device_batch", ptr(mb), B, cap, ncap, c_n, 4, C.c_float(0.25), 0, 0, None, ptr(pick), c_R,
+                  ptr(ws), wsb, s)
+        nR = self._read(counts.ptr, 8 * B, i32)                                # ---- read-back 1 of 2: B pairs of counts
+        ns, Rs = [int(v) for v in nR[:B]], [int(v) for v in nR[B:]]
+        for b in range(B):
+            if ns[b] > cap:
+                raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (ns[b], threshold, cap))
+            if ns[b] > ncap:   # more matches than the bound: the frame repeats its NMS alone, as in detect()
+                wsb = L.frcnn_nms_workspace_bytes(ns[b])
+                ws = self._buf("nms_ws_full", (wsb,), np.uint8)
+                _lib.call("frcnn_nms_device", C.c_void_p(mb.ptr + 16 * b * cap), ns[b], 4, C.c_float(0.25), 0, 0,
+                          C.c_void_p(pick.ptr + 8 * b * cap), C.c_void_p(counts.ptr + 4 * (B + b)), ptr(ws), wsb, s)
+                Rs[b] = int(self._read(counts.ptr + 4 * (B + b), 4, i32)[0])
+        dev = []
+        for b in range(B):
+            n, R = ns[b], Rs[b]
+            dev.append(dict(p=DeviceTensor(mp.ptr + 4 * b * cap, (n,), np.float32, owner=mp),
+                            idx=DeviceTensor(mi.ptr + 16 * b * cap, (n, 4), i32, owner=mi),
+                            rect=DeviceTensor(mr.ptr + 32 * b * cap, (n, 4), np.float64, owner=mr),
+                            box=DeviceTensor(mb.ptr + 16 * b * cap, (n, 4), np.float32, owner=mb),
+                            pick=DeviceTensor(pick.ptr + 8 * b * cap, (R if n else 0,), np.int64, owner=pick)))
+        Rmax = max([Rs[b] for b in range(B) if ns[b] > 0] + [0])
+        if Rmax == 0:   # no frame has a match (:71)
+            return [[] for _ in range(B)], [_BatchRecord(ns[b], 0, 0, dev[b]) for b in range(B)]
+        # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into the frame's
+        #         segment (Rmax rows per frame) -- the launches detect() makes, on the frame's own rows
+        cnet.evaluate()
+        fmC, fmH, fmW = fshape
+        bbox_all = self._buf("b_bbox", (B, Rmax, 4)); cls_all = self._buf("b_cls_out", (B, Rmax, ncls))
+        bb = self._buf("b_bb", (B, Rmax, 5)); kc = self._buf("b_kc", (B, Rmax), i32); keep_row = self._buf("b_keep_row", (B, Rmax), i32)
+        r2 = self._buf("b_r2", (B, Rmax, 4), np.float64)
+        dwins = self._buf("wins", (Rmax, 4), i32)
+        D = kh * kw * planes
+        dcls = self._buf("cls", (Rmax,), i32); dconf = self._buf("conf", (Rmax,))
+        # first row of frame b in the net's input / output arrays: its own segment, or (shared pass) the prefix sum of R
+        row0, total = {}, 0
+        for b in range(B):
+            if ns[b] > 0:
+                row0[b] = total if shared else b * Rmax
+                total += Rs[b]
+        cinput_buf = self._buf("b_cinput", (total, D)) if shared else self._buf("cinput", (Rmax, D))
+
+        def pooled(b):    # ROI windows (objective.lua:5-13 for every candidate) and ROI pooling of frame b -> its input rows
+            R = Rs[b]
+            _lib.call("frcnn_roi_windows", C.c_void_p(mr.ptr + 32 * b * cap), C.c_void_p(pick.ptr + 8 * b * cap), R,
+                      self._loc_layers.ctypes.data_as(C.c_void_p), len(self._loc_layers), fmH, fmW, ptr(dwins), s)
+            cinput = DeviceTensor(cinput_buf.ptr + (4 * D * row0[b] if shared else 0), (R, D), np.float32, owner=cinput_buf)
+            _lib.call("frcnn_roi_pool_forward", C.c_void_p(fms.ptr + 4 * b * fslot), fmC, fmH, fmW, ptr(dwins), R, kh, kw,
+                      ptr(cinput), None, s)
+            return cinput
+
+        def outputs(b):   # (the net writes into the frame's rows: its own output buffers are reused by the next pass)
+            return (DeviceTensor(bbox_all.ptr + 16 * row0[b], (Rs[b], 4), np.float32, owner=bbox_all),
+                    DeviceTensor(cls_all.ptr + 4 * ncls * row0[b], (Rs[b], ncls), np.float32, owner=cls_all))
+        if shared:
+            for b in sorted(row0):
+                dev[b].update(pooled=pooled(b))
+            cnet.forward(DeviceTensor(cinput_buf.ptr, (total, D), np.float32, owner=cinput_buf),
+                         out=(DeviceTensor(bbox_all.ptr, (total, 4), np.float32, owner=bbox_all),
+                              DeviceTensor(cls_all.ptr, (total, ncls), np.float32, owner=cls_all)))  # :101, all frames
+        for b in range(B):
+            R = Rs[b]
+            if ns[b] == 0:     # no candidates: an empty segment of the per-class NMS
+                _lib.call("frcnn_zero", C.c_void_p(counts.ptr + 4 * (2 * B + b)), 4, s)
+                continue
+            if self.verbose:
+                print("candidates: %d" % R)
+            rect_b, pick_b = C.c_void_p(mr.ptr + 32 * b * cap), C.c_void_p(pick.ptr + 8 * b * cap)
+            bbox_b, cls_b = outputs(b)
+            if not shared:
+                cnet.forward(pooled(b), out=(bbox_b, cls_b))  # :101
+            dev[b].update(bbox=bbox_b, cls=cls_b)
+            _lib.call("frcnn_cnet_decode", ptr(cls_b), R, ncls, ptr(dcls), ptr(dconf), s)  # :110-113
+            _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(bbox_b), rect_b, pick_b, R, bgclass, 0.2,
+                      C.c_void_p(bb.ptr + 20 * b * Rmax), C.c_void_p(kc.ptr + 4 * b * Rmax), C.c_void_p(keep_row.ptr + 4 * b * Rmax),
+                      C.c_void_p(r2.ptr + 32 * b * Rmax), C.c_void_p(counts.ptr + 4 * (2 * B + b)), s)
+        # ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame, rows only suppress rows of their own class),
+        #         ONE gather of every frame's winner records behind a header of the frame's four counts
+        wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
+        ws2 = self._buf("b_nms_ws2", (wsb2,), np.uint8)
+        wpick = self._buf("b_wpick", (B, Rmax), np.int64)
+        _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(0.1), 0, 0, ptr(kc), ptr(wpick), c_W,
+                  ptr(ws2), wsb2, s)
+        out = self._buf("b_winners", (B, Rmax + 1, 16), np.float64)
+        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb), ptr(r2), ptr(pick),
+                  cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
+        raw = self._read(out.ptr, B * (Rmax + 1) * 128, np.float64).reshape(B, Rmax + 1, 16)   # ---- read-back 2 of 2
+        results, recs = [], []
+        for b in range(B):
+            hdr = raw[b, 0].view(i32)
+            recs.append(_BatchRecord(ns[b], Rs[b] if ns[b] else 0, int(hdr[2]), dev[b]))
+            if ns[b] == 0:
+                results.append([])
+                continue
+            w = raw[b, 1:1 + int(hdr[3])]
+            # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
+            results.append(_Detections(w[np.argsort(w[:, 0], kind="stable")].copy(), self.anchors))
+        return results, recs

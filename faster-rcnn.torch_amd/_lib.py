@@ -57,6 +57,10 @@ _SIGS = {
     "frcnn_nms_device": ([vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_nms_device_classes": ([vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_nms_device_n": ([vp, C.c_int, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
+    "frcnn_nms_batch_workspace_bytes": ([C.c_int, C.c_int], C.c_size_t),
+    "frcnn_nms_device_batch": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t,
+                               vp], C.c_int),
+    "frcnn_detect_gather_batch": ([vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_roi_windows": ([vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
     "frcnn_detect_post": ([vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_detect_gather": ([vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
@@ -72,6 +76,9 @@ _SIGS = {
     "frcnn_roi_pool_backward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp], C.c_int),
     "frcnn_rpn_scan_workspace_bytes": ([vp, vp], C.c_size_t),
     "frcnn_rpn_scan": ([vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
+    "frcnn_rpn_scan_batch_workspace_bytes": ([vp, vp, C.c_int], C.c_size_t),
+    "frcnn_rpn_scan_batch": ([vp, vp, vp, C.c_int, C.c_longlong, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp,
+                             vp, C.c_size_t, vp], C.c_int),
     "frcnn_rpn_loss": ([vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp], C.c_int),
     "frcnn_loss_accumulate": ([vp, C.c_int, vp, vp], C.c_int),
     "frcnn_linear_forward": ([vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp], C.c_int),

@@ -161,6 +161,21 @@ int frcnn_nms_device_n(const float* boxes, int n_cap, const int* n_dev, int ncol
   FR_CHECK(n_dev, "frcnn_nms_device_n: NULL device count");
   return nms_device(boxes, n_cap, ncols, overlap, key_mode, key_col, pick, count, ws, ws_bytes, S(stream), cls, n_dev);
 }
+size_t frcnn_nms_batch_workspace_bytes(int B, int n_cap) { return nms_batch_workspace_bytes(B, n_cap); }
+int frcnn_nms_device_batch(const float* boxes, int B, long long row_stride, int n_cap, const int* n_dev, int ncols, float overlap,
+                           int key_mode, int key_col, const int* cls, long long* pick, int* count, void* ws, size_t ws_bytes,
+                           void* stream) {
+  FR_CHECK(B <= 0 || (boxes && pick && count), "frcnn_nms_device_batch: NULL argument");
+  return nms_device_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, overlap, key_mode, key_col, cls, pick, count, ws,
+                          ws_bytes, S(stream));
+}
+int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
+                              const float* bb, const double* r2, const long long* pick, long long match_stride,
+                              const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {
+  FR_CHECK(B <= 0 || (counts && rec), "frcnn_detect_gather_batch: NULL argument");
+  return detect_gather_batch(wpick, counts, B, row_stride, keep_row, kc, bb, r2, pick, (long)match_stride, match_p, match_rect,
+                             match_idx, rec, S(stream));
+}
 int frcnn_roi_windows(const double* rect, const long long* pick, int k, const int* layers_host, int nlayers, int fmH, int fmW,
                       int* wins, void* stream) {
   FR_CHECK(rect && wins && (layers_host || nlayers == 0), "frcnn_roi_windows: NULL argument");
@@ -350,6 +365,21 @@ int frcnn_rpn_scan(const float* const* maps, const int* H, const int* W, const f
   to_layers(maps, H, W, &L);
   return rpn_scan(L, anchor_w, anchor_h, img_w, img_h, p_threshold, cap, match_p, match_idx, match_rect,
                   match_box, count, ws, ws_bytes, S(stream));
+}
+size_t frcnn_rpn_scan_batch_workspace_bytes(const int* H, const int* W, int B) {
+  RpnLayers L;
+  to_layers(nullptr, H, W, &L);
+  return rpn_scan_batch_workspace_bytes(L, B);
+}
+int frcnn_rpn_scan_batch(const float* const* maps, const int* H, const int* W, int B, long long slot_stride, const float* anchor_w,
+                         const float* anchor_h, double img_w, double img_h, double p_threshold, int cap, float* match_p,
+                         int* match_idx, double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
+                         void* stream) {
+  FR_CHECK(maps && H && W, "frcnn_rpn_scan_batch: NULL argument");
+  RpnLayers L;
+  to_layers(maps, H, W, &L);
+  return rpn_scan_batch(L, B, (long)slot_stride, anchor_w, anchor_h, img_w, img_h, p_threshold, cap, match_p, match_idx,
+                        match_rect, match_box, count, ws, ws_bytes, S(stream));
 }
 int frcnn_rpn_loss(const float* const* maps, float* const* deltas, const int* H, const int* W, const int* ex_idx,
                    const double* ex_anchor, const double* ex_roi, const int* ex_class, int npos, int nneg,

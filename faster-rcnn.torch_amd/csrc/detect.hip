@@ -147,4 +147,40 @@ int detect_gather(const long long* wpick, const int* nwin_dev, int cap, const in
   return FRCNN_OK;
 }
 
+// The same for B frames in one launch (Detector:detect_batch), the winner tables of all frames in ONE buffer: frame b's table is
+// rec + b * (row_stride + 1) * 16 doubles -- a 128-byte header whose first four ints are the frame's counts (matches,
+// candidates, survivors of the class test, winners: counts[k * B + b]), then one record per winner.  The per-candidate arrays
+// (wpick, keep_row, kc, bb, r2) hold row_stride rows per frame, the match arrays (pick, mp, rect, midx) match_stride rows.
+__global__ void detect_gather_batch_kernel(const long long* __restrict__ wpick, const int* __restrict__ counts, int B, int row_stride,
+                                           const int* __restrict__ keep_row, const int* __restrict__ kc, const float* __restrict__ bb,
+                                           const double* __restrict__ r2, const long long* __restrict__ pick, long match_stride,
+                                           const float* __restrict__ mp, const double* __restrict__ rect,
+                                           const int* __restrict__ midx, double* __restrict__ rec) {
+  const int b = blockIdx.y;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  double* tab = rec + (size_t)b * ((size_t)row_stride + 1) * 16;
+  if (q < 4) reinterpret_cast<int*>(tab)[q] = counts[q * B + b];
+  if (q >= min(counts[3 * B + b], row_stride)) return;
+  const size_t so = (size_t)b * row_stride, mo = (size_t)b * match_stride;
+  const size_t j = so + (size_t)(wpick[so + q] - 1);
+  const int r = keep_row[j];
+  const size_t i = mo + (size_t)(pick[mo + r] - 1);
+  double* o = tab + 16 * ((size_t)q + 1);
+  o[0] = kc[j]; o[1] = r + 1; o[2] = bb[5 * j + 4]; o[3] = mp[i];
+  for (int t = 0; t < 4; ++t) { o[4 + t] = rect[4 * i + t]; o[8 + t] = r2[4 * j + t]; o[12 + t] = midx[4 * i + t]; }
+}
+
+int detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
+                        const float* bb, const double* r2, const long long* pick, long match_stride, const float* mp,
+                        const double* rect, const int* midx, double* rec, hipStream_t s) {
+  if (B <= 0) return FRCNN_OK;
+  FR_CHECK(B <= 65535 && row_stride >= 0 && match_stride >= 0, "detect_gather_batch: bad sizes (B %d, strides %d / %ld)", B,
+           row_stride, match_stride);
+  // (row_stride == 0: one block per frame still writes the header)
+  FR_LAUNCH(KC_ELEMWISE, 0, B * (row_stride + 1) * 128.0, s, detect_gather_batch_kernel, dim3(std::max(cdiv(row_stride, 64), 1), B),
+            dim3(64), 0, wpick, counts, B, row_stride, keep_row, kc, bb, r2, pick, match_stride, mp, rect, midx, rec);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
 }  // namespace frcnn

@@ -20,8 +20,10 @@ namespace frcnn {
 // n_dev (optional, every kernel): the row count lives in device memory (the match count a scan just produced, the
 // number of candidates that passed the class test): n = min(*n_dev, n) -- the launch is sized for the host-side bound
 // and the pipeline that feeds it never waits for a read-back (Detector.lua:39-85 without a host round trip).
-__global__ void nms_prep_kernel(const float* __restrict__ boxes, int n, const int* __restrict__ n_dev, int ncols, int key_mode,
-                                int key_col, float* __restrict__ area, float* __restrict__ key) {
+// (Every stage's code is a body shared by two kernels: the single-problem kernel, launched as before, and the segmented
+// kernel of nms_device_batch further down, which takes the segment from a grid dimension and offsets the pointers.)
+__device__ __forceinline__ void nms_prep_body(const float* __restrict__ boxes, int n, const int* __restrict__ n_dev, int ncols,
+                                              int key_mode, int key_col, float* __restrict__ area, float* __restrict__ key) {
   if (n_dev) n = min(*n_dev, n);
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -34,6 +36,10 @@ __global__ void nms_prep_kernel(const float* __restrict__ boxes, int n, const in
   area[i] = a;
   key[i] = key_mode == 2 ? b[key_col - 1] : (key_mode == 1 ? a : b[3]);
 }
+__global__ void nms_prep_kernel(const float* __restrict__ boxes, int n, const int* __restrict__ n_dev, int ncols, int key_mode,
+                                int key_col, float* __restrict__ area, float* __restrict__ key) {
+  nms_prep_body(boxes, n, n_dev, ncols, key_mode, key_col, area, key);
+}
 
 // rank[i] = #{ j : key[j] < key[i]  or (key[j] == key[i] and j < i) }; sorted[n-1-rank] = i.
 // 2-D grid: block (x, y) counts, for its 256 keys i, the 256 keys j of slice y (one LDS image, one barrier, 64 broadcast reads of
@@ -42,7 +48,7 @@ __global__ void nms_prep_kernel(const float* __restrict__ boxes, int n, const in
 // slices of 256 instead of 1024 keys -- a thread's 1 024 dependent compare steps were the whole 30 us of the launch at any n,
 // with one block per compute unit.
 #define NMS_RANK_SLICE 256
-__global__ __launch_bounds__(256) void nms_rank_kernel(const float* __restrict__ key, int n, const int* __restrict__ n_dev, int* __restrict__ rank) {
+__device__ __forceinline__ void nms_rank_body(const float* __restrict__ key, int n, const int* __restrict__ n_dev, int* __restrict__ rank) {
   __shared__ __attribute__((aligned(16))) float sk[NMS_RANK_SLICE];
   if (n_dev) n = min(*n_dev, n);
   const int ib = blockIdx.x, jb = blockIdx.y, t = threadIdx.x;
@@ -73,18 +79,24 @@ __global__ __launch_bounds__(256) void nms_rank_kernel(const float* __restrict__
   }
   if (i < n && r) atomicAdd(rank + i, r);
 }
-__global__ void nms_scatter_kernel(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
+__global__ __launch_bounds__(256) void nms_rank_kernel(const float* __restrict__ key, int n, const int* __restrict__ n_dev, int* __restrict__ rank) {
+  nms_rank_body(key, n, n_dev, rank);
+}
+__device__ __forceinline__ void nms_scatter_body(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
   if (n_dev) n = min(*n_dev, n);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) sorted[n - 1 - rank[i]] = i;
 }
+__global__ void nms_scatter_kernel(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
+  nms_scatter_body(rank, n, n_dev, sorted);
+}
 
 // mask[a][w] bit b: box at sorted position a suppresses box at sorted position w*64+b (b > a)
 // cls (optional): rows only suppress rows of the same class -- the per-class NMS problems of Detector.lua:125-136 in one pass
-__global__ void nms_mask_kernel(const float* __restrict__ boxes, int ncols, const float* __restrict__ area,
-                                const int* __restrict__ sorted, int n, const int* __restrict__ n_dev, int nw, float thr,
-                                const int* __restrict__ cls, unsigned long long* __restrict__ mask,
-                                unsigned long long* __restrict__ diagT) {
+__device__ __forceinline__ void nms_mask_body(const float* __restrict__ boxes, int ncols, const float* __restrict__ area,
+                                              const int* __restrict__ sorted, int n, const int* __restrict__ n_dev, int nw, float thr,
+                                              const int* __restrict__ cls, unsigned long long* __restrict__ mask,
+                                              unsigned long long* __restrict__ diagT) {
   const int rb = blockIdx.y, cb = blockIdx.x;
   if (cb < rb) return;
   if (n_dev) n = min(*n_dev, n);
@@ -138,6 +150,12 @@ __global__ void nms_mask_kernel(const float* __restrict__ boxes, int ncols, cons
     diagT[rpos] = col;
   }
 }
+__global__ void nms_mask_kernel(const float* __restrict__ boxes, int ncols, const float* __restrict__ area,
+                                const int* __restrict__ sorted, int n, const int* __restrict__ n_dev, int nw, float thr,
+                                const int* __restrict__ cls, unsigned long long* __restrict__ mask,
+                                unsigned long long* __restrict__ diagT) {
+  nms_mask_body(boxes, ncols, area, sorted, n, n_dev, nw, thr, cls, mask, diagT);
+}
 
 // OR of a 64-bit value over the 64 lanes of a wave, returned wave-uniform: data-parallel-primitive moves inside the vector ALU
 // (row shifts, then the two row broadcasts), twelve instructions and two readlanes -- a shuffle through the LDS crossbar costs a
@@ -190,11 +208,11 @@ __device__ __forceinline__ unsigned long long nms_wave_or64(unsigned long long v
 // carries a release fence for GLOBAL memory, which on gfx950 is `s_waitcnt vmcnt(0)`: it would wait for the pick store of the step
 // and, with it, for every operand requested ahead.  Nothing in global memory is exchanged between the waves of this kernel.
 #define NMS_STEP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-__global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_kernel(const unsigned long long* __restrict__ mask,
-                                                                     const unsigned long long* __restrict__ diagT,
-                                                                     const int* __restrict__ sorted, int n,
-                                                                     const int* __restrict__ n_dev, int nwp,
-                                                                     long long* __restrict__ pick, int* __restrict__ count) {
+__device__ __forceinline__ void nms_reduce_body(const unsigned long long* __restrict__ mask,
+                                                const unsigned long long* __restrict__ diagT,
+                                                const int* __restrict__ sorted, int n,
+                                                const int* __restrict__ n_dev, int nwp,
+                                                long long* __restrict__ pick, int* __restrict__ count) {
   extern __shared__ unsigned long long removed[];  // [nw + NMS_NU + 1]
   if (n_dev) n = min(*n_dev, n);
   const int nw = (n + 63) >> 6;   // words of this run; nwp = pitch of the mask rows (the host-side bound)
@@ -370,6 +388,52 @@ __global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_kernel(const unsig
   if (tid == 0) *count = cnt_all;
 }
 #undef NMS_STEP_BARRIER
+__global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_kernel(const unsigned long long* __restrict__ mask,
+                                                                     const unsigned long long* __restrict__ diagT,
+                                                                     const int* __restrict__ sorted, int n,
+                                                                     const int* __restrict__ n_dev, int nwp,
+                                                                     long long* __restrict__ pick, int* __restrict__ count) {
+  nms_reduce_body(mask, diagT, sorted, n, n_dev, nwp, pick, count);
+}
+
+// ---- B independent problems in one pass (Detector:detect_batch): segment b = a grid dimension of every stage.  Its boxes are
+// rows [b * row_stride, b * row_stride + n_b) of `boxes` (cls likewise), n_b = min(n_dev[b], n), its work arrays slice b of
+// arrays of n entries per segment, its mask B_b = mask + b * n * nw words, its picks pick + b * row_stride (1-based rows WITHIN
+// the segment), its survivor count count[b].  The bodies above run unchanged on the offset pointers, so a segment's result
+// is that of the single-problem kernels on its rows; nothing is shared between segments (no tie rule across them).
+__global__ void nms_prep_batch_kernel(const float* __restrict__ boxes, long row_stride, int n, const int* __restrict__ n_dev,
+                                      int ncols, int key_mode, int key_col, float* __restrict__ area, float* __restrict__ key) {
+  const int b = blockIdx.y;
+  nms_prep_body(boxes + (size_t)b * row_stride * ncols, n, n_dev + b, ncols, key_mode, key_col, area + (size_t)b * n,
+                key + (size_t)b * n);
+}
+__global__ __launch_bounds__(256) void nms_rank_batch_kernel(const float* __restrict__ key, int n, const int* __restrict__ n_dev,
+                                                             int* __restrict__ rank) {
+  const int b = blockIdx.z;
+  nms_rank_body(key + (size_t)b * n, n, n_dev + b, rank + (size_t)b * n);
+}
+__global__ void nms_scatter_batch_kernel(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
+  const int b = blockIdx.y;
+  nms_scatter_body(rank + (size_t)b * n, n, n_dev + b, sorted + (size_t)b * n);
+}
+__global__ void nms_mask_batch_kernel(const float* __restrict__ boxes, long row_stride, int ncols, const float* __restrict__ area,
+                                      const int* __restrict__ sorted, int n, const int* __restrict__ n_dev, int nw, float thr,
+                                      const int* __restrict__ cls, unsigned long long* __restrict__ mask,
+                                      unsigned long long* __restrict__ diagT) {
+  const int b = blockIdx.z;
+  nms_mask_body(boxes + (size_t)b * row_stride * ncols, ncols, area + (size_t)b * n, sorted + (size_t)b * n, n, n_dev + b, nw, thr,
+                cls ? cls + (size_t)b * row_stride : nullptr, mask + (size_t)b * n * nw, diagT + (size_t)b * n);
+}
+// one workgroup per segment: B greedy scans side by side on B compute units, the pass as long as the longest of them
+__global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_batch_kernel(const unsigned long long* __restrict__ mask,
+                                                                           const unsigned long long* __restrict__ diagT,
+                                                                           const int* __restrict__ sorted, int n,
+                                                                           const int* __restrict__ n_dev, int nwp, long row_stride,
+                                                                           long long* __restrict__ pick, int* __restrict__ count) {
+  const int b = blockIdx.x;
+  nms_reduce_body(mask + (size_t)b * n * nwp, diagT + (size_t)b * n, sorted + (size_t)b * n, n, n_dev + b, nwp,
+                  pick + (size_t)b * row_stride, count + b);
+}
 
 size_t nms_workspace_bytes(int n) {
   size_t nw = (size_t)cdiv(n, 64);
@@ -413,6 +477,62 @@ int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode
             boxes, ncols, area, sorted, n, n_dev, nw, overlap, cls, mask, diagT);
   FR_LAUNCH(KC_NMS, 0, 8.0 * n * nw / 2, s, nms_reduce_kernel, dim3(1), dim3(NMS_RED_THREADS), (size_t)(nw + NMS_NU + 1) * 8, mask,
             (const unsigned long long*)diagT, sorted, n, n_dev, nw, pick, count);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// Workspace of nms_device_batch: the work arrays of all segments side by side ([4][B][n] area, key, sorted, rank -- so that the
+// rank array's zero fill is one memset), then B masks, then B transposed diagonals.
+size_t nms_batch_workspace_bytes(int B, int n) {
+  if (B <= 0 || n <= 0) return 256;
+  size_t nw = (size_t)cdiv(n, 64);
+  size_t b = 0;
+  b += (size_t)B * n * 4 * 4;
+  b = (b + 255) / 256 * 256;
+  b += (size_t)B * n * nw * 8;
+  b = (b + 255) / 256 * 256;
+  b += (size_t)B * n * 8;
+  return b + 256;
+}
+
+int nms_device_batch(const float* boxes, int B, long row_stride, int n, const int* n_dev, int ncols, float overlap, int key_mode,
+                     int key_col, const int* cls, long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (B <= 0) return FRCNN_OK;
+  if (n <= 0) {  // nms.lua:26-28, every segment
+    FR_HIP(hipMemsetAsync(count, 0, sizeof(int) * (size_t)B, s));
+    return FRCNN_OK;
+  }
+  FR_CHECK(n_dev, "nms_batch: NULL device counts");
+  FR_CHECK(B <= 65535, "nms_batch: %d segments (at most 65535)", B);
+  FR_CHECK(row_stride >= n, "nms_batch: row stride %ld < %d rows per segment", row_stride, n);
+  FR_CHECK(ncols >= 4, "nms: boxes need >= 4 columns (got %d)", ncols);
+  FR_CHECK(key_mode >= 0 && key_mode <= 2, "nms: bad key_mode %d", key_mode);
+  FR_CHECK(key_mode != 2 || (key_col >= 1 && key_col <= ncols), "nms: key column %d out of range", key_col);
+  FR_CHECK(ws_bytes >= nms_batch_workspace_bytes(B, n), "nms_batch: workspace too small (%zu < %zu)", ws_bytes,
+           nms_batch_workspace_bytes(B, n));
+  const int nw = cdiv(n, 64);
+  FR_CHECK((size_t)(nw + NMS_NU + 1) * 8 <= 64 * 1024, "nms: n=%d too large (max 523968)", n);
+  const size_t Bn = (size_t)B * n;
+  char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+  float* area = (float*)base;
+  float* key = area + Bn;
+  int* sorted = (int*)(key + Bn);
+  int* rank = sorted + Bn;
+  size_t off = (Bn * 16 + 255) / 256 * 256;
+  unsigned long long* mask = (unsigned long long*)(base + off);
+  unsigned long long* diagT = (unsigned long long*)(base + (off + Bn * nw * 8 + 255) / 256 * 256);
+  FR_LAUNCH(KC_NMS, 0, 20.0 * Bn, s, nms_prep_batch_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, boxes, row_stride, n, n_dev,
+            ncols, key_mode, key_col, area, key);
+  FR_HIP(hipMemsetAsync(rank, 0, Bn * 4, s));
+  FR_LAUNCH(KC_NMS, 0, 8.0 * Bn, s, nms_rank_batch_kernel, dim3(cdiv(n, 256), cdiv(n, NMS_RANK_SLICE), B), dim3(256), 0,
+            (const float*)key, n, n_dev, rank);
+  FR_LAUNCH(KC_NMS, 0, 8.0 * Bn, s, nms_scatter_batch_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, (const int*)rank, n, n_dev,
+            sorted);
+  FR_LAUNCH(KC_NMS, 3.5 * Bn * (double)n, 8.0 * Bn * nw / 2, s, nms_mask_batch_kernel, dim3(nw, nw, B), dim3(64), 0, boxes,
+            row_stride, ncols, (const float*)area, (const int*)sorted, n, n_dev, nw, overlap, cls, mask, diagT);
+  FR_LAUNCH(KC_NMS, 0, 8.0 * Bn * nw / 2, s, nms_reduce_batch_kernel, dim3(B), dim3(NMS_RED_THREADS), (size_t)(nw + NMS_NU + 1) * 8,
+            (const unsigned long long*)mask, (const unsigned long long*)diagT, (const int*)sorted, n, n_dev, nw, row_stride, pick,
+            count);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }

@@ -19,11 +19,13 @@ struct ScanArgs {
   int start[5];  // prefix of 3*H*W per layer
 };
 
-__global__ void rpn_scan_kernel(ScanArgs a, const float* __restrict__ aw, const float* __restrict__ ah,
-                                double img_w, double img_h, double thr, unsigned char* __restrict__ flag,
-                                float* __restrict__ dp, double* __restrict__ drect) {
+// (the code of both kernels is a body shared with the batched forms below, which take the frame from a grid dimension: the maps
+// of frame b lie map_off floats behind a.map[]; first / step: the kernel's grid-stride loop over the anchors)
+__device__ __forceinline__ void rpn_scan_body(const ScanArgs& a, size_t map_off, int first, int step, const float* __restrict__ aw,
+                                              const float* __restrict__ ah, double img_w, double img_h, double thr,
+                                              unsigned char* __restrict__ flag, float* __restrict__ dp, double* __restrict__ drect) {
   const int total = a.start[4];
-  for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < total; n += gridDim.x * blockDim.x) {
+  for (int n = first; n < total; n += step) {
     int l = n >= a.start[3] ? 3 : (n >= a.start[2] ? 2 : (n >= a.start[1] ? 1 : 0));
     int r = n - a.start[l];
     int asp = r % 3;
@@ -31,7 +33,7 @@ __global__ void rpn_scan_kernel(ScanArgs a, const float* __restrict__ aw, const 
     const int W = a.W[l];
     const long hw = (long)a.H[l] * W;
     const int y = pix / W, x = pix - y * W;
-    const float* m = a.map[l] + (size_t)(asp * 6) * hw + pix;
+    const float* m = a.map[l] + map_off + (size_t)(asp * 6) * hw + pix;
     const float v0 = m[0], v1 = m[hw];
     // nn.LogSoftMax (max-shifted), fp32 result like the reference's CudaTensor
     const double mx = v0 > v1 ? (double)v0 : (double)v1;
@@ -59,14 +61,19 @@ __global__ void rpn_scan_kernel(ScanArgs a, const float* __restrict__ aw, const 
     flag[n] = f;
   }
 }
+__global__ void rpn_scan_kernel(ScanArgs a, const float* __restrict__ aw, const float* __restrict__ ah,
+                                double img_w, double img_h, double thr, unsigned char* __restrict__ flag,
+                                float* __restrict__ dp, double* __restrict__ drect) {
+  rpn_scan_body(a, 0, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, aw, ah, img_w, img_h, thr, flag, dp, drect);
+}
 
 // single workgroup, ordered compaction by wave ballots
-__global__ __launch_bounds__(1024) void rpn_compact_kernel(ScanArgs a, const unsigned char* __restrict__ flag,
-                                                           const float* __restrict__ dp,
-                                                           const double* __restrict__ drect, int cap,
-                                                           float* __restrict__ match_p, int* __restrict__ match_idx,
-                                                           double* __restrict__ match_rect,
-                                                           float* __restrict__ match_box, int* __restrict__ count) {
+__device__ __forceinline__ void rpn_compact_body(const ScanArgs& a, const unsigned char* __restrict__ flag,
+                                                 const float* __restrict__ dp,
+                                                 const double* __restrict__ drect, int cap,
+                                                 float* __restrict__ match_p, int* __restrict__ match_idx,
+                                                 double* __restrict__ match_rect,
+                                                 float* __restrict__ match_box, int* __restrict__ count) {
   __shared__ int wave_cnt[16];
   __shared__ int base_sh;
   const int total = a.start[4];
@@ -105,6 +112,44 @@ __global__ __launch_bounds__(1024) void rpn_compact_kernel(ScanArgs a, const uns
   }
   if (threadIdx.x == 0) *count = base_sh;
 }
+__global__ __launch_bounds__(1024) void rpn_compact_kernel(ScanArgs a, const unsigned char* __restrict__ flag,
+                                                           const float* __restrict__ dp,
+                                                           const double* __restrict__ drect, int cap,
+                                                           float* __restrict__ match_p, int* __restrict__ match_idx,
+                                                           double* __restrict__ match_rect,
+                                                           float* __restrict__ match_box, int* __restrict__ count) {
+  rpn_compact_body(a, flag, dp, drect, cap, match_p, match_idx, match_rect, match_box, count);
+}
+
+// ---- B frames in one pass (Detector:detect_batch).  Frame b's head maps are a.map[l] + b * slot_stride floats, its scratch
+// slice b of the workspace (ws_stride bytes apart, laid out like the single-frame workspace), its matches rows
+// [b * cap, b * cap + count[b]) of the match arrays.  The threshold test is one launch with the frame as grid dimension y, the
+// ordered compaction one launch of one workgroup per frame.
+struct ScanSlice { double* drect; float* dp; unsigned char* flag; };
+__device__ __forceinline__ ScanSlice rpn_scan_slice(char* ws, size_t ws_stride, int b, int total) {
+  char* base = ws + (size_t)b * ws_stride;
+  ScanSlice v;
+  v.drect = (double*)base;
+  v.dp = (float*)(base + (size_t)total * 32);
+  v.flag = (unsigned char*)(base + (size_t)total * 36 + 64);
+  return v;
+}
+__global__ void rpn_scan_batch_kernel(ScanArgs a, long slot_stride, const float* __restrict__ aw, const float* __restrict__ ah,
+                                      double img_w, double img_h, double thr, char* __restrict__ ws, size_t ws_stride) {
+  const int b = blockIdx.y;
+  const ScanSlice v = rpn_scan_slice(ws, ws_stride, b, a.start[4]);
+  rpn_scan_body(a, (size_t)b * slot_stride, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, aw, ah, img_w, img_h,
+                thr, v.flag, v.dp, v.drect);
+}
+__global__ __launch_bounds__(1024) void rpn_compact_batch_kernel(ScanArgs a, char* __restrict__ ws, size_t ws_stride, int cap,
+                                                                 float* __restrict__ match_p, int* __restrict__ match_idx,
+                                                                 double* __restrict__ match_rect, float* __restrict__ match_box,
+                                                                 int* __restrict__ count) {
+  const int b = blockIdx.x;
+  const ScanSlice v = rpn_scan_slice(ws, ws_stride, b, a.start[4]);
+  const size_t o = (size_t)b * cap;
+  rpn_compact_body(a, v.flag, v.dp, v.drect, cap, match_p + o, match_idx + 4 * o, match_rect + 4 * o, match_box + 4 * o, count + b);
+}
 
 static void fill_scan_args(const RpnLayers& L, ScanArgs* a) {
   a->start[0] = 0;
@@ -142,6 +187,37 @@ int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, d
   FR_LAUNCH(KC_RPN, 0, n * 1.0, s, rpn_compact_kernel, dim3(1), dim3(1024), 0, a,
             (const unsigned char*)flag, (const float*)dp, (const double*)drect, cap, match_p, match_idx,
             match_rect, match_box, count);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+static size_t rpn_scan_slice_bytes(size_t n) { return (n * 40 + ((n + 255) / 256) * 256 + 255) / 256 * 256; }
+size_t rpn_scan_batch_workspace_bytes(const RpnLayers& L, int B) {
+  ScanArgs a;
+  fill_scan_args(L, &a);
+  return 256 + (size_t)std::max(B, 0) * rpn_scan_slice_bytes((size_t)a.start[4]);
+}
+
+int rpn_scan_batch(const RpnLayers& L, int B, long slot_stride, const float* anchor_w, const float* anchor_h, double img_w,
+                   double img_h, double p_threshold, int cap, float* match_p, int* match_idx, double* match_rect,
+                   float* match_box, int* count, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (B <= 0) return FRCNN_OK;
+  ScanArgs a;
+  fill_scan_args(L, &a);
+  for (int l = 0; l < 4; ++l)
+    FR_CHECK(L.H[l] <= 200 && L.W[l] <= 200, "rpn_scan: head map %d is %dx%d, anchor tables hold 200 (Anchors.lua:15)",
+             l + 1, L.H[l], L.W[l]);
+  FR_CHECK(B <= 65535, "rpn_scan_batch: %d frames (at most 65535)", B);
+  FR_CHECK(cap >= 0 && slot_stride >= 0, "rpn_scan_batch: negative cap / slot stride");
+  const size_t n = (size_t)a.start[4];
+  FR_CHECK(ws_bytes >= rpn_scan_batch_workspace_bytes(L, B), "rpn_scan_batch: workspace too small");
+  char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+  const size_t ws_stride = rpn_scan_slice_bytes(n);
+  int grid = (int)std::min<size_t>((n + 255) / 256, 1024);
+  FR_LAUNCH(KC_RPN, 0, B * n * 24.0, s, rpn_scan_batch_kernel, dim3(grid, B), dim3(256), 0, a, slot_stride, anchor_w, anchor_h,
+            img_w, img_h, p_threshold, base, ws_stride);
+  FR_LAUNCH(KC_RPN, 0, B * n * 1.0, s, rpn_compact_batch_kernel, dim3(B), dim3(1024), 0, a, base, ws_stride, cap, match_p,
+            match_idx, match_rect, match_box, count);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }

@@ -156,18 +156,36 @@ def mean_average_precision(detections, ground_truth, iou_threshold=0.5, use_07_m
     return dict(mAP=float(np.mean(list(ap.values()))) if ap else float("nan"), ap=ap, npos=npos_of, tp=tp_total, fp=fp_total)
 
 
-def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False):
-    """Detector:detect on `count` validation images (main.lua:198-206) scored against their ground truth."""
+def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False, batch=1):
+    """Detector:detect on `count` validation images (main.lua:198-206) scored against their ground truth.
+    batch > 1: up to that many consecutive frames of one size go through Detector.detect_batch in one call (same detections,
+    two host waits per chunk instead of two per frame); 1 is the frame-by-frame loop of the reference."""
     detections, ground_truth = [], []
     images = 0
+    pending = []     # (image id, frame) of one size, waiting for detect_batch
+
+    def flush():
+        for (image_id, _), winners in zip(pending, detector.detect_batch([img for _, img in pending])):
+            for w in winners:
+                detections.append((image_id, int(w["class"]), float(w["confidence"]), w["r2"]))
+        del pending[:]
     while images < count:
         for x in batch_iterator.nextValidation(1):
             image_id = images
             images += 1
             for roi in x["rois"]:
                 ground_truth.append((image_id, int(roi.class_index), roi.rect))
+            if batch > 1:
+                if pending and tuple(pending[0][1].shape) != tuple(x["img"].shape):
+                    flush()
+                pending.append((image_id, x["img"]))
+                if len(pending) >= batch:
+                    flush()
+                continue
             for w in detector.detect(x["img"]):
                 detections.append((image_id, int(w["class"]), float(w["confidence"]), w["r2"]))
+    if pending:
+        flush()
     res = mean_average_precision(detections, ground_truth, iou_threshold, use_07_metric)
     res.update(images=images, detections=len(detections), ground_truth=len(ground_truth))
     return res

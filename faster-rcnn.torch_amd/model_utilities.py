@@ -253,12 +253,14 @@ class ClassificationNet(object):
     def evaluate(self):
         self.train = False
 
-    def forward(self, cinput):
+    def forward(self, cinput, out=None):
+        """out (optional): (bbox R x 4, cls R x (classes + 1)) device tensors of the caller to write the outputs to, instead of
+        the module-owned buffers the next call reuses."""
         nat = self.native
         cinput = to_device(cinput)
         R, D = cinput.shape
         nc = nat.desc.class_count + 1
-        bbox = self._buf("bbox", (R, 4)); cls = self._buf("cls", (R, nc))
+        bbox, cls = out if out is not None else (self._buf("bbox", (R, 4)), self._buf("cls", (R, nc)))
         arr, keep = _mask_ptrs(self.drop_masks, nat.desc.ncls)
         nat.seed += 1
         self._input = cinput

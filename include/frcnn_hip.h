@@ -142,6 +142,16 @@ int frcnn_nms_device_classes(const float *boxes, int n, int ncols, float overlap
  * without a host round trip for the count in between.  cls may be NULL. */
 int frcnn_nms_device_n(const float *boxes, int n_cap, const int *n_dev, int ncols, float overlap, int key_mode, int key_col,
                        const int *cls, long long *pick, int *count, void *workspace, size_t workspace_bytes, void *stream);
+/* B independent problems in ONE pass (Detector:detect_batch; every stage one launch with the segment as a grid dimension, the
+ * greedy scans as B workgroups side by side).  Segment b: rows boxes + b*row_stride*ncols, count min(n_dev[b], n_cap) (device
+ * int[B], required), cls + b*row_stride (optional), picks pick + b*row_stride (1-based rows WITHIN the segment), survivor
+ * count count[b].  row_stride >= n_cap.  Per segment the result is bit for bit frcnn_nms_device_n on that segment; a segment
+ * with count 0 writes count[b] = 0 and nothing else.  Workspace: frcnn_nms_batch_workspace_bytes(B, n_cap) -- the masks are
+ * n_cap^2 / 8 bytes per segment (33.5 MB at 16 384). */
+size_t frcnn_nms_batch_workspace_bytes(int B, int n_cap);
+int frcnn_nms_device_batch(const float *boxes, int B, long long row_stride, int n_cap, const int *n_dev, int ncols, float overlap,
+                           int key_mode, int key_col, const int *cls, long long *pick, int *count, void *workspace,
+                           size_t workspace_bytes, void *stream);
 /* ---- Detector:detect glue kept on the device (Detector.lua:88-136; csrc/detect.hip) ------------------------------
  * frcnn_roi_windows: extract_roi_pooling_input (objective.lua:5-13) for k ROIs at once -- Localizer:inputToFeatureRect
  * (Localizer.lua:41-67, the reference's double arithmetic incl. its dH/dW mix-ups) over layers_host[nlayers][6] =
@@ -162,6 +172,13 @@ int frcnn_detect_post(const int *cls, const float *conf, const float *bbox, cons
 int frcnn_detect_gather(const long long *wpick, const int *nwin_dev, int cap, const int *keep_row, const int *kc,
                         const float *bb, const double *r2, const long long *pick, const float *match_p,
                         const double *match_rect, const int *match_idx, double *rec, void *stream);
+/* frcnn_detect_gather for B frames in one launch, all winner tables in ONE buffer (one read-back): frame b's table starts at
+ * rec + b*(row_stride + 1)*16 doubles -- a 128-byte header whose first four ints are the frame's counts, then one record per
+ * winner q < min(winners, row_stride).  counts: device int[4][B] = {matches, candidates, survivors of the class test,
+ * winners} per frame.  wpick / keep_row / kc / bb / r2 hold row_stride rows per frame, pick / match_* match_stride rows. */
+int frcnn_detect_gather_batch(const long long *wpick, const int *counts, int B, int row_stride, const int *keep_row,
+                              const int *kc, const float *bb, const double *r2, const long long *pick, long long match_stride,
+                              const float *match_p, const double *match_rect, const int *match_idx, double *rec, void *stream);
 /* Host-pointer variant (the reference's nms runs on CPU FloatTensors): uploads, runs the same
  * kernels, downloads, synchronises. */
 int frcnn_nms_host(const float *boxes_host, int n, int ncols, float overlap, int key_mode,
@@ -223,6 +240,15 @@ int frcnn_rpn_scan(const float *const *maps_host, const int *H_host, const int *
                    double p_threshold, int cap, float *match_p, int *match_idx,
                    double *match_rect, float *match_box, int *count, void *workspace,
                    size_t workspace_bytes, void *stream);
+/* The same for B frames in one pass (Detector:detect_batch): maps_host are the four maps of frame 0, frame b's are slot_stride
+ * floats further (every map); one launch for the threshold test, one for the ordered compaction with one workgroup per
+ * frame.  Frame b's matches are rows [b*cap, b*cap + min(count[b], cap)) of the match arrays, count: device int[B].  Per
+ * frame bit-identical to frcnn_rpn_scan. */
+size_t frcnn_rpn_scan_batch_workspace_bytes(const int *H_host, const int *W_host, int B);
+int frcnn_rpn_scan_batch(const float *const *maps_host, const int *H_host, const int *W_host, int B, long long slot_stride,
+                         const float *anchor_w, const float *anchor_h, double img_w, double img_h, double p_threshold,
+                         int cap, float *match_p, int *match_idx, double *match_rect, float *match_box, int *count,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- sparse RPN loss: objective.lua:91-140 (+ cnet targets, objective.lua:149-159) ---- */
 /* Examples: positives first (npos) then negatives (nneg).  ex_idx int[E][4] {layer,aspect,y,x}
