@@ -6,6 +6,9 @@
 -- `scores`, which nms.lua:37-43 ignores: boxes are processed by descending max-y.  That behaviour is reproduced.
 -- 1:1 with the tested Python host mirror (faster-rcnn.torch_amd/Detector.py); checked statically, not executed here.
 --
+-- Not in the reference, off by default: cfg.proposals = { order = 'y2' | 'score', pre_nms_top_n = K, post_nms_top_n = M }
+-- (main.lua calls Detector(model) unchanged, so the settings ride on the model's cfg; Detector.proposal_settings).
+--
 --   main.lua:  require 'Detector'  ->  require 'Detector_hip'
 local ffi = require 'ffi'
 local hip = require 'frcnn_hip'
@@ -28,19 +31,90 @@ function Detector:__init(model)                                         -- Detec
   self.aw = hip.to_device(self.anchors.w)
   self.ah = hip.to_device(self.anchors.h)
   self.scratch = hip.scratch()
+  self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n = Detector.proposal_settings(self.model.cfg.proposals)
 end
 
-function Detector:detect(input)                                         -- Detector.lua:17-141
-  local model = self.model
-  local cfg = model.cfg
-  local pnet = model.pnet
-  local cnet = model.cnet
-  local kh, kw = cfg.roi_pooling.kh, cfg.roi_pooling.kw
-  local bgclass = cfg.class_count + 1
-  local ncls = cfg.class_count + 1
-  local cnet_input_planes = model.layers[#model.layers].filters
-  local D = kh * kw * cnet_input_planes
+-- cfg.proposals -> order, pre_nms_top_n, post_nms_top_n (validated on the host, before any device call).
+--   order           'y2' (default: the reference -- nms.lua ignores the scores it is handed, boxes go by descending max-y) or
+--                   'score': the first NMS runs on rows {box, p} keyed by p (key_mode 2, key_col 5), the per-class NMS keyed by
+--                   the confidence (key_col 5); the NMS tie rule is unchanged
+--   pre_nms_top_n   nil or K >= 1: only the K' = min(n, K) best-ranked of a frame's n matches reach the first NMS.  Rank: the
+--                   match's fp32 p compared as a value (-0 equals +0, a NaN ranks below everything), ties are broken by the
+--                   lower scan row.  The selected rows keep their scan order, so K >= n changes nothing.  Either order.
+--   post_nms_top_n  nil or M >= 1: the candidates are the first min(R, M) picks of the first NMS; needs order = 'score'
+function Detector.proposal_settings(t)
+  if t == nil then t = {} end
+  if type(t) ~= 'table' then error('cfg.proposals must be a table of {order, pre_nms_top_n, post_nms_top_n}') end
+  for k, _ in pairs(t) do
+    if k ~= 'order' and k ~= 'pre_nms_top_n' and k ~= 'post_nms_top_n' then
+      error('cfg.proposals: unknown key ' .. tostring(k))
+    end
+  end
+  local order = t.order
+  if order == nil then order = 'y2' end
+  if order ~= 'y2' and order ~= 'score' then error('cfg.proposals.order must be "y2" or "score"') end
+  local function top_n(name)
+    local v = t[name]
+    if v == nil then return nil end
+    if type(v) ~= 'number' or v ~= math.floor(v) then error('cfg.proposals.' .. name .. ' is not an integer') end
+    if v < 1 then error('cfg.proposals.' .. name .. ' must be at least 1') end
+    return v
+  end
+  local pre, post = top_n('pre_nms_top_n'), top_n('post_nms_top_n')
+  if post ~= nil and order ~= 'score' then
+    error('cfg.proposals.post_nms_top_n needs order = "score": the first picks in max-y order are not the best')
+  end
+  return order, pre, post
+end
+
+-- pre_nms_top_n: the min(n_b, K) best-scoring rows of every frame's matches (B x cap rows, device counts cnt), gathered in
+-- scan order into compact arrays of kcap = min(cap, K) rows per frame; count = the selected counts (device int[B])
+function Detector:select_rows(mp, mi, mr, mb, B, cap, K, cnt, pre)
   local scratch = self.scratch
+  local kcap = math.min(cap, K)
+  local sel = ffi.cast('int*', scratch(pre .. 'sel', 4 * B * kcap).ptr)
+  local kcnt = ffi.cast('int*', scratch(pre .. 'sel_count', 4 * B).ptr)
+  local wsb = tonumber(C.frcnn_topk_select_workspace_bytes(B, cap))
+  local ws = scratch(pre .. 'sel_ws', wsb)
+  check(C.frcnn_topk_select(mp, B, cap, cap, cnt, K, sel, kcap, kcnt, ws.ptr, wsb, nil))
+  local out = { count = kcnt, stride = kcap,
+                p = ffi.cast('float*', scratch(pre .. 'sel_p', 4 * B * kcap).ptr),
+                idx = ffi.cast('int*', scratch(pre .. 'sel_idx', 16 * B * kcap).ptr),
+                rect = ffi.cast('double*', scratch(pre .. 'sel_rect', 32 * B * kcap).ptr),
+                box = ffi.cast('float*', scratch(pre .. 'sel_box', 16 * B * kcap).ptr),
+                box5 = ffi.cast('float*', scratch(pre .. 'sel_box5', 20 * B * kcap).ptr),
+                row = ffi.cast('int*', scratch(pre .. 'sel_row', 4 * B * kcap).ptr) }
+  check(C.frcnn_rpn_gather_rows(mp, mi, mr, mb, B, cap, cap, sel, kcap, kcnt, kcap, out.p, out.idx, out.rect, out.box, out.box5,
+                                out.row, kcap, nil))
+  return out
+end
+
+-- order = 'score' without a cap: rows {box, p} of every match (the count read on the device), the first NMS's input
+function Detector:score_rows(mp, mb, B, cap, cnt, pre)
+  local box5 = ffi.cast('float*', self.scratch(pre .. 'box5', 20 * B * cap).ptr)
+  check(C.frcnn_rpn_gather_rows(mp, nil, nil, mb, B, cap, cap, nil, 0, cnt, cap, nil, nil, nil, nil, box5, nil, cap, nil))
+  return box5
+end
+
+-- post_nms_top_n: the candidate counts clamped on the host; the device copy (what the winner table's header reports) follows
+function Detector:clamp_candidates(dev, count, B)
+  local changed = false
+  for b = 0, B - 1 do
+    if count[b] > self.post_nms_top_n then
+      count[b] = self.post_nms_top_n
+      changed = true
+    end
+  end
+  if changed then check(C.frcnn_memcpy_h2d(dev, count, 4 * B, nil)) end
+end
+
+-- Detector.lua:17-85: proposal net, scan, (selection), first NMS, read-back 1 of 2 -> a table { outputs, mp, mi, mr (the match
+-- arrays the rest of the frame reads: the selected rows under pre_nms_top_n), row (their 1-based original scan rows, or nil),
+-- dpick, cnt, matches (the count before the cap), nm (rows of the match arrays), R (candidates) }
+function Detector:first_stage(input)
+  local pnet = self.model.pnet
+  local scratch = self.scratch
+  local order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
 
   local input_size = input:size()
   pnet:evaluate()                                                       -- :31
@@ -68,26 +142,81 @@ function Detector:detect(input)                                         -- Detec
   -- NON-MAXIMUM SUPPRESSION (:74-85) on the device, the match count read from DEVICE memory (no round trip between scan
   -- and NMS); the score tensor is ignored by nms.lua -> key = max-y
   -- (launch and workspace sized for a bound on the matches, not for every anchor of the maps; a frame with more matches
-  -- repeats the pass sized by the count just read)
+  -- repeats the pass sized by the count just read.  Under pre_nms_top_n = K the bound is min(cap, K), the rows are the K
+  -- best-scoring matches, and no frame can exceed it)
   local ncap = math.min(cap, 16384)
+  local ndev, boxes, ncols, key_mode, key_col, row = cnt, mb, 4, 0, 0, nil
+  if order == 'score' and pre == nil then boxes, ncols = self:score_rows(mp, mb, 1, cap, cnt, ''), 5 end
+  if pre ~= nil then
+    local sel = self:select_rows(mp, mi, mr, mb, 1, cap, pre, cnt, '')
+    mp, mi, mr, mb, row = sel.p, sel.idx, sel.rect, sel.box, sel.row
+    ncap, ndev, boxes = sel.stride, sel.count, sel.box
+    if order == 'score' then boxes, ncols = sel.box5, 5 end
+  end
+  if order == 'score' then key_mode, key_col = 2, 5 end
   local nwsb = tonumber(C.frcnn_nms_workspace_bytes(ncap))
   local nws = scratch('nms_ws', nwsb)
   local dpick = ffi.cast('long long*', scratch('pick', 8 * cap).ptr)
-  check(C.frcnn_nms_device_n(mb, ncap, cnt, 4, 0.25, 0, 0, nil, dpick, cnt + 1, nws.ptr, nwsb, nil))
+  check(C.frcnn_nms_device_n(boxes, ncap, ndev, ncols, 0.25, key_mode, key_col, nil, dpick, cnt + 1, nws.ptr, nwsb, nil))
   local count = ffi.new('int[2]')
   check(C.frcnn_memcpy_d2h(count, cnt, 8, nil))                          -- ---- read-back 1 of 2: two counts
   check(C.frcnn_stream_sync(nil))
   if count[0] > cap then
     error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[0], cap))
   end
-  if count[0] > ncap then
-    nwsb = tonumber(C.frcnn_nms_workspace_bytes(count[0]))
+  local matches = count[0]
+  local nm = matches
+  if pre ~= nil then nm = math.min(matches, pre) end
+  if nm > ncap then
+    nwsb = tonumber(C.frcnn_nms_workspace_bytes(nm))
     nws = scratch('nms_ws_full', nwsb)
-    check(C.frcnn_nms_device(mb, count[0], 4, 0.25, 0, 0, dpick, cnt + 1, nws.ptr, nwsb, nil))
+    check(C.frcnn_nms_device(boxes, nm, ncols, 0.25, key_mode, key_col, dpick, cnt + 1, nws.ptr, nwsb, nil))
     check(C.frcnn_memcpy_d2h(count + 1, cnt + 1, 4, nil))
     check(C.frcnn_stream_sync(nil))
   end
-  local nm, R = count[0], count[1]
+  if post ~= nil then self:clamp_candidates(cnt + 1, count + 1, 1) end
+  return { outputs = outputs, mp = mp, mi = mi, mr = mr, row = row, dpick = dpick, cnt = cnt, matches = matches, nm = nm,
+           R = count[1] }
+end
+
+-- Detector:proposals(input) -- the candidates of the first NMS (Detector.lua:17-85) without the classification net: a list of
+-- { p, a, r, l } as in a detection, in pick order (under the proposal settings of this Detector)
+function Detector:proposals(input)
+  local st = self:first_stage(input)
+  local list = {}
+  if st.nm == 0 or st.R == 0 then return list end
+  local nm, R = st.nm, st.R
+  local hp, hi, hr = ffi.new('float[?]', nm), ffi.new('int[?]', 4 * nm), ffi.new('double[?]', 4 * nm)
+  local hpick = ffi.new('long long[?]', R)
+  check(C.frcnn_memcpy_d2h(hp, st.mp, 4 * nm, nil))
+  check(C.frcnn_memcpy_d2h(hi, st.mi, 16 * nm, nil))
+  check(C.frcnn_memcpy_d2h(hr, st.mr, 32 * nm, nil))
+  check(C.frcnn_memcpy_d2h(hpick, st.dpick, 8 * R, nil))
+  check(C.frcnn_stream_sync(nil))
+  for q = 0, R - 1 do
+    local i = tonumber(hpick[q]) - 1
+    local l, a, y, x = hi[4 * i], hi[4 * i + 1], hi[4 * i + 2], hi[4 * i + 3]
+    list[#list + 1] = { p = hp[i], a = self.anchors:get(l, a, y, x), l = l,
+                        r = Rect.new(hr[4 * i], hr[4 * i + 1], hr[4 * i + 2], hr[4 * i + 3]) }
+  end
+  return list
+end
+
+function Detector:detect(input)                                         -- Detector.lua:17-141
+  local model = self.model
+  local cfg = model.cfg
+  local cnet = model.cnet
+  local kh, kw = cfg.roi_pooling.kh, cfg.roi_pooling.kw
+  local bgclass = cfg.class_count + 1
+  local ncls = cfg.class_count + 1
+  local cnet_input_planes = model.layers[#model.layers].filters
+  local D = kh * kw * cnet_input_planes
+  local scratch = self.scratch
+  local key_mode, key_col = 0, 0
+  if self.proposal_order == 'score' then key_mode, key_col = 2, 5 end
+
+  local st = self:first_stage(input)                                    -- :17-85
+  local outputs, mp, mi, mr, dpick, cnt, nm, R = st.outputs, st.mp, st.mi, st.mr, st.dpick, st.cnt, st.nm, st.R
 
   local winners = {}
   if nm > 0 then                                                        -- :71
@@ -120,11 +249,11 @@ function Detector:detect(input)                                         -- Detec
     check(C.frcnn_detect_post(dcls, dconf, bbox_out.ptr, mr, dpick, R, bgclass, 0.2, dbb, dkc, dkeep, dr2, cnt + 2, nil))
     -- per-class NMS (:125-136), every class in ONE device pass: rows only suppress rows of their own class; a stable
     -- partition of the picks by class is, per class, exactly nms(bb, 0.1, bb[{{}, 5}]) -- the score tensor is ignored by
-    -- nms.lua:42, the key is max-y.  The survivor count is read from device memory.
+    -- nms.lua:42, the key is max-y (order = 'score': column 5, the confidence).  The survivor count is read from device memory.
     local cwsb = tonumber(C.frcnn_nms_workspace_bytes(R))
     local cws = scratch('nms_ws2', cwsb)
     local cpick = ffi.cast('long long*', scratch('wpick', 8 * R).ptr)
-    check(C.frcnn_nms_device_n(dbb, R, cnt + 2, 5, 0.1, 0, 0, dkc, cpick, cnt + 3, cws.ptr, cwsb, nil))
+    check(C.frcnn_nms_device_n(dbb, R, cnt + 2, 5, 0.1, key_mode, key_col, dkc, cpick, cnt + 3, cws.ptr, cwsb, nil))
     -- one record of 16 doubles per winner behind a 128-byte header that carries the four counts
     local out = ffi.cast('double*', scratch('winners', 128 * (R + 1)).ptr)
     check(C.frcnn_memcpy_d2d(out, cnt, 16, nil))
@@ -235,27 +364,46 @@ function Detector:detect_chunk(frames, shared)
   local mb = ffi.cast('float*', scratch('b_match_box', 16 * B * cap).ptr)
   check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap,
                                mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
-  -- ---- 3. ONE segmented NMS, the match counts read from device memory, sized for the bound of detect()
+  -- ---- 3. ONE segmented NMS, the match counts read from device memory, sized for the bound of detect().  Under
+  --         pre_nms_top_n the match arrays are replaced by the compact arrays of the selected rows (`cap` rows a frame from
+  --         here on: min(cap, K)), which no frame can exceed; order = 'score': rows {box, p} keyed by p
+  local order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
+  local key_mode, key_col = 0, 0
+  if order == 'score' then key_mode, key_col = 2, 5 end
+  local anchors = cap
   local ncap = math.min(cap, 16384)
+  local ndev, boxes, ncols = cnt, mb, 4
+  if order == 'score' and pre == nil then boxes, ncols = self:score_rows(mp, mb, B, cap, cnt, 'b_'), 5 end
+  if pre ~= nil then
+    local sel = self:select_rows(mp, mi, mr, mb, B, cap, pre, cnt, 'b_')
+    mp, mi, mr, mb = sel.p, sel.idx, sel.rect, sel.box
+    cap, ncap, ndev, boxes = sel.stride, sel.stride, sel.count, sel.box
+    if order == 'score' then boxes, ncols = sel.box5, 5 end
+  end
   local nwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, ncap))
   local nws = scratch('b_nms_ws', nwsb)
   local dpick = ffi.cast('long long*', scratch('b_pick', 8 * B * cap).ptr)
-  check(C.frcnn_nms_device_batch(mb, B, cap, ncap, cnt, 4, 0.25, 0, 0, nil, dpick, cnt + B, nws.ptr, nwsb, nil))
+  check(C.frcnn_nms_device_batch(boxes, B, cap, ncap, ndev, ncols, 0.25, key_mode, key_col, nil, dpick, cnt + B, nws.ptr, nwsb, nil))
   local count = ffi.new('int[?]', 2 * B)
   check(C.frcnn_memcpy_d2h(count, cnt, 8 * B, nil))                      -- ---- read-back 1 of 2: B pairs of counts
   check(C.frcnn_stream_sync(nil))
   local Rmax = 0
   for b = 0, B - 1 do
-    if count[b] > cap then
-      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], cap))
+    if count[b] > anchors then
+      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], anchors))
     end
+    if pre ~= nil then count[b] = math.min(count[b], pre) end           -- rows of the (compact) match arrays from here on
     if count[b] > ncap then                                             -- the frame repeats its NMS alone, as in detect()
       local fwsb = tonumber(C.frcnn_nms_workspace_bytes(count[b]))
       local fws = scratch('nms_ws_full', fwsb)
-      check(C.frcnn_nms_device(mb + 4 * b * cap, count[b], 4, 0.25, 0, 0, dpick + b * cap, cnt + B + b, fws.ptr, fwsb, nil))
+      check(C.frcnn_nms_device(boxes + ncols * b * cap, count[b], ncols, 0.25, key_mode, key_col, dpick + b * cap, cnt + B + b,
+                               fws.ptr, fwsb, nil))
       check(C.frcnn_memcpy_d2h(count + B + b, cnt + B + b, 4, nil))
       check(C.frcnn_stream_sync(nil))
     end
+  end
+  if post ~= nil then self:clamp_candidates(cnt + B, count + B, B) end
+  for b = 0, B - 1 do
     if count[b] > 0 then Rmax = math.max(Rmax, count[B + b]) end
   end
   local results = {}
@@ -323,7 +471,8 @@ function Detector:detect_chunk(frames, shared)
   local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, Rmax))
   local cws = scratch('b_nms_ws2', cwsb)
   local cpick = ffi.cast('long long*', scratch('b_wpick', 8 * B * Rmax).ptr)
-  check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 0.1, 0, 0, dkc, cpick, cnt + 3 * B, cws.ptr, cwsb, nil))
+  check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 0.1, key_mode, key_col, dkc, cpick, cnt + 3 * B, cws.ptr, cwsb,
+                                 nil))
   local out = ffi.cast('double*', scratch('b_winners', 128 * B * (Rmax + 1)).ptr)
   check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb, dr2, dpick, cap, mp, mr, mi, out, nil))
   local h = ffi.new('double[?]', 16 * B * (Rmax + 1))

@@ -8,7 +8,13 @@ by descending max-y.  That behaviour is reproduced.
 The frame stays on the device between its big steps: scan -> NMS (the match count is read by the NMS kernels from
 device memory), ONE read-back of two counts (the cnet's row count sizes its launches), then ROI windows -> ROI pooling
 -> cnet -> class test + rect decode + ordered compaction -> per-class NMS -> one record per winner, and ONE read-back
-of the winner table.  The list detect() returns builds its {p, a, r, l, r2, class, confidence} tables on access."""
+of the winner table.  The list detect() returns builds its {p, a, r, l, r2, class, confidence} tables on access.
+
+Not in the reference, off by default (cfg["proposals"] / Detector(..., proposals=...), see proposal_settings): the proposal
+layer's two caps and score-ordered NMS.  pre_nms_top_n = K keeps the K best-scoring matches in front of the first NMS
+(frcnn_topk_select + frcnn_rpn_gather_rows: the selected rows keep their scan order, everything downstream runs unchanged on
+compact arrays, the first NMS is sized by min(anchors, K)); order = "score" keys both NMS passes by the score instead of max-y;
+post_nms_top_n = M keeps the first min(R, M) picks of the first NMS."""
 import ctypes as C
 import math
 
@@ -25,6 +31,48 @@ from .objective import roi_window, roi_windows
 from .tensor import DeviceTensor, ptr, stream_ptr, to_device
 
 ASPECTS = 3   # anchors per map position (Anchors.lua:108-109)
+
+PROPOSAL_DEFAULTS = dict(order="y2", pre_nms_top_n=None, post_nms_top_n=None)
+
+
+def proposal_settings(cfg_or_table):
+    """cfg["proposals"] -- or the table itself, or None -- -> (order, pre_nms_top_n, post_nms_top_n), validated on the host.
+      order           "y2" (default: the reference -- nms.lua ignores the scores it is handed, boxes go by descending max-y) or
+                      "score": the first NMS runs on rows {box, p} keyed by p (key_mode 2, key_col 5), the per-class NMS keyed
+                      by the confidence (key_col 5); the NMS tie rule is unchanged
+      pre_nms_top_n   None or K >= 1: only the K' = min(n, K) best-ranked of a frame's n matches reach the first NMS.  Rank:
+                      the match's fp32 p compared as a value (-0 equals +0, a NaN ranks below everything), ties are broken by
+                      the lower scan row.  The selected rows keep their scan order, so K >= n changes nothing.  Either order.
+      post_nms_top_n  None or M >= 1: the candidates are the first min(R, M) picks of the first NMS.  Needs order = "score": the
+                      first M picks in max-y order are not the best M.
+    Raises ValueError (before any device call) for an unknown key, an unknown order, a bool or non-integer or < 1 cap, and
+    post_nms_top_n without order = "score"."""
+    t = cfg_or_table
+    if isinstance(t, dict) and ("proposals" in t or "class_count" in t):     # a model's cfg
+        t = t.get("proposals")
+    if t is None:
+        t = {}
+    if not isinstance(t, dict):
+        raise ValueError("cfg.proposals must be a table of {order, pre_nms_top_n, post_nms_top_n}")
+    unknown = sorted(set(t) - set(PROPOSAL_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError("cfg.proposals: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    order = t.get("order", "y2")
+    if not isinstance(order, str) or order not in ("y2", "score"):
+        raise ValueError("cfg.proposals.order = %r (\"y2\" or \"score\")" % (order,))
+    caps = []
+    for k in ("pre_nms_top_n", "post_nms_top_n"):
+        v = t.get(k)
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("cfg.proposals.%s = %r is not an integer" % (k, v))
+            if v < 1:
+                raise ValueError("cfg.proposals.%s = %d (at least 1)" % (k, v))
+            v = int(v)
+        caps.append(v)
+    if caps[1] is not None and order != "score":
+        raise ValueError("cfg.proposals.post_nms_top_n needs order = \"score\": the first picks in max-y order are not the best")
+    return order, caps[0], caps[1]
 
 
 class _Detections(object):
@@ -73,13 +121,18 @@ class _BatchRecord(object):
     """One frame's entry of Detector.last_batch: reads like a dict with the keys n, idx, box, rect, p (the frame's scan rows),
     pick (1-based candidate rows, pick order), cnet (dict bbox, cls; None for a frame without matches), kept; and pooled --
     the classification net's input rows, kept only by a shared_cnet pass and only for the last chunk of a call (else None).
-    The arrays stay on the device and are fetched when they are looked at, like last_scan / last_pick / last_cnet of detect()."""
+    The arrays stay on the device and are fetched when they are looked at, like last_scan / last_pick / last_cnet of detect().
+    Under pre_nms_top_n the scan rows are the SELECTED rows (n of them) and two more keys exist: row (their 1-based original
+    scan rows) and matches (the frame's match count before the cap)."""
     _KEYS = ("n", "idx", "box", "rect", "p", "pick", "cnet", "kept", "pooled")
 
-    def __init__(self, n, R, kept, dev):
+    def __init__(self, n, R, kept, dev, matches=None):
         self._v = dict(n=n, R=R, kept=kept)
         self._dev = dev      # name -> DeviceTensor (views of the chunk's buffers until detach())
         self._view = True
+        if matches is not None:
+            self._v["matches"] = matches
+            self._KEYS = self._KEYS + ("row", "matches")
 
     def detach(self):
         """A private device copy of the frame's arrays (one allocation; the copies are queued on the stream, no wait): the
@@ -120,10 +173,14 @@ class _BatchRecord(object):
 
 
 class Detector(object):
-    def __init__(self, model, static_weights=False):  # Detector.lua:8-15
+    proposal_settings = staticmethod(proposal_settings)
+
+    def __init__(self, model, static_weights=False, proposals=None):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
         the convolution weights once instead of once per frame (option static_weights of the C ABI; a training-mode pass or
-        another Detector(..., static_weights=...) drops the packs)."""
+        another Detector(..., static_weights=...) drops the packs).
+        proposals: a table as proposal_settings takes it; None: model["cfg"]["proposals"] (absent: the reference's behaviour)."""
+        self.set_proposals(proposals if proposals is not None else model["cfg"])
         self.model = model
         if static_weights or os.environ.get("FRCNN_STATIC_WEIGHTS"):
             _lib.call("frcnn_set_option", b"static_weights", 1)
@@ -141,6 +198,10 @@ class Detector(object):
         self.last_scan = None
         self._last = {}
         self.last_batch = []
+
+    def set_proposals(self, cfg_or_table):
+        """Validates a table as proposal_settings takes it and makes it this Detector's setting from the next frame on."""
+        self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n = proposal_settings(cfg_or_table)
 
     def __del__(self):
         if getattr(self, "_host", None):
@@ -208,16 +269,50 @@ class Detector(object):
             L["cnet_host"] = dict(bbox=L["bbox"].numpy(), cls=L["cls"].numpy())
         return L.get("cnet_host")
 
-    def detect(self, input):  # Detector.lua:17-141
-        model = self.model
-        cfg = model["cfg"]
-        pnet, cnet = model["pnet"], model["cnet"]
-        kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
-        bgclass = cfg["class_count"] + 1
-        ncls = cfg["class_count"] + 1
-        planes = model["layers"][-1]["filters"]
+    def _select(self, mp, mi, mr, mb, B, cap, K, c_n, pre=""):
+        """pre_nms_top_n: the min(n_b, K) best-scoring rows of every frame's matches (B x cap rows, device counts c_n), gathered
+        in scan order into compact arrays of kcap = min(cap, K) rows per frame -> dict(p, idx, rect, box, box5, row, cnt (device
+        int32[B]: the selected counts), stride)."""
+        kcap = min(cap, K)
+        sel = self._buf(pre + "sel", (B, kcap), np.int32)
+        cnt = self._buf(pre + "sel_count", (B,), np.int32)
+        wsb = _lib.load().frcnn_topk_select_workspace_bytes(B, cap)
+        ws = self._buf(pre + "sel_ws", (wsb,), np.uint8)
+        s = stream_ptr()
+        _lib.call("frcnn_topk_select", ptr(mp), B, cap, cap, c_n, K, ptr(sel), kcap, ptr(cnt), ptr(ws), wsb, s)
+        out = dict(p=self._buf(pre + "sel_p", (B, kcap)), idx=self._buf(pre + "sel_idx", (B, kcap, 4), np.int32),
+                   rect=self._buf(pre + "sel_rect", (B, kcap, 4), np.float64), box=self._buf(pre + "sel_box", (B, kcap, 4)),
+                   box5=self._buf(pre + "sel_box5", (B, kcap, 5)), row=self._buf(pre + "sel_row", (B, kcap), np.int32))
+        _lib.call("frcnn_rpn_gather_rows", ptr(mp), ptr(mi), ptr(mr), ptr(mb), B, cap, cap, ptr(sel), kcap, ptr(cnt), kcap,
+                  ptr(out["p"]), ptr(out["idx"]), ptr(out["rect"]), ptr(out["box"]), ptr(out["box5"]), ptr(out["row"]), kcap, s)
+        out.update(cnt=cnt, stride=kcap)
+        return out
+
+    def _box5(self, mp, mb, B, cap, c_n, pre=""):
+        """order = "score" without a cap: rows {box, p} of every match (the count read on the device), the first NMS's input."""
+        box5 = self._buf(pre + "box5", (B, cap, 5))
+        _lib.call("frcnn_rpn_gather_rows", ptr(mp), None, None, ptr(mb), B, cap, cap, None, 0, c_n, cap, None, None, None, None,
+                  ptr(box5), None, cap, stream_ptr())
+        return box5
+
+    def _clamp_candidates(self, dev_ptr, Rs):
+        """post_nms_top_n: the candidate counts clamped on the host -> (the clamped list, True when any changed); the device
+        copy behind dev_ptr (what the winner table's header reports) follows."""
+        out = [min(R, self.post_nms_top_n) for R in Rs]
+        if out == Rs:
+            return out, False
+        host = np.array(out, np.int32)
+        _lib.call("frcnn_memcpy_h2d", C.c_void_p(dev_ptr), host.ctypes.data_as(C.c_void_p), host.nbytes, stream_ptr())
+        self._clamped = host     # (pageable memory: the copy has been staged when the call returns; kept anyway)
+        return out, True
+
+    def _first_stage(self, input):
+        """Detector.lua:17-85: proposal net, scan, (selection), first NMS, read-back 1 of 2 -> (outputs, m, pick, counts, R);
+        m: the match arrays the rest of the frame reads (the selected rows under pre_nms_top_n).  Leaves last_scan / last_pick."""
+        pnet = self.model["pnet"]
         s = stream_ptr()
         L = _lib.load()
+        order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
 
         inp = to_device(input)
         _, H, W = inp.shape
@@ -231,29 +326,73 @@ class Detector(object):
         # ignored by nms.lua -> key = max-y
         # The launch and its workspace are sized for a BOUND on the matches, not for every anchor of the maps (vgg_large:
         # 45 015 anchors -> 253 MB of masks and a 704 x 704 tile grid per frame for a few hundred matches); a frame with more
-        # matches than the bound repeats the pass sized by the count just read.
+        # matches than the bound repeats the pass sized by the count just read.  Under pre_nms_top_n = K the bound is
+        # min(cap, K), the rows are the K best-scoring matches, and no frame can exceed it.
         ncap = min(cap, self.NMS_FIRST_CAP)
+        n_dev, boxes, ncols, key_mode, key_col = counts, m["box"], 4, 0, 0
+        if pre is not None:
+            sel = self._select(m["p"], m["idx"], m["rect"], m["box"], 1, cap, pre, ptr(counts))
+            m = dict(m, p=sel["p"], idx=sel["idx"], rect=sel["rect"], box=sel["box"], box5=sel["box5"], row=sel["row"])
+            ncap, n_dev, boxes = sel["stride"], sel["cnt"], sel["box"]
+        if order == "score":
+            boxes = m["box5"] if pre is not None else self._box5(m["p"], m["box"], 1, cap, ptr(counts))
+            ncols, key_mode, key_col = 5, 2, 5
         wsb = L.frcnn_nms_workspace_bytes(ncap)
         ws = self._buf("nms_ws", (wsb,), np.uint8)
         pick = self._buf("nms_pick", (cap,), np.int64)
-        _lib.call("frcnn_nms_device_n", ptr(m["box"]), ncap, ptr(counts), 4, C.c_float(0.25), 0, 0, None, ptr(pick),
+        _lib.call("frcnn_nms_device_n", ptr(boxes), ncap, ptr(n_dev), ncols, C.c_float(0.25), key_mode, key_col, None, ptr(pick),
                   C.c_void_p(counts.ptr + 4), ptr(ws), wsb, s)
-        n, R = [int(v) for v in self._read(counts.ptr, 8, np.int32)]          # ---- read-back 1 of 2: two counts
-        if n > cap:
-            raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (n, m["threshold"], cap))
+        matches, R = [int(v) for v in self._read(counts.ptr, 8, np.int32)]          # ---- read-back 1 of 2: two counts
+        if matches > cap:
+            raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (matches, m["threshold"], cap))
+        n = matches if pre is None else min(matches, pre)
         if n > ncap:
             wsb = L.frcnn_nms_workspace_bytes(n)
             ws = self._buf("nms_ws_full", (wsb,), np.uint8)
-            _lib.call("frcnn_nms_device", ptr(m["box"]), n, 4, C.c_float(0.25), 0, 0, ptr(pick), C.c_void_p(counts.ptr + 4),
-                      ptr(ws), wsb, s)
+            _lib.call("frcnn_nms_device", ptr(boxes), n, ncols, C.c_float(0.25), key_mode, key_col, ptr(pick),
+                      C.c_void_p(counts.ptr + 4), ptr(ws), wsb, s)
             R = int(self._read(counts.ptr + 4, 4, np.int32)[0])
+        if post is not None:
+            R = self._clamp_candidates(counts.ptr + 4, [R])[0][0]
         self.last_scan = dict(n=n, p=DeviceTensor(m["p"].ptr, (n,), np.float32, owner=m["p"]),
                               idx=DeviceTensor(m["idx"].ptr, (n, 4), np.int32, owner=m["idx"]),
                               rect=DeviceTensor(m["rect"].ptr, (n, 4), np.float64, owner=m["rect"]),
                               box=DeviceTensor(m["box"].ptr, (n, 4), np.float32, owner=m["box"]))
+        if pre is not None:   # the rows above are the selected ones: their 1-based original scan rows, the count before the cap
+            self.last_scan.update(row=DeviceTensor(m["row"].ptr, (n,), np.int32, owner=m["row"]), matches=matches)
         self._last = dict(pick=pick, R=R)
         if n == 0:  # :71
             self._last["pick_host"] = np.zeros(0, np.int64)
+        return outputs, m, pick, counts, n, R
+
+    def proposals(self, input):
+        """The candidates of the first NMS (Detector.lua:17-85) without the classification net: a list of {p, a, r, l} as in a
+        detection, in pick order (under the proposal settings of this Detector)."""
+        _, _, _, _, n, R = self._first_stage(input)
+        if n == 0 or R == 0:
+            return []
+        sc = self.last_scan
+        p, idx, rect = sc["p"].numpy(), sc["idx"].numpy(), sc["rect"].numpy()
+        out = []
+        for i in (self.last_pick - 1).tolist():
+            ix = [int(t) for t in idx[i]]
+            out.append(dict(p=float(p[i]), r=Rect(*rect[i].tolist()), l=ix[0], a=self.anchors.get(*ix)))
+        return out
+
+    def detect(self, input):  # Detector.lua:17-141
+        model = self.model
+        cfg = model["cfg"]
+        cnet = model["cnet"]
+        kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
+        bgclass = cfg["class_count"] + 1
+        ncls = cfg["class_count"] + 1
+        planes = model["layers"][-1]["filters"]
+        s = stream_ptr()
+        L = _lib.load()
+        key_mode, key_col = (2, 5) if self.proposal_order == "score" else (0, 0)
+
+        outputs, m, pick, counts, n, R = self._first_stage(input)   # :17-85
+        if n == 0:  # :71
             return []
         if self.verbose:
             print("candidates: %d" % R)
@@ -276,13 +415,13 @@ class Detector(object):
         _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(bbox_out), ptr(m["rect"]), ptr(pick), R, bgclass, 0.2,
                   ptr(bb), ptr(kc), ptr(keep_row), ptr(r2), C.c_void_p(counts.ptr + 8), s)
         # Per-class NMS (:125-136), all classes in ONE device pass (rows only suppress rows of their own class; a stable
-        # partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y), the survivor
-        # count read from device memory
+        # partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
+        # column under order = "score"), the survivor count read from device memory
         wsb2 = L.frcnn_nms_workspace_bytes(R)
         ws2 = self._buf("nms_ws2", (wsb2,), np.uint8)
         wpick = self._buf("wpick", (R,), np.int64)
-        _lib.call("frcnn_nms_device_n", ptr(bb), R, C.c_void_p(counts.ptr + 8), 5, C.c_float(0.1), 0, 0, ptr(kc), ptr(wpick),
-                  C.c_void_p(counts.ptr + 12), ptr(ws2), wsb2, s)
+        _lib.call("frcnn_nms_device_n", ptr(bb), R, C.c_void_p(counts.ptr + 8), 5, C.c_float(0.1), key_mode, key_col, ptr(kc),
+                  ptr(wpick), C.c_void_p(counts.ptr + 12), ptr(ws2), wsb2, s)
         # one record per winner, behind a 128-byte header that carries the four counts
         out = self._buf("winners", (R + 1, 16), np.float64)
         _lib.call("frcnn_memcpy_d2d", ptr(out), ptr(counts), 16, s)
@@ -378,24 +517,43 @@ class Detector(object):
         threshold = 0.95
         _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, B, slot, ptr(self._aw), ptr(self._ah), float(W), float(H), threshold, cap,
                   ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
-        # ---- 3. ONE segmented NMS (:74-85), the match counts read from device memory, sized for the bound of detect()
+        # ---- 3. ONE segmented NMS (:74-85), the match counts read from device memory, sized for the bound of detect().
+        #         Under pre_nms_top_n the match arrays are replaced by the compact arrays of the selected rows (`cap` rows a
+        #         frame from here on: min(cap, K)), which no frame can exceed; order = "score": rows {box, p} keyed by p.
+        order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
+        key_mode, key_col = (2, 5) if order == "score" else (0, 0)
         ncap = min(cap, self.NMS_FIRST_CAP)
+        c_first, boxes, ncols, row, matches, anchors = c_n, mb, 4, None, None, cap
+        if order == "score" and pre is None:
+            boxes, ncols = self._box5(mp, mb, B, cap, c_n, "b_"), 5
+        if pre is not None:
+            sel = self._select(mp, mi, mr, mb, B, cap, pre, c_n, "b_")
+            mp, mi, mr, mb, row = sel["p"], sel["idx"], sel["rect"], sel["box"], sel["row"]
+            cap = ncap = sel["stride"]
+            c_first, boxes = ptr(sel["cnt"]), mb
+            if order == "score":
+                boxes, ncols = sel["box5"], 5
         wsb = L.frcnn_nms_batch_workspace_bytes(B, ncap)
         ws = self._buf("b_nms_ws", (wsb,), np.uint8)
         pick = self._buf("b_nms_pick", (B, cap), np.int64)
-        _lib.call("frcnn_nms_device_batch", ptr(mb), B, cap, ncap, c_n, 4, C.c_float(0.25), 0, 0, None, ptr(pick), c_R,
-                  ptr(ws), wsb, s)
+        _lib.call("frcnn_nms_device_batch", ptr(boxes), B, cap, ncap, c_first, ncols, C.c_float(0.25), key_mode, key_col, None,
+                  ptr(pick), c_R, ptr(ws), wsb, s)
         nR = self._read(counts.ptr, 8 * B, i32)                                # ---- read-back 1 of 2: B pairs of counts
         ns, Rs = [int(v) for v in nR[:B]], [int(v) for v in nR[B:]]
         for b in range(B):
-            if ns[b] > cap:
-                raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (ns[b], threshold, cap))
+            if ns[b] > anchors:
+                raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (ns[b], threshold, anchors))
+        if pre is not None:
+            matches, ns = ns, [min(n, pre) for n in ns]
+        for b in range(B):
             if ns[b] > ncap:   # more matches than the bound: the frame repeats its NMS alone, as in detect()
                 wsb = L.frcnn_nms_workspace_bytes(ns[b])
                 ws = self._buf("nms_ws_full", (wsb,), np.uint8)
-                _lib.call("frcnn_nms_device", C.c_void_p(mb.ptr + 16 * b * cap), ns[b], 4, C.c_float(0.25), 0, 0,
-                          C.c_void_p(pick.ptr + 8 * b * cap), C.c_void_p(counts.ptr + 4 * (B + b)), ptr(ws), wsb, s)
+                _lib.call("frcnn_nms_device", C.c_void_p(boxes.ptr + 4 * ncols * b * cap), ns[b], ncols, C.c_float(0.25), key_mode,
+                          key_col, C.c_void_p(pick.ptr + 8 * b * cap), C.c_void_p(counts.ptr + 4 * (B + b)), ptr(ws), wsb, s)
                 Rs[b] = int(self._read(counts.ptr + 4 * (B + b), 4, i32)[0])
+        if post is not None:
+            Rs = self._clamp_candidates(counts.ptr + 4 * B, Rs)[0]
         dev = []
         for b in range(B):
             n, R = ns[b], Rs[b]
@@ -404,9 +562,14 @@ class Detector(object):
                             rect=DeviceTensor(mr.ptr + 32 * b * cap, (n, 4), np.float64, owner=mr),
                             box=DeviceTensor(mb.ptr + 16 * b * cap, (n, 4), np.float32, owner=mb),
                             pick=DeviceTensor(pick.ptr + 8 * b * cap, (R if n else 0,), np.int64, owner=pick)))
+            if row is not None:
+                dev[b].update(row=DeviceTensor(row.ptr + 4 * b * cap, (n,), i32, owner=row))
+
+        def record(b, R, kept):
+            return _BatchRecord(ns[b], R, kept, dev[b], matches[b] if matches is not None else None)
         Rmax = max([Rs[b] for b in range(B) if ns[b] > 0] + [0])
         if Rmax == 0:   # no frame has a match (:71)
-            return [[] for _ in range(B)], [_BatchRecord(ns[b], 0, 0, dev[b]) for b in range(B)]
+            return [[] for _ in range(B)], [record(b, 0, 0) for b in range(B)]
         # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into the frame's
         #         segment (Rmax rows per frame) -- the launches detect() makes, on the frame's own rows
         cnet.evaluate()
@@ -464,8 +627,8 @@ class Detector(object):
         wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
         ws2 = self._buf("b_nms_ws2", (wsb2,), np.uint8)
         wpick = self._buf("b_wpick", (B, Rmax), np.int64)
-        _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(0.1), 0, 0, ptr(kc), ptr(wpick), c_W,
-                  ptr(ws2), wsb2, s)
+        _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(0.1), key_mode, key_col, ptr(kc), ptr(wpick),
+                  c_W, ptr(ws2), wsb2, s)
         out = self._buf("b_winners", (B, Rmax + 1, 16), np.float64)
         _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb), ptr(r2), ptr(pick),
                   cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
@@ -473,7 +636,7 @@ class Detector(object):
         results, recs = [], []
         for b in range(B):
             hdr = raw[b, 0].view(i32)
-            recs.append(_BatchRecord(ns[b], Rs[b] if ns[b] else 0, int(hdr[2]), dev[b]))
+            recs.append(record(b, Rs[b] if ns[b] else 0, int(hdr[2])))
             if ns[b] == 0:
                 results.append([])
                 continue

@@ -52,7 +52,7 @@ void prof_after(int klass, double flops, double bytes, hipStream_t s) {
 using namespace frcnn;
 
 static_assert(frcnn::KC_COUNT == FRCNN_KC_COUNT && frcnn::KC_IMAGE == FRCNN_KC_IMAGE && frcnn::KC_OPTIM == FRCNN_KC_OPTIM &&
-              frcnn::KC_CONV_IGEMM_K3 == FRCNN_KC_CONV_IGEMM_K3, "kernel classes of common.h and frcnn_hip.h differ");
+              frcnn::KC_CONV_IGEMM_K3 == FRCNN_KC_CONV_IGEMM_K3 && frcnn::KC_TOPK == FRCNN_KC_TOPK, "kernel classes of common.h and frcnn_hip.h differ");
 
 extern "C" {
 
@@ -168,6 +168,18 @@ int frcnn_nms_device_batch(const float* boxes, int B, long long row_stride, int 
   FR_CHECK(B <= 0 || (boxes && pick && count), "frcnn_nms_device_batch: NULL argument");
   return nms_device_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, overlap, key_mode, key_col, cls, pick, count, ws,
                           ws_bytes, S(stream));
+}
+size_t frcnn_topk_select_workspace_bytes(int B, int n_cap) { return topk_select_workspace_bytes(B, n_cap); }
+int frcnn_topk_select(const float* score, int B, long long stride, int n_cap, const int* n_dev, int K, int* sel_row,
+                      long long sel_stride, int* k_dev, void* ws, size_t ws_bytes, void* stream) {
+  return topk_select(score, B, (long)stride, n_cap, n_dev, K, sel_row, (long)sel_stride, k_dev, ws, ws_bytes, S(stream));
+}
+int frcnn_rpn_gather_rows(const float* match_p, const int* match_idx, const double* match_rect, const float* match_box, int B,
+                          long long src_stride, int src_rows, const int* sel_row, long long sel_stride, const int* k_dev, int k_cap,
+                          float* dst_p, int* dst_idx, double* dst_rect, float* dst_box, float* box5, int* row,
+                          long long dst_stride, void* stream) {
+  return rpn_gather_rows(match_p, match_idx, match_rect, match_box, B, (long)src_stride, src_rows, sel_row, (long)sel_stride,
+                         k_dev, k_cap, dst_p, dst_idx, dst_rect, dst_box, box5, row, (long)dst_stride, S(stream));
 }
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,

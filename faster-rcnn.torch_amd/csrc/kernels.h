@@ -275,6 +275,13 @@ int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode
 size_t nms_batch_workspace_bytes(int B, int n);
 int nms_device_batch(const float* boxes, int B, long row_stride, int n, const int* n_dev, int ncols, float overlap, int key_mode,
                      int key_col, const int* cls, long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+// ---- proposal selection in front of the first NMS (topk.hip): the K best-scoring rows of a segment, in scan order
+size_t topk_select_workspace_bytes(int B, int n_cap);
+int topk_select(const float* score, int B, long stride, int n_cap, const int* n_dev, int K, int* sel_row, long sel_stride,
+                int* k_dev, void* ws, size_t ws_bytes, hipStream_t s);
+int rpn_gather_rows(const float* p, const int* idx, const double* rect, const float* box, int B, long src_stride, int src_rows,
+                    const int* sel_row, long sel_stride, const int* k_dev, int k_cap, float* dst_p, int* dst_idx,
+                    double* dst_rect, float* dst_box, float* box5, int* row, long dst_stride, hipStream_t s);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

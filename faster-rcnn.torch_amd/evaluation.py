@@ -11,6 +11,9 @@ PASCAL-VOC style mean average precision over `BatchIterator:nextValidation` (Bat
       its Rect.IoU (Rect.lua:138-141) with a not yet matched ground-truth box of class c in the same image is >= iou_threshold
       (0.5); detections are taken in order of decreasing confidence; AP is the area under the monotone precision envelope
       (VOC2010+) or the 11-point average (use_07_metric=True); mAP averages the classes that have ground truth.
+  proposal_recall(detector, batch_iterator, count) -> {recall, ground_truth, proposals_per_image}: the share of ground-truth
+      boxes that some candidate of the first NMS (Detector.proposals: no classification net) covers with Rect.IoU >=
+      iou_threshold -- the figure by which the proposal settings (order, pre_nms_top_n, post_nms_top_n) are chosen.
 
 All arithmetic of the networks runs through the C ABI (frcnn_pnet_forward, frcnn_rpn_loss, frcnn_loss_accumulate,
 frcnn_roi_pool_forward, frcnn_cnet_forward, frcnn_cnet_losses, Detector.detect); the bookkeeping here is host code."""
@@ -189,3 +192,22 @@ def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_
     res = mean_average_precision(detections, ground_truth, iou_threshold, use_07_metric)
     res.update(images=images, detections=len(detections), ground_truth=len(ground_truth))
     return res
+
+
+def proposal_recall(detector, batch_iterator, count, iou_threshold=0.5):
+    """Detector.proposals on `count` validation images against their ground truth, classes ignored: a ground-truth box counts
+    as recalled when the rect `r` of some proposal of its image has Rect.IoU (Rect.lua:138-141) >= iou_threshold with it.
+    -> dict(recall (nan without ground truth), ground_truth, proposals_per_image).  Host bookkeeping: `detector` is any object
+    with proposals(img) -> [{r: Rect, ...}], `batch_iterator` any with nextValidation(n) -> [{img, rois}]."""
+    images = hit = total = proposals = 0
+    while images < count:
+        for x in batch_iterator.nextValidation(1):
+            images += 1
+            props = detector.proposals(x["img"])
+            proposals += len(props)
+            for roi in x["rois"]:
+                total += 1
+                if any(Rect.IoU(p["r"], roi.rect) >= iou_threshold for p in props):
+                    hit += 1
+    return dict(recall=hit / float(total) if total else float("nan"), ground_truth=total,
+                proposals_per_image=proposals / float(images) if images else 0.0)

@@ -112,7 +112,8 @@ int frcnn_add(float *y, const float *x, long long n, void *stream);   /* y:add(x
 #define FRCNN_KC_IMAGE 10
 #define FRCNN_KC_CONV_X3 11      /* 3x3 forward + input gradient, split-bf16 operand form */
 #define FRCNN_KC_CONV_WGRADX 12  /* 3x3 weight gradient, split-bf16 operand form */
-#define FRCNN_KC_COUNT 13
+#define FRCNN_KC_TOPK 13         /* proposal selection in front of the first NMS (frcnn_topk_select, frcnn_rpn_gather_rows) */
+#define FRCNN_KC_COUNT 14
 /* class_mask: bit k set -> every launch of kernel class k is bracketed by two hipEvents on its
  * launch stream (0 = profiling off). */
 int frcnn_prof_enable(int class_mask);
@@ -249,6 +250,41 @@ int frcnn_rpn_scan_batch(const float *const *maps_host, const int *H_host, const
                          const float *anchor_w, const float *anchor_h, double img_w, double img_h, double p_threshold,
                          int cap, float *match_p, int *match_idx, double *match_rect, float *match_box, int *count,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- score-ordered proposals with pre- and post-NMS caps (not in the reference; csrc/topk.hip) -----------------------
+ * Detector.lua:39-85 hands every anchor with exp(p) > 0.95 to nms(), which ignores the scores it is given (key = max-y).  A
+ * host may instead (cfg.proposals = { order = "y2" | "score", pre_nms_top_n = K, post_nms_top_n = M }; default: the reference)
+ *   - keep only the K best-scoring matches in front of the first NMS (pre_nms_top_n; either order),
+ *   - run both NMS passes keyed by the score (order = "score": the first on rows {box, p} with key_mode 2, key_col 5, the
+ *     per-class one with key_col 5, the confidence; the NMS tie rule is the one of frcnn_nms_device),
+ *   - keep only the first min(R, M) picks of the first NMS as candidates (post_nms_top_n; needs order = "score"; a clamp of
+ *     the count on the host after the first read-back, no kernel).
+ * RANK of a match: its fp32 p (the log-probability frcnn_rpn_scan stores), compared as fp32 VALUES: -0 equals +0, a NaN
+ * ranks below everything (the scan never produces one); ties are broken by the LOWER scan row.
+ * SELECTION: the K' = min(n, K) best-ranked rows, and they KEEP THEIR SCAN ORDER (ascending original row).  For K >= n the
+ * selection is the identity, and everything downstream is bit-identical to the uncapped run with the same order.
+ *
+ * frcnn_topk_select: B segments in one launch (one workgroup per segment).  Segment b: keys score + b*stride, row count
+ * min(n_dev[b], n_cap) read from DEVICE memory (as in frcnn_nms_device_batch; stride >= n_cap); writes the ascending 0-based
+ * rows of the selected set to sel_row + b*sel_stride (sel_stride >= min(n_cap, K)) and k_dev[b] = K'.  A segment of count 0
+ * writes k_dev[b] = 0 and nothing else; no segment stores outside [0, K') of its slice.  Exact and deterministic (radix
+ * select on the order-preserving integer image of the key, integer counts only): the result depends on the data alone.
+ * K >= 1.  Workspace: frcnn_topk_select_workspace_bytes(B, n_cap) (the keys' images). */
+size_t frcnn_topk_select_workspace_bytes(int B, int n_cap);
+int frcnn_topk_select(const float *score, int B, long long stride, int n_cap, const int *n_dev, int K, int *sel_row,
+                      long long sel_stride, int *k_dev, void *workspace, size_t workspace_bytes, void *stream);
+/* frcnn_rpn_gather_rows: the match arrays of frcnn_rpn_scan[_batch] (src_stride rows per segment, src_rows of them valid)
+ * gathered into compact arrays of the same layouts (dst_stride rows per segment), all segments in one launch.  Row
+ * j < min(k_dev[b], k_cap) of segment b comes from source row sel_row[b*sel_stride + j] (0-based, as frcnn_topk_select wrote
+ * it; sel_row NULL: row j itself, k_dev then being the scan's own count).  Destinations, any of which may be NULL: dst_p,
+ * dst_idx[4], dst_rect[4] (double), dst_box[4], box5[5] = {box, p} (the first NMS's input under order = "score"), row = the
+ * 1-based original scan row.  frcnn_roi_windows, frcnn_detect_post and frcnn_detect_gather[_batch] then run unchanged on the
+ * compact arrays; with sel_row NULL the call only builds box5 for all matches -- no host round trip between scan and NMS in
+ * any mode.  The 16-byte rows (idx, box, rect) must be 16-byte aligned. */
+int frcnn_rpn_gather_rows(const float *match_p, const int *match_idx, const double *match_rect, const float *match_box, int B,
+                          long long src_stride, int src_rows, const int *sel_row, long long sel_stride, const int *k_dev,
+                          int k_cap, float *dst_p, int *dst_idx, double *dst_rect, float *dst_box, float *box5, int *row,
+                          long long dst_stride, void *stream);
 
 /* ---- sparse RPN loss: objective.lua:91-140 (+ cnet targets, objective.lua:149-159) ---- */
 /* Examples: positives first (npos) then negatives (nneg).  ex_idx int[E][4] {layer,aspect,y,x}
