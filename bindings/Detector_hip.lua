@@ -206,7 +206,9 @@ function Detector:detect(input)                                         -- Detec
   local model = self.model
   local cfg = model.cfg
   local cnet = model.cnet
-  local kh, kw = cfg.roi_pooling.kh, cfg.roi_pooling.kw
+  local kh, kw, method, sampling = hip.roi_pooling_settings(cfg)
+  local inv_sx, inv_sy = 0, 0                        -- RoIAlign reads the rects and the picks as they are: no window kernel
+  if method == 'align' then inv_sx, inv_sy = hip.align_geometry(self.localizer) end
   local bgclass = cfg.class_count + 1
   local ncls = cfg.class_count + 1
   local cnet_input_planes = model.layers[#model.layers].filters
@@ -232,10 +234,14 @@ function Detector:detect(input)                                         -- Detec
       local o = 6 * (i - 1)
       layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
     end
-    local dwins = ffi.cast('int*', scratch('wins', 16 * R).ptr)
-    check(C.frcnn_roi_windows(mr, dpick, R, layers, nl, fs[2], fs[3], dwins, nil))
     local cinput = hip.view(scratch('cinput', 4 * R * D).ptr, { R, D })
-    check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
+    if method == 'align' then
+      check(C.frcnn_roi_align_forward(fm.ptr, fs[1], fs[2], fs[3], mr, dpick, R, inv_sx, inv_sy, kh, kw, sampling, cinput.ptr, nil))
+    else
+      local dwins = ffi.cast('int*', scratch('wins', 16 * R).ptr)
+      check(C.frcnn_roi_windows(mr, dpick, R, layers, nl, fs[2], fs[3], dwins, nil))
+      check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
+    end
     local coutputs = cnet:forward(cinput)                               -- :101
     local bbox_out, cls_out = coutputs[1], coutputs[2]
     local dcls = ffi.cast('int*', scratch('cls', 4 * R).ptr)
@@ -319,7 +325,9 @@ function Detector:detect_chunk(frames, shared)
   local cfg = model.cfg
   local pnet = model.pnet
   local cnet = model.cnet
-  local kh, kw = cfg.roi_pooling.kh, cfg.roi_pooling.kw
+  local kh, kw, method, sampling = hip.roi_pooling_settings(cfg)
+  local inv_sx, inv_sy = 0, 0                        -- RoIAlign reads the rects and the picks as they are: no window kernel
+  if method == 'align' then inv_sx, inv_sy = hip.align_geometry(self.localizer) end
   local bgclass = cfg.class_count + 1
   local ncls = cfg.class_count + 1
   local D = kh * kw * model.layers[#model.layers].filters
@@ -435,9 +443,14 @@ function Detector:detect_chunk(frames, shared)
   local cbuf = ffi.cast('float*', shared and scratch('b_cinput', 4 * total * D).ptr or scratch('cinput', 4 * Rmax * D).ptr)
   local function pooled(b)              -- ROI windows and ROI pooling of frame b -> its input rows
     local R = count[B + b]
-    check(C.frcnn_roi_windows(mr + 4 * b * cap, dpick + b * cap, R, layers, nl, fs[2], fs[3], dwins, nil))
     local cinput = hip.view(shared and (cbuf + row0[b] * D) or cbuf, { R, D })
-    check(C.frcnn_roi_pool_forward(fms + b * fslot, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
+    if method == 'align' then
+      check(C.frcnn_roi_align_forward(fms + b * fslot, fs[1], fs[2], fs[3], mr + 4 * b * cap, dpick + b * cap, R, inv_sx, inv_sy,
+                                      kh, kw, sampling, cinput.ptr, nil))
+    else
+      check(C.frcnn_roi_windows(mr + 4 * b * cap, dpick + b * cap, R, layers, nl, fs[2], fs[3], dwins, nil))
+      check(C.frcnn_roi_pool_forward(fms + b * fslot, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
+    end
     return cinput
   end
   local all_bbox, all_cls

@@ -12,7 +12,7 @@
 -- The CPU nn classes stay what they are (BatchIterator.lua uses them on FloatTensors); only their :cuda() is replaced: it
 -- returns the device-side object.  Strided views (out[{{lo,hi}, y, x}], fmap[{{}, {y0,y1}, {x0,x1}}]) are added to the
 -- binding's tensor type here: small ones go through the host element by element, the ROI window is handled in place by
--- frcnn_roi_pool_forward / _backward.
+-- frcnn_roi_pool_forward / _backward (and, for cfg.roi_pooling.method = 'align', roi_align on frcnn_roi_align_forward / _backward).
 local ffi = require 'ffi'
 local hip = require 'frcnn_hip'
 local C, check = hip.C, hip.check
@@ -189,6 +189,48 @@ local function amp_new(kw, kh)
   return amp
 end
 
+-- ------------------------------------------------------------------------------------------ RoIAlign (cfg.roi_pooling.method = 'align')
+-- The stand-alone counterpart of the module above for a configuration that asks for RoIAlign: roi_align(cfg, localizer), or
+-- roi_align(kw, kh, sampling_ratio, inv_sx, inv_sy).  There is no window view: forward takes the FULL C x H x W map and the
+-- input-space rect (a Rect or {minX, minY, maxX, maxY}), backward returns the gradient of the full map.
+local function roi_align_new(a, b, g, inv_sx, inv_sy)
+  local kw, kh = a, b
+  if type(a) == 'table' then                        -- (cfg, localizer)
+    local method
+    kh, kw, method, g = hip.roi_pooling_settings(a)
+    if method ~= 'align' then error('roi_align: cfg.roi_pooling.method is "' .. method .. '"', 2) end
+    inv_sx, inv_sy = hip.align_geometry(b)
+  end
+  g = g or 2
+  if g ~= math.floor(g) or g < 1 or g > 4 then error('roi_align: sampling ratio outside 1..4', 2) end
+  local ra = { kw = kw, kh = kh, sampling_ratio = g, inv_sx = inv_sx or 1 / 16, inv_sy = inv_sy or 1 / 16 }
+  function ra:cuda() return self end
+  local function upload(rect)
+    local r = ffi.new('double[4]', rect.minX or rect[1], rect.minY or rect[2], rect.maxX or rect[3], rect.maxY or rect[4])
+    local rd = ibuf('rect', 32)
+    check(C.frcnn_memcpy_h2d(rd.ptr, r, 32, nil)); check(C.frcnn_stream_sync(nil))
+    return ffi.cast('const double*', rd.ptr)
+  end
+  function ra:forward(map, rect)
+    local Cn, H, W = map.sizes[1], map.sizes[2], map.sizes[3]
+    local out = hip.tensor({ Cn, self.kh, self.kw })
+    check(C.frcnn_roi_align_forward(map.ptr, Cn, H, W, upload(rect), nil, 1, self.inv_sx, self.inv_sy, self.kh, self.kw,
+                                    self.sampling_ratio, out.ptr, nil))
+    self.output = out
+    return out
+  end
+  function ra:backward(map, rect, gradOutput)
+    local Cn, H, W = map.sizes[1], map.sizes[2], map.sizes[3]
+    local g_out = hip.is_tensor(gradOutput) and gradOutput or hip.to_device(gradOutput)
+    local gmap = hip.tensor({ Cn, H, W }):zero()
+    check(C.frcnn_roi_align_backward(gmap.ptr, Cn, H, W, g_out.ptr, upload(rect), nil, 1, self.inv_sx, self.inv_sy, self.kh, self.kw,
+                                     self.sampling_ratio, nil))
+    self.gradInput = gmap
+    return gmap
+  end
+  return ra
+end
+
 -- ------------------------------------------------------------------------------------------ LogSoftMax and the criteria
 -- All of them see a handful of numbers per call (2 class logits, 4 box values, R x n log-probabilities): host arithmetic
 -- in double on values read back, results as Lua numbers / small device tensors -- the same values the batched kernels
@@ -316,5 +358,5 @@ if nn then
   device_twin(nn.SmoothL1Criterion, smooth_l1_new)
 end
 
-return { adaptive_max_pooling = amp_new, log_softmax = lsm_new, cross_entropy = cross_entropy_new, class_nll = class_nll_new,
+return { adaptive_max_pooling = amp_new, roi_align = roi_align_new, log_softmax = lsm_new, cross_entropy = cross_entropy_new, class_nll = class_nll_new,
          smooth_l1 = smooth_l1_new }

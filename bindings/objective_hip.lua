@@ -33,7 +33,10 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
   local bgclass = cfg.class_count + 1                                   -- :20
   local nheads = #model.anchor_nets
   local localizer = Localizer.new(pnet.outnode.children[nheads + 1])   -- :22 (children[5])
-  local kh, kw = cfg.roi_pooling.kh, cfg.roi_pooling.kw
+  local kh, kw, method, sampling = hip.roi_pooling_settings(cfg)
+  local align = method == 'align'                    -- RoIAlign: the double rects themselves in the place of the snapped windows
+  local inv_sx, inv_sy = 0, 0
+  if align then inv_sx, inv_sy = hip.align_geometry(localizer) end
   local cnet_input_planes = model.layers[#model.layers].filters
   local D = kh * kw * cnet_input_planes
   local ncls = cfg.class_count + 1
@@ -100,7 +103,7 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         local ex_roi = ffi.new('double[?]', 4 * np1)
         local ex_idx = ffi.new('int[?]', 4 * E)
         local ex_class = ffi.new('int[?]', np1)
-        local wins = ffi.new('int[?]', 4 * E)
+        local wins = ffi.new(align and 'double[?]' or 'int[?]', 4 * E)
         local seen, sp = {}, {}
         for l = 1, nheads do seen[l] = {}; sp[l] = {} end
         for i = 1, E do
@@ -118,8 +121,12 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
             ex_class[i - 1] = roi.class_index
             pooled = roi.rect                                           -- positives pool the ground-truth rect (:117)
           end
-          local _, idx = extract_roi_pooling_input(pooled, localizer, fm)
-          wins[o], wins[o + 1], wins[o + 2], wins[o + 3] = idx[2][1], idx[2][2], idx[3][1], idx[3][2]
+          if align then
+            wins[o], wins[o + 1], wins[o + 2], wins[o + 3] = pooled.minX, pooled.minY, pooled.maxX, pooled.maxY
+          else
+            local _, idx = extract_roi_pooling_input(pooled, localizer, fm)
+            wins[o], wins[o + 1], wins[o + 2], wins[o + 3] = idx[2][1], idx[2][2], idx[3][1], idx[3][2]
+          end
           -- where delta_outputs[l] will be non-zero (hint for the sparse anchor-net backward)
           local pos = (a.index[2] - 1) * outputs[a.layer]:size(3) + (a.index[3] - 1)
           if not seen[a.layer][pos] then
@@ -134,14 +141,15 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         for l = 1, nheads do
           for _, v in ipairs(sp[l]) do sp_all[k] = v; k = k + 1 end
         end
-        local b_anchor, b_roi, b_idx, b_class, b_wins, b_sp = 32 * E, 32 * np1, 16 * E, 4 * np1, 16 * E, 4 * nsp
-        local total = b_anchor + b_roi + b_idx + b_class + b_wins + b_sp
+        local b_anchor, b_roi, b_idx, b_class, b_wins, b_sp = 32 * E, 32 * np1, 16 * E, 4 * np1, (align and 32 or 16) * E, 4 * nsp
+        local pad = align and (-(b_anchor + b_roi + b_idx + b_class)) % 8 or 0      -- (the rects are doubles: 8-byte offset)
+        local total = b_anchor + b_roi + b_idx + b_class + pad + b_wins + b_sp
         local blob = ffi.new('uint8_t[?]', total)
         local o = 0
         ffi.copy(blob + o, ex_anchor, b_anchor); local o_anchor = o; o = o + b_anchor
         ffi.copy(blob + o, ex_roi, b_roi); local o_roi = o; o = o + b_roi
         ffi.copy(blob + o, ex_idx, b_idx); local o_idx = o; o = o + b_idx
-        ffi.copy(blob + o, ex_class, b_class); local o_class = o; o = o + b_class
+        ffi.copy(blob + o, ex_class, b_class); local o_class = o; o = o + b_class + pad
         ffi.copy(blob + o, wins, b_wins); local o_wins = o; o = o + b_wins
         if nsp > 0 then ffi.copy(blob + o, sp_all, b_sp) end
         local o_sp = o
@@ -170,9 +178,15 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         else
         -- ---- ROI pooling of every example in one launch (:117-119, :137-139) ---------------------------------
         local cinput = hip.view(scratch('cinput', 4 * E * D).ptr, { E, D })
-        local pidx = ffi.cast('int*', scratch('pidx', 4 * E * D).ptr)
-        check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], ffi.cast('const int*', dblob + o_wins), E, kh, kw,
-                                       cinput.ptr, pidx, nil))
+        local pidx
+        if align then
+          check(C.frcnn_roi_align_forward(fm.ptr, fs[1], fs[2], fs[3], ffi.cast('const double*', dblob + o_wins), nil, E, inv_sx,
+                                          inv_sy, kh, kw, sampling, cinput.ptr, nil))
+        else
+          pidx = ffi.cast('int*', scratch('pidx', 4 * E * D).ptr)
+          check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], ffi.cast('const int*', dblob + o_wins), E, kh, kw,
+                                         cinput.ptr, pidx, nil))
+        end
         -- ---- fine-tuning stage (:146-186) --------------------------------------------------------------------
         local coutputs = cnet:forward(cinput)                           -- :164
         local crout, ccout = coutputs[1], coutputs[2]
@@ -182,7 +196,10 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         check(C.frcnn_cnet_losses(crout.ptr, crtarget, ccout.ptr, cctarget, E, npos, ncls, crdelta.ptr, ccdelta.ptr,
                                   ffi.cast('double*', acc.ptr) + 4, nil))               -- :170-177
         local post_roi_delta = cnet:backward(cinput, { crdelta, ccdelta })              -- :179
-        if frozen_blocks < nblocks then                 -- (a frozen backbone: the library left the input gradient unwritten)
+        if frozen_blocks < nblocks and align then       -- (a frozen backbone: the library left the input gradient unwritten)
+          check(C.frcnn_roi_align_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr,
+                                           ffi.cast('const double*', dblob + o_wins), nil, E, inv_sx, inv_sy, kh, kw, sampling, nil))
+        elseif frozen_blocks < nblocks then
           check(C.frcnn_roi_pool_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr, pidx, E,
                                           kh, kw, nil))                                 -- :182-185
         end

@@ -27,7 +27,7 @@ from .Anchors import Anchors
 from .Localizer import Localizer
 from .Rect import Rect
 from .nms import nms
-from .objective import roi_window, roi_windows
+from .objective import align_geometry, roi_pooling_settings, roi_window, roi_windows
 from .tensor import DeviceTensor, ptr, stream_ptr, to_device
 
 ASPECTS = 3   # anchors per map position (Anchors.lua:108-109)
@@ -187,6 +187,8 @@ class Detector(object):
         cfg = model["cfg"]
         self.anchors = Anchors(model["pnet"], cfg["scales"])
         self.localizer = Localizer(model["pnet"].outnode.children[-1])
+        # cfg["roi_pooling"]: the grid and the region feature (roi_pooling_settings; "align" needs a centred backbone)
+        self._roi_settings()
         self._loc_layers = np.array([[l["kW"], l["kH"], l["dW"], l["dH"], l["padW"], l["padH"]] for l in self.localizer.layers],
                                     dtype=np.int32).reshape(-1, 6)
         self._aw = DeviceTensor.from_numpy(self.anchors.w)
@@ -383,7 +385,8 @@ class Detector(object):
         model = self.model
         cfg = model["cfg"]
         cnet = model["cnet"]
-        kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
+        roi = self._roi_settings()
+        kh, kw = roi[0], roi[1]
         bgclass = cfg["class_count"] + 1
         ncls = cfg["class_count"] + 1
         planes = model["layers"][-1]["filters"]
@@ -400,11 +403,8 @@ class Detector(object):
         cnet.evaluate()
         fm = outputs[-1]
         fmC, fmH, fmW = fm.shape
-        dwins = self._buf("wins", (R, 4), np.int32)
-        _lib.call("frcnn_roi_windows", ptr(m["rect"]), ptr(pick), R, self._loc_layers.ctypes.data_as(C.c_void_p),
-                  len(self._loc_layers), fmH, fmW, ptr(dwins), s)               # objective.lua:5-13 for every candidate
         cinput = self._buf("cinput", (R, kh * kw * planes))
-        _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(dwins), R, kh, kw, ptr(cinput), None, s)
+        self._pool(roi, ptr(fm), fmC, fmH, fmW, ptr(m["rect"]), ptr(pick), R, cinput, s)
         bbox_out, cls_out = cnet.forward(cinput)  # :101
         self._last.update(bbox=bbox_out, cls=cls_out)
         dcls = self._buf("cls", (R,), np.int32); dconf = self._buf("conf", (R,))
@@ -435,6 +435,27 @@ class Detector(object):
         # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
         order = np.argsort(rec[:, 0], kind="stable")
         return _Detections(rec[order], self.anchors)
+
+    def _roi_settings(self):
+        """cfg["roi_pooling"] as it stands -> (kh, kw, g, inv_sx, inv_sy) with g = 0 for the max pool; validated before any
+        device call (roi_pooling_settings; "align" needs a centred backbone)."""
+        kh, kw, method, g = roi_pooling_settings(self.model["cfg"])
+        if method != "align":
+            return kh, kw, 0, 0.0, 0.0
+        return (kh, kw, g) + align_geometry(self.localizer)
+
+    def _pool(self, roi, fm, fmC, fmH, fmW, rect, pick, R, cinput, s, rows=None):
+        """The region features of R candidates (rows pick of rect) into cinput, roi = _roi_settings(): the ROI windows
+        (objective.lua:5-13 for every candidate; the window buffer sized for `rows`) and their max pooling, or -- RoIAlign -- one
+        launch that reads the rects and the picks as they are."""
+        kh, kw, g, inv_sx, inv_sy = roi
+        if g:
+            _lib.call("frcnn_roi_align_forward", fm, fmC, fmH, fmW, rect, pick, R, inv_sx, inv_sy, kh, kw, g, ptr(cinput), s)
+            return
+        dwins = self._buf("wins", (rows or R, 4), np.int32)
+        _lib.call("frcnn_roi_windows", rect, pick, R, self._loc_layers.ctypes.data_as(C.c_void_p), len(self._loc_layers), fmH, fmW,
+                  ptr(dwins), s)
+        _lib.call("frcnn_roi_pool_forward", fm, fmC, fmH, fmW, ptr(dwins), R, kh, kw, ptr(cinput), None, s)
 
     BATCH = 8   # frames per chunk of detect_batch: bounds the memory of a call (INTEGRATION.md)
 
@@ -469,7 +490,8 @@ class Detector(object):
         model = self.model
         cfg = model["cfg"]
         pnet, cnet = model["pnet"], model["cnet"]
-        kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
+        roi = self._roi_settings()
+        kh, kw = roi[0], roi[1]
         bgclass = cfg["class_count"] + 1
         ncls = cfg["class_count"] + 1
         planes = model["layers"][-1]["filters"]
@@ -577,7 +599,6 @@ class Detector(object):
         bbox_all = self._buf("b_bbox", (B, Rmax, 4)); cls_all = self._buf("b_cls_out", (B, Rmax, ncls))
         bb = self._buf("b_bb", (B, Rmax, 5)); kc = self._buf("b_kc", (B, Rmax), i32); keep_row = self._buf("b_keep_row", (B, Rmax), i32)
         r2 = self._buf("b_r2", (B, Rmax, 4), np.float64)
-        dwins = self._buf("wins", (Rmax, 4), i32)
         D = kh * kw * planes
         dcls = self._buf("cls", (Rmax,), i32); dconf = self._buf("conf", (Rmax,))
         # first row of frame b in the net's input / output arrays: its own segment, or (shared pass) the prefix sum of R
@@ -588,13 +609,11 @@ class Detector(object):
                 total += Rs[b]
         cinput_buf = self._buf("b_cinput", (total, D)) if shared else self._buf("cinput", (Rmax, D))
 
-        def pooled(b):    # ROI windows (objective.lua:5-13 for every candidate) and ROI pooling of frame b -> its input rows
+        def pooled(b):    # the region features of frame b's candidates (_pool) -> its input rows
             R = Rs[b]
-            _lib.call("frcnn_roi_windows", C.c_void_p(mr.ptr + 32 * b * cap), C.c_void_p(pick.ptr + 8 * b * cap), R,
-                      self._loc_layers.ctypes.data_as(C.c_void_p), len(self._loc_layers), fmH, fmW, ptr(dwins), s)
             cinput = DeviceTensor(cinput_buf.ptr + (4 * D * row0[b] if shared else 0), (R, D), np.float32, owner=cinput_buf)
-            _lib.call("frcnn_roi_pool_forward", C.c_void_p(fms.ptr + 4 * b * fslot), fmC, fmH, fmW, ptr(dwins), R, kh, kw,
-                      ptr(cinput), None, s)
+            self._pool(roi, C.c_void_p(fms.ptr + 4 * b * fslot), fmC, fmH, fmW, C.c_void_p(mr.ptr + 32 * b * cap),
+                       C.c_void_p(pick.ptr + 8 * b * cap), R, cinput, s, rows=Rmax)
             return cinput
 
         def outputs(b):   # (the net writes into the frame's rows: its own output buffers are reused by the next pass)

@@ -61,6 +61,19 @@ class Localizer(object):
             maxY = np.maximum(np.where(exact, ay / dW + 1, np.ceil(ay / dH) + 1), minY + 1)
         return np.stack([np.floor(minX), np.floor(minY), np.ceil(maxX), np.ceil(maxY)], 1)
 
+    def stride(self):
+        """(Sx, Sy): input pixels per cell of the output map, the products of dW and of dH over the layers."""
+        sx = sy = 1
+        for l in self.layers:
+            sx *= l["dW"]; sy *= l["dH"]
+        return sx, sy
+
+    def centred(self):
+        """True when every layer has kW - dW == 2 padW and kH - dH == 2 padH (3x3 / pad 1 convolutions, 2x2 / stride 2 pools):
+        cell i of the output map then covers input pixels [i S, (i+1) S) and its centre sits at (i + 0.5) S -- the coordinate
+        convention of RoIAlign (cfg["roi_pooling"]["method"] = "align"), which does not go through inputToFeatureRect."""
+        return all(l["kW"] - l["dW"] == 2 * l["padW"] and l["kH"] - l["dH"] == 2 * l["padH"] for l in self.layers)
+
     def featureToInputRect(self, minX, minY, maxX, maxY, layer_index=None):  # Localizer.lua:69-79
         n = layer_index or len(self.layers)
         for l in reversed(self.layers[:n]):

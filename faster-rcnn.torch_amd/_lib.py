@@ -78,6 +78,10 @@ _SIGS = {
     "frcnn_act_backward": ([vp, vp, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_roi_pool_forward": ([vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp], C.c_int),
     "frcnn_roi_pool_backward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp], C.c_int),
+    "frcnn_roi_align_forward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, vp,
+                                 vp], C.c_int),
+    "frcnn_roi_align_backward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                  vp], C.c_int),
     "frcnn_rpn_scan_workspace_bytes": ([vp, vp], C.c_size_t),
     "frcnn_rpn_scan": ([vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_rpn_scan_batch_workspace_bytes": ([vp, vp, C.c_int], C.c_size_t),

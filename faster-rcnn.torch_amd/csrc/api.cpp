@@ -361,6 +361,27 @@ int frcnn_roi_pool_backward(float* gmap, int C, int H, int W, const float* gout,
   return roi_pool_backward(gmap, C, H, W, gout, idx, R, kh, kw, S(stream));
 }
 
+static int roi_align_check(const char* who, const void* map, int C, int H, int W, const void* rows, const double* rect, int kh, int kw,
+                           int g) {
+  FR_CHECK(map && rows && rect, "%s: NULL argument", who);
+  FR_CHECK(C >= 1 && H >= 1 && W >= 1 && kh >= 1 && kw >= 1, "%s: map %d x %d x %d, grid %d x %d", who, C, H, W, kh, kw);
+  FR_CHECK((long)H * W < (1L << 31), "%s: a plane of %d x %d cells", who, H, W);
+  FR_CHECK(g >= 1 && g <= 4, "%s: sampling ratio %d outside 1..4", who, g);
+  return FRCNN_OK;
+}
+int frcnn_roi_align_forward(const float* fmap, int C, int H, int W, const double* rect, const long long* pick, int R, double inv_sx,
+                            double inv_sy, int kh, int kw, int g, float* out, void* stream) {
+  if (R <= 0) return FRCNN_OK;
+  FR_TRY(roi_align_check("frcnn_roi_align_forward", fmap, C, H, W, out, rect, kh, kw, g));
+  return roi_align_forward(fmap, C, H, W, rect, pick, R, inv_sx, inv_sy, kh, kw, g, out, S(stream));
+}
+int frcnn_roi_align_backward(float* gmap, int C, int H, int W, const float* gout, const double* rect, const long long* pick, int R,
+                             double inv_sx, double inv_sy, int kh, int kw, int g, void* stream) {
+  if (R <= 0) return FRCNN_OK;
+  FR_TRY(roi_align_check("frcnn_roi_align_backward", gmap, C, H, W, gout, rect, kh, kw, g));
+  return roi_align_backward(gmap, C, H, W, gout, rect, pick, R, inv_sx, inv_sy, kh, kw, g, S(stream));
+}
+
 static void to_layers(const float* const* maps, const int* H, const int* W, RpnLayers* L) {
   for (int l = 0; l < 4; ++l) { L->map[l] = maps ? maps[l] : nullptr; L->H[l] = H[l]; L->W[l] = W[l]; }
 }

@@ -244,6 +244,14 @@ int roi_pool_forward(const float* fmap, int C, int H, int W, const int* wins, in
 int roi_pool_backward(float* gmap, int C, int H, int W, const float* gout, const int* idx, int R,
                       int kh, int kw, hipStream_t s);
 
+// ---------------------------------------------------------------- roi align (roi_align.hip)
+// rect: device double[n][4] input-space rects; pick: optional 1-based rows of rect (as in roi_windows); inv_sx / inv_sy: one over
+// the backbone's stride; g x g samples per bin.  out rows as roi_pool_forward's; backward: gmap += scatter(gout).
+int roi_align_forward(const float* fmap, int C, int H, int W, const double* rect, const long long* pick, int R, double inv_sx,
+                      double inv_sy, int kh, int kw, int g, float* out, hipStream_t s);
+int roi_align_backward(float* gmap, int C, int H, int W, const float* gout, const double* rect, const long long* pick, int R,
+                       double inv_sx, double inv_sy, int kh, int kw, int g, hipStream_t s);
+
 // ---------------------------------------------------------------- rpn (rpn.hip)
 struct RpnLayers {
   const float* map[4];

@@ -4,6 +4,7 @@
 // of the reference's per-ROI module call.  Gather/argmax work, no MFMA; reads hit the 2.2 MB map
 // in L2, writes are R x C*kh*kw contiguous rows (the cnet input batch).
 #include "kernels.h"
+#include "roi_fix.h"
 
 namespace frcnn {
 
@@ -144,10 +145,8 @@ __global__ void roi_pool_backward_lds_kernel(float* __restrict__ gmap, int C, in
   }
 }
 
-// Deterministic variants: the contributions are accumulated in 64-bit fixed point (value * 2^44, rounded to nearest): integer
-// addition is exact, so the sum does not depend on the order in which the atomics land.  |g| < 2^18, resolution 6e-14.
-#define ROI_FIX_SCALE 17592186044416.0   /* 2^44 */
-__device__ __forceinline__ long long roi_to_fix(float g) { return __double2ll_rn((double)g * ROI_FIX_SCALE); }
+// Deterministic variants: the contributions are accumulated in 64-bit fixed point (roi_fix.h: value * 2^44, rounded to nearest):
+// integer addition is exact, so the sum does not depend on the order in which the atomics land.
 __global__ void roi_pool_backward_lds_det_kernel(float* __restrict__ gmap, int C, int HW, const float* __restrict__ gout,
                                                  const int* __restrict__ idx, int R, int cell) {
   extern __shared__ unsigned long long fplane[];
@@ -187,6 +186,12 @@ __global__ void roi_fix_apply_kernel(const unsigned long long* __restrict__ fix,
   }
 }
 
+int roi_fix_apply(const unsigned long long* fix, long n, float* gmap, hipStream_t s) {
+  FR_LAUNCH(KC_ROI, 0, n * 16.0, s, roi_fix_apply_kernel, dim3((int)std::min<long>(cdivl(n, 256), 4096)), dim3(256), 0, fix, n, gmap);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
 // delta_outputs[5][idx]:add(amp:backward(...))  (objective.lua:182-185): windows of different
 // ROIs overlap, so this is a scatter-ADD; fp32 atomics in L2.
 __global__ void roi_pool_backward_kernel(float* __restrict__ gmap, int C, long HW,
@@ -216,8 +221,8 @@ int roi_pool_backward(float* gmap, int C, int H, int W, const float* gout, const
       int grid = (int)std::min<long>(cdivl(total, 256), 4096);
       FR_LAUNCH(KC_ROI, 0, total * 12.0, s, roi_pool_backward_det_kernel, dim3(grid), dim3(256), 0, (unsigned long long*)ws, C,
                 (long)H * W, gout, idx, total, kh * kw);
-      FR_LAUNCH(KC_ROI, 0, n * 16.0, s, roi_fix_apply_kernel, dim3((int)std::min<long>(cdivl(n, 256), 4096)), dim3(256), 0,
-                (const unsigned long long*)ws, n, gmap);
+      FR_LAUNCH_CHECK();
+      return roi_fix_apply((const unsigned long long*)ws, n, gmap, s);
     }
     FR_LAUNCH_CHECK();
     return FRCNN_OK;

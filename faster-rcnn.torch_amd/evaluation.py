@@ -16,7 +16,7 @@ PASCAL-VOC style mean average precision over `BatchIterator:nextValidation` (Bat
       iou_threshold -- the figure by which the proposal settings (order, pre_nms_top_n, post_nms_top_n) are chosen.
 
 All arithmetic of the networks runs through the C ABI (frcnn_pnet_forward, frcnn_rpn_loss, frcnn_loss_accumulate,
-frcnn_roi_pool_forward, frcnn_cnet_forward, frcnn_cnet_losses, Detector.detect); the bookkeeping here is host code."""
+frcnn_roi_pool_forward or frcnn_roi_align_forward, frcnn_cnet_forward, frcnn_cnet_losses, Detector.detect); the bookkeeping here is host code."""
 import ctypes as C
 
 import numpy as np
@@ -26,7 +26,7 @@ from .Anchors import MT19937
 from .BatchIterator import assemble_examples
 from .Localizer import Localizer
 from .Rect import Rect
-from .objective import roi_windows
+from .objective import align_geometry, roi_pooling_settings, roi_windows
 from .synthetic import clean_examples, output_map_sizes
 from .tensor import DeviceTensor, ptr, stream_ptr, to_device
 
@@ -39,10 +39,12 @@ def validation_losses(model, batch_iterator, count, seed=1234, negatives=16):
     pnet, cnet, native = model["pnet"], model["cnet"], model["native"]
     bgclass = cfg["class_count"] + 1
     ncls = cfg["class_count"] + 1
-    kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
+    kh, kw, method, sampling = roi_pooling_settings(cfg)
     planes = model["layers"][-1]["filters"]
     D = kh * kw * planes
     localizer = Localizer(pnet.outnode.children[-1])
+    align = method == "align"
+    inv_sx, inv_sy = align_geometry(localizer) if align else (0.0, 0.0)
     anchors = batch_iterator.anchors
     rng = MT19937(seed)
     acc = torch.zeros(8, dtype=torch.float64, device="cuda")     # {cls, reg, -, -, creg, ccls, -, -} like the objective
@@ -77,7 +79,8 @@ def validation_losses(model, batch_iterator, count, seed=1234, negatives=16):
                     ex_class[:npos] = [e[1].class_index for e in pos]
                 fm = outputs[-1]
                 fmC, fmH, fmW = fm.shape
-                wins = roi_windows(np.concatenate([ex_roi[:npos], ex_anchor[npos:]], 0), localizer, fmH, fmW)
+                pooled = np.concatenate([ex_roi[:npos], ex_anchor[npos:]], 0)
+                wins = np.ascontiguousarray(pooled) if align else roi_windows(pooled, localizer, fmH, fmW)   # (RoIAlign: the rects themselves)
                 d_idx, d_anchor = DeviceTensor.from_numpy(ex_idx), DeviceTensor.from_numpy(ex_anchor)
                 d_roi, d_class, d_wins = DeviceTensor.from_numpy(ex_roi), DeviceTensor.from_numpy(ex_class), DeviceTensor.from_numpy(wins)
                 # anchor losses on the sampled anchors (objective.lua:91-140); the gradients it also writes go to scratch maps
@@ -92,8 +95,13 @@ def validation_losses(model, batch_iterator, count, seed=1234, negatives=16):
                           bgclass, ptr(ex_loss), ptr(crtarget), ptr(cctarget), s)
                 _lib.call("frcnn_loss_accumulate", ptr(ex_loss), E, C.c_void_p(acc.data_ptr()), s)
                 # region classification on the pooled examples (:117-119, :137-139, :146-177), forward only
-                cinput = DeviceTensor.empty((E, D)); pidx = DeviceTensor.empty((E, D), np.int32)
-                _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(d_wins), E, kh, kw, ptr(cinput), ptr(pidx), s)
+                cinput = DeviceTensor.empty((E, D)); pidx = None
+                if align:
+                    _lib.call("frcnn_roi_align_forward", ptr(fm), fmC, fmH, fmW, ptr(d_wins), None, E, inv_sx, inv_sy, kh, kw,
+                              sampling, ptr(cinput), s)
+                else:
+                    pidx = DeviceTensor.empty((E, D), np.int32)
+                    _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(d_wins), E, kh, kw, ptr(cinput), ptr(pidx), s)
                 crout, ccout = cnet.forward(cinput)
                 crdelta = DeviceTensor.empty((E, 4)); ccdelta = DeviceTensor.empty((E, ncls))
                 _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), E, npos, ncls,

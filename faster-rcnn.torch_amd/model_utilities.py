@@ -42,7 +42,8 @@ class NativeModel(object):
             d.cls_n[i] = l["n"]; d.cls_bn[i] = 1 if l.get("batch_norm") else 0
             d.cls_dropout[i] = float(l.get("dropout") or 0.0)
         d.class_count = cfg["class_count"]
-        d.kh = cfg["roi_pooling"]["kh"]; d.kw = cfg["roi_pooling"]["kw"]
+        from .objective import roi_pooling_settings
+        d.kh, d.kw = roi_pooling_settings(cfg)[:2]
         self.desc = d
         h = C.c_void_p()
         _lib.call("frcnn_model_create", C.byref(d), C.byref(h))

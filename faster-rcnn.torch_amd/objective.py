@@ -49,6 +49,49 @@ def extract_roi_pooling_input(input_rect, localizer, feature_layer_output):  # o
     return win, idx
 
 
+ROI_POOLING_DEFAULTS = dict(method="max", sampling_ratio=2)
+
+
+def roi_pooling_settings(cfg):
+    """cfg["roi_pooling"] of a model's cfg -> (kh, kw, method, g), validated on the host.
+      kh, kw          the grid of bins (the classification net's input is filters x kh x kw)
+      method          "max" (default: the reference -- the rect goes through Localizer:inputToFeatureRect, is snapped to whole
+                      cells and max-pooled) or "align": RoIAlign, bilinear sampling at un-snapped coordinates averaged per bin
+                      (frcnn_roi_align_forward / _backward; the backbone must be Localizer.centred(): align_geometry)
+      sampling_ratio  g x g samples per bin, an integer 1..4, default 2; only read under "align"
+    Raises ValueError (before any device call) for an unknown key, an unknown method, a bool or non-integer or out-of-range
+    sampling_ratio."""
+    t = cfg.get("roi_pooling")
+    if not isinstance(t, dict):
+        raise ValueError("cfg.roi_pooling must be a table of {kh, kw, method, sampling_ratio}")
+    unknown = sorted(set(t) - set(("kh", "kw")) - set(ROI_POOLING_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError("cfg.roi_pooling: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    kh, kw = t["kh"], t["kw"]
+    method = t.get("method", "max")
+    if not isinstance(method, str) or method not in ("max", "align"):
+        raise ValueError("cfg.roi_pooling.method = %r (\"max\" or \"align\")" % (method,))
+    g = ROI_POOLING_DEFAULTS["sampling_ratio"]
+    if method == "align":
+        g = t.get("sampling_ratio", g)
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+            raise ValueError("cfg.roi_pooling.sampling_ratio = %r is not an integer" % (g,))
+        if not 1 <= g <= 4:
+            raise ValueError("cfg.roi_pooling.sampling_ratio = %d outside 1..4" % g)
+    return kh, kw, method, int(g)
+
+
+def align_geometry(localizer):
+    """(1 / Sx, 1 / Sy) as frcnn_roi_align_* take them; raises ValueError for a backbone that is not centred.  The kernels multiply
+    by these where the statement divides by the stride: the same number for a power-of-two stride (16 for both models); for any
+    other stride a coordinate may differ from minX / Sx in its last bit."""
+    if not localizer.centred():
+        raise ValueError("cfg.roi_pooling.method = \"align\" needs a centred backbone (every layer k - d == 2 pad): "
+                         "Localizer.centred() is false")
+    sx, sy = localizer.stride()
+    return 1.0 / sx, 1.0 / sy
+
+
 class _Scratch(object):
     """Per-objective device scratch that grows on demand (no allocation in the steady state)."""
 
@@ -264,7 +307,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     bgclass = cfg["class_count"] + 1  # :20
     localizer = Localizer(pnet.outnode.children[4] if len(pnet.outnode.children) == 5
                           else pnet.outnode.children[-1])  # :22 children[5]
-    kh, kw = cfg["roi_pooling"]["kh"], cfg["roi_pooling"]["kw"]
+    kh, kw, method, sampling = roi_pooling_settings(cfg)
+    align = method == "align"
+    inv_sx, inv_sy = align_geometry(localizer) if align else (0.0, 0.0)
     cnet_input_planes = model["layers"][-1]["filters"]
     D = kh * kw * cnet_input_planes
     ncls = cfg["class_count"] + 1
@@ -343,17 +388,21 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 raise _lib.FrcnnError("roi.class_index %d outside 1..%d (class_count)"
                                       % (int(ex_class[:npos].min() if ex_class[:npos].min() < 1 else ex_class[:npos].max()),
                                          cfg["class_count"]))
-        # positives pool the GT rect (:117), negatives pool the anchor rect itself (:137)
-        wins = roi_windows(np.concatenate([ex_roi[:npos], ex_anchor[npos:]], 0), localizer, fmH, fmW)
+        # positives pool the GT rect (:117), negatives pool the anchor rect itself (:137); RoIAlign takes the (E, 4) double rects
+        # themselves in the place of the snapped windows
+        pooled = np.concatenate([ex_roi[:npos], ex_anchor[npos:]], 0)
+        wins = np.ascontiguousarray(pooled) if align else roi_windows(pooled, localizer, fmH, fmW)
         # positions where delta_outputs[l] will be non-zero (hint for the sparse head backward)
         sp = []
         for l in range(4):
             sel = ex_idx[ex_idx[:, 0] == l + 1]
             sp.append(np.unique((sel[:, 2] - 1) * sizes[l][1] + (sel[:, 3] - 1)).astype(np.int32))
         sp_all = np.concatenate(sp)
-        blob = np.concatenate([ex_anchor.view(np.uint8).ravel(), ex_roi.view(np.uint8).ravel(),
-                               ex_idx.view(np.uint8).ravel(), ex_class.view(np.uint8).ravel(),
-                               wins.view(np.uint8).ravel(), sp_all.view(np.uint8).ravel()])
+        head = [ex_anchor.view(np.uint8).ravel(), ex_roi.view(np.uint8).ravel(), ex_idx.view(np.uint8).ravel(),
+                ex_class.view(np.uint8).ravel()]
+        if align:   # (the rects are doubles: their offset in the blob is rounded up to 8 bytes)
+            head.append(np.zeros(-sum(a.size for a in head) % 8, np.uint8))
+        blob = np.concatenate(head + [wins.view(np.uint8).ravel(), sp_all.view(np.uint8).ravel()])
         prep.update(ex_anchor=ex_anchor, ex_roi=ex_roi, ex_idx=ex_idx, ex_class=ex_class, wins=wins, sp=sp, blob=blob)
         return prep
 
@@ -476,6 +525,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 d_roi = dblob.ptr + o; o += ex_roi.nbytes
                 d_idx = dblob.ptr + o; o += ex_idx.nbytes
                 d_class = dblob.ptr + o; o += ex_class.nbytes
+                if align:
+                    o += -o % 8
                 d_wins = dblob.ptr + o; o += wins.nbytes
                 for l in range(4):
                     _lib.call("frcnn_pnet_set_sparse_deltas", native.h, l + 1, C.c_void_p(dblob.ptr + o), len(sp[l]))
@@ -498,9 +549,14 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             elif E > 0:
                 # ---- ROI pooling of every example in one launch (:117-119, :137-139) ---------
                 cinput = scratch.get("cinput", (E, D))
-                pidx = scratch.get("pidx", (E, D), np.int32)
-                _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, C.c_void_p(d_wins), E, kh, kw,
-                          ptr(cinput), ptr(pidx), s)
+                if align:
+                    debug["rects"] = wins
+                    _lib.call("frcnn_roi_align_forward", ptr(fm), fmC, fmH, fmW, C.c_void_p(d_wins), None, E, inv_sx, inv_sy,
+                              kh, kw, sampling, ptr(cinput), s)
+                else:
+                    pidx = scratch.get("pidx", (E, D), np.int32)
+                    _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, C.c_void_p(d_wins), E, kh, kw,
+                              ptr(cinput), ptr(pidx), s)
                 # ---- fine-tuning stage (:146-186) --------------------------------------------
                 coutputs = cnet.forward(cinput)  # :164
                 crout, ccout = coutputs
@@ -510,7 +566,10 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), E, npos, ncls,
                           ptr(crdelta), ptr(ccdelta), C.c_void_p(acc_dev.ptr + 4 * 8), s)  # :170-177
                 post_roi_delta = cnet.backward(cinput, [crdelta, ccdelta])  # :179
-                if not trunk_frozen:   # (a frozen backbone: the library left the input gradient unwritten)
+                if not trunk_frozen and align:   # (a frozen backbone: the library left the input gradient unwritten)
+                    _lib.call("frcnn_roi_align_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),
+                              C.c_void_p(d_wins), None, E, inv_sx, inv_sy, kh, kw, sampling, s)
+                elif not trunk_frozen:
                     _lib.call("frcnn_roi_pool_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),
                               ptr(pidx), E, kh, kw, s)  # :182-185
             if E == 0:
@@ -756,7 +815,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     # those of the last pass queued.  The optimisers of utilities update these slices only.
     lossAndGradient.trainable_ranges = lambda: stage_ranges()[3]
     lossAndGradient.pass_ranges = lambda: stage[0]
-    lossAndGradient.debug = debug   # (tests: the scratch buffers and the example count of the image being processed)
+    lossAndGradient.debug = debug   # (tests: the scratch buffers, the example count and -- RoIAlign -- the rects of the image being processed)
     return lossAndGradient
 
 

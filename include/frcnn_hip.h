@@ -226,6 +226,29 @@ int frcnn_roi_pool_forward(const float *fmap, int C, int H, int W, const int *wi
 int frcnn_roi_pool_backward(float *gmap, int C, int H, int W, const float *gout, const int *idx,
                             int R, int kh, int kw, void *stream);
 
+/* ---- RoIAlign, the alternative region feature (cfg.roi_pooling.method = "align"; not in the reference; csrc/roi_align.hip)
+ * Bilinear sampling at un-snapped coordinates, g x g samples averaged per bin (the torchvision `aligned=True` rule).
+ * rect: device double[n][4] of INPUT-space rects {minX, minY, maxX, maxY}; pick: optional device int64[R] of 1-based rows of
+ * rect, NULL = rows 0..R-1 (as in frcnn_roi_windows: the Detector hands over match_rect and the first NMS's picks as they
+ * are).  inv_sx / inv_sy: one over the backbone's stride (Localizer.stride(); the backbone must be centred: cell i covers input
+ * pixels [i S, (i+1) S)).  The kernels multiply by inv_sx where the convention reads minX/Sx: the same number for a power-of-two
+ * stride (16 for both models); for another stride a coordinate may differ from the quotient in its last bit.  1 <= g <= 4.
+ * All in double, in this order:
+ *     x1 = minX*inv_sx - 0.5                y1 = minY*inv_sy - 0.5
+ *     w  = max((maxX-minX)*inv_sx, 0)       h  = max((maxY-minY)*inv_sy, 0)         bin_w = w/kw    bin_h = h/kh
+ *     sample (i, j, iy, ix):  y = y1 + (i + (iy+0.5)/g)*bin_h ,  x = x1 + (j + (ix+0.5)/g)*bin_w
+ * A sample with y < -1 || y > H || x < -1 || x > W contributes 0.  Otherwise y = max(y, 0), y_lo = (int)y; y_lo >= H-1:
+ * y_lo = y_hi = H-1, y = y_lo; else y_hi = y_lo + 1; ly = y - y_lo; the same in x.  Weights (1-ly)(1-lx), (1-ly)lx, ly(1-lx),
+ * ly*lx, computed in double and rounded to fp32.  out[r][c][i][j] = the fp32 sum over the g*g samples (iy outer, ix inner, the
+ * four taps in the order above) times 1/g^2; rows [R][C*kh*kw] like frcnn_roi_pool_forward.  No atomics: two runs are bit-equal.
+ * R <= 0: no launch. */
+int frcnn_roi_align_forward(const float *fmap, int C, int H, int W, const double *rect, const long long *pick, int R,
+                            double inv_sx, double inv_sy, int kh, int kw, int g, float *out, void *stream);
+/* gmap[C][H][W] += scatter: every bin spreads gout/g^2 over its 4 g^2 taps.  No index tensor: the geometry is recomputed from
+ * the rects.  Option "deterministic": 64-bit fixed-point accumulation, the result does not depend on the order of the atomics. */
+int frcnn_roi_align_backward(float *gmap, int C, int H, int W, const float *gout, const double *rect, const long long *pick,
+                             int R, double inv_sx, double inv_sy, int kh, int kw, int g, void *stream);
+
 /* ---- RPN anchor scan: Detector.lua:39-66 --------------------------------------------- */
 /* maps_host: 4 device pointers to the [18][H_l][W_l] head outputs (pnet outputs 1..4).
  * anchor_w / anchor_h: the fp32 tables of Anchors.lua:18-19, [4][3][200][2].
