@@ -1,9 +1,13 @@
 -- Detector_hip.lua -- drop-in for the reference's Detector.lua on libfrcnn_hip.so: the same class (`Detector(model)`,
 -- `:detect(input) -> winners`, each winner a table { p, a, r, l, r2, class, confidence }), the same pipeline and
 -- thresholds (p > 0.95, NMS 0.25, class ~= background and p > 0.2, per-class NMS 0.1) -- but the 26 544-iteration
--- Lua loop of Detector.lua:39-66 is one scan + compaction kernel (frcnn_rpn_scan), the per-candidate pooling loop
+-- Lua loop of Detector.lua:39-66 is one scan + compaction kernel (frcnn_rpn_scan_batch), the per-candidate pooling loop
 -- (:94-98) one batched kernel, and the first NMS runs on the device.  Both NMS calls of the reference pass a tensor as
 -- `scores`, which nms.lua:37-43 ignores: boxes are processed by descending max-y.  That behaviour is reproduced.
+-- There is ONE pipeline, written for a chunk of B frames of one size (first_stage + detect_chunk: frcnn_rpn_scan_batch,
+-- frcnn_nms_device_batch twice, frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound):
+-- detect_batch runs it on chunks of Detector.BATCH frames, detect(input) on the chunk { input }, which reads the proposal
+-- net's outputs where the net left them (no device copies); proposals(input) runs its first stage.
 -- 1:1 with the tested Python host mirror (faster-rcnn.torch_amd/Detector.py); checked statically, not executed here.
 --
 -- Not in the reference, off by default: cfg.proposals = { order = 'y2' | 'score', pre_nms_top_n = K, post_nms_top_n = M }
@@ -108,84 +112,120 @@ function Detector:clamp_candidates(dev, count, B)
   if changed then check(C.frcnn_memcpy_h2d(dev, count, 4 * B, nil)) end
 end
 
--- Detector.lua:17-85: proposal net, scan, (selection), first NMS, read-back 1 of 2 -> a table { outputs, mp, mi, mr (the match
--- arrays the rest of the frame reads: the selected rows under pre_nms_top_n), row (their 1-based original scan rows, or nil),
--- dpick, cnt, matches (the count before the cap), nm (rows of the match arrays), R (candidates) }
-function Detector:first_stage(input)
+-- The ONE pipeline, for a chunk of B frames of one size; Detector:detect(input) is the chunk { input }.
+Detector.BATCH = 8              -- frames per chunk of detect_batch
+Detector.NMS_FIRST_CAP = 16384  -- rows the first NMS launch is sized for (see first_stage)
+
+-- Detector.lua:17-85 for a chunk: the proposal net frame by frame, ONE scan, (selection or score rows), ONE segmented first
+-- NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> a table { B, cnt (device int[4][B]),
+-- cap (rows a frame in mp, mi, mr, dpick: the match arrays the rest of the chunk reads, the selected rows under
+-- pre_nms_top_n), fm, fslot, fs (frame b's last feature map at fm + b * fslot), count (host int[2][B]: rows and candidates per
+-- frame), key_mode, key_col (of both NMS passes) }.  prefix: of the scratch names ('' for detect and proposals, 'b_' for
+-- detect_batch: neither overwrites what the other left behind)
+function Detector:first_stage(frames, prefix)
   local pnet = self.model.pnet
   local scratch = self.scratch
-  local order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
+  local B = #frames
 
-  local input_size = input:size()
+  -- counts (device int[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
+  local cnt = ffi.cast('int*', scratch(prefix .. 'counts', 16 * B).ptr)
+  local input_size = frames[1]:size()
   pnet:evaluate()                                                       -- :31
-  input = hip.to_device(input)                                          -- :32
-  local outputs = pnet:forward(input)                                   -- :33
-
-  -- ---- :39-66 on the device: log-softmax of every anchor's two logits, p > 0.95, decode, overlap test, compaction
-  local Hs, Ws, maps = ffi.new('int[4]'), ffi.new('int[4]'), ffi.new('const float*[4]')
-  for i = 1, 4 do
-    local s = outputs[i]:size()
-    Hs[i - 1], Ws[i - 1], maps[i - 1] = s[2], s[3], outputs[i].ptr
+  -- ---- 1. per frame: the proposal net; its head maps and last feature map are copied to the frame's slot (the net reuses its
+  --         output buffers).  A chunk of ONE frame reads the net's buffers where they are: no copies
+  local Hs, Ws, maps, hoff = ffi.new('int[4]'), ffi.new('int[4]'), ffi.new('const float*[4]'), { 0 }
+  local slot, fslot, heads, fm, fs
+  for b = 0, B - 1 do
+    local outputs = pnet:forward(hip.to_device(frames[b + 1]))          -- :32-33
+    if b == 0 then
+      for i = 1, 4 do
+        local s = outputs[i]:size()
+        Hs[i - 1], Ws[i - 1] = s[2], s[3]
+        hoff[i + 1] = hoff[i] + math.floor((s[1] * s[2] * s[3] + 63) / 64) * 64
+      end
+      slot = hoff[5]
+      fs = outputs[self.nheads + 1]:size()
+      fslot = math.floor((fs[1] * fs[2] * fs[3] + 63) / 64) * 64
+      if B == 1 then
+        for i = 1, 4 do maps[i - 1] = outputs[i].ptr end
+        fm = ffi.cast('float*', outputs[self.nheads + 1].ptr)
+      else
+        heads = ffi.cast('float*', scratch(prefix .. 'heads', 4 * B * slot).ptr)
+        fm = ffi.cast('float*', scratch(prefix .. 'fm', 4 * B * fslot).ptr)
+        for i = 0, 3 do maps[i] = heads + hoff[i + 1] end
+      end
+    end
+    if B > 1 then
+      for i = 1, 4 do
+        check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[i], outputs[i].ptr, 4 * 18 * Hs[i - 1] * Ws[i - 1], nil))
+      end
+      check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[self.nheads + 1].ptr, 4 * fs[1] * fs[2] * fs[3], nil))
+    end
   end
+  -- ---- 2. ONE scan over the B slots (:39-66 on the device: log-softmax of every anchor's two logits, p > 0.95, decode,
+  --         overlap test, compaction): frame b's matches at rows [b * cap, b * cap + n_b)
   local cap = 0   -- every anchor of the four maps may pass: the buffers hold them all (vgg_large 1000x600: 45 015)
   for i = 0, 3 do cap = cap + ASPECTS * Hs[i] * Ws[i] end
-  local wsb = tonumber(C.frcnn_rpn_scan_workspace_bytes(Hs, Ws))
-  local ws = scratch('scan_ws', wsb)
-  local mp = ffi.cast('float*', scratch('match_p', 4 * cap).ptr)
-  local mi = ffi.cast('int*', scratch('match_idx', 16 * cap).ptr)
-  local mr = ffi.cast('double*', scratch('match_rect', 32 * cap).ptr)
-  local mb = ffi.cast('float*', scratch('match_box', 16 * cap).ptr)
-  -- counts (device int[4]): matches, NMS candidates, candidates that pass the class test, winners
-  local cnt = ffi.cast('int*', scratch('counts', 16).ptr)
-  check(C.frcnn_rpn_scan(maps, Hs, Ws, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap, mp, mi, mr, mb,
-                         cnt, ws.ptr, wsb, nil))
-  -- NON-MAXIMUM SUPPRESSION (:74-85) on the device, the match count read from DEVICE memory (no round trip between scan
-  -- and NMS); the score tensor is ignored by nms.lua -> key = max-y
-  -- (launch and workspace sized for a bound on the matches, not for every anchor of the maps; a frame with more matches
-  -- repeats the pass sized by the count just read.  Under pre_nms_top_n = K the bound is min(cap, K), the rows are the K
-  -- best-scoring matches, and no frame can exceed it)
-  local ncap = math.min(cap, 16384)
-  local ndev, boxes, ncols, key_mode, key_col, row = cnt, mb, 4, 0, 0, nil
-  if order == 'score' and pre == nil then boxes, ncols = self:score_rows(mp, mb, 1, cap, cnt, ''), 5 end
+  local wsb = tonumber(C.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B))
+  local ws = scratch(prefix .. 'scan_ws', wsb)
+  local mp = ffi.cast('float*', scratch(prefix .. 'match_p', 4 * B * cap).ptr)
+  local mi = ffi.cast('int*', scratch(prefix .. 'match_idx', 16 * B * cap).ptr)
+  local mr = ffi.cast('double*', scratch(prefix .. 'match_rect', 32 * B * cap).ptr)
+  local mb = ffi.cast('float*', scratch(prefix .. 'match_box', 16 * B * cap).ptr)
+  check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap,
+                               mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
+  -- ---- 3. ONE segmented NMS (:74-85) on the device, the match counts read from DEVICE memory (no round trip between scan
+  --         and NMS); the score tensor is ignored by nms.lua -> key = max-y.  Launch and workspace are sized for a bound on
+  --         the matches, not for every anchor of the maps; a frame with more matches repeats the pass alone, sized by the
+  --         count just read.  Under pre_nms_top_n = K the match arrays are replaced by the compact arrays of the K
+  --         best-scoring rows (`cap` rows a frame from here on: min(cap, K)), which no frame can exceed; order = 'score':
+  --         rows {box, p} keyed by p
+  local order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
+  local key_mode, key_col = 0, 0
+  if order == 'score' then key_mode, key_col = 2, 5 end
+  local anchors = cap
+  local ncap = math.min(cap, Detector.NMS_FIRST_CAP)
+  local ndev, boxes, ncols = cnt, mb, 4
+  if order == 'score' and pre == nil then boxes, ncols = self:score_rows(mp, mb, B, cap, cnt, prefix), 5 end
   if pre ~= nil then
-    local sel = self:select_rows(mp, mi, mr, mb, 1, cap, pre, cnt, '')
-    mp, mi, mr, mb, row = sel.p, sel.idx, sel.rect, sel.box, sel.row
-    ncap, ndev, boxes = sel.stride, sel.count, sel.box
+    local sel = self:select_rows(mp, mi, mr, mb, B, cap, pre, cnt, prefix)
+    mp, mi, mr, mb = sel.p, sel.idx, sel.rect, sel.box
+    cap, ncap, ndev, boxes = sel.stride, sel.stride, sel.count, sel.box
     if order == 'score' then boxes, ncols = sel.box5, 5 end
   end
-  if order == 'score' then key_mode, key_col = 2, 5 end
-  local nwsb = tonumber(C.frcnn_nms_workspace_bytes(ncap))
-  local nws = scratch('nms_ws', nwsb)
-  local dpick = ffi.cast('long long*', scratch('pick', 8 * cap).ptr)
-  check(C.frcnn_nms_device_n(boxes, ncap, ndev, ncols, 0.25, key_mode, key_col, nil, dpick, cnt + 1, nws.ptr, nwsb, nil))
-  local count = ffi.new('int[2]')
-  check(C.frcnn_memcpy_d2h(count, cnt, 8, nil))                          -- ---- read-back 1 of 2: two counts
+  local nwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, ncap))
+  local nws = scratch(prefix .. 'nms_ws', nwsb)
+  local dpick = ffi.cast('long long*', scratch(prefix .. 'pick', 8 * B * cap).ptr)
+  check(C.frcnn_nms_device_batch(boxes, B, cap, ncap, ndev, ncols, 0.25, key_mode, key_col, nil, dpick, cnt + B, nws.ptr, nwsb, nil))
+  local count = ffi.new('int[?]', 2 * B)
+  check(C.frcnn_memcpy_d2h(count, cnt, 8 * B, nil))                      -- ---- read-back 1 of 2: B pairs of counts
   check(C.frcnn_stream_sync(nil))
-  if count[0] > cap then
-    error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[0], cap))
+  for b = 0, B - 1 do
+    if count[b] > anchors then
+      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], anchors))
+    end
+    if pre ~= nil then count[b] = math.min(count[b], pre) end           -- rows of the (compact) match arrays from here on
+    if count[b] > ncap then
+      local fwsb = tonumber(C.frcnn_nms_workspace_bytes(count[b]))
+      local fws = scratch(prefix .. 'nms_ws_full', fwsb)
+      check(C.frcnn_nms_device(boxes + ncols * b * cap, count[b], ncols, 0.25, key_mode, key_col, dpick + b * cap, cnt + B + b,
+                               fws.ptr, fwsb, nil))
+      check(C.frcnn_memcpy_d2h(count + B + b, cnt + B + b, 4, nil))
+      check(C.frcnn_stream_sync(nil))
+    end
   end
-  local matches = count[0]
-  local nm = matches
-  if pre ~= nil then nm = math.min(matches, pre) end
-  if nm > ncap then
-    nwsb = tonumber(C.frcnn_nms_workspace_bytes(nm))
-    nws = scratch('nms_ws_full', nwsb)
-    check(C.frcnn_nms_device(boxes, nm, ncols, 0.25, key_mode, key_col, dpick, cnt + 1, nws.ptr, nwsb, nil))
-    check(C.frcnn_memcpy_d2h(count + 1, cnt + 1, 4, nil))
-    check(C.frcnn_stream_sync(nil))
-  end
-  if post ~= nil then self:clamp_candidates(cnt + 1, count + 1, 1) end
-  return { outputs = outputs, mp = mp, mi = mi, mr = mr, row = row, dpick = dpick, cnt = cnt, matches = matches, nm = nm,
-           R = count[1] }
+  if post ~= nil then self:clamp_candidates(cnt + B, count + B, B) end
+  return { B = B, cnt = cnt, cap = cap, mp = mp, mi = mi, mr = mr, dpick = dpick, fm = fm, fslot = fslot, fs = fs, count = count,
+           key_mode = key_mode, key_col = key_col }
 end
 
 -- Detector:proposals(input) -- the candidates of the first NMS (Detector.lua:17-85) without the classification net: a list of
 -- { p, a, r, l } as in a detection, in pick order (under the proposal settings of this Detector)
 function Detector:proposals(input)
-  local st = self:first_stage(input)
+  local st = self:first_stage({ input }, '')
   local list = {}
-  if st.nm == 0 or st.R == 0 then return list end
-  local nm, R = st.nm, st.R
+  local nm, R = st.count[0], st.count[1]
+  if nm == 0 or R == 0 then return list end
   local hp, hi, hr = ffi.new('float[?]', nm), ffi.new('int[?]', 4 * nm), ffi.new('double[?]', 4 * nm)
   local hpick = ffi.new('long long[?]', R)
   check(C.frcnn_memcpy_d2h(hp, st.mp, 4 * nm, nil))
@@ -203,104 +243,18 @@ function Detector:proposals(input)
 end
 
 function Detector:detect(input)                                         -- Detector.lua:17-141
-  local model = self.model
-  local cfg = model.cfg
-  local cnet = model.cnet
-  local kh, kw, method, sampling = hip.roi_pooling_settings(cfg)
-  local inv_sx, inv_sy = 0, 0                        -- RoIAlign reads the rects and the picks as they are: no window kernel
-  if method == 'align' then inv_sx, inv_sy = hip.align_geometry(self.localizer) end
-  local bgclass = cfg.class_count + 1
-  local ncls = cfg.class_count + 1
-  local cnet_input_planes = model.layers[#model.layers].filters
-  local D = kh * kw * cnet_input_planes
-  local scratch = self.scratch
-  local key_mode, key_col = 0, 0
-  if self.proposal_order == 'score' then key_mode, key_col = 2, 5 end
-
-  local st = self:first_stage(input)                                    -- :17-85
-  local outputs, mp, mi, mr, dpick, cnt, nm, R = st.outputs, st.mp, st.mi, st.mr, st.dpick, st.cnt, st.nm, st.R
-
-  local winners = {}
-  if nm > 0 then                                                        -- :71
-    print(string.format('candidates: %d', R))                           -- :87
-    -- REGION CLASSIFICATION (:90-101): every candidate's window (objective.lua:5-13 for all of them in one kernel), one
-    -- pooling launch (no indices: there is no backward pass), one cnet pass
-    cnet:evaluate()
-    local fm = outputs[self.nheads + 1]
-    local fs = fm:size()
-    local nl = #self.localizer.layers
-    local layers = ffi.new('int[?]', 6 * nl)
-    for i, l in ipairs(self.localizer.layers) do
-      local o = 6 * (i - 1)
-      layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
-    end
-    local cinput = hip.view(scratch('cinput', 4 * R * D).ptr, { R, D })
-    if method == 'align' then
-      check(C.frcnn_roi_align_forward(fm.ptr, fs[1], fs[2], fs[3], mr, dpick, R, inv_sx, inv_sy, kh, kw, sampling, cinput.ptr, nil))
-    else
-      local dwins = ffi.cast('int*', scratch('wins', 16 * R).ptr)
-      check(C.frcnn_roi_windows(mr, dpick, R, layers, nl, fs[2], fs[3], dwins, nil))
-      check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
-    end
-    local coutputs = cnet:forward(cinput)                               -- :101
-    local bbox_out, cls_out = coutputs[1], coutputs[2]
-    local dcls = ffi.cast('int*', scratch('cls', 4 * R).ptr)
-    local dconf = ffi.cast('float*', scratch('conf', 4 * R).ptr)
-    check(C.frcnn_cnet_decode(cls_out.ptr, R, ncls, dcls, dconf, nil))  -- :110-113 (arg-max of the log-probs)
-    -- :106-122 on the device: class test, r2 = Anchors.anchorToInput(r, bbox) in double, survivors compacted in order
-    local dbb = ffi.cast('float*', scratch('bb5', 20 * R).ptr)
-    local dkc = ffi.cast('int*', scratch('bbcls', 4 * R).ptr)
-    local dkeep = ffi.cast('int*', scratch('keep_row', 4 * R).ptr)
-    local dr2 = ffi.cast('double*', scratch('r2', 32 * R).ptr)
-    check(C.frcnn_detect_post(dcls, dconf, bbox_out.ptr, mr, dpick, R, bgclass, 0.2, dbb, dkc, dkeep, dr2, cnt + 2, nil))
-    -- per-class NMS (:125-136), every class in ONE device pass: rows only suppress rows of their own class; a stable
-    -- partition of the picks by class is, per class, exactly nms(bb, 0.1, bb[{{}, 5}]) -- the score tensor is ignored by
-    -- nms.lua:42, the key is max-y (order = 'score': column 5, the confidence).  The survivor count is read from device memory.
-    local cwsb = tonumber(C.frcnn_nms_workspace_bytes(R))
-    local cws = scratch('nms_ws2', cwsb)
-    local cpick = ffi.cast('long long*', scratch('wpick', 8 * R).ptr)
-    check(C.frcnn_nms_device_n(dbb, R, cnt + 2, 5, 0.1, key_mode, key_col, dkc, cpick, cnt + 3, cws.ptr, cwsb, nil))
-    -- one record of 16 doubles per winner behind a 128-byte header that carries the four counts
-    local out = ffi.cast('double*', scratch('winners', 128 * (R + 1)).ptr)
-    check(C.frcnn_memcpy_d2d(out, cnt, 16, nil))
-    check(C.frcnn_detect_gather(cpick, cnt + 3, R, dkeep, dkc, dbb, dr2, dpick, mp, mr, mi, out + 16, nil))
-    local h = ffi.new('double[?]', 16 * (R + 1))
-    check(C.frcnn_memcpy_d2h(h, out, 128 * (R + 1), nil))                -- ---- read-back 2 of 2: the winner table
-    check(C.frcnn_stream_sync(nil))
-    local nwin = ffi.cast('int*', h)[3]
-    -- classes in ascending order (the reference iterates with pairs(): unspecified), pick order within a class
-    local byclass, classes = {}, {}
-    for q = 1, nwin do
-      local v = h + 16 * q
-      local l, a, y, x = tonumber(v[12]), tonumber(v[13]), tonumber(v[14]), tonumber(v[15])
-      local det = { p = v[3], a = self.anchors:get(l, a, y, x), l = l, r = Rect.new(v[4], v[5], v[6], v[7]),
-                    r2 = Rect.new(v[8], v[9], v[10], v[11]), class = tonumber(v[0]), confidence = v[2] }
-      if not byclass[det.class] then
-        byclass[det.class] = {}
-        classes[#classes + 1] = det.class
-      end
-      table.insert(byclass[det.class], det)
-    end
-    table.sort(classes)
-    for _, ci in ipairs(classes) do
-      for _, x in ipairs(byclass[ci]) do table.insert(winners, x) end
-    end
-  end
-
-  return winners
+  return self:detect_chunk({ input }, false, '')[1]
 end
 
 -- Detector:detect_batch(inputs, shared_cnet) -- detect() for a list of frames of ONE size: a list with one entry per frame,
 -- in order, each what detect(frame) returns.  Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
 -- head maps and last feature map are copied to the frame's slot), then ONE scan, ONE segmented NMS, per frame with
--- candidates the pooling / classification net / class test of detect(), ONE segmented per-class NMS and ONE gather; the
--- host waits twice per chunk instead of twice per frame.  Bit-identical to detect() frame by frame.
+-- candidates the pooling / classification net / class test, ONE segmented per-class NMS and ONE gather; the host waits
+-- twice per chunk instead of twice per frame.  Bit-identical to detect() frame by frame: detect() is a chunk of one.
 -- shared_cnet = true: ONE classification-net pass over the candidates of all frames of a chunk (frame b's rows at the prefix
 -- sum of the candidate counts); everything up to the pooled rows stays bit-identical, the net's outputs agree with detect()'s
 -- within the net's own error only (input scale and Linear form depend on the whole tensor / the row count).
 -- 1:1 with Detector.detect_batch of the Python host mirror.
-Detector.BATCH = 8
-
 function Detector:detect_batch(inputs, shared_cnet)
   local nframes = #inputs
   for i = 2, nframes do                                                 -- refused before anything is queued
@@ -314,16 +268,17 @@ function Detector:detect_batch(inputs, shared_cnet)
   while lo <= nframes do
     local chunk = {}
     for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do chunk[#chunk + 1] = inputs[i] end
-    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet)) do results[#results + 1] = winners end
+    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet, 'b_')) do results[#results + 1] = winners end
     lo = lo + Detector.BATCH
   end
   return results
 end
 
-function Detector:detect_chunk(frames, shared)
+-- detect() of a chunk of frames -> one list of winners per frame: first_stage, then -- unless no frame has a match -- per
+-- frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather, read-back 2 of 2
+function Detector:detect_chunk(frames, shared, prefix)
   local model = self.model
   local cfg = model.cfg
-  local pnet = model.pnet
   local cnet = model.cnet
   local kh, kw, method, sampling = hip.roi_pooling_settings(cfg)
   local inv_sx, inv_sy = 0, 0                        -- RoIAlign reads the rects and the picks as they are: no window kernel
@@ -332,85 +287,11 @@ function Detector:detect_chunk(frames, shared)
   local ncls = cfg.class_count + 1
   local D = kh * kw * model.layers[#model.layers].filters
   local scratch = self.scratch
-  local B = #frames
 
-  -- counts (device int[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
-  local cnt = ffi.cast('int*', scratch('b_counts', 16 * B).ptr)
-  local input_size = frames[1]:size()
-  pnet:evaluate()
-  -- ---- 1. per frame: the proposal net; its outputs are copied to the frame's slot (the net reuses its output buffers)
-  local Hs, Ws, maps, hoff = ffi.new('int[4]'), ffi.new('int[4]'), ffi.new('const float*[4]'), { 0 }
-  local slot, fslot, heads, fms, fs
-  for b = 0, B - 1 do
-    local outputs = pnet:forward(hip.to_device(frames[b + 1]))
-    if b == 0 then
-      for i = 1, 4 do
-        local s = outputs[i]:size()
-        Hs[i - 1], Ws[i - 1] = s[2], s[3]
-        hoff[i + 1] = hoff[i] + math.floor((s[1] * s[2] * s[3] + 63) / 64) * 64
-      end
-      slot = hoff[5]
-      fs = outputs[self.nheads + 1]:size()
-      fslot = math.floor((fs[1] * fs[2] * fs[3] + 63) / 64) * 64
-      heads = ffi.cast('float*', scratch('b_heads', 4 * B * slot).ptr)
-      fms = ffi.cast('float*', scratch('b_fm', 4 * B * fslot).ptr)
-      for i = 0, 3 do maps[i] = heads + hoff[i + 1] end
-    end
-    for i = 1, 4 do
-      check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[i], outputs[i].ptr, 4 * 18 * Hs[i - 1] * Ws[i - 1], nil))
-    end
-    check(C.frcnn_memcpy_d2d(fms + b * fslot, outputs[self.nheads + 1].ptr, 4 * fs[1] * fs[2] * fs[3], nil))
-  end
-  -- ---- 2. ONE scan over the B slots: frame b's matches at rows [b * cap, b * cap + n_b)
-  local cap = 0
-  for i = 0, 3 do cap = cap + ASPECTS * Hs[i] * Ws[i] end
-  local wsb = tonumber(C.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B))
-  local ws = scratch('b_scan_ws', wsb)
-  local mp = ffi.cast('float*', scratch('b_match_p', 4 * B * cap).ptr)
-  local mi = ffi.cast('int*', scratch('b_match_idx', 16 * B * cap).ptr)
-  local mr = ffi.cast('double*', scratch('b_match_rect', 32 * B * cap).ptr)
-  local mb = ffi.cast('float*', scratch('b_match_box', 16 * B * cap).ptr)
-  check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap,
-                               mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
-  -- ---- 3. ONE segmented NMS, the match counts read from device memory, sized for the bound of detect().  Under
-  --         pre_nms_top_n the match arrays are replaced by the compact arrays of the selected rows (`cap` rows a frame from
-  --         here on: min(cap, K)), which no frame can exceed; order = 'score': rows {box, p} keyed by p
-  local order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
-  local key_mode, key_col = 0, 0
-  if order == 'score' then key_mode, key_col = 2, 5 end
-  local anchors = cap
-  local ncap = math.min(cap, 16384)
-  local ndev, boxes, ncols = cnt, mb, 4
-  if order == 'score' and pre == nil then boxes, ncols = self:score_rows(mp, mb, B, cap, cnt, 'b_'), 5 end
-  if pre ~= nil then
-    local sel = self:select_rows(mp, mi, mr, mb, B, cap, pre, cnt, 'b_')
-    mp, mi, mr, mb = sel.p, sel.idx, sel.rect, sel.box
-    cap, ncap, ndev, boxes = sel.stride, sel.stride, sel.count, sel.box
-    if order == 'score' then boxes, ncols = sel.box5, 5 end
-  end
-  local nwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, ncap))
-  local nws = scratch('b_nms_ws', nwsb)
-  local dpick = ffi.cast('long long*', scratch('b_pick', 8 * B * cap).ptr)
-  check(C.frcnn_nms_device_batch(boxes, B, cap, ncap, ndev, ncols, 0.25, key_mode, key_col, nil, dpick, cnt + B, nws.ptr, nwsb, nil))
-  local count = ffi.new('int[?]', 2 * B)
-  check(C.frcnn_memcpy_d2h(count, cnt, 8 * B, nil))                      -- ---- read-back 1 of 2: B pairs of counts
-  check(C.frcnn_stream_sync(nil))
+  local st = self:first_stage(frames, prefix)                           -- :17-85
+  local B, cnt, cap, mp, mi, mr, dpick, count = st.B, st.cnt, st.cap, st.mp, st.mi, st.mr, st.dpick, st.count
+  local fm, fslot, fs, key_mode, key_col = st.fm, st.fslot, st.fs, st.key_mode, st.key_col
   local Rmax = 0
-  for b = 0, B - 1 do
-    if count[b] > anchors then
-      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], anchors))
-    end
-    if pre ~= nil then count[b] = math.min(count[b], pre) end           -- rows of the (compact) match arrays from here on
-    if count[b] > ncap then                                             -- the frame repeats its NMS alone, as in detect()
-      local fwsb = tonumber(C.frcnn_nms_workspace_bytes(count[b]))
-      local fws = scratch('nms_ws_full', fwsb)
-      check(C.frcnn_nms_device(boxes + ncols * b * cap, count[b], ncols, 0.25, key_mode, key_col, dpick + b * cap, cnt + B + b,
-                               fws.ptr, fwsb, nil))
-      check(C.frcnn_memcpy_d2h(count + B + b, cnt + B + b, 4, nil))
-      check(C.frcnn_stream_sync(nil))
-    end
-  end
-  if post ~= nil then self:clamp_candidates(cnt + B, count + B, B) end
   for b = 0, B - 1 do
     if count[b] > 0 then Rmax = math.max(Rmax, count[B + b]) end
   end
@@ -418,6 +299,9 @@ function Detector:detect_chunk(frames, shared)
   for b = 1, B do results[b] = {} end
   if Rmax == 0 then return results end                                  -- :71, every frame
   -- ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into its segment
+  --         (the net owns its outputs and reuses them, so a frame's class test follows its pass at once; the Python mirror, whose
+  --         net writes into the frame's own rows, queues the passes of all frames first: per frame the same launches in the same
+  --         order, and for one frame the same order altogether)
   cnet:evaluate()
   local nl = #self.localizer.layers
   local layers = ffi.new('int[?]', 6 * nl)
@@ -426,12 +310,12 @@ function Detector:detect_chunk(frames, shared)
     layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
   end
   local dwins = ffi.cast('int*', scratch('wins', 16 * Rmax).ptr)
-  local dcls = ffi.cast('int*', scratch('cls', 4 * Rmax).ptr)
-  local dconf = ffi.cast('float*', scratch('conf', 4 * Rmax).ptr)
-  local dbb = ffi.cast('float*', scratch('b_bb5', 20 * B * Rmax).ptr)
-  local dkc = ffi.cast('int*', scratch('b_bbcls', 4 * B * Rmax).ptr)
-  local dkeep = ffi.cast('int*', scratch('b_keep_row', 4 * B * Rmax).ptr)
-  local dr2 = ffi.cast('double*', scratch('b_r2', 32 * B * Rmax).ptr)
+  local dcls = ffi.cast('int*', scratch(prefix .. 'cls', 4 * Rmax).ptr)
+  local dconf = ffi.cast('float*', scratch(prefix .. 'conf', 4 * Rmax).ptr)
+  local dbb = ffi.cast('float*', scratch(prefix .. 'bb5', 20 * B * Rmax).ptr)
+  local dkc = ffi.cast('int*', scratch(prefix .. 'bbcls', 4 * B * Rmax).ptr)
+  local dkeep = ffi.cast('int*', scratch(prefix .. 'keep_row', 4 * B * Rmax).ptr)
+  local dr2 = ffi.cast('double*', scratch(prefix .. 'r2', 32 * B * Rmax).ptr)
   -- first row of frame b in the shared pass's input / output: the prefix sum of the candidate counts
   local row0, total = {}, 0
   for b = 0, B - 1 do
@@ -440,16 +324,18 @@ function Detector:detect_chunk(frames, shared)
       total = total + count[B + b]
     end
   end
-  local cbuf = ffi.cast('float*', shared and scratch('b_cinput', 4 * total * D).ptr or scratch('cinput', 4 * Rmax * D).ptr)
-  local function pooled(b)              -- ROI windows and ROI pooling of frame b -> its input rows
+  local cbuf = ffi.cast('float*', scratch(prefix .. 'cinput', 4 * (shared and total or Rmax) * D).ptr)
+  -- the region features of frame b -> its input rows: every candidate's window (objective.lua:5-13 for all of them in one
+  -- kernel) and one pooling launch (no indices: there is no backward pass), or one RoIAlign launch
+  local function pooled(b)
     local R = count[B + b]
     local cinput = hip.view(shared and (cbuf + row0[b] * D) or cbuf, { R, D })
     if method == 'align' then
-      check(C.frcnn_roi_align_forward(fms + b * fslot, fs[1], fs[2], fs[3], mr + 4 * b * cap, dpick + b * cap, R, inv_sx, inv_sy,
+      check(C.frcnn_roi_align_forward(fm + b * fslot, fs[1], fs[2], fs[3], mr + 4 * b * cap, dpick + b * cap, R, inv_sx, inv_sy,
                                       kh, kw, sampling, cinput.ptr, nil))
     else
       check(C.frcnn_roi_windows(mr + 4 * b * cap, dpick + b * cap, R, layers, nl, fs[2], fs[3], dwins, nil))
-      check(C.frcnn_roi_pool_forward(fms + b * fslot, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
+      check(C.frcnn_roi_pool_forward(fm + b * fslot, fs[1], fs[2], fs[3], dwins, R, kh, kw, cinput.ptr, nil, nil))
     end
     return cinput
   end
@@ -472,21 +358,25 @@ function Detector:detect_chunk(frames, shared)
         local coutputs = cnet:forward(pooled(b))                        -- :101
         bbox_ptr, cls_ptr = coutputs[1].ptr, coutputs[2].ptr
       end
-      check(C.frcnn_cnet_decode(cls_ptr, R, ncls, dcls, dconf, nil))
+      check(C.frcnn_cnet_decode(cls_ptr, R, ncls, dcls, dconf, nil))    -- :110-113 (arg-max of the log-probs)
+      -- :106-122 on the device: class test, r2 = Anchors.anchorToInput(r, bbox) in double, survivors compacted in order
       check(C.frcnn_detect_post(dcls, dconf, bbox_ptr, mr + 4 * b * cap, dpick + b * cap, R, bgclass, 0.2,
                                 dbb + 5 * b * Rmax, dkc + b * Rmax, dkeep + b * Rmax, dr2 + 4 * b * Rmax, cnt + 2 * B + b, nil))
     else
       check(C.frcnn_zero(cnt + 2 * B + b, 4, nil))                      -- no candidates: an empty segment of the per-class NMS
     end
   end
-  -- ---- 5. ONE segmented per-class NMS (one segment per frame), ONE gather of every frame's winner records behind a
-  --         header of the frame's four counts
+  -- ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame), every class in ONE device pass: rows only suppress
+  --         rows of their own class; a stable partition of the picks by class is, per class, exactly nms(bb, 0.1, bb[{{}, 5}])
+  --         -- the score tensor is ignored by nms.lua:42, the key is max-y (order = 'score': column 5, the confidence).  The
+  --         survivor counts are read from device memory.  ONE gather of every frame's winner records (16 doubles each) behind
+  --         a 128-byte header of the frame's four counts
   local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, Rmax))
-  local cws = scratch('b_nms_ws2', cwsb)
-  local cpick = ffi.cast('long long*', scratch('b_wpick', 8 * B * Rmax).ptr)
+  local cws = scratch(prefix .. 'nms_ws2', cwsb)
+  local cpick = ffi.cast('long long*', scratch(prefix .. 'wpick', 8 * B * Rmax).ptr)
   check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 0.1, key_mode, key_col, dkc, cpick, cnt + 3 * B, cws.ptr, cwsb,
                                  nil))
-  local out = ffi.cast('double*', scratch('b_winners', 128 * B * (Rmax + 1)).ptr)
+  local out = ffi.cast('double*', scratch(prefix .. 'winners', 128 * B * (Rmax + 1)).ptr)
   check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb, dr2, dpick, cap, mp, mr, mi, out, nil))
   local h = ffi.new('double[?]', 16 * B * (Rmax + 1))
   check(C.frcnn_memcpy_d2h(h, out, 128 * B * (Rmax + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table

@@ -1,6 +1,6 @@
 """Detector -- host-side mirror of Detector.lua.  detect(input) keeps the reference's pipeline and
 thresholds (p > 0.95, NMS 0.25, class != background and p > 0.2, per-class NMS 0.1) but the 26 544
-iteration Lua loop of Detector.lua:39-66 is one scan+compaction kernel (frcnn_rpn_scan), the per-ROI
+iteration Lua loop of Detector.lua:39-66 is one scan+compaction kernel (frcnn_rpn_scan_batch), the per-ROI
 pooling loop (:94-98) one batched kernel, and both NMS passes run on the device.  Note that both NMS
 calls of the reference pass a tensor as `scores`, which nms.lua:37-43 ignores: boxes are processed
 by descending max-y.  That behaviour is reproduced.
@@ -9,6 +9,11 @@ The frame stays on the device between its big steps: scan -> NMS (the match coun
 device memory), ONE read-back of two counts (the cnet's row count sizes its launches), then ROI windows -> ROI pooling
 -> cnet -> class test + rect decode + ordered compaction -> per-class NMS -> one record per winner, and ONE read-back
 of the winner table.  The list detect() returns builds its {p, a, r, l, r2, class, confidence} tables on access.
+
+There is ONE pipeline, written for a chunk of B frames of one size (_first_stage + _detect_chunk: frcnn_rpn_scan_batch,
+frcnn_nms_device_batch twice, frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound).
+detect_batch(frames) runs it on chunks of BATCH frames, detect(input) on the chunk [input], proposals(input) runs its first
+stage on [input].  A chunk of one frame reads the proposal net's outputs where the model left them: no device copies.
 
 Not in the reference, off by default (cfg["proposals"] / Detector(..., proposals=...), see proposal_settings): the proposal
 layer's two caps and score-ordered NMS.  pre_nms_top_n = K keeps the K best-scoring matches in front of the first NMS
@@ -118,7 +123,7 @@ def _frame_shape(x):
 
 
 class _BatchRecord(object):
-    """One frame's entry of Detector.last_batch: reads like a dict with the keys n, idx, box, rect, p (the frame's scan rows),
+    """One frame's entry of Detector.last_batch, and what last_scan / last_pick / last_cnet / _last read after detect(): reads like a dict with the keys n, idx, box, rect, p (the frame's scan rows),
     pick (1-based candidate rows, pick order), cnet (dict bbox, cls; None for a frame without matches), kept; and pooled --
     the classification net's input rows, kept only by a shared_cnet pass and only for the last chunk of a call (else None).
     The arrays stay on the device and are fetched when they are looked at, like last_scan / last_pick / last_cnet of detect().
@@ -152,8 +157,18 @@ class _BatchRecord(object):
                 c.copy_(t)
             self._dev[k] = c
 
+    def scan(self):
+        """Detector.last_scan of the frame: n and the device arrays of its scan rows (row and matches under pre_nms_top_n)."""
+        out = dict(n=self._v["n"], **{k: self._dev[k] for k in ("p", "idx", "rect", "box", "row") if k in self._dev})
+        if "matches" in self._v:
+            out["matches"] = self._v["matches"]
+        return out
+
     def keys(self):
         return list(self._KEYS)
+
+    def get(self, k, default=None):
+        return self[k] if k in self else default
 
     def __contains__(self, k):
         return k in self._KEYS
@@ -198,7 +213,7 @@ class Detector(object):
         self._host_bytes = 0
         self.verbose = False
         self.last_scan = None
-        self._last = {}
+        self._last = {}              # the last frame's _BatchRecord after detect() or proposals()
         self.last_batch = []
 
     def set_proposals(self, cfg_or_table):
@@ -213,7 +228,7 @@ class Detector(object):
                 pass
 
     def _buf(self, name, shape, dtype=np.float32):
-        need = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+        need = int(math.prod(shape)) * np.dtype(dtype).itemsize   # (plain ints: a frame asks for some thirty buffers)
         b = self._bufs.get(name)
         if b is None or b.nbytes < need:
             b = DeviceTensor.empty((max(need, 256),), np.uint8)
@@ -235,41 +250,17 @@ class Detector(object):
         raw = (C.c_char * int(nbytes)).from_address(self._host)
         return np.frombuffer(raw, dtype=dtype).copy()
 
-    def scan(self, outputs, img_w, img_h, threshold=0.95, counts=None):
-        """Detector.lua:39-66 on device -> dict(cap, p, idx, rect, box (device arrays of `cap` rows), cnt (device count)).
-        Nothing is read back here."""
-        Hs = (C.c_int * 4)(*[outputs[i].shape[1] for i in range(4)])
-        Ws = (C.c_int * 4)(*[outputs[i].shape[2] for i in range(4)])
-        maps = (C.c_void_p * 4)(*[outputs[i].ptr for i in range(4)])
-        wsb = _lib.load().frcnn_rpn_scan_workspace_bytes(Hs, Ws)
-        ws = self._buf("scan_ws", (wsb,), np.uint8)
-        # every anchor of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is
-        # ever truncated
-        cap = ASPECTS * sum(outputs[i].shape[1] * outputs[i].shape[2] for i in range(4))
-        mp = self._buf("match_p", (cap,)); mi = self._buf("match_idx", (cap, 4), np.int32)
-        mr = self._buf("match_rect", (cap, 4), np.float64); mb = self._buf("match_box", (cap, 4))
-        cnt = counts if counts is not None else self._buf("count", (4,), np.int32)
-        _lib.call("frcnn_rpn_scan", maps, Hs, Ws, ptr(self._aw), ptr(self._ah), float(img_w), float(img_h),
-                  float(threshold), cap, ptr(mp), ptr(mi), ptr(mr), ptr(mb), ptr(cnt), ptr(ws), wsb, stream_ptr())
-        return dict(cap=cap, p=mp, idx=mi, rect=mr, box=mb, cnt=cnt, threshold=threshold)
-
-    NMS_FIRST_CAP = 16384   # rows the first NMS launch is sized for (see detect)
+    NMS_FIRST_CAP = 16384   # rows the first NMS launch is sized for (see _first_stage)
 
     @property
     def last_pick(self):
         """1-based rows of the match arrays that survived the first NMS, in pick order (Detector.lua:82)."""
-        L = self._last
-        if "pick_host" not in L and "pick" in L:
-            L["pick_host"] = L["pick"].numpy()[:L["R"]].copy()
-        return L.get("pick_host")
+        return self._last.get("pick")
 
     @property
     def last_cnet(self):
         """cnet outputs of the last frame's candidates: dict(bbox R x 4, cls R x (classes + 1) log-probabilities)."""
-        L = self._last
-        if "cnet_host" not in L and "bbox" in L:
-            L["cnet_host"] = dict(bbox=L["bbox"].numpy(), cls=L["cls"].numpy())
-        return L.get("cnet_host")
+        return self._last.get("cnet")
 
     def _select(self, mp, mi, mr, mb, B, cap, K, c_n, pre=""):
         """pre_nms_top_n: the min(n_b, K) best-scoring rows of every frame's matches (B x cap rows, device counts c_n), gathered
@@ -308,133 +299,27 @@ class Detector(object):
         self._clamped = host     # (pageable memory: the copy has been staged when the call returns; kept anyway)
         return out, True
 
-    def _first_stage(self, input):
-        """Detector.lua:17-85: proposal net, scan, (selection), first NMS, read-back 1 of 2 -> (outputs, m, pick, counts, R);
-        m: the match arrays the rest of the frame reads (the selected rows under pre_nms_top_n).  Leaves last_scan / last_pick."""
-        pnet = self.model["pnet"]
-        s = stream_ptr()
-        L = _lib.load()
-        order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
-
-        inp = to_device(input)
-        _, H, W = inp.shape
-        pnet.evaluate()  # :31
-        outputs = pnet.forward(inp)  # :33
-        # counts (device int32[4]): matches, NMS candidates, candidates that pass the class test, winners
-        counts = self._buf("counts", (4,), np.int32)
-        m = self.scan(outputs, W, H, counts=counts)  # :39-66
-        cap = m["cap"]
-        # NON-MAXIMUM SUPPRESSION (:74-85) on the device, the match count read from device memory; the score tensor is
-        # ignored by nms.lua -> key = max-y
-        # The launch and its workspace are sized for a BOUND on the matches, not for every anchor of the maps (vgg_large:
-        # 45 015 anchors -> 253 MB of masks and a 704 x 704 tile grid per frame for a few hundred matches); a frame with more
-        # matches than the bound repeats the pass sized by the count just read.  Under pre_nms_top_n = K the bound is
-        # min(cap, K), the rows are the K best-scoring matches, and no frame can exceed it.
-        ncap = min(cap, self.NMS_FIRST_CAP)
-        n_dev, boxes, ncols, key_mode, key_col = counts, m["box"], 4, 0, 0
-        if pre is not None:
-            sel = self._select(m["p"], m["idx"], m["rect"], m["box"], 1, cap, pre, ptr(counts))
-            m = dict(m, p=sel["p"], idx=sel["idx"], rect=sel["rect"], box=sel["box"], box5=sel["box5"], row=sel["row"])
-            ncap, n_dev, boxes = sel["stride"], sel["cnt"], sel["box"]
-        if order == "score":
-            boxes = m["box5"] if pre is not None else self._box5(m["p"], m["box"], 1, cap, ptr(counts))
-            ncols, key_mode, key_col = 5, 2, 5
-        wsb = L.frcnn_nms_workspace_bytes(ncap)
-        ws = self._buf("nms_ws", (wsb,), np.uint8)
-        pick = self._buf("nms_pick", (cap,), np.int64)
-        _lib.call("frcnn_nms_device_n", ptr(boxes), ncap, ptr(n_dev), ncols, C.c_float(0.25), key_mode, key_col, None, ptr(pick),
-                  C.c_void_p(counts.ptr + 4), ptr(ws), wsb, s)
-        matches, R = [int(v) for v in self._read(counts.ptr, 8, np.int32)]          # ---- read-back 1 of 2: two counts
-        if matches > cap:
-            raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (matches, m["threshold"], cap))
-        n = matches if pre is None else min(matches, pre)
-        if n > ncap:
-            wsb = L.frcnn_nms_workspace_bytes(n)
-            ws = self._buf("nms_ws_full", (wsb,), np.uint8)
-            _lib.call("frcnn_nms_device", ptr(boxes), n, ncols, C.c_float(0.25), key_mode, key_col, ptr(pick),
-                      C.c_void_p(counts.ptr + 4), ptr(ws), wsb, s)
-            R = int(self._read(counts.ptr + 4, 4, np.int32)[0])
-        if post is not None:
-            R = self._clamp_candidates(counts.ptr + 4, [R])[0][0]
-        self.last_scan = dict(n=n, p=DeviceTensor(m["p"].ptr, (n,), np.float32, owner=m["p"]),
-                              idx=DeviceTensor(m["idx"].ptr, (n, 4), np.int32, owner=m["idx"]),
-                              rect=DeviceTensor(m["rect"].ptr, (n, 4), np.float64, owner=m["rect"]),
-                              box=DeviceTensor(m["box"].ptr, (n, 4), np.float32, owner=m["box"]))
-        if pre is not None:   # the rows above are the selected ones: their 1-based original scan rows, the count before the cap
-            self.last_scan.update(row=DeviceTensor(m["row"].ptr, (n,), np.int32, owner=m["row"]), matches=matches)
-        self._last = dict(pick=pick, R=R)
-        if n == 0:  # :71
-            self._last["pick_host"] = np.zeros(0, np.int64)
-        return outputs, m, pick, counts, n, R
-
     def proposals(self, input):
         """The candidates of the first NMS (Detector.lua:17-85) without the classification net: a list of {p, a, r, l} as in a
         detection, in pick order (under the proposal settings of this Detector)."""
-        _, _, _, _, n, R = self._first_stage(input)
-        if n == 0 or R == 0:
+        st = self._first_stage([input], "")
+        rec = self._records(st)[0]
+        self.last_scan, self._last = rec.scan(), rec
+        if st["ns"][0] == 0 or st["Rs"][0] == 0:
             return []
-        sc = self.last_scan
-        p, idx, rect = sc["p"].numpy(), sc["idx"].numpy(), sc["rect"].numpy()
+        p, idx, rect = rec["p"], rec["idx"], rec["rect"]
         out = []
-        for i in (self.last_pick - 1).tolist():
+        for i in (rec["pick"] - 1).tolist():
             ix = [int(t) for t in idx[i]]
             out.append(dict(p=float(p[i]), r=Rect(*rect[i].tolist()), l=ix[0], a=self.anchors.get(*ix)))
         return out
 
     def detect(self, input):  # Detector.lua:17-141
-        model = self.model
-        cfg = model["cfg"]
-        cnet = model["cnet"]
-        roi = self._roi_settings()
-        kh, kw = roi[0], roi[1]
-        bgclass = cfg["class_count"] + 1
-        ncls = cfg["class_count"] + 1
-        planes = model["layers"][-1]["filters"]
-        s = stream_ptr()
-        L = _lib.load()
-        key_mode, key_col = (2, 5) if self.proposal_order == "score" else (0, 0)
-
-        outputs, m, pick, counts, n, R = self._first_stage(input)   # :17-85
-        if n == 0:  # :71
-            return []
-        if self.verbose:
-            print("candidates: %d" % R)
-        # REGION CLASSIFICATION (:90-101)
-        cnet.evaluate()
-        fm = outputs[-1]
-        fmC, fmH, fmW = fm.shape
-        cinput = self._buf("cinput", (R, kh * kw * planes))
-        self._pool(roi, ptr(fm), fmC, fmH, fmW, ptr(m["rect"]), ptr(pick), R, cinput, s)
-        bbox_out, cls_out = cnet.forward(cinput)  # :101
-        self._last.update(bbox=bbox_out, cls=cls_out)
-        dcls = self._buf("cls", (R,), np.int32); dconf = self._buf("conf", (R,))
-        _lib.call("frcnn_cnet_decode", ptr(cls_out), R, ncls, ptr(dcls), ptr(dconf), s)  # :110-113
-        # :106-122 on the device: class test, r2 = Anchors.anchorToInput(r, bbox) in double, survivors compacted in order
-        bb = self._buf("bb", (R, 5)); kc = self._buf("kc", (R,), np.int32); keep_row = self._buf("keep_row", (R,), np.int32)
-        r2 = self._buf("r2", (R, 4), np.float64)
-        _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(bbox_out), ptr(m["rect"]), ptr(pick), R, bgclass, 0.2,
-                  ptr(bb), ptr(kc), ptr(keep_row), ptr(r2), C.c_void_p(counts.ptr + 8), s)
-        # Per-class NMS (:125-136), all classes in ONE device pass (rows only suppress rows of their own class; a stable
-        # partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
-        # column under order = "score"), the survivor count read from device memory
-        wsb2 = L.frcnn_nms_workspace_bytes(R)
-        ws2 = self._buf("nms_ws2", (wsb2,), np.uint8)
-        wpick = self._buf("wpick", (R,), np.int64)
-        _lib.call("frcnn_nms_device_n", ptr(bb), R, C.c_void_p(counts.ptr + 8), 5, C.c_float(0.1), key_mode, key_col, ptr(kc),
-                  ptr(wpick), C.c_void_p(counts.ptr + 12), ptr(ws2), wsb2, s)
-        # one record per winner, behind a 128-byte header that carries the four counts
-        out = self._buf("winners", (R + 1, 16), np.float64)
-        _lib.call("frcnn_memcpy_d2d", ptr(out), ptr(counts), 16, s)
-        _lib.call("frcnn_detect_gather", ptr(wpick), C.c_void_p(counts.ptr + 12), R, ptr(keep_row), ptr(kc), ptr(bb), ptr(r2),
-                  ptr(pick), ptr(m["p"]), ptr(m["rect"]), ptr(m["idx"]), C.c_void_p(out.ptr + 128), s)
-        raw = self._read(out.ptr, (R + 1) * 128, np.float64).reshape(R + 1, 16)   # ---- read-back 2 of 2: the winner table
-        hdr = raw[0].view(np.int32)
-        nwin = int(hdr[3])
-        self._last.update(kept=int(hdr[2]))
-        rec = raw[1:1 + nwin]
-        # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
-        order = np.argsort(rec[:, 0], kind="stable")
-        return _Detections(rec[order], self.anchors)
+        """The pipeline of detect_batch on a chunk of this one frame (whatever to_device takes; buffers without the b_ prefix, so
+        what a detect_batch call left behind stays as it is).  last_scan, last_pick, last_cnet and _last read the frame's record."""
+        (winners,), (rec,) = self._detect_chunk([input], False, "")
+        self.last_scan, self._last = rec.scan(), rec
+        return winners
 
     def _roi_settings(self):
         """cfg["roi_pooling"] as it stands -> (kh, kw, g, inv_sx, inv_sy) with g = 0 for the max pool; validated before any
@@ -464,8 +349,9 @@ class Detector(object):
         detect(frame) returns.  The frames are processed in chunks of BATCH: the proposal net runs frame by frame, everything
         between and after those passes once per chunk -- one scan, one segmented NMS, (per frame: pooling, classification net,
         class test), one segmented per-class NMS, one gather -- and the host waits twice per chunk instead of twice per frame.
-        Results are bit-identical to detect(): every stage of a frame sees the inputs detect() gives it, through the same
-        kernels or through kernels that share their code.  last_batch holds one record per frame (_BatchRecord).
+        Results are bit-identical to detect(), which is this pipeline on a chunk of one frame: every stage of a frame sees the
+        inputs it sees there, through the same kernels, and a segment of a kernel computes what a one-segment launch computes.
+        last_batch holds one record per frame (_BatchRecord).
         shared_cnet=True: ONE classification-net pass over the candidates of all frames of a chunk (frame b's rows at the
         prefix sum of the candidate counts) instead of one per frame -- the large Linear streams its weights once per chunk.
         Everything up to the pooled rows stays bit-identical to detect(); the net's outputs do NOT (the two-plane form scales
@@ -480,38 +366,34 @@ class Detector(object):
         for lo in range(0, len(frames), step):
             for r in records:     # (the records of the previous chunk view buffers this chunk writes)
                 r.detach()
-            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet))
+            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet), "b_")
             results += res
             records += rec
         self.last_batch = records
         return results
 
-    def _detect_chunk(self, frames, shared):
-        model = self.model
-        cfg = model["cfg"]
-        pnet, cnet = model["pnet"], model["cnet"]
-        roi = self._roi_settings()
-        kh, kw = roi[0], roi[1]
-        bgclass = cfg["class_count"] + 1
-        ncls = cfg["class_count"] + 1
-        planes = model["layers"][-1]["filters"]
+    def _first_stage(self, frames, pre):
+        """Detector.lua:17-85 for a chunk of B frames of one size: the proposal net frame by frame, ONE scan, (selection or score
+        rows), ONE segmented first NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> dict(B,
+        counts (device int32[4][B]), cap (rows a frame in p, idx, rect, pick: the match arrays the rest of the chunk reads, the
+        selected rows under pre_nms_top_n), fm, fslot, fshape (frame b's last feature map at fm + 4 * b * fslot), ns, Rs (rows and
+        candidates per frame), key (key_mode, key_col of both NMS passes), and box, row, matches for _records).
+        pre: prefix of the buffer names ("" for detect() and proposals(), "b_" for detect_batch: neither overwrites what the other
+        left behind)."""
+        pnet = self.model["pnet"]
         s = stream_ptr()
         L = _lib.load()
         B = len(frames)
         i32 = np.int32
 
-        # counts (device int32[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
-        counts = self._buf("b_counts", (4, B), i32)
-        c_n, c_R, c_K, c_W = [C.c_void_p(counts.ptr + 4 * B * k) for k in range(4)]
         # ---- 1. per frame: the proposal net; its head maps and last feature map go to the frame's slot (the model owns and
-        #         reuses its output buffers).  A chunk of ONE frame reads the model's buffers where they are, as detect() does.
-        pnet.evaluate()
-        heads = fms = None
+        #         reuses its output buffers).  A chunk of ONE frame reads the model's buffers where they are: no copies.
+        pnet.evaluate()  # :31
         for b, f in enumerate(frames):
             inp = to_device(f)
             _, H, W = inp.shape
-            outputs = pnet.forward(inp)
-            if heads is None:
+            outputs = pnet.forward(inp)  # :33
+            if b == 0:
                 hshape = [o.shape for o in outputs[:4]]
                 hoff = [0]
                 for shp in hshape:
@@ -520,44 +402,51 @@ class Detector(object):
                 fshape = outputs[-1].shape
                 fslot = (int(np.prod(fshape)) + 63) // 64 * 64
                 if B == 1:
-                    heads, fms = outputs, outputs[-1]
+                    heads, fm = [o.ptr for o in outputs[:4]], outputs[-1].ptr
                     break
-                heads = self._buf("b_heads", (B, slot))
-                fms = self._buf("b_fm", (B, fslot))
+                heads_buf = self._buf(pre + "heads", (B, slot))
+                heads, fm = [heads_buf.ptr + 4 * hoff[i] for i in range(4)], self._buf(pre + "fm", (B, fslot)).ptr
             for i in range(4):
-                _lib.call("frcnn_memcpy_d2d", C.c_void_p(heads.ptr + 4 * (b * slot + hoff[i])), ptr(outputs[i]), outputs[i].nbytes, s)
-            _lib.call("frcnn_memcpy_d2d", C.c_void_p(fms.ptr + 4 * b * fslot), ptr(outputs[-1]), outputs[-1].nbytes, s)
-        # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b)
+                _lib.call("frcnn_memcpy_d2d", C.c_void_p(heads[i] + 4 * b * slot), ptr(outputs[i]), outputs[i].nbytes, s)
+            _lib.call("frcnn_memcpy_d2d", C.c_void_p(fm + 4 * b * fslot), ptr(outputs[-1]), outputs[-1].nbytes, s)
+        # counts (device int32[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
+        counts = self._buf(pre + "counts", (4, B), i32)
+        c_n, c_R = C.c_void_p(counts.ptr), C.c_void_p(counts.ptr + 4 * B)
+        # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b).  Every anchor
+        #         of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is ever truncated
         Hs = (C.c_int * 4)(*[shp[1] for shp in hshape])
         Ws = (C.c_int * 4)(*[shp[2] for shp in hshape])
-        maps = (C.c_void_p * 4)(*[heads[i].ptr if B == 1 else heads.ptr + 4 * hoff[i] for i in range(4)])
+        maps = (C.c_void_p * 4)(*heads)
         cap = ASPECTS * sum(shp[1] * shp[2] for shp in hshape)
         wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B)
-        ws = self._buf("b_scan_ws", (wsb,), np.uint8)
-        mp = self._buf("b_match_p", (B, cap)); mi = self._buf("b_match_idx", (B, cap, 4), i32)
-        mr = self._buf("b_match_rect", (B, cap, 4), np.float64); mb = self._buf("b_match_box", (B, cap, 4))
+        ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
+        mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
+        mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
         threshold = 0.95
         _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, B, slot, ptr(self._aw), ptr(self._ah), float(W), float(H), threshold, cap,
                   ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
-        # ---- 3. ONE segmented NMS (:74-85), the match counts read from device memory, sized for the bound of detect().
-        #         Under pre_nms_top_n the match arrays are replaced by the compact arrays of the selected rows (`cap` rows a
-        #         frame from here on: min(cap, K)), which no frame can exceed; order = "score": rows {box, p} keyed by p.
-        order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
+        # ---- 3. ONE segmented NMS (:74-85) on the device, the match counts read from device memory; the score tensor is ignored
+        #         by nms.lua -> key = max-y.  The launch and its workspace are sized for a BOUND on the matches, not for every
+        #         anchor of the maps (vgg_large: 45 015 anchors -> 253 MB of masks and a 704 x 704 tile grid per frame for a few
+        #         hundred matches); a frame with more matches than the bound repeats the pass alone, sized by the count just read.
+        #         Under pre_nms_top_n = K the match arrays are replaced by the compact arrays of the K best-scoring rows (`cap`
+        #         rows a frame from here on: min(cap, K)), which no frame can exceed; order = "score": rows {box, p} keyed by p.
+        order, pre_n, post_n = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
         key_mode, key_col = (2, 5) if order == "score" else (0, 0)
         ncap = min(cap, self.NMS_FIRST_CAP)
         c_first, boxes, ncols, row, matches, anchors = c_n, mb, 4, None, None, cap
-        if order == "score" and pre is None:
-            boxes, ncols = self._box5(mp, mb, B, cap, c_n, "b_"), 5
-        if pre is not None:
-            sel = self._select(mp, mi, mr, mb, B, cap, pre, c_n, "b_")
+        if order == "score" and pre_n is None:
+            boxes, ncols = self._box5(mp, mb, B, cap, c_n, pre), 5
+        if pre_n is not None:
+            sel = self._select(mp, mi, mr, mb, B, cap, pre_n, c_n, pre)
             mp, mi, mr, mb, row = sel["p"], sel["idx"], sel["rect"], sel["box"], sel["row"]
             cap = ncap = sel["stride"]
             c_first, boxes = ptr(sel["cnt"]), mb
             if order == "score":
                 boxes, ncols = sel["box5"], 5
         wsb = L.frcnn_nms_batch_workspace_bytes(B, ncap)
-        ws = self._buf("b_nms_ws", (wsb,), np.uint8)
-        pick = self._buf("b_nms_pick", (B, cap), np.int64)
+        ws = self._buf(pre + "nms_ws", (wsb,), np.uint8)
+        pick = self._buf(pre + "nms_pick", (B, cap), np.int64)
         _lib.call("frcnn_nms_device_batch", ptr(boxes), B, cap, ncap, c_first, ncols, C.c_float(0.25), key_mode, key_col, None,
                   ptr(pick), c_R, ptr(ws), wsb, s)
         nR = self._read(counts.ptr, 8 * B, i32)                                # ---- read-back 1 of 2: B pairs of counts
@@ -565,101 +454,133 @@ class Detector(object):
         for b in range(B):
             if ns[b] > anchors:
                 raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (ns[b], threshold, anchors))
-        if pre is not None:
-            matches, ns = ns, [min(n, pre) for n in ns]
+        if pre_n is not None:
+            matches, ns = ns, [min(n, pre_n) for n in ns]
         for b in range(B):
-            if ns[b] > ncap:   # more matches than the bound: the frame repeats its NMS alone, as in detect()
+            if ns[b] > ncap:
                 wsb = L.frcnn_nms_workspace_bytes(ns[b])
-                ws = self._buf("nms_ws_full", (wsb,), np.uint8)
+                ws = self._buf(pre + "nms_ws_full", (wsb,), np.uint8)
                 _lib.call("frcnn_nms_device", C.c_void_p(boxes.ptr + 4 * ncols * b * cap), ns[b], ncols, C.c_float(0.25), key_mode,
                           key_col, C.c_void_p(pick.ptr + 8 * b * cap), C.c_void_p(counts.ptr + 4 * (B + b)), ptr(ws), wsb, s)
                 Rs[b] = int(self._read(counts.ptr + 4 * (B + b), 4, i32)[0])
-        if post is not None:
+        if post_n is not None:
             Rs = self._clamp_candidates(counts.ptr + 4 * B, Rs)[0]
-        dev = []
-        for b in range(B):
-            n, R = ns[b], Rs[b]
-            dev.append(dict(p=DeviceTensor(mp.ptr + 4 * b * cap, (n,), np.float32, owner=mp),
-                            idx=DeviceTensor(mi.ptr + 16 * b * cap, (n, 4), i32, owner=mi),
-                            rect=DeviceTensor(mr.ptr + 32 * b * cap, (n, 4), np.float64, owner=mr),
-                            box=DeviceTensor(mb.ptr + 16 * b * cap, (n, 4), np.float32, owner=mb),
-                            pick=DeviceTensor(pick.ptr + 8 * b * cap, (R if n else 0,), np.int64, owner=pick)))
-            if row is not None:
-                dev[b].update(row=DeviceTensor(row.ptr + 4 * b * cap, (n,), i32, owner=row))
+        return dict(B=B, counts=counts, cap=cap, p=mp, idx=mi, rect=mr, box=mb, row=row, pick=pick, fm=fm, fslot=fslot, fshape=fshape,
+                    ns=ns, Rs=Rs, matches=matches, key=(key_mode, key_col))
 
-        def record(b, R, kept):
-            return _BatchRecord(ns[b], R, kept, dev[b], matches[b] if matches is not None else None)
+    def _records(self, st, more=None):
+        """One _BatchRecord per frame of the chunk _first_stage returned st for (views of the chunk's buffers, kept = 0);
+        more[b]: further device arrays of frame b (bbox, cls, pooled).  Host work only: _detect_chunk calls it with the whole
+        chunk queued, in front of its second wait, not between read-back 1 and the launches that wait for it."""
+        cap, row, matches = st["cap"], st["row"], st["matches"]
+        records = []
+        for b in range(st["B"]):
+            n = st["ns"][b]
+            R = st["Rs"][b] if n else 0  # :71
+            dev = dict(p=DeviceTensor(st["p"].ptr + 4 * b * cap, (n,), np.float32, owner=st["p"]),
+                       idx=DeviceTensor(st["idx"].ptr + 16 * b * cap, (n, 4), np.int32, owner=st["idx"]),
+                       rect=DeviceTensor(st["rect"].ptr + 32 * b * cap, (n, 4), np.float64, owner=st["rect"]),
+                       box=DeviceTensor(st["box"].ptr + 16 * b * cap, (n, 4), np.float32, owner=st["box"]),
+                       pick=DeviceTensor(st["pick"].ptr + 8 * b * cap, (R,), np.int64, owner=st["pick"]), **(more or {}).get(b, {}))
+            if row is not None:   # the rows above are the selected ones: their 1-based original scan rows
+                dev.update(row=DeviceTensor(row.ptr + 4 * b * cap, (n,), np.int32, owner=row))
+            records.append(_BatchRecord(n, R, 0, dev, matches[b] if matches is not None else None))
+        return records
+
+    def _detect_chunk(self, frames, shared, pre):
+        """detect() of a chunk of frames -> (one result per frame, their records): _first_stage, then -- unless no frame has a match
+        -- per frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather and
+        read-back 2 of 2."""
+        model = self.model
+        cfg = model["cfg"]
+        cnet = model["cnet"]
+        roi = self._roi_settings()
+        kh, kw = roi[0], roi[1]
+        bgclass = cfg["class_count"] + 1
+        ncls = cfg["class_count"] + 1
+        planes = model["layers"][-1]["filters"]
+        s = stream_ptr()
+        L = _lib.load()
+        i32 = np.int32
+
+        st = self._first_stage(frames, pre)   # :17-85
+        B, counts, cap, mp, mi, mr, pick = st["B"], st["counts"], st["cap"], st["p"], st["idx"], st["rect"], st["pick"]
+        ns, Rs, (key_mode, key_col) = st["ns"], st["Rs"], st["key"]
+        c_K, c_W = C.c_void_p(counts.ptr + 8 * B), C.c_void_p(counts.ptr + 12 * B)
         Rmax = max([Rs[b] for b in range(B) if ns[b] > 0] + [0])
         if Rmax == 0:   # no frame has a match (:71)
-            return [[] for _ in range(B)], [record(b, 0, 0) for b in range(B)]
-        # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into the frame's
-        #         segment (Rmax rows per frame) -- the launches detect() makes, on the frame's own rows
+            return [[] for _ in range(B)], self._records(st)
+        # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) into the frame's rows.  These launches come first:
+        #         the device has been idle since read-back 1, and whatever else the host prepares it prepares while they run
         cnet.evaluate()
-        fmC, fmH, fmW = fshape
-        bbox_all = self._buf("b_bbox", (B, Rmax, 4)); cls_all = self._buf("b_cls_out", (B, Rmax, ncls))
-        bb = self._buf("b_bb", (B, Rmax, 5)); kc = self._buf("b_kc", (B, Rmax), i32); keep_row = self._buf("b_keep_row", (B, Rmax), i32)
-        r2 = self._buf("b_r2", (B, Rmax, 4), np.float64)
+        fmC, fmH, fmW = st["fshape"]
         D = kh * kw * planes
-        dcls = self._buf("cls", (Rmax,), i32); dconf = self._buf("conf", (Rmax,))
-        # first row of frame b in the net's input / output arrays: its own segment, or (shared pass) the prefix sum of R
-        row0, total = {}, 0
+        # first row of frame b in the net's input / output arrays: its own segment (Rmax rows per frame), or (shared pass) the
+        # prefix sum of R
+        row0, total, more = {}, 0, {}
         for b in range(B):
             if ns[b] > 0:
                 row0[b] = total if shared else b * Rmax
                 total += Rs[b]
-        cinput_buf = self._buf("b_cinput", (total, D)) if shared else self._buf("cinput", (Rmax, D))
+        cinput_buf = self._buf(pre + "cinput", (total if shared else Rmax, D))
+        bbox_all = self._buf(pre + "bbox", (B, Rmax, 4)); cls_all = self._buf(pre + "cls_out", (B, Rmax, ncls))
 
         def pooled(b):    # the region features of frame b's candidates (_pool) -> its input rows
             R = Rs[b]
             cinput = DeviceTensor(cinput_buf.ptr + (4 * D * row0[b] if shared else 0), (R, D), np.float32, owner=cinput_buf)
-            self._pool(roi, C.c_void_p(fms.ptr + 4 * b * fslot), fmC, fmH, fmW, C.c_void_p(mr.ptr + 32 * b * cap),
+            self._pool(roi, C.c_void_p(st["fm"] + 4 * b * st["fslot"]), fmC, fmH, fmW, C.c_void_p(mr.ptr + 32 * b * cap),
                        C.c_void_p(pick.ptr + 8 * b * cap), R, cinput, s, rows=Rmax)
             return cinput
-
-        def outputs(b):   # (the net writes into the frame's rows: its own output buffers are reused by the next pass)
-            return (DeviceTensor(bbox_all.ptr + 16 * row0[b], (Rs[b], 4), np.float32, owner=bbox_all),
-                    DeviceTensor(cls_all.ptr + 4 * ncls * row0[b], (Rs[b], ncls), np.float32, owner=cls_all))
+        for b in sorted(row0):
+            if self.verbose:
+                print("candidates: %d" % Rs[b])
+            # (the net writes into the frame's rows: its own output buffers are reused by the next pass)
+            more[b] = dict(bbox=DeviceTensor(bbox_all.ptr + 16 * row0[b], (Rs[b], 4), np.float32, owner=bbox_all),
+                           cls=DeviceTensor(cls_all.ptr + 4 * ncls * row0[b], (Rs[b], ncls), np.float32, owner=cls_all))
+            if shared:
+                more[b].update(pooled=pooled(b))
+            else:
+                cnet.forward(pooled(b), out=(more[b]["bbox"], more[b]["cls"]))  # :101
         if shared:
-            for b in sorted(row0):
-                dev[b].update(pooled=pooled(b))
             cnet.forward(DeviceTensor(cinput_buf.ptr, (total, D), np.float32, owner=cinput_buf),
                          out=(DeviceTensor(bbox_all.ptr, (total, 4), np.float32, owner=bbox_all),
                               DeviceTensor(cls_all.ptr, (total, ncls), np.float32, owner=cls_all)))  # :101, all frames
+        # ---- then, per frame, the class test (:106-122) into the frame's segment: r2 = Anchors.anchorToInput(r, bbox) in double,
+        #      survivors compacted in order
+        bb = self._buf(pre + "bb", (B, Rmax, 5)); kc = self._buf(pre + "kc", (B, Rmax), i32)
+        keep_row = self._buf(pre + "keep_row", (B, Rmax), i32); r2 = self._buf(pre + "r2", (B, Rmax, 4), np.float64)
+        dcls = self._buf(pre + "cls", (Rmax,), i32); dconf = self._buf(pre + "conf", (Rmax,))
         for b in range(B):
-            R = Rs[b]
             if ns[b] == 0:     # no candidates: an empty segment of the per-class NMS
                 _lib.call("frcnn_zero", C.c_void_p(counts.ptr + 4 * (2 * B + b)), 4, s)
                 continue
-            if self.verbose:
-                print("candidates: %d" % R)
-            rect_b, pick_b = C.c_void_p(mr.ptr + 32 * b * cap), C.c_void_p(pick.ptr + 8 * b * cap)
-            bbox_b, cls_b = outputs(b)
-            if not shared:
-                cnet.forward(pooled(b), out=(bbox_b, cls_b))  # :101
-            dev[b].update(bbox=bbox_b, cls=cls_b)
-            _lib.call("frcnn_cnet_decode", ptr(cls_b), R, ncls, ptr(dcls), ptr(dconf), s)  # :110-113
-            _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(bbox_b), rect_b, pick_b, R, bgclass, 0.2,
-                      C.c_void_p(bb.ptr + 20 * b * Rmax), C.c_void_p(kc.ptr + 4 * b * Rmax), C.c_void_p(keep_row.ptr + 4 * b * Rmax),
-                      C.c_void_p(r2.ptr + 32 * b * Rmax), C.c_void_p(counts.ptr + 4 * (2 * B + b)), s)
-        # ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame, rows only suppress rows of their own class),
-        #         ONE gather of every frame's winner records behind a header of the frame's four counts
+            _lib.call("frcnn_cnet_decode", ptr(more[b]["cls"]), Rs[b], ncls, ptr(dcls), ptr(dconf), s)  # :110-113
+            _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(more[b]["bbox"]), C.c_void_p(mr.ptr + 32 * b * cap),
+                      C.c_void_p(pick.ptr + 8 * b * cap), Rs[b], bgclass, 0.2, C.c_void_p(bb.ptr + 20 * b * Rmax),
+                      C.c_void_p(kc.ptr + 4 * b * Rmax), C.c_void_p(keep_row.ptr + 4 * b * Rmax), C.c_void_p(r2.ptr + 32 * b * Rmax),
+                      C.c_void_p(counts.ptr + 4 * (2 * B + b)), s)
+        # ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame, rows only suppress rows of their own class: a stable
+        #         partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
+        #         column under order = "score"), the survivor counts read from device memory; ONE gather of every frame's winner
+        #         records behind a 128-byte header of the frame's four counts
         wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
-        ws2 = self._buf("b_nms_ws2", (wsb2,), np.uint8)
-        wpick = self._buf("b_wpick", (B, Rmax), np.int64)
+        ws2 = self._buf(pre + "nms_ws2", (wsb2,), np.uint8)
+        wpick = self._buf(pre + "wpick", (B, Rmax), np.int64)
         _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(0.1), key_mode, key_col, ptr(kc), ptr(wpick),
                   c_W, ptr(ws2), wsb2, s)
-        out = self._buf("b_winners", (B, Rmax + 1, 16), np.float64)
+        out = self._buf(pre + "winners", (B, Rmax + 1, 16), np.float64)
         _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb), ptr(r2), ptr(pick),
                   cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
+        records = self._records(st, more)
         raw = self._read(out.ptr, B * (Rmax + 1) * 128, np.float64).reshape(B, Rmax + 1, 16)   # ---- read-back 2 of 2
-        results, recs = [], []
+        results = []
         for b in range(B):
             hdr = raw[b, 0].view(i32)
-            recs.append(record(b, Rs[b] if ns[b] else 0, int(hdr[2])))
+            records[b]._v.update(kept=int(hdr[2]))
             if ns[b] == 0:
                 results.append([])
                 continue
             w = raw[b, 1:1 + int(hdr[3])]
             # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
             results.append(_Detections(w[np.argsort(w[:, 0], kind="stable")].copy(), self.anchors))
-        return results, recs
+        return results, records

@@ -143,7 +143,8 @@ int frcnn_nms_device_classes(const float *boxes, int n, int ncols, float overlap
  * without a host round trip for the count in between.  cls may be NULL. */
 int frcnn_nms_device_n(const float *boxes, int n_cap, const int *n_dev, int ncols, float overlap, int key_mode, int key_col,
                        const int *cls, long long *pick, int *count, void *workspace, size_t workspace_bytes, void *stream);
-/* B independent problems in ONE pass (Detector:detect_batch; every stage one launch with the segment as a grid dimension, the
+/* B independent problems in ONE pass (Detector:detect_batch, and :detect with B = 1; every stage one launch with the segment
+ * as a grid dimension, the
  * greedy scans as B workgroups side by side).  Segment b: rows boxes + b*row_stride*ncols, count min(n_dev[b], n_cap) (device
  * int[B], required), cls + b*row_stride (optional), picks pick + b*row_stride (1-based rows WITHIN the segment), survivor
  * count count[b].  row_stride >= n_cap.  Per segment the result is bit for bit frcnn_nms_device_n on that segment; a segment
@@ -173,7 +174,8 @@ int frcnn_detect_post(const int *cls, const float *conf, const float *bbox, cons
 int frcnn_detect_gather(const long long *wpick, const int *nwin_dev, int cap, const int *keep_row, const int *kc,
                         const float *bb, const double *r2, const long long *pick, const float *match_p,
                         const double *match_rect, const int *match_idx, double *rec, void *stream);
-/* frcnn_detect_gather for B frames in one launch, all winner tables in ONE buffer (one read-back): frame b's table starts at
+/* frcnn_detect_gather for B frames in one launch (Detector:detect_batch, and Detector:detect with B = 1), all winner tables in
+ * ONE buffer (one read-back): frame b's table starts at
  * rec + b*(row_stride + 1)*16 doubles -- a 128-byte header whose first four ints are the frame's counts, then one record per
  * winner q < min(winners, row_stride).  counts: device int[4][B] = {matches, candidates, survivors of the class test,
  * winners} per frame.  wpick / keep_row / kc / bb / r2 hold row_stride rows per frame, pick / match_* match_stride rows. */
@@ -264,7 +266,8 @@ int frcnn_rpn_scan(const float *const *maps_host, const int *H_host, const int *
                    double p_threshold, int cap, float *match_p, int *match_idx,
                    double *match_rect, float *match_box, int *count, void *workspace,
                    size_t workspace_bytes, void *stream);
-/* The same for B frames in one pass (Detector:detect_batch): maps_host are the four maps of frame 0, frame b's are slot_stride
+/* The same for B frames in one pass (Detector:detect_batch, and Detector:detect with B = 1): maps_host are the four maps of
+ * frame 0, frame b's are slot_stride
  * floats further (every map); one launch for the threshold test, one for the ordered compaction with one workgroup per
  * frame.  Frame b's matches are rows [b*cap, b*cap + min(count[b], cap)) of the match arrays, count: device int[B].  Per
  * frame bit-identical to frcnn_rpn_scan. */

@@ -407,6 +407,38 @@ def test_detect_batch_host_waits(F, amplified, monkeypatch):
     assert not reads3 and not fwd
 
 
+def test_detect_host_waits_and_copies(F, amplified, monkeypatch):
+    """detect() is the one-frame chunk of the detect_batch pipeline on the model's own output buffers: two waits, one
+    proposal-net pass, no device-to-device copy; the batched scan and gather once each, the batched NMS twice."""
+    import torch
+    s = amplified
+    f = F.synthetic_image(H, W, 5)
+    pnet, cnet = s["model"]["pnet"], s["model"]["cnet"]
+    fwd, cfwd, calls, reads = [], [], [], []
+    orig_fwd, orig_cfwd, orig_call = pnet.forward, cnet.forward, F._lib.call
+    monkeypatch.setattr(pnet, "forward", lambda img, **kw: fwd.append(1) or orig_fwd(img, **kw))
+    monkeypatch.setattr(cnet, "forward", lambda x, **kw: cfwd.append(1) or orig_cfwd(x, **kw))
+    monkeypatch.setattr(F._lib, "call", lambda name, *a, **kw: calls.append(name) or orig_call(name, *a, **kw))
+    d = F.Detector(s["model"])
+    orig_read = d._read
+    d._read = lambda *a, **kw: reads.append(a[1]) or orig_read(*a, **kw)
+    win = d.detect(f)
+    seen = list(calls)                                   # (looking at last_pick below copies from the device too)
+    R = len(d.last_pick)
+    assert d.last_scan["n"] > 0 and R > 0 and type(win).__name__ == "_Detections"
+    assert reads == [8, (R + 1) * 128], reads
+    assert len(fwd) == 1 and len(cfwd) == 1
+    assert seen.count("frcnn_memcpy_d2d") == 0
+    assert seen.count("frcnn_rpn_scan_batch") == 1 and seen.count("frcnn_detect_gather_batch") == 1
+    assert seen.count("frcnn_nms_device_batch") == 2
+    # un-amplified weights, no anchor passes 0.95: the frame stops after the first wait, in front of the classification net
+    s["weights"].copy_(torch.from_numpy(s["w"]))
+    del fwd[:], cfwd[:], reads[:]
+    win = d.detect(f)
+    assert win == [] and isinstance(win, list)
+    assert reads == [8] and len(fwd) == 1 and not cfwd
+
+
 def _iou_border_pairs(boxes, thr, eps=1e-5):
     """number of box pairs whose nms.lua IoU (the +1 convention of nms.lua:35,88-94) lies within eps of thr"""
     b = boxes.astype(np.float64)

@@ -453,15 +453,17 @@ def test_shared_cnet_keeps_working_under_the_settings(F, setup):
 
 def test_proposals_are_the_candidates_detect_used(F, setup):
     s = setup
-    for t in (None, dict(order="score", pre_nms_top_n=100, post_nms_top_n=M_POST)):
+    for t in (None, dict(order="score", pre_nms_top_n=100, post_nms_top_n=M_POST),
+              dict(order="score", pre_nms_top_n=50, post_nms_top_n=10)):
         d = F.Detector(s["model"], proposals=t)
         for f in s["frames"][:3]:
             props = d.proposals(f)
-            pick = d.last_pick.copy()
+            pick, p_scan = d.last_pick.copy(), d.last_scan["p"].numpy()
             d.detect(f)
             assert np.array_equal(d.last_pick, pick) and len(props) == len(pick) > 0
             m = d.last_scan
             p, idx, rect = m["p"].numpy(), m["idx"].numpy(), m["rect"].numpy()
+            assert np.array_equal(p.view(np.uint32), p_scan.view(np.uint32))     # one first stage behind both
             for x, i in zip(props, (pick - 1).tolist()):
                 assert x["p"] == float(p[i]) and x["l"] == int(idx[i][0])
                 assert (x["r"].minX, x["r"].minY, x["r"].maxX, x["r"].maxY) == tuple(rect[i].tolist())

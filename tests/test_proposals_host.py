@@ -189,15 +189,18 @@ def test_lua_binding_declares_and_the_drop_in_calls_them():
     assert "Detector.proposal_settings(self.model.cfg.proposals)" in det
     assert re.search(r"^function Detector\.proposal_settings\(t\)", det, re.M)
     assert re.search(r"^function Detector:proposals\(input\)", det, re.M)
-    assert re.search(r"^function Detector:first_stage\(input\)", det, re.M)
+    assert re.search(r"^function Detector:first_stage\(frames, prefix\)", det, re.M)
     for call in ("C.frcnn_topk_select_workspace_bytes(", "C.frcnn_topk_select(", "C.frcnn_rpn_gather_rows("):
         assert call in det, call
     # both hosts refuse the same things
     for needle in ("unknown key", "is not an integer", "at least 1", "needs order = \"score\""):
         assert needle in det, needle
-    # both NMS passes take the key from the setting, in detect() and in detect_chunk()
-    assert det.count("key_mode, key_col = 2, 5") == 3
-    assert len(re.findall(r"C\.frcnn_nms_device_(?:n|batch)\([^\n]*key_mode, key_col", det)) == 4
+    # every NMS call of the one pipeline (first pass, its repeat over the bound, per-class pass) takes the key from the setting
+    assert det.count("key_mode, key_col = 2, 5") >= 1
+    calls = re.findall(r"C\.frcnn_nms_device\w*\([^;]*?\)\)", det)
+    assert len(calls) >= 3 and len(calls) == len(re.findall(r"C\.frcnn_nms_device\w*\(", det))
+    for call in calls:
+        assert "key_mode, key_col" in " ".join(call.split()), call
     assert "'pre_nms_top_n'" in det and "'post_nms_top_n'" in det and "self:clamp_candidates(" in det
 
 
