@@ -435,20 +435,23 @@ int channel_sum(const float* g, int C, long hw, float* gbias, hipStream_t s) {
   return FRCNN_OK;
 }
 
-// gb[o] += sum_r g[r][o]  (row-major R x O; nn.Linear bias gradient): 64 columns x 16 row groups per block
+// gb[o] += sum_r g[r][o]  (row-major R x O; nn.Linear bias gradient): 64 columns x 16 row groups per block.  fp64 partial sums,
+// like the batch normalisation's column sums (cnet.hip): in front of a BatchNormalization the true sum is zero and what is left is
+// rounding -- fp32 partial sums left six times the rounding of the summed values themselves at a thousand rows
+// (tests/test_gpu_cnet_shapes.py)
 __global__ __launch_bounds__(1024) void channel_sum_cols_kernel(const float* __restrict__ g, int R, int O, float* gb) {
-  __shared__ float sh[16 * 64];
+  __shared__ double sh[16 * 64];
   const int tx = threadIdx.x, ty = threadIdx.y;
   const int o = blockIdx.x * 64 + tx;
-  float sacc = 0.f;
+  double sacc = 0.0;
   if (o < O) for (int r = ty; r < R; r += 16) sacc += g[(size_t)r * O + o];
   sh[ty * 64 + tx] = sacc;
   __syncthreads();
   if (ty == 0 && o < O) {
-    float t = 0.f;
+    double t = 0.0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) t += sh[k * 64 + tx];
-    gb[o] += t;
+    gb[o] = (float)((double)gb[o] + t);
   }
 }
 int channel_sum_cols(const float* g, int R, int O, float* gb, hipStream_t s) {

@@ -1,0 +1,251 @@
+"""The tables of tests/test_gpu_cnet_shapes.py -- class-layer tables, backbones, class counts, row counts, seeds -- and a
+plain restatement of the shape rules that decide which code path the classification net takes (csrc/gemm.hip gemm_f32,
+csrc/cnet.hip, csrc/net.cpp frcnn_cnet_forward / frcnn_cnet_backward), with the library's default options.
+
+As in tests/width_plan.py the restatement only LABELS the GPU cases with the branches they reach, so that
+tests/test_cnet_plan.py can check that the tables still reach every one of them: it is no evidence that a branch
+computes the right thing.  The GPU tests against the oracle are."""
+import numpy as np
+
+import width_plan as WP
+from width_plan import cdiv
+
+ROI_CELLS = WP.ROI_CELLS
+BACKBONE = [8, 12, 16]          # layers_of(BACKBONE + [L]): the classification net's input is D = 36 * L wide
+HEADS = [(3, 24, 3), (3, 24, 4), (5, 24, 4), (7, 24, 4)]   # util.TINY_HEADS: every model's four narrow anchor nets (the tests here run the classification net only)
+WEIGHT_SEED = 11                # combine_and_flatten_parameters(seed=...) of every model
+
+# ---- class-layer tables: (n, batch_norm, dropout) per hidden layer ------------------------------------------------------
+TABLES = {
+    "std": [(48, True, .5), (32, False, .5)],                       # the reference shape
+    "ragged": [(50, True, .5), (30, False, .5)],                    # widths no multiples of 4 / 16; 30 features: unfused heads
+    "bn_last": [(512, False, .5), (40, True, .5)],                  # flat kernel folds 4 slabs, BN kernel folds 2, BN at the top
+    "bn_both": [(48, True, .5), (32, True, .5)],
+    "wide_second": [(48, True, .5), (512, False, .5)],              # layer 1's input gradient: K = 512, 2 slabs into layer 0's backward
+    "one": [(64, True, .5)],
+    "three": [(48, True, .5), (40, False, 0.), (24, True, .5)],
+    "none": [],
+    "heads_1024": [(64, True, .5), (1024, False, .5)],              # the largest dynamic LDS the heads kernels ask for
+    "heads_1032": [(64, True, .5), (1032, False, .5)],              # one step past it: separate launches
+}
+CLASS_COUNT = 16                # config/duplo.lua
+CLASS_COUNTS = (1, 15, 27, 28, 63, 64, 200)   # nc = 2, 16, 28, 29, 64, 65, 201 (on std, L = 32)
+
+# (table, L, class_count): one model each
+MODELS = ([("std", 32, CLASS_COUNT), ("std", 64, CLASS_COUNT)] +
+          [(t, 32, CLASS_COUNT) for t in ("ragged", "bn_last", "bn_both", "wide_second", "one", "three", "none")] +
+          [("none", 16, CLASS_COUNT), ("heads_1024", 32, CLASS_COUNT), ("heads_1032", 32, CLASS_COUNT)] +
+          [("std", 32, cc) for cc in CLASS_COUNTS] +
+          [("heads_1024", 32, 27)])   # 32 outputs x 1024 features: the largest LDS request of the heads' backward kernel
+
+ROWS_FULL = (1, 2, 3, 5, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049)
+ROWS_SHORT = (1, 5, 257, 1025)
+EVAL_TABLES = ("std", "bn_both")
+EVAL_ROWS = (5, 1025, 2049)
+EVAL_BACKWARD_ROWS = (5, 1025)
+DRAW_TABLES = ("std", "bn_last", "three")
+DRAW_ROWS = (5, 1025)
+DET_TABLES = ("std", "bn_last")
+DET_ROWS = (5, 1025)
+ASYNC_TABLES = ("std", "wide_second")   # also run with option cnet_wgrad_async 0 and 1
+
+
+def model_id(key):
+    return "%s-L%d-c%d" % key
+
+
+def rows_of(key):
+    return ROWS_FULL if key[0] == "std" and key[2] == CLASS_COUNT else ROWS_SHORT
+
+
+def cls_of(table):
+    """-> class_layers of F.create_model / O.make_model"""
+    out = []
+    for n, bn, p in TABLES[table]:
+        l = dict(n=n, dropout=p)
+        if bn:
+            l["batch_norm"] = True
+        out.append(l)
+    return out
+
+
+def cases():
+    """[(model key, R)]: every training case of part a"""
+    return [(k, R) for k in MODELS for R in rows_of(k)]
+
+
+# ---- seeds --------------------------------------------------------------------------------------------------------------
+# The seed of a case's inputs (inputs() below).  A batch-normalised column whose two or three values nearly coincide
+# amplifies the rounding of the product in front of it by up to 1 / sqrt(1e-5); whether a case has one depends on the
+# seed alone.  Every case's seed passes the conditioning probe of test_gpu_cnet_shapes.py (the oracle on x and on
+# x * (1 + 1e-6 randn): outputs and gradInput move by at most 1e-5), checked on the CPU with the real initialisation
+# (WEIGHT_SEED).  The default seed is R: with these tables and WEIGHT_SEED every case passes with it (the oracle moves by
+# 4.4e-6 at most, bn_both at R = 5).  A case that fails the probe after a change of the tables gets another seed here,
+# (table, L, class_count, R): seed -- never a wider bar, and it is never dropped.
+SEED_OVERRIDES = {
+}
+
+
+def seed_of(key, R):
+    return SEED_OVERRIDES.get((key[0], key[1], key[2], R), R)
+
+
+def inputs(key, R, seed):
+    """-> dict(x, x2, masks, gb, gc): the input, the probe's perturbed input, the explicit keep masks (None for a layer
+    without dropout) and the two output gradients of a case, drawn as test_gpu_widths.py::test_cnet_rows draws them
+    (unit-variance bbox gradients at every R)."""
+    table, L, cc = key
+    rng = np.random.RandomState(seed)
+    D = ROI_CELLS * L
+    x = rng.randn(R, D).astype(np.float32)
+    masks = [(rng.rand(R, n) > 0.5).astype(np.float32) if p > 0 else None for n, bn, p in TABLES[table]]
+    gb = rng.randn(R, 4).astype(np.float32)
+    gc = (rng.randn(R, cc + 1) / R).astype(np.float32)
+    x2 = (x * (1 + 1e-6 * rng.randn(R, D))).astype(np.float32)
+    return dict(x=x, x2=x2, masks=masks, gb=gb, gc=gc)
+
+
+# ---- the dropout draw ---------------------------------------------------------------------------------------------------
+def splitmix64(z):
+    """common.h frcnn_splitmix64 on a uint64 array (wrapping arithmetic)"""
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def keep_mask(seed, count, p):
+    """common.h frcnn_keep_mask for elements 0 .. count - 1 of stream `seed`: splitmix64 of seed * 0x100000001B3 + i in
+    wrapping uint64, its top 24 bits / 2^24 in float32, kept (1) when not below float32 p"""
+    with np.errstate(over="ignore"):
+        z = np.full(count, (seed * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) + np.arange(count, dtype=np.uint64)
+    u = (splitmix64(z) >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return np.where(u < np.float32(p), np.float32(0), np.float32(1)).astype(np.float32)
+
+
+# ---- the shape rules ----------------------------------------------------------------------------------------------------
+GBK = 32            # gemm.hip
+FB_CB, FB_RG, FB_KEEP = 4, 256, 4   # cnet.hip: the fused kernels' block and the rows a thread keeps
+BN_CB, BN_RG = 16, 64               # cnet.hip: the separate kernels' block
+
+
+def gemm_splits(M, N, K):
+    """gemm.hip gemm_f32: the number of split-K slabs of C[M][N] = A[M][K] B[K][N]."""
+    TNs = 128 if (N >= 2048 and K >= 512) else 64
+    tiles = cdiv(M, 64) * cdiv(N, TNs)
+    slots = 1280 if TNs == 128 else 2048
+    splitK = max(1, min(K // 256, 16, slots // tiles))
+    kPerSplit = cdiv(cdiv(K, splitK), GBK) * GBK
+    return cdiv(K, kPerSplit)
+
+
+def fold_state(M, N, K, defer):
+    """"none": the product stores its result; "consumer": 2..8 slabs left to the launch that reads them (GemmFold);
+    "launch": a fold launch of the product's own (more than 8 slabs, or nobody to defer to)."""
+    s = gemm_splits(M, N, K)
+    if s == 1:
+        return "none"
+    return "consumer" if (defer and s <= 8) else "launch"
+
+
+def heads_fused_eligible(nf, nc):
+    """cnet.hip cnet_heads_fused_eligible"""
+    return 4 + nc <= 32 and nf % 8 == 0 and nf <= 1024
+
+
+def rows_keep(R):
+    """cnet.hip: a thread of the fused kernels keeps its rows in registers"""
+    return R <= FB_RG * FB_KEEP
+
+
+def labels_of_case(key, R, fuse=True, wgrad_async=True, deterministic=False):
+    """The branches one training forward + backward of model `key` at R rows reaches (net.cpp frcnn_cnet_forward /
+    frcnn_cnet_backward; linear_x_eligible is false at every size of these tables: the products are gemm_f32's)."""
+    table, L, cc = key
+    layers = TABLES[table]
+    D, nc = ROI_CELLS * L, cc + 1
+    labels = set()
+    rows = "rows_keep" if rows_keep(R) else "rows_tall"
+    labels.add(rows)
+    labels.add({0: "no_hidden_layer", 1: "one_layer", 2: "two_layers", 3: "three_layers"}[len(layers)])
+    async_ = wgrad_async and not deterministic
+    fin = D
+    for l, (n, bn, p) in enumerate(layers):
+        assert not any(WP.linear_x_eligible(role, R, fin, n) for role in (1, 2, 4)), (key, R, l)
+        if n % FB_CB or n % BN_CB:
+            labels.add("ragged_width" if n % FB_CB else "ragged_width_16")
+        if fuse:
+            st = fold_state(R, n, fin, True)
+            labels.add("fold_%s" % st)
+            labels.add("fold_%s+%s" % (st, rows))
+            if bn:
+                labels.add("bn_fused")
+                labels.add("bn_fold_%s+%s" % (st, rows))
+            elif st == "consumer":
+                labels.add("flat_fold")
+        elif bn:
+            labels.add("bn_separate")
+        # backward: this layer's input gradient gin[R][fin] = g[R][n] W[n][fin] is folded by the layer below
+        gdefer = fuse and async_ and l > 0 and layers[l - 1][1]
+        if fold_state(R, fin, n, gdefer) == "consumer":
+            labels.add("dgrad_fold_deferred")
+        fin = n
+    nf = fin
+    if fuse and heads_fused_eligible(nf, nc):
+        labels.add("heads_fused")
+        if not layers:
+            labels.add("heads_on_input")
+        if (4 + nc) % 2 == 0:
+            labels.add("heads_even_outputs")
+        if 4 + nc == 32:
+            labels.add("heads_32_outputs")
+        if nf == 1024:
+            labels.add("heads_lds_max")
+            if 4 + nc == 32:
+                labels.add("heads_lds_max_backward")
+        if R > 4 * 256:
+            labels.add("heads_grid_stride")
+        if R % 4:
+            labels.add("heads_partial_block")
+        if layers and not layers[-1][1] and not deterministic:   # top_act_done
+            labels.add("top_act_in_heads")
+    else:
+        if 4 + nc > 32:
+            labels.add("heads_unfused_nc")
+        if nf % 8 or nf > 1024:
+            labels.add("heads_unfused_nf")
+        if nc > 64:
+            labels.add("lsm_lane_stride")
+    if layers and layers[-1][1]:
+        labels.add("top_bn")
+    return labels
+
+
+def labels_of_model(key, **kw):
+    labels = set()
+    for R in rows_of(key):
+        labels |= labels_of_case(key, R, **kw)
+    return labels
+
+
+def labels_of_tables(models=None):
+    labels = set()
+    for key in (MODELS if models is None else models):
+        labels |= labels_of_model(key)
+    return labels
+
+
+REQUIRED = {
+    "rows_keep", "rows_tall",
+    "fold_none", "fold_consumer", "fold_launch",
+    "fold_none+rows_keep", "fold_none+rows_tall", "fold_consumer+rows_keep", "fold_consumer+rows_tall",
+    "fold_launch+rows_keep", "fold_launch+rows_tall",
+    "bn_fused", "flat_fold",
+    "heads_fused", "heads_unfused_nc", "heads_unfused_nf", "heads_on_input",
+    "heads_even_outputs", "heads_32_outputs", "heads_lds_max",
+    "top_act_in_heads", "top_bn",
+    "dgrad_fold_deferred",
+    "no_hidden_layer", "one_layer", "three_layers",
+    "ragged_width",
+}
