@@ -76,6 +76,14 @@ _SIGS = {
     "frcnn_maxpool_act_backward": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_act_forward": ([vp, C.c_int, C.c_longlong, vp, vp, vp, vp], C.c_int),
     "frcnn_act_backward": ([vp, vp, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_amax_record_floats": ([], C.c_int),
+    "frcnn_tensor_absmax": ([vp, C.c_longlong, vp, vp], C.c_int),
+    "frcnn_maxpool_act_forward_rec": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_maxpool_act_backward_rec": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_act_backward_rec": ([vp, vp, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_conv2d_forward_rec": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp], C.c_int),
+    "frcnn_conv2d_backward_input_rec": ([vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp,
+                                         vp], C.c_int),
     "frcnn_roi_pool_forward": ([vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp], C.c_int),
     "frcnn_roi_pool_backward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp], C.c_int),
     "frcnn_roi_align_forward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, vp,

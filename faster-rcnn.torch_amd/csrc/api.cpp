@@ -250,27 +250,39 @@ static int scale_fits_f16_form(const float* in_scale, int C, hipStream_t s, bool
   return FRCNN_OK;
 }
 
+// The split-operand form of the two entry points below.  f16: the two-plane fp16 form (records: rec_in = the caller's record of
+// the launch's input tensor or null = taken here; rec_out = conv_x3's amax_out), else three bf16 planes.
+static int conv2d_split(const float* in, int Kc, int H, int W, const float* in_slope, const float* in_scale, const float* weight,
+                        const float* bias, int O, int C, int M, int k, int mode, int pad, float* out, int out_mode, bool f16,
+                        const float* rec_in, float* rec_out, const X3PostAct* post, hipStream_t s) {
+  float* wp = nullptr;
+  FR_HIP(hipMalloc((void**)&wp, conv_x3_pack_bytes(Kc, M, k)));
+  float* am = nullptr;
+  int rcx = f16 ? x3_f16_records(&am) : FRCNN_OK;
+  float* const amw = am ? am + AMAX_REC : nullptr;          // the weights' record
+  float* const aws = am ? am + 2 * AMAX_REC : nullptr;      // their largest magnitude
+  if (am && rcx == FRCNN_OK) {
+    if (!rec_in) rcx = tensor_absmax(in, (long)Kc * H * W, am, s);
+    if (rcx == FRCNN_OK) rcx = tensor_absmax(weight, (long)O * C * k * k, amw, s);
+  }
+  if (rcx == FRCNN_OK) rcx = conv_x3_pack(weight, O, C, k, mode, wp, s, H + 2 * pad - k + 1, W + 2 * pad - k + 1, amw, aws);
+  if (rcx == FRCNN_OK)
+    rcx = conv_x3(in, Kc, H, W, in_slope, in_scale, wp, bias, M, k, pad, out, out_mode, 0, s, 0, post, am ? (rec_in ? rec_in : am) : nullptr,
+                  aws, rec_out);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(wp); (void)hipFree(am);
+  return rcx;
+}
+
 int frcnn_conv2d_forward(const float* in, int C, int H, int W, const float* in_slope, const float* in_scale,
                          const float* weight, const float* bias, int O, int k, int pad, float* out,
                          void* stream) {
   float* wf = nullptr;
   if (conv_x3_eligible(C, O, k) && (k == 3 || (!in_slope && !in_scale))) {   // split-bf16 operand form (convx.hip)
-    FR_HIP(hipMalloc((void**)&wf, conv_x3_pack_bytes(C, O, k)));
-    float* am = nullptr;
     bool unit = true;
-    int rcx = scale_fits_f16_form(in_scale, C, S(stream), &unit);
-    if (rcx == FRCNN_OK && unit) rcx = x3_f16_records(&am);
-    float* const amw = am ? am + AMAX_REC : nullptr;          // the weights' record
-    float* const aws = am ? am + 2 * AMAX_REC : nullptr;      // their largest magnitude
-    if (am && rcx == FRCNN_OK) {
-      rcx = tensor_absmax(in, (long)C * H * W, am, S(stream));
-      if (rcx == FRCNN_OK) rcx = tensor_absmax(weight, (long)O * C * k * k, amw, S(stream));
-    }
-    if (rcx == FRCNN_OK) rcx = conv_x3_pack(weight, O, C, k, 0, wf, S(stream), H + 2 * pad - k + 1, W + 2 * pad - k + 1, amw, aws);
-    if (rcx == FRCNN_OK) rcx = conv_x3(in, C, H, W, in_slope, in_scale, wf, bias, O, k, pad, out, OUT_STORE, 0, S(stream), 0, nullptr, am, aws);
-    (void)hipStreamSynchronize(S(stream));
-    (void)hipFree(wf); (void)hipFree(am);
-    return rcx;
+    FR_TRY(scale_fits_f16_form(in_scale, C, S(stream), &unit));
+    return conv2d_split(in, C, H, W, in_slope, in_scale, weight, bias, O, C, O, k, 0, pad, out, OUT_STORE, unit, nullptr, nullptr, nullptr,
+                        S(stream));
   }
   FR_HIP(hipMalloc((void**)&wf, conv_pack_floats(C, O, k) * 4));
   int rc = conv_pack_weights(weight, O, C, k, wf, nullptr, S(stream));
@@ -282,22 +294,9 @@ int frcnn_conv2d_forward(const float* in, int C, int H, int W, const float* in_s
 int frcnn_conv2d_backward_input(const float* gout, int O, int Ho, int Wo, const float* weight, int C, int k,
                                 int pad, float* gin, int accumulate, void* stream) {
   float* wd = nullptr;
-  if (conv_x3_eligible(O, C, k)) {
-    FR_HIP(hipMalloc((void**)&wd, conv_x3_pack_bytes(O, C, k)));
-    float* am = nullptr;
-    int rcx = x3_f16_records(&am);
-    float* const amw = am ? am + AMAX_REC : nullptr;
-    float* const aws = am ? am + 2 * AMAX_REC : nullptr;
-    if (am && rcx == FRCNN_OK) {
-      rcx = tensor_absmax(gout, (long)O * Ho * Wo, am, S(stream));
-      if (rcx == FRCNN_OK) rcx = tensor_absmax(weight, (long)O * C * k * k, amw, S(stream));
-    }
-    if (rcx == FRCNN_OK) rcx = conv_x3_pack(weight, O, C, k, 1, wd, S(stream), Ho + 2 * (k - 1 - pad) - k + 1, Wo + 2 * (k - 1 - pad) - k + 1, amw, aws);
-    if (rcx == FRCNN_OK) rcx = conv_x3(gout, O, Ho, Wo, nullptr, nullptr, wd, nullptr, C, k, k - 1 - pad, gin, accumulate ? OUT_ADD : OUT_STORE, 0, S(stream), 0, nullptr, am, aws);
-    (void)hipStreamSynchronize(S(stream));
-    (void)hipFree(wd); (void)hipFree(am);
-    return rcx;
-  }
+  if (conv_x3_eligible(O, C, k))
+    return conv2d_split(gout, O, Ho, Wo, nullptr, nullptr, weight, nullptr, O, C, C, k, 1, k - 1 - pad, gin, accumulate ? OUT_ADD : OUT_STORE,
+                        true, nullptr, nullptr, nullptr, S(stream));
   FR_HIP(hipMalloc((void**)&wd, conv_pack_floats(O, C, k) * 4));
   int rc = conv_pack_weights(weight, O, C, k, nullptr, wd, S(stream));
   if (rc == FRCNN_OK)
@@ -306,6 +305,38 @@ int frcnn_conv2d_backward_input(const float* gout, int O, int Ho, int Wo, const 
   (void)hipStreamSynchronize(S(stream));
   (void)hipFree(wd);
   return rc;
+}
+// ---- the same two in the fp16 form only, with the records in the caller's hands (include/frcnn_hip.h "magnitude records")
+int frcnn_amax_record_floats(void) { return AMAX_REC; }
+int frcnn_tensor_absmax(const float* x, long long n, float* rec, void* stream) {
+  FR_CHECK(x && rec && n >= 1, "frcnn_tensor_absmax: bad arguments");
+  return tensor_absmax(x, (long)n, rec, S(stream));
+}
+int frcnn_conv2d_forward_rec(const float* in, int C, int H, int W, const float* in_slope, const float* in_scale, const float* weight,
+                             const float* bias, int O, int k, int pad, float* out, const float* rec_in, float* rec_out, void* stream) {
+  FR_CHECK(in && weight && out, "frcnn_conv2d_forward_rec: NULL argument");
+  FR_CHECK(conv_x3_eligible(C, O, k) && (k == 3 || (!in_slope && !in_scale)),
+           "frcnn_conv2d_forward_rec: %d channels -> %d filters, %dx%d does not take the split form", C, O, k, k);
+  FR_CHECK(get_x3_f16(), "frcnn_conv2d_forward_rec: option x3_f16 is off");
+  bool unit = true;
+  FR_TRY(scale_fits_f16_form(in_scale, C, S(stream), &unit));
+  FR_CHECK(unit, "frcnn_conv2d_forward_rec: an entry of in_scale exceeds 1: the launch would not take the fp16 form");
+  return conv2d_split(in, C, H, W, in_slope, in_scale, weight, bias, O, C, O, k, 0, pad, out, OUT_STORE, true, rec_in, rec_out, nullptr,
+                      S(stream));
+}
+int frcnn_conv2d_backward_input_rec(const float* gout, int O, int Ho, int Wo, const float* weight, int C, int k, int pad, float* gin,
+                                    int accumulate, const float* rec_g, float* rec_out, const float* post_x, const float* post_slope,
+                                    const float* post_scale, float* gslope, void* stream) {
+  FR_CHECK(gout && weight && gin, "frcnn_conv2d_backward_input_rec: NULL argument");
+  FR_CHECK(conv_x3_eligible(O, C, k), "frcnn_conv2d_backward_input_rec: %d filters -> %d channels, %dx%d does not take the split form",
+           O, C, k, k);
+  FR_CHECK(get_x3_f16(), "frcnn_conv2d_backward_input_rec: option x3_f16 is off");
+  FR_CHECK(post_x || (!post_slope && !post_scale && !gslope), "frcnn_conv2d_backward_input_rec: a fused activation backward needs post_x");
+  FR_CHECK(!post_x || (post_slope && k == 3 && !accumulate),
+           "frcnn_conv2d_backward_input_rec: the fused activation backward belongs to a storing 3x3 launch with a slope");
+  const X3PostAct post{post_x, post_slope, post_scale, gslope};
+  return conv2d_split(gout, O, Ho, Wo, nullptr, nullptr, weight, nullptr, O, C, C, k, 1, k - 1 - pad, gin, accumulate ? OUT_ADD : OUT_STORE,
+                      true, rec_g, rec_out, post_x ? &post : nullptr, S(stream));
 }
 int frcnn_conv2d_backward_weight(const float* in, int C, int H, int W, const float* in_slope,
                                  const float* in_scale, const float* gout, int O, int k, int pad,
@@ -342,6 +373,18 @@ int frcnn_maxpool_act_backward(const float* gpool, const unsigned char* idx, con
                                const float* slope, const float* scale, float* gx, float* gbias, float* gslope,
                                void* stream) {
   return maxpool_act_backward(gpool, idx, x, C, H, W, slope, scale, gx, gbias, gslope, S(stream));
+}
+int frcnn_maxpool_act_forward_rec(const float* x, int C, int H, int W, const float* slope, const float* scale, float* out,
+                                  unsigned char* idx, void* stream, float* rec) {
+  return maxpool_act_forward(x, C, H, W, slope, scale, out, idx, S(stream), rec);
+}
+int frcnn_maxpool_act_backward_rec(const float* gpool, const unsigned char* idx, const float* x, int C, int H, int W, const float* slope,
+                                   const float* scale, float* gx, float* gbias, float* gslope, void* stream, float* rec) {
+  return maxpool_act_backward(gpool, idx, x, C, H, W, slope, scale, gx, gbias, gslope, S(stream), rec);
+}
+int frcnn_act_backward_rec(const float* gy, const float* x, int C, long long hw, const float* slope, const float* scale, float* gx,
+                           float* gbias, float* gslope, void* stream, float* rec) {
+  return act_backward(gy, x, C, hw, slope, scale, gx, gbias, gslope, S(stream), rec);
 }
 int frcnn_act_forward(const float* x, int C, long long hw, const float* slope, const float* scale, float* y,
                       void* stream) {

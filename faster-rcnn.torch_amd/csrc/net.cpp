@@ -158,6 +158,15 @@ struct frcnn_model {
   DevBuf amax, amax_ws, amax_jobs;   // the records; the weight scalars; AmaxJob table of the weight tensors
   int n_amax = 0, n_amax_jobs = 0, amax_grid = 0;
   float* rec(int id) const { return (float*)amax.p + (size_t)id * AMAX_REC; }
+  // am_live[id]: record id was handed to the launch that writes it in the last pass (forward pass: outputs, pooled maps, weights;
+  // backward pass: output gradients) -- what frcnn_model_debug_buffer's record kinds may show.  rec_w: rec for a producer.
+  std::vector<unsigned char> am_live;
+  float* rec_w(int id) { am_live[id] = 1; return rec(id); }
+  // the weight records a tensor_absmax_multi launch of the forward pass writes: every owner's, or the backbone's only
+  void weights_live(bool heads_too) {
+    for (auto& c : convs) if (c.x_f || c.x_d) am_live[c.am + 2] = 1;
+    for (auto& hd : heads) if (heads_too && (hd.c3.x_f || hd.c3.x_d)) am_live[hd.c3.am + 2] = 1;
+  }
   bool f16_packed = false;     // the current packs are in the fp16 form
   long eval_packs_gen = -1;    // option static_weights: generation (g_static_gen) the evaluate-mode packs were made in, -1 = none
   const float* eval_packs_w = nullptr;
@@ -454,6 +463,7 @@ static int ensure_shapes(frcnn_model* m, int H, int W) {
       for (auto& hd : m->heads) { hd.c3.am = n; n += 3; }
       for (auto& b : m->blocks) b.am = n++;
       m->n_amax = n;
+      m->am_live.assign((size_t)n, 0);
       FR_TRY(m->amax.ensure((size_t)n * AMAX_REC * 4));
       FR_TRY(m->amax_ws.ensure((size_t)n * 4));
       std::vector<AmaxJob> aj;
@@ -1026,6 +1036,7 @@ static int pnet_forward_impl(frcnn_model* m, const float* w, const float* img, i
   const bool f16 = get_x3_f16() && m->n_amax_jobs > 0;
   const bool reuse = !training && g_static_weights && m->eval_packs_gen == g_static_gen && m->eval_packs_w == w && m->f16_packed == f16;
   m->f16_packed = f16;
+  std::fill(m->am_live.begin(), m->am_live.end(), 0);
   // ... or every owner's packs were renewed from this weight vector since the last pass (frcnn_pnet_refresh_packs: the update
   // ran beside the previous backward pass).  One-shot: the promise covers the pass that consumes it.
   const bool fresh = training && !m->groups.empty() && m->fresh_mask == (1u << m->groups.size()) - 1 && m->fresh_w == w && m->fresh_f16 == f16 &&
@@ -1046,6 +1057,7 @@ static int pnet_forward_impl(frcnn_model* m, const float* w, const float* img, i
       FR_TRY(tensor_absmax_multi(w, (const AmaxJob*)m->amax_jobs.p + m->am_bb_off, m->am_bb_n, m->am_bb_grid, s));
     else if (f16)   // the weight tensors' magnitudes first: their packs are scaled by them
       FR_TRY(tensor_absmax_multi(w, (const AmaxJob*)m->amax_jobs.p, m->n_amax_jobs, m->amax_grid, s));
+    if (f16) m->weights_live(!skip_heads);
     if (training && any_compact(m))
       FR_TRY(pack_compact(m, w, f16, s));   // the step's own table: the compact blocks' jobs gather the kept filters / channels
     else if (training)
@@ -1078,15 +1090,16 @@ static int pnet_forward_impl(frcnn_model* m, const float* w, const float* img, i
         const int cin = st == 0 ? c.Cin : blk.nkK, mo = st == 0 ? blk.nkM : c.Cout;
         FR_TRY(conv_x3(cur, cin, c.H, c.W, cur_slope, nullptr, c.wx.p, st == 0 ? blk.dc_bias.f() : w + c.b_off, mo, c.k, c.pad, c.x.f(),
                        OUT_STORE, 0, s, 0, nullptr, f16 ? cur_am : nullptr, f16 ? m->amax_ws.f() + c.am : nullptr,
-                       want_am ? m->rec(c.am) : nullptr));
+                       want_am ? m->rec_w(c.am) : nullptr));
       } else if (c.x_f)
         FR_TRY(conv_x3(cur, c.Cin, c.H, c.W, cur_slope, cur_scale, c.wx.p, w + c.b_off, c.Cout, c.k, c.pad, c.x.f(), OUT_STORE, 0, s, 0,
-                       nullptr, f16 ? cur_am : nullptr, f16 ? m->amax_ws.f() + c.am : nullptr, want_am ? m->rec(c.am) : nullptr));
+                       nullptr, f16 ? cur_am : nullptr, f16 ? m->amax_ws.f() + c.am : nullptr, want_am ? m->rec_w(c.am) : nullptr));
       else
         FR_TRY(conv_igemm(cur, c.Cin, c.H, c.W, cur_slope, cur_scale, c.wf.f(), w + c.b_off, c.Cout, c.k, c.pad,
                           c.x.f(), OUT_STORE, 0, s, 0, last ? &pl : nullptr, last ? &pooled_in_conv : nullptr));
+      if (pooled_in_conv && pl.amax) m->am_live[blk.am] = 1;   // (the launch took pl and kept the pooled map's record)
       if (want_am) {
-        if (!c.x_f) FR_TRY(tensor_absmax(c.x.f(), (long)c.Cout * c.Ho * c.Wo, m->rec(c.am), s));   // (the fp32 kernel keeps no record)
+        if (!c.x_f) FR_TRY(tensor_absmax(c.x.f(), (long)c.Cout * c.Ho * c.Wo, m->rec_w(c.am), s));   // (the fp32 kernel keeps no record)
         cur_am = m->rec(c.am);
       }
       cur = c.x.f();
@@ -1096,7 +1109,7 @@ static int pnet_forward_impl(frcnn_model* m, const float* w, const float* img, i
     const Conv& lc = m->convs[blk.first_conv + blk.nconv - 1];
     if (!pooled_in_conv)
       FR_TRY(maxpool_act_forward(cur, lc.Cout, lc.Ho, lc.Wo, cur_slope, cur_scale, blk.pooled.f(),
-                                 (unsigned char*)blk.pidx.p, s, f16 ? m->rec(blk.am) : nullptr));
+                                 (unsigned char*)blk.pidx.p, s, f16 ? m->rec_w(blk.am) : nullptr));
     // (pooled inside the fp32 kernel of the first layer: that launch kept the pooled map's record)
     cur = blk.pooled.f();
     cur_slope = nullptr;
@@ -1200,6 +1213,34 @@ int frcnn_model_debug_buffer(frcnn_model* m, int kind, int index, void** ptr, lo
       FR_CHECK(index >= 0 && index < (int)m->cls.size() && m->R > 0, "debug_buffer: classification layer %d (after frcnn_cnet_forward)", index);
       const ClsLayer& L = m->cls[index]; b = L.bn ? &L.pre : &L.lin; n = (size_t)m->R * L.n * 4;
     } break;
+    case 7: case 11: {   // a backbone convolution's output / finished output gradient as stored (compact in a compact block)
+      FR_CHECK(index >= 0 && index < (int)m->convs.size() && m->H > 0, "debug_buffer: backbone convolution %d (after a forward pass)", index);
+      const Conv& c = m->convs[index];
+      const Block& k = m->blocks[c.block];
+      b = kind == 7 ? &c.x : &c.gx; n = (size_t)((k.dc_on && c.step == 0) ? k.nkM : c.Cout) * c.Ho * c.Wo * 4;
+    } break;
+    case 9: {
+      FR_CHECK(index >= 0 && index < (int)m->blocks.size() && m->H > 0, "debug_buffer: block %d (after a forward pass)", index);
+      const Block& k = m->blocks[index]; b = &k.pooled; n = (size_t)m->d.filters[index] * k.Hp * k.Wp * 4;
+    } break;
+    case 5: case 6: case 8: case 10: {   // magnitude records: only what the last pass wrote
+      const int nc = (int)m->convs.size();
+      int id = -1;
+      FR_CHECK(m->H > 0, "debug_buffer: magnitude records exist after a forward pass");
+      if (kind == 6) {
+        FR_CHECK(index >= 0 && index < (int)m->blocks.size(), "debug_buffer: block %d out of range", index);
+        id = m->blocks[index].am;
+      } else if (kind == 10) {
+        FR_CHECK(index >= 0 && index < nc + (int)m->heads.size(), "debug_buffer: weight tensor %d out of range", index);
+        id = (index < nc ? m->convs[index].am : m->heads[index - nc].c3.am) + 2;
+      } else {
+        FR_CHECK(index >= 0 && index < nc, "debug_buffer: backbone convolution %d out of range", index);
+        id = m->convs[index].am + (kind == 8 ? 1 : 0);
+      }
+      FR_CHECK(id >= 0 && id < (int)m->am_live.size() && m->am_live[id], "debug_buffer: the last pass kept no magnitude record of kind %d, index %d", kind, index);
+      *ptr = m->rec(id); *bytes = (long long)AMAX_REC * 4;
+      return FRCNN_OK;
+    }
     default: FR_CHECK(false, "debug_buffer: unknown kind %d", kind);
   }
   FR_CHECK(b->p && b->bytes >= n, "debug_buffer: buffer not allocated yet");
@@ -1648,6 +1689,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
   FR_CHECK(m->H > 0 && m->training, "pnet_backward: needs a preceding training-mode forward "
                                     "(nn.SpatialDropout: backprop only defined while training)");
   const int nb = (int)m->blocks.size();
+  for (auto& c : m->convs) m->am_live[c.am + 1] = 0;
   bool heads_tail = false;   // anchor nets still computing their parameter gradients on their own streams: joined at the end
   if (m->heads_begun) {   // started by frcnn_pnet_backward_heads_begin: wait for the side stream
     if (!m->heads_joined) {
@@ -1758,10 +1800,10 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
       } else if (st == blk.nconv - 1) {
         FR_TRY(maxpool_act_backward(blk.gpooled.f(), (const unsigned char*)blk.pidx.p, c.x.f(), c.Cout, c.Ho, c.Wo,
                                     w + c.a_off, scale, c.gx.f(), grad + c.b_off, grad + c.a_off, s,
-                                    (c.x_d && m->f16_packed) ? m->rec(c.am + 1) : nullptr));
+                                    (c.x_d && m->f16_packed) ? m->rec_w(c.am + 1) : nullptr));
       } else {
         FR_TRY(act_backward(c.gx.f(), c.x.f(), c.Cout, (long)c.Ho * c.Wo, w + c.a_off, scale, c.gx.f(),
-                            grad + c.b_off, grad + c.a_off, s, (c.x_d && m->f16_packed) ? m->rec(c.am + 1) : nullptr));
+                            grad + c.b_off, grad + c.a_off, s, (c.x_d && m->f16_packed) ? m->rec_w(c.am + 1) : nullptr));
       }
       // accGradParameters: the input is the previous conv's x (activation fused) or a pooled map / image
       const float* in; const float* in_slope = nullptr; const float* in_scale = nullptr;
@@ -1833,7 +1875,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
         Conv& pc = m->convs[blk.first_conv + st - 1];
         X3PostAct post{pc.x.f(), w + pc.a_off, (st - 1 == 0 && blk.has_drop && !dc) ? blk.scale.f() : nullptr, grad + pc.a_off};
         FR_TRY(conv_x3(c.gx.f(), dg_k, c.Ho, c.Wo, nullptr, nullptr, c.wxd.p, nullptr, dg_m, c.k, c.k - 1 - c.pad, gin, gmode, fl, s, 0, &post, ag, aw,
-                       (pc.x_d && m->f16_packed) ? m->rec(pc.am + 1) : nullptr));
+                       (pc.x_d && m->f16_packed) ? m->rec_w(pc.am + 1) : nullptr));
         act_done = true;
       } else if (c.x_d)
         FR_TRY(conv_x3(c.gx.f(), dg_k, c.Ho, c.Wo, nullptr, nullptr, c.wxd.p, nullptr, dg_m, c.k, c.k - 1 - c.pad, gin, gmode, fl, s, 0, nullptr, ag, aw));

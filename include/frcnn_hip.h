@@ -217,6 +217,42 @@ int frcnn_act_forward(const float *x, int C, long long hw, const float *slope, c
 int frcnn_act_backward(const float *gy, const float *x, int C, long long hw, const float *slope,
                        const float *scale, float *gx, float *gbias, float *gslope, void *stream);
 
+/* ---- magnitude records of the two-plane fp16 form (option "x3_f16") ----------------------------
+ * The split convolutions scale each operand by a power of two taken from the tensor's largest magnitude.  That number
+ * travels as a RECORD: device memory of frcnn_amax_record_floats() floats, rec[0] = the bit pattern of an int n
+ * (1 <= n <= 16384), rec[1..n] = one max|x| per block of the launch that wrote the tensor; the tensor's largest magnitude
+ * is the maximum of the n entries.  A launch that keeps a record rewrites the count and all its n entries; nothing else.
+ * The entry points above take the records they need in passes of their own; the *_rec forms below let a host that drives
+ * single layers chain them instead (the producer of a tensor keeps the record its consumer reads), and let tests read what
+ * each producer keeps. */
+int frcnn_amax_record_floats(void);
+/* rec = the record of x[0..n) (n >= 1; x at any 4-byte boundary), in a pass of its own. */
+int frcnn_tensor_absmax(const float *x, long long n, float *rec, void *stream);
+/* The entry points of the same names that also keep the record of what they store (out / gx) in rec (NULL: none). */
+int frcnn_maxpool_act_forward_rec(const float *x, int C, int H, int W, const float *slope,
+                                  const float *scale, float *out, unsigned char *idx, void *stream, float *rec);
+int frcnn_maxpool_act_backward_rec(const float *gpool, const unsigned char *idx, const float *x, int C,
+                                   int H, int W, const float *slope, const float *scale, float *gx,
+                                   float *gbias, float *gslope, void *stream, float *rec);
+int frcnn_act_backward_rec(const float *gy, const float *x, int C, long long hw, const float *slope,
+                           const float *scale, float *gx, float *gbias, float *gslope, void *stream, float *rec);
+/* frcnn_conv2d_forward in the two-plane fp16 form.  rec_in: the record of `in` kept by its producer (NULL: taken here in a
+ * pass over `in`); rec_out: receives the record of `out` (NULL: none).  An error, and nothing is launched, when the shape
+ * does not take the split form, when option "x3_f16" is off, or when an entry of in_scale exceeds 1 in magnitude. */
+int frcnn_conv2d_forward_rec(const float *in, int C, int H, int W, const float *in_slope,
+                             const float *in_scale, const float *weight, const float *bias, int O,
+                             int k, int pad, float *out, const float *rec_in, float *rec_out, void *stream);
+/* frcnn_conv2d_backward_input in the two-plane fp16 form.  rec_g: the record of gout (NULL: taken here); rec_out: receives
+ * the record of what is stored in gin (with accumulate: of the sums).  post_x != NULL (k = 3, accumulate = 0): gin passes
+ * through the backward of the nn.PReLU + nn.SpatialDropout in front of this convolution inside the launch --
+ * gin = prelu'(post_x) * post_scale[c] * (W^T (*) gout), *gslope += sum over post_x <= 0 of post_x * post_scale[c] * (...) --
+ * with post_x float [C][H][W] the pre-activation values, post_slope a device scalar, post_scale float [C] or NULL, gslope a
+ * device scalar or NULL.  Same refusals as frcnn_conv2d_forward_rec. */
+int frcnn_conv2d_backward_input_rec(const float *gout, int O, int Ho, int Wo, const float *weight,
+                                    int C, int k, int pad, float *gin, int accumulate, const float *rec_g,
+                                    float *rec_out, const float *post_x, const float *post_slope,
+                                    const float *post_scale, float *gslope, void *stream);
+
 /* ---- extract_roi_pooling_input + nn.SpatialAdaptiveMaxPooling, batched over ROIs
  *      (objective.lua:5-13,117-118,137-138,182-185; Detector.lua:96-97) ----------------- */
 /* wins: int[R][4] = {row_lo,row_hi,col_lo,col_hi}, 1-based inclusive (objective.lua:11).
@@ -493,7 +529,20 @@ int frcnn_pnet_output(frcnn_model *, int i, float **ptr_host, int *C_host, int *
  *   kind 1: arg-max of block `index`'s 2x2 ceil-mode max pool (unsigned char [C][Hp][Wp], value dy*2+dx; :23)
  *   kind 2: pre-activation output of anchor net `index`'s k x k convolution (float [n][Ho][Wo]; :31)
  *   kind 3: input of classification layer `index`'s PReLU (float [R][n]; :85-86), after frcnn_cnet_forward
- *   kind 4: the nn.SpatialDropout scale vector of block `index` in the last pass (float [C]; a 0/1 keep vector while training) */
+ *   kind 4: the nn.SpatialDropout scale vector of block `index` in the last pass (float [C]; a 0/1 keep vector while training)
+ * Magnitude records (see frcnn_amax_record_floats; option "x3_f16") and the tensors they describe.  A record kind is an
+ * error unless the LAST pass handed that record to the launch that writes it (a forward pass for kinds 5, 6 and 10, a
+ * backward pass for kind 8): a layer whose consumer does not take the fp16 form, a frozen block, a pass that re-used
+ * packs made earlier (weights) or option "x3_f16" off keep none.
+ *   kind 5: record of backbone convolution `index`'s stored output -- the tensor of kind 0, except that a compact block
+ *           (option "drop_compact") stores its first convolution's output compact: float [nkM][Ho][Wo], row i < nk = the i-th
+ *           kept channel, rows nk..nkM-1 (padding to a multiple of 64) = 0; kind 7 returns that tensor as stored
+ *   kind 6: record of block `index`'s pooled map; kind 9: that map (float [C][Hp][Wp])
+ *   kind 7: backbone convolution `index`'s output as stored (kind 0 without the dense layout of a compact block)
+ *   kind 8: after frcnn_pnet_backward, record of the finished gradient of convolution `index`'s output (through the
+ *           pooling / activation backward); kind 11: that tensor (float [O][Ho][Wo]; compact as kind 7 in a compact block)
+ *   kind 10: record of the weight tensor of backbone convolution `index` (index < number of backbone convolutions) or of
+ *            anchor net index - that number's k x k convolution */
 int frcnn_model_debug_buffer(frcnn_model *, int kind, int index, void **ptr_host, long long *bytes_host);
 /* delta_outputs[i] (objective.lua:78-84): gradient buffers with the shapes of the outputs. */
 int frcnn_pnet_delta(frcnn_model *, int i, float **ptr_host);
