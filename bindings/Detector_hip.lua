@@ -12,6 +12,8 @@
 --
 -- Not in the reference, off by default: cfg.proposals = { order = 'y2' | 'score', pre_nms_top_n = K, post_nms_top_n = M }
 -- (main.lua calls Detector(model) unchanged, so the settings ride on the model's cfg; Detector.proposal_settings).
+-- Likewise cfg.nms = { method = 'hard' | 'linear' | 'gaussian', overlap, sigma, min_score } (Detector.nms_settings): Soft-NMS in
+-- the per-class pass.  Under 'linear' or 'gaussian' a winner's confidence is its DECAYED log-score, the one it was ranked by.
 --
 --   main.lua:  require 'Detector'  ->  require 'Detector_hip'
 local ffi = require 'ffi'
@@ -36,6 +38,41 @@ function Detector:__init(model)                                         -- Detec
   self.ah = hip.to_device(self.anchors.h)
   self.scratch = hip.scratch()
   self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n = Detector.proposal_settings(self.model.cfg.proposals)
+  self.nms_method, self.nms_overlap, self.nms_sigma, self.nms_min_score = Detector.nms_settings(self.model.cfg.nms)
+end
+
+-- cfg.nms -> method, overlap, sigma, min_score (validated on the host, before any device call).  The setting governs the
+-- per-class pass only (Detector.lua:125-136); the first NMS is untouched.
+--   method     'hard' (default: the reference -- a box that overlaps a better one of its class by more than `overlap` is deleted),
+--              'linear' (its confidence is multiplied by 1 - IoU instead) or 'gaussian' (every box of the class has its
+--              confidence multiplied by exp(-IoU^2 / sigma)); a box is dropped when its confidence falls below min_score
+--   overlap    Nt, in (0, 1]; default 0.1, the reference's threshold
+--   sigma      > 0; default 0.5
+--   min_score  in [0, 1), a probability; default 0.001; 0 keeps every class-test survivor
+function Detector.nms_settings(t)
+  if t == nil then t = {} end
+  if type(t) ~= 'table' then error('cfg.nms must be a table of {method, overlap, sigma, min_score}') end
+  for k, _ in pairs(t) do
+    if k ~= 'method' and k ~= 'overlap' and k ~= 'sigma' and k ~= 'min_score' then
+      error('cfg.nms: unknown key ' .. tostring(k))
+    end
+  end
+  local method = t.method
+  if method == nil then method = 'hard' end
+  if method ~= 'hard' and method ~= 'linear' and method ~= 'gaussian' then
+    error('cfg.nms.method must be "hard", "linear" or "gaussian"')
+  end
+  local function number(name, default)
+    local v = t[name]
+    if v == nil then return default end
+    if type(v) ~= 'number' then error('cfg.nms.' .. name .. ' is not a number') end
+    return v
+  end
+  local overlap, sigma, min_score = number('overlap', 0.1), number('sigma', 0.5), number('min_score', 0.001)
+  if not (overlap > 0 and overlap <= 1) then error('cfg.nms.overlap must be in (0, 1]') end
+  if not (sigma > 0 and sigma < math.huge) then error('cfg.nms.sigma must be > 0') end
+  if not (min_score >= 0 and min_score < 1) then error('cfg.nms.min_score must be in [0, 1)') end
+  return method, overlap, sigma, min_score
 end
 
 -- cfg.proposals -> order, pre_nms_top_n, post_nms_top_n (validated on the host, before any device call).
@@ -371,13 +408,31 @@ function Detector:detect_chunk(frames, shared, prefix)
   --         -- the score tensor is ignored by nms.lua:42, the key is max-y (order = 'score': column 5, the confidence).  The
   --         survivor counts are read from device memory.  ONE gather of every frame's winner records (16 doubles each) behind
   --         a 128-byte header of the frame's four counts
-  local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, Rmax))
-  local cws = scratch(prefix .. 'nms_ws2', cwsb)
+  --         Under a soft method (cfg.nms): ONE frcnn_soft_nms_batch launch instead, on the log-confidences (log_domain 1,
+  --         min_score as a log), which writes every winner's decayed score into column 5 of a COPY of bb; the gather reads that
+  --         copy, so a winner's confidence is the score it was picked at
   local cpick = ffi.cast('long long*', scratch(prefix .. 'wpick', 8 * B * Rmax).ptr)
-  check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 0.1, key_mode, key_col, dkc, cpick, cnt + 3 * B, cws.ptr, cwsb,
-                                 nil))
+  local dbb_win = dbb
+  if self.nms_method ~= 'hard' then
+    if Rmax > 16384 then error('Detector: more candidates in a frame than the 16384 a soft per-class NMS takes') end
+    dbb_win = ffi.cast('float*', scratch(prefix .. 'bb_soft', 20 * B * Rmax).ptr)
+    check(C.frcnn_memcpy_d2d(dbb_win, dbb, 20 * B * Rmax, nil))
+    local swsb = tonumber(C.frcnn_soft_nms_workspace_bytes(B, Rmax))
+    local sws = scratch(prefix .. 'soft_nms_ws', swsb)
+    local log_min = -math.huge
+    if self.nms_min_score > 0 then log_min = math.log(self.nms_min_score) end
+    local method = 2
+    if self.nms_method == 'linear' then method = 1 end
+    check(C.frcnn_soft_nms_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 5, method, self.nms_overlap, self.nms_sigma, log_min, 1, dkc,
+                                 cpick, cnt + 3 * B, dbb_win + 4, 5, sws.ptr, swsb, nil))
+  else
+    local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, Rmax))
+    local cws = scratch(prefix .. 'nms_ws2', cwsb)
+    check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, self.nms_overlap, key_mode, key_col, dkc, cpick, cnt + 3 * B,
+                                   cws.ptr, cwsb, nil))
+  end
   local out = ffi.cast('double*', scratch(prefix .. 'winners', 128 * B * (Rmax + 1)).ptr)
-  check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb, dr2, dpick, cap, mp, mr, mi, out, nil))
+  check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb_win, dr2, dpick, cap, mp, mr, mi, out, nil))
   local h = ffi.new('double[?]', 16 * B * (Rmax + 1))
   check(C.frcnn_memcpy_d2h(h, out, 128 * B * (Rmax + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table
   check(C.frcnn_stream_sync(nil))

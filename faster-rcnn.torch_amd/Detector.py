@@ -19,7 +19,13 @@ Not in the reference, off by default (cfg["proposals"] / Detector(..., proposals
 layer's two caps and score-ordered NMS.  pre_nms_top_n = K keeps the K best-scoring matches in front of the first NMS
 (frcnn_topk_select + frcnn_rpn_gather_rows: the selected rows keep their scan order, everything downstream runs unchanged on
 compact arrays, the first NMS is sized by min(anchors, K)); order = "score" keys both NMS passes by the score instead of max-y;
-post_nms_top_n = M keeps the first min(R, M) picks of the first NMS."""
+post_nms_top_n = M keeps the first min(R, M) picks of the first NMS.
+
+Not in the reference either, off by default (cfg["nms"] / Detector(..., nms=...), see nms_settings): Soft-NMS in the per-class
+pass (step 5 of _detect_chunk; the first NMS is untouched).  Under method "linear" or "gaussian" the neighbours of a winner keep
+living with a lowered confidence instead of being deleted (frcnn_soft_nms_batch in place of frcnn_nms_device_batch, on the
+log-probabilities the class test produced: log_domain 1).  A winner's `confidence` is then its DECAYED log-score, the one it
+was ranked by; the undecayed one remains last_cnet["cls"][candidate - 1, class - 1]."""
 import ctypes as C
 import math
 
@@ -80,6 +86,51 @@ def proposal_settings(cfg_or_table):
     return order, caps[0], caps[1]
 
 
+NMS_DEFAULTS = dict(method="hard", overlap=0.1, sigma=0.5, min_score=0.001)
+NMS_METHODS = ("hard", "linear", "gaussian")   # method 0, 1, 2 of frcnn_soft_nms_batch
+
+
+def nms_settings(cfg_or_table):
+    """cfg["nms"] -- or the table itself, or None -- -> (method, overlap, sigma, min_score, overlap_given), validated on the host.
+    The setting governs the per-class pass only (Detector.lua:125-136); the first NMS is untouched.
+      method     "hard" (default: the reference -- a box that overlaps a better one of its class by more than `overlap` is
+                 deleted), "linear" (its confidence is multiplied by 1 - IoU instead) or "gaussian" (every box of the class has
+                 its confidence multiplied by exp(-IoU^2 / sigma)); a box is dropped when its confidence falls below min_score
+      overlap    Nt, in (0, 1]; default 0.1 (the reference's threshold).  "hard" without it: the parent's launches and results
+                 exactly; "hard" with it: the same kernels with that threshold
+      sigma      > 0; default 0.5
+      min_score  in [0, 1), a probability; default 0.001.  0 keeps every class-test survivor
+    Raises ValueError (before any device call) for an unknown key, an unknown method, a bool or a non-number, and a value
+    outside its range."""
+    t = cfg_or_table
+    if isinstance(t, dict) and ("nms" in t or "class_count" in t):     # a model's cfg
+        t = t.get("nms")
+    if t is None:
+        t = {}
+    if not isinstance(t, dict):
+        raise ValueError("cfg.nms must be a table of {method, overlap, sigma, min_score}")
+    unknown = sorted(set(t) - set(NMS_DEFAULTS), key=str)
+    if unknown:
+        raise ValueError("cfg.nms: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    method = t.get("method", NMS_DEFAULTS["method"])
+    if not isinstance(method, str) or method not in NMS_METHODS:
+        raise ValueError("cfg.nms.method = %r (\"hard\", \"linear\" or \"gaussian\")" % (method,))
+    vals = []
+    for k in ("overlap", "sigma", "min_score"):
+        v = t.get(k, NMS_DEFAULTS[k])
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError("cfg.nms.%s = %r is not a number" % (k, v))
+        vals.append(float(v))
+    overlap, sigma, min_score = vals
+    if not (0.0 < overlap <= 1.0):
+        raise ValueError("cfg.nms.overlap = %r (in (0, 1])" % (overlap,))
+    if not (sigma > 0.0) or math.isinf(sigma):
+        raise ValueError("cfg.nms.sigma = %r (> 0)" % (sigma,))
+    if not (0.0 <= min_score < 1.0):
+        raise ValueError("cfg.nms.min_score = %r (in [0, 1))" % (min_score,))
+    return method, overlap, sigma, min_score, "overlap" in t
+
+
 class _Detections(object):
     """The list Detector:detect returns (Detector.lua:138-140): one table {p, a, r, l, r2, class, confidence} per winner,
     classes ascending (pairs() order is unspecified in Lua), pick order within a class.  Backed by the winner records the
@@ -128,7 +179,8 @@ class _BatchRecord(object):
     the classification net's input rows, kept only by a shared_cnet pass and only for the last chunk of a call (else None).
     The arrays stay on the device and are fetched when they are looked at, like last_scan / last_pick / last_cnet of detect().
     Under pre_nms_top_n the scan rows are the SELECTED rows (n of them) and two more keys exist: row (their 1-based original
-    scan rows) and matches (the frame's match count before the cap)."""
+    scan rows) and matches (the frame's match count before the cap).  Under a soft per-class NMS (cfg["nms"]) two more: bb (K x 5:
+    the class test's survivors {x1 y1 x2 y2 log-confidence} as the pass read them) and kc (K: their classes)."""
     _KEYS = ("n", "idx", "box", "rect", "p", "pick", "cnet", "kept", "pooled")
 
     def __init__(self, n, R, kept, dev, matches=None):
@@ -187,15 +239,33 @@ class _BatchRecord(object):
         return v[k]
 
 
-class Detector(object):
+class _DetectorType(type):
+    """Detector(model, ..., nms=table): the per-class NMS setting is a keyword of the class call, not of __init__, whose
+    parameter list (model, static_weights, proposals) stays what it was.  The table is validated before anything is built --
+    before any device call -- and set on the finished object; without it __init__ has read model["cfg"]["nms"]."""
+
+    def __call__(cls, *args, nms=None, **kw):
+        if nms is not None:
+            nms_settings(nms)
+        d = super().__call__(*args, **kw)
+        if nms is not None:
+            d.set_nms(nms)
+        return d
+
+
+class Detector(object, metaclass=_DetectorType):
     proposal_settings = staticmethod(proposal_settings)
+    nms_settings = staticmethod(nms_settings)
 
     def __init__(self, model, static_weights=False, proposals=None):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
         the convolution weights once instead of once per frame (option static_weights of the C ABI; a training-mode pass or
         another Detector(..., static_weights=...) drops the packs).
-        proposals: a table as proposal_settings takes it; None: model["cfg"]["proposals"] (absent: the reference's behaviour)."""
+        proposals: a table as proposal_settings takes it; None: model["cfg"]["proposals"] (absent: the reference's behaviour).
+        The per-class NMS is model["cfg"]["nms"] (absent: the reference's hard cut at 0.1) unless the call names one:
+        Detector(model, nms=table), a table as nms_settings takes it (see _DetectorType)."""
         self.set_proposals(proposals if proposals is not None else model["cfg"])
+        self.set_nms(model["cfg"])
         self.model = model
         if static_weights or os.environ.get("FRCNN_STATIC_WEIGHTS"):
             _lib.call("frcnn_set_option", b"static_weights", 1)
@@ -219,6 +289,10 @@ class Detector(object):
     def set_proposals(self, cfg_or_table):
         """Validates a table as proposal_settings takes it and makes it this Detector's setting from the next frame on."""
         self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n = proposal_settings(cfg_or_table)
+
+    def set_nms(self, cfg_or_table):
+        """Validates a table as nms_settings takes it and makes it this Detector's per-class NMS from the next frame on."""
+        self.nms_method, self.nms_overlap, self.nms_sigma, self.nms_min_score, _ = nms_settings(cfg_or_table)
 
     def __del__(self):
         if getattr(self, "_host", None):
@@ -563,13 +637,30 @@ class Detector(object):
         #         partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
         #         column under order = "score"), the survivor counts read from device memory; ONE gather of every frame's winner
         #         records behind a 128-byte header of the frame's four counts
-        wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
-        ws2 = self._buf(pre + "nms_ws2", (wsb2,), np.uint8)
+        #         Under a soft method (cfg["nms"]): ONE frcnn_soft_nms_batch launch instead, on the log-confidences (log_domain 1,
+        #         min_score as a log), which writes every winner's decayed score into column 5 of a COPY of bb; the gather reads
+        #         that copy, so a winner's confidence is the score it was picked at
         wpick = self._buf(pre + "wpick", (B, Rmax), np.int64)
-        _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(0.1), key_mode, key_col, ptr(kc), ptr(wpick),
-                  c_W, ptr(ws2), wsb2, s)
+        soft = self.nms_method != "hard"
+        bb_win = bb
+        if soft:
+            if Rmax > 16384:
+                raise _lib.FrcnnError("Detector: %d candidates in a frame, more than the 16384 a soft per-class NMS takes" % Rmax)
+            bb_win = self._buf(pre + "bb_soft", (B, Rmax, 5))
+            _lib.call("frcnn_memcpy_d2d", ptr(bb_win), ptr(bb), 20 * B * Rmax, s)
+            wsb2 = L.frcnn_soft_nms_workspace_bytes(B, Rmax)
+            ws2 = self._buf(pre + "soft_nms_ws", (wsb2,), np.uint8)
+            log_min = float(math.log(self.nms_min_score)) if self.nms_min_score > 0.0 else -math.inf
+            _lib.call("frcnn_soft_nms_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, 5, NMS_METHODS.index(self.nms_method),
+                      C.c_float(self.nms_overlap), C.c_float(self.nms_sigma), C.c_float(log_min), 1, ptr(kc), ptr(wpick), c_W,
+                      C.c_void_p(bb_win.ptr + 16), 5, ptr(ws2), wsb2, s)
+        else:
+            wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
+            ws2 = self._buf(pre + "nms_ws2", (wsb2,), np.uint8)
+            _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(self.nms_overlap), key_mode, key_col, ptr(kc),
+                      ptr(wpick), c_W, ptr(ws2), wsb2, s)
         out = self._buf(pre + "winners", (B, Rmax + 1, 16), np.float64)
-        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb), ptr(r2), ptr(pick),
+        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2), ptr(pick),
                   cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
         records = self._records(st, more)
         raw = self._read(out.ptr, B * (Rmax + 1) * 128, np.float64).reshape(B, Rmax + 1, 16)   # ---- read-back 2 of 2
@@ -577,6 +668,11 @@ class Detector(object):
         for b in range(B):
             hdr = raw[b, 0].view(i32)
             records[b]._v.update(kept=int(hdr[2]))
+            if soft:    # the class test's survivors as the pass read them (views of the chunk's buffers until detach())
+                K = int(hdr[2])
+                records[b]._dev.update(bb=DeviceTensor(bb.ptr + 20 * b * Rmax, (K, 5), np.float32, owner=bb),
+                                       kc=DeviceTensor(kc.ptr + 4 * b * Rmax, (K,), np.int32, owner=kc))
+                records[b]._KEYS = records[b]._KEYS + ("bb", "kc")
             if ns[b] == 0:
                 results.append([])
                 continue

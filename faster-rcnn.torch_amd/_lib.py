@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("FRCNN_LIB_PATH") or os.path.join(_HERE, "libfrcnn_hip.so")   # (FRCNN_LIB_PATH: A/B builds of the library)
 
 KC_NAMES = ["conv_igemm_k3", "conv_igemm_other", "conv_wgrad_k3", "conv_wgrad_other", "gemm", "elemwise",
-            "roi", "rpn", "nms", "optim", "image", "conv_x3", "conv_wgradx", "topk"]
+            "roi", "rpn", "nms", "optim", "image", "conv_x3", "conv_wgradx", "soft_nms", "topk"]
 
 
 class FrcnnError(RuntimeError):
@@ -60,6 +60,9 @@ _SIGS = {
     "frcnn_nms_batch_workspace_bytes": ([C.c_int, C.c_int], C.c_size_t),
     "frcnn_nms_device_batch": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t,
                                vp], C.c_int),
+    "frcnn_soft_nms_workspace_bytes": ([C.c_int, C.c_int], C.c_size_t),
+    "frcnn_soft_nms_batch": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
+                             vp, vp, vp, vp, C.c_longlong, vp, C.c_size_t, vp], C.c_int),
     "frcnn_topk_select_workspace_bytes": ([C.c_int, C.c_int], C.c_size_t),
     "frcnn_topk_select": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, C.c_longlong, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_rpn_gather_rows": ([vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_longlong, vp, C.c_int, vp, vp, vp, vp, vp, vp,

@@ -52,7 +52,8 @@ void prof_after(int klass, double flops, double bytes, hipStream_t s) {
 using namespace frcnn;
 
 static_assert(frcnn::KC_COUNT == FRCNN_KC_COUNT && frcnn::KC_IMAGE == FRCNN_KC_IMAGE && frcnn::KC_OPTIM == FRCNN_KC_OPTIM &&
-              frcnn::KC_CONV_IGEMM_K3 == FRCNN_KC_CONV_IGEMM_K3 && frcnn::KC_TOPK == FRCNN_KC_TOPK, "kernel classes of common.h and frcnn_hip.h differ");
+              frcnn::KC_CONV_IGEMM_K3 == FRCNN_KC_CONV_IGEMM_K3 && frcnn::KC_TOPK == FRCNN_KC_TOPK &&
+              frcnn::KC_SOFT_NMS == FRCNN_KC_SOFT_NMS, "kernel classes of common.h and frcnn_hip.h differ");
 
 extern "C" {
 
@@ -168,6 +169,13 @@ int frcnn_nms_device_batch(const float* boxes, int B, long long row_stride, int 
   FR_CHECK(B <= 0 || (boxes && pick && count), "frcnn_nms_device_batch: NULL argument");
   return nms_device_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, overlap, key_mode, key_col, cls, pick, count, ws,
                           ws_bytes, S(stream));
+}
+size_t frcnn_soft_nms_workspace_bytes(int B, int n_cap) { return soft_nms_workspace_bytes(B, n_cap); }
+int frcnn_soft_nms_batch(const float* boxes, int B, long long row_stride, int n_cap, const int* n_dev, int ncols, int score_col,
+                         int method, float overlap, float sigma, float min_score, int log_domain, const int* cls, long long* pick,
+                         int* count, float* score_out, long long score_stride, void* ws, size_t ws_bytes, void* stream) {
+  return soft_nms_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, score_col, method, overlap, sigma, min_score, log_domain,
+                        cls, pick, count, score_out, (long)score_stride, ws, ws_bytes, S(stream));
 }
 size_t frcnn_topk_select_workspace_bytes(int B, int n_cap) { return topk_select_workspace_bytes(B, n_cap); }
 int frcnn_topk_select(const float* score, int B, long long stride, int n_cap, const int* n_dev, int K, int* sel_row,

@@ -61,6 +61,7 @@ enum KClass {
   KC_IMAGE,               // BatchIterator:processImage kernels (image.hip)
   KC_CONV_X3,             // conv_x3_kernel: 3x3 fwd + dgrad in the split-bf16 operand form (convx.hip) -- the dominant kernel
   KC_CONV_WGRADX,         // conv_wgradx_kernel (+ its slab fold): 3x3 weight gradient in the same form (wgradx.hip)
+  KC_SOFT_NMS,            // Soft-NMS of the per-class pass: the greedy loop of soft_nms.hip (one launch per chunk)
   KC_TOPK,                // proposal selection in front of the first NMS: topk_select + rpn_gather_rows (topk.hip)
   KC_COUNT
 };

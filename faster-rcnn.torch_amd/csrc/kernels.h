@@ -283,6 +283,11 @@ int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode
 size_t nms_batch_workspace_bytes(int B, int n);
 int nms_device_batch(const float* boxes, int B, long row_stride, int n, const int* n_dev, int ncols, float overlap, int key_mode,
                      int key_col, const int* cls, long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+// ---- Soft-NMS for the per-class pass (soft_nms.hip): B segments, one workgroup each; semantics in include/frcnn_hip.h
+size_t soft_nms_workspace_bytes(int B, int n_cap);
+int soft_nms_batch(const float* boxes, int B, long row_stride, int n_cap, const int* n_dev, int ncols, int score_col, int method,
+                   float overlap, float sigma, float min_score, int log_domain, const int* cls, long long* pick, int* count,
+                   float* score_out, long score_stride, void* ws, size_t ws_bytes, hipStream_t s);
 // ---- proposal selection in front of the first NMS (topk.hip): the K best-scoring rows of a segment, in scan order
 size_t topk_select_workspace_bytes(int B, int n_cap);
 int topk_select(const float* score, int B, long stride, int n_cap, const int* n_dev, int K, int* sel_row, long sel_stride,

@@ -112,8 +112,9 @@ int frcnn_add(float *y, const float *x, long long n, void *stream);   /* y:add(x
 #define FRCNN_KC_IMAGE 10
 #define FRCNN_KC_CONV_X3 11      /* 3x3 forward + input gradient, split-bf16 operand form */
 #define FRCNN_KC_CONV_WGRADX 12  /* 3x3 weight gradient, split-bf16 operand form */
-#define FRCNN_KC_TOPK 13         /* proposal selection in front of the first NMS (frcnn_topk_select, frcnn_rpn_gather_rows) */
-#define FRCNN_KC_COUNT 14
+#define FRCNN_KC_SOFT_NMS 13     /* Soft-NMS of the per-class pass (frcnn_soft_nms_batch); numbered in front of TOPK, which stays last */
+#define FRCNN_KC_TOPK 14         /* proposal selection in front of the first NMS (frcnn_topk_select, frcnn_rpn_gather_rows) */
+#define FRCNN_KC_COUNT 15
 /* class_mask: bit k set -> every launch of kernel class k is bracketed by two hipEvents on its
  * launch stream (0 = profiling off). */
 int frcnn_prof_enable(int class_mask);
@@ -154,6 +155,42 @@ size_t frcnn_nms_batch_workspace_bytes(int B, int n_cap);
 int frcnn_nms_device_batch(const float *boxes, int B, long long row_stride, int n_cap, const int *n_dev, int ncols, float overlap,
                            int key_mode, int key_col, const int *cls, long long *pick, int *count, void *workspace,
                            size_t workspace_bytes, void *stream);
+/* ---- Soft-NMS (Bodla et al. 2017; not in the reference; csrc/soft_nms.hip) ----------------------------------------------
+ * The per-class pass of Detector.lua:125-136 deletes every box that overlaps a better one of its class by more than 0.1;
+ * Soft-NMS lowers the neighbours' scores instead (cfg.nms = { method = "hard" | "linear" | "gaussian", overlap, sigma,
+ * min_score }; default: the reference).  One SEGMENT is one frame's rows: n rows of ncols fp32 columns, columns 1-4 =
+ * x1 y1 x2 y2, column score_col (1-based, 5 .. ncols) the score, cls[i] an optional integer class.
+ *   method 0 hard, 1 linear, 2 gaussian; overlap = Nt; sigma > 0; min_score; log_domain 0: scores are plain non-negative
+ *   numbers, 1: scores are log-probabilities (what frcnn_detect_post puts in bb[:,4]) and decays are ADDED, and min_score
+ *   is a log too.
+ *   s[i] = score column; row i is alive iff s[i] >= min_score (a NaN is never alive)
+ *   repeat: m = the alive, unpicked row of largest s (compared as fp32 values); ties: the HIGHER row id (the tie rule of
+ *           frcnn_nms_device: ascending key, ties ascending row, picks from the end); none left -> stop
+ *           pick m; score_out[m] = s[m]; for every alive unpicked j with cls[j] == cls[m] (all j when cls is NULL):
+ *             hard:     if !(iou <= Nt): j dies
+ *             linear:   if !(iou <= Nt): s[j] = s[j] * (1 - iou)               (log_domain: s[j] + log1pf(-iou))
+ *             gaussian: (every j)        s[j] = s[j] * expf(-(iou*iou)/sigma)  (log_domain: s[j] - (iou*iou)/sigma)
+ *             then: if !(s[j] >= min_score): j dies
+ * All arithmetic is fp32, every operation rounded on its own; area and IoU are those of frcnn_nms_device:
+ * area = (x2-x1+1)*(y2-y1+1), w = max(0, (xx2 + (-1)*xx1) + 1), iou = (w*h) / ((area_j + area_m) - w*h).  hard (either
+ * domain), linear with log_domain 0 and gaussian with log_domain 1 contain no transcendental and are EXACT (a function of the
+ * inputs' bits); linear with log_domain 1 (log1pf) and gaussian with log_domain 0 (expf) are within the math library's error.
+ * No atomics: the result depends on the data alone.
+ * Outputs: pick[0 .. count) = 1-based rows within the segment in pick order -- the scores at pick never increase along it, so
+ * it is the rows sorted by final score descending, ties by the higher row, and a stable partition by class gives the
+ * per-class lists (as frcnn_nms_device_classes); score_out[row * score_stride] (optional) = the score at pick, written for
+ * picked rows only.  Nothing is stored outside [0, count) of pick, for unpicked rows, or -- beyond count[b] = 0 -- for an
+ * empty segment.
+ * Segments as in frcnn_nms_device_batch: segment b = boxes + b*row_stride*ncols, count min(n_dev[b], n_cap) read on the
+ * device, row_stride >= n_cap; cls, pick and score_out are offset by b*row_stride rows; one workgroup per segment, whose
+ * result does not depend on its slot or its neighbours.  n_cap <= 16 384.  Errors (before any launch): B < 1, n_cap out of
+ * range, row_stride < n_cap, ncols < 5, score_col outside [5, ncols], bad method, sigma <= 0, NULL boxes / n_dev / pick /
+ * count, short workspace (frcnn_soft_nms_workspace_bytes(B, n_cap)). */
+size_t frcnn_soft_nms_workspace_bytes(int B, int n_cap);
+int frcnn_soft_nms_batch(const float *boxes, int B, long long row_stride, int n_cap, const int *n_dev, int ncols, int score_col,
+                         int method, float overlap, float sigma, float min_score, int log_domain, const int *cls,
+                         long long *pick, int *count, float *score_out, long long score_stride, void *workspace,
+                         size_t workspace_bytes, void *stream);
 /* ---- Detector:detect glue kept on the device (Detector.lua:88-136; csrc/detect.hip) ------------------------------
  * frcnn_roi_windows: extract_roi_pooling_input (objective.lua:5-13) for k ROIs at once -- Localizer:inputToFeatureRect
  * (Localizer.lua:41-67, the reference's double arithmetic incl. its dH/dW mix-ups) over layers_host[nlayers][6] =
