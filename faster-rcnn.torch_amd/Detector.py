@@ -37,13 +37,29 @@ from . import _lib
 from .Anchors import Anchors
 from .Localizer import Localizer
 from .Rect import Rect
-from .nms import nms
+from .nms import SOFT_NMS_METHODS, nms
 from .objective import align_geometry, roi_pooling_settings, roi_window, roi_windows
 from .tensor import DeviceTensor, ptr, stream_ptr, to_device
 
 ASPECTS = 3   # anchors per map position (Anchors.lua:108-109)
 
 PROPOSAL_DEFAULTS = dict(order="y2", pre_nms_top_n=None, post_nms_top_n=None)
+
+
+def _settings_table(cfg_or_table, name, defaults):
+    """The table cfg[name] of a model's cfg -- or the table itself, or None (-> {}) -- refused (ValueError) unless it is a table
+    with keys of `defaults` only: the prologue of proposal_settings and nms_settings."""
+    t = cfg_or_table
+    if isinstance(t, dict) and (name in t or "class_count" in t):     # a model's cfg
+        t = t.get(name)
+    if t is None:
+        t = {}
+    if not isinstance(t, dict):
+        raise ValueError("cfg.%s must be a table of {%s}" % (name, ", ".join(defaults)))
+    unknown = sorted(set(t) - set(defaults), key=str)
+    if unknown:
+        raise ValueError("cfg.%s: unknown key(s) %s" % (name, ", ".join(map(str, unknown))))
+    return t
 
 
 def proposal_settings(cfg_or_table):
@@ -58,16 +74,7 @@ def proposal_settings(cfg_or_table):
                       first M picks in max-y order are not the best M.
     Raises ValueError (before any device call) for an unknown key, an unknown order, a bool or non-integer or < 1 cap, and
     post_nms_top_n without order = "score"."""
-    t = cfg_or_table
-    if isinstance(t, dict) and ("proposals" in t or "class_count" in t):     # a model's cfg
-        t = t.get("proposals")
-    if t is None:
-        t = {}
-    if not isinstance(t, dict):
-        raise ValueError("cfg.proposals must be a table of {order, pre_nms_top_n, post_nms_top_n}")
-    unknown = sorted(set(t) - set(PROPOSAL_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError("cfg.proposals: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    t = _settings_table(cfg_or_table, "proposals", PROPOSAL_DEFAULTS)
     order = t.get("order", "y2")
     if not isinstance(order, str) or order not in ("y2", "score"):
         raise ValueError("cfg.proposals.order = %r (\"y2\" or \"score\")" % (order,))
@@ -87,7 +94,6 @@ def proposal_settings(cfg_or_table):
 
 
 NMS_DEFAULTS = dict(method="hard", overlap=0.1, sigma=0.5, min_score=0.001)
-NMS_METHODS = ("hard", "linear", "gaussian")   # method 0, 1, 2 of frcnn_soft_nms_batch
 
 
 def nms_settings(cfg_or_table):
@@ -102,18 +108,9 @@ def nms_settings(cfg_or_table):
       min_score  in [0, 1), a probability; default 0.001.  0 keeps every class-test survivor
     Raises ValueError (before any device call) for an unknown key, an unknown method, a bool or a non-number, and a value
     outside its range."""
-    t = cfg_or_table
-    if isinstance(t, dict) and ("nms" in t or "class_count" in t):     # a model's cfg
-        t = t.get("nms")
-    if t is None:
-        t = {}
-    if not isinstance(t, dict):
-        raise ValueError("cfg.nms must be a table of {method, overlap, sigma, min_score}")
-    unknown = sorted(set(t) - set(NMS_DEFAULTS), key=str)
-    if unknown:
-        raise ValueError("cfg.nms: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    t = _settings_table(cfg_or_table, "nms", NMS_DEFAULTS)
     method = t.get("method", NMS_DEFAULTS["method"])
-    if not isinstance(method, str) or method not in NMS_METHODS:
+    if not isinstance(method, str) or method not in SOFT_NMS_METHODS:
         raise ValueError("cfg.nms.method = %r (\"hard\", \"linear\" or \"gaussian\")" % (method,))
     vals = []
     for k in ("overlap", "sigma", "min_score"):
@@ -181,15 +178,21 @@ class _BatchRecord(object):
     Under pre_nms_top_n the scan rows are the SELECTED rows (n of them) and two more keys exist: row (their 1-based original
     scan rows) and matches (the frame's match count before the cap).  Under a soft per-class NMS (cfg["nms"]) two more: bb (K x 5:
     the class test's survivors {x1 y1 x2 y2 log-confidence} as the pass read them) and kc (K: their classes)."""
-    _KEYS = ("n", "idx", "box", "rect", "p", "pick", "cnet", "kept", "pooled")
+    _KEYS = ("n", "idx", "box", "rect", "p", "pick", "cnet", "kept", "pooled")   # of every record
 
-    def __init__(self, n, R, kept, dev, matches=None):
-        self._v = dict(n=n, R=R, kept=kept)
+    def __init__(self, n, R, dev, matches=None):
+        self._v = dict(n=n, R=R, kept=0)
         self._dev = dev      # name -> DeviceTensor (views of the chunk's buffers until detach())
         self._view = True
         if matches is not None:
             self._v["matches"] = matches
-            self._KEYS = self._KEYS + ("row", "matches")
+
+    def finish(self, kept, bb=None, kc=None):
+        """What read-back 2 brings: the class test's survivor count, and -- a soft per-class NMS -- its rows as the pass read
+        them (device arrays of `kept` rows)."""
+        self._v["kept"] = kept
+        if bb is not None:
+            self._dev.update(bb=bb, kc=kc)
 
     def detach(self):
         """A private device copy of the frame's arrays (one allocation; the copies are queued on the stream, no wait): the
@@ -217,18 +220,24 @@ class _BatchRecord(object):
         return out
 
     def keys(self):
-        return list(self._KEYS)
+        """The keys of every record, then those of what this one holds: row, matches (pre_nms_top_n); bb, kc (a soft pass)."""
+        ks = list(self._KEYS)
+        if "matches" in self._v:
+            ks += ["row", "matches"]
+        if "bb" in self._dev:
+            ks += ["bb", "kc"]
+        return ks
 
     def get(self, k, default=None):
         return self[k] if k in self else default
 
     def __contains__(self, k):
-        return k in self._KEYS
+        return k in self.keys()
 
     def __getitem__(self, k):
         v = self._v
         if k not in v:
-            if k not in self._KEYS:
+            if k not in self:
                 raise KeyError(k)
             if k == "pooled":
                 v[k] = self._dev[k].numpy() if k in self._dev else None
@@ -239,33 +248,23 @@ class _BatchRecord(object):
         return v[k]
 
 
-class _DetectorType(type):
-    """Detector(model, ..., nms=table): the per-class NMS setting is a keyword of the class call, not of __init__, whose
-    parameter list (model, static_weights, proposals) stays what it was.  The table is validated before anything is built --
-    before any device call -- and set on the finished object; without it __init__ has read model["cfg"]["nms"]."""
-
-    def __call__(cls, *args, nms=None, **kw):
-        if nms is not None:
-            nms_settings(nms)
-        d = super().__call__(*args, **kw)
-        if nms is not None:
-            d.set_nms(nms)
-        return d
-
-
-class Detector(object, metaclass=_DetectorType):
+class Detector(object):
     proposal_settings = staticmethod(proposal_settings)
     nms_settings = staticmethod(nms_settings)
 
-    def __init__(self, model, static_weights=False, proposals=None):  # Detector.lua:8-15
+    def __init__(self, model, static_weights=False, proposals=None, nms=None):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
         the convolution weights once instead of once per frame (option static_weights of the C ABI; a training-mode pass or
         another Detector(..., static_weights=...) drops the packs).
         proposals: a table as proposal_settings takes it; None: model["cfg"]["proposals"] (absent: the reference's behaviour).
-        The per-class NMS is model["cfg"]["nms"] (absent: the reference's hard cut at 0.1) unless the call names one:
-        Detector(model, nms=table), a table as nms_settings takes it (see _DetectorType)."""
+        nms: the per-class NMS, a table as nms_settings takes it -- validated first, before the model is looked at; None:
+        model["cfg"]["nms"] (absent: the reference's hard cut at 0.1)."""
+        if nms is not None:
+            nms_settings(nms)
         self.set_proposals(proposals if proposals is not None else model["cfg"])
         self.set_nms(model["cfg"])
+        if nms is not None:
+            self.set_nms(nms)
         self.model = model
         if static_weights or os.environ.get("FRCNN_STATIC_WEIGHTS"):
             _lib.call("frcnn_set_option", b"static_weights", 1)
@@ -362,14 +361,14 @@ class Detector(object, metaclass=_DetectorType):
                   ptr(box5), None, cap, stream_ptr())
         return box5
 
-    def _clamp_candidates(self, dev_ptr, Rs):
+    def _clamp_candidates(self, c_R, Rs):
         """post_nms_top_n: the candidate counts clamped on the host -> (the clamped list, True when any changed); the device
-        copy behind dev_ptr (what the winner table's header reports) follows."""
+        copy c_R (what the winner table's header reports) follows."""
         out = [min(R, self.post_nms_top_n) for R in Rs]
         if out == Rs:
             return out, False
         host = np.array(out, np.int32)
-        _lib.call("frcnn_memcpy_h2d", C.c_void_p(dev_ptr), host.ctypes.data_as(C.c_void_p), host.nbytes, stream_ptr())
+        _lib.call("frcnn_memcpy_h2d", ptr(c_R), host.ctypes.data_as(C.c_void_p), host.nbytes, stream_ptr())
         self._clamped = host     # (pageable memory: the copy has been staged when the call returns; kept anyway)
         return out, True
 
@@ -450,7 +449,7 @@ class Detector(object, metaclass=_DetectorType):
         """Detector.lua:17-85 for a chunk of B frames of one size: the proposal net frame by frame, ONE scan, (selection or score
         rows), ONE segmented first NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> dict(B,
         counts (device int32[4][B]), cap (rows a frame in p, idx, rect, pick: the match arrays the rest of the chunk reads, the
-        selected rows under pre_nms_top_n), fm, fslot, fshape (frame b's last feature map at fm + 4 * b * fslot), ns, Rs (rows and
+        selected rows under pre_nms_top_n), fm, fshape (frame b's last feature map is fm.segment(b)), ns, Rs (rows and
         candidates per frame), key (key_mode, key_col of both NMS passes), and box, row, matches for _records).
         pre: prefix of the buffer names ("" for detect() and proposals(), "b_" for detect_batch: neither overwrites what the other
         left behind)."""
@@ -476,21 +475,22 @@ class Detector(object, metaclass=_DetectorType):
                 fshape = outputs[-1].shape
                 fslot = (int(np.prod(fshape)) + 63) // 64 * 64
                 if B == 1:
-                    heads, fm = [o.ptr for o in outputs[:4]], outputs[-1].ptr
+                    heads, fm = [ptr(o) for o in outputs[:4]], outputs[-1].view(1, *fshape)
                     break
-                heads_buf = self._buf(pre + "heads", (B, slot))
-                heads, fm = [heads_buf.ptr + 4 * hoff[i] for i in range(4)], self._buf(pre + "fm", (B, fslot)).ptr
+                heads_buf, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
+                heads = [ptr(heads_buf.offset_view(hoff[i], hshape[i])) for i in range(4)]
             for i in range(4):
-                _lib.call("frcnn_memcpy_d2d", C.c_void_p(heads[i] + 4 * b * slot), ptr(outputs[i]), outputs[i].nbytes, s)
-            _lib.call("frcnn_memcpy_d2d", C.c_void_p(fm + 4 * b * fslot), ptr(outputs[-1]), outputs[-1].nbytes, s)
+                _lib.call("frcnn_memcpy_d2d", ptr(heads_buf.segment(b).offset_view(hoff[i], hshape[i])), ptr(outputs[i]),
+                          outputs[i].nbytes, s)
+            _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
         # counts (device int32[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
         counts = self._buf(pre + "counts", (4, B), i32)
-        c_n, c_R = C.c_void_p(counts.ptr), C.c_void_p(counts.ptr + 4 * B)
+        c_n, c_R = ptr(counts.segment(0)), counts.segment(1)
         # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b).  Every anchor
         #         of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is ever truncated
         Hs = (C.c_int * 4)(*[shp[1] for shp in hshape])
         Ws = (C.c_int * 4)(*[shp[2] for shp in hshape])
-        maps = (C.c_void_p * 4)(*heads)
+        maps = (C.c_void_p * 4)(*[h.value for h in heads])
         cap = ASPECTS * sum(shp[1] * shp[2] for shp in hshape)
         wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B)
         ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
@@ -522,8 +522,8 @@ class Detector(object, metaclass=_DetectorType):
         ws = self._buf(pre + "nms_ws", (wsb,), np.uint8)
         pick = self._buf(pre + "nms_pick", (B, cap), np.int64)
         _lib.call("frcnn_nms_device_batch", ptr(boxes), B, cap, ncap, c_first, ncols, C.c_float(0.25), key_mode, key_col, None,
-                  ptr(pick), c_R, ptr(ws), wsb, s)
-        nR = self._read(counts.ptr, 8 * B, i32)                                # ---- read-back 1 of 2: B pairs of counts
+                  ptr(pick), ptr(c_R), ptr(ws), wsb, s)
+        nR = self._read(counts.ptr, counts.nbytes // 2, i32)                   # ---- read-back 1 of 2: B pairs of counts
         ns, Rs = [int(v) for v in nR[:B]], [int(v) for v in nR[B:]]
         for b in range(B):
             if ns[b] > anchors:
@@ -534,31 +534,29 @@ class Detector(object, metaclass=_DetectorType):
             if ns[b] > ncap:
                 wsb = L.frcnn_nms_workspace_bytes(ns[b])
                 ws = self._buf(pre + "nms_ws_full", (wsb,), np.uint8)
-                _lib.call("frcnn_nms_device", C.c_void_p(boxes.ptr + 4 * ncols * b * cap), ns[b], ncols, C.c_float(0.25), key_mode,
-                          key_col, C.c_void_p(pick.ptr + 8 * b * cap), C.c_void_p(counts.ptr + 4 * (B + b)), ptr(ws), wsb, s)
-                Rs[b] = int(self._read(counts.ptr + 4 * (B + b), 4, i32)[0])
+                c_Rb = c_R.offset_view(b, (1,))
+                _lib.call("frcnn_nms_device", ptr(boxes.segment(b)), ns[b], ncols, C.c_float(0.25), key_mode, key_col,
+                          ptr(pick.segment(b)), ptr(c_Rb), ptr(ws), wsb, s)
+                Rs[b] = int(self._read(c_Rb.ptr, c_Rb.dtype.itemsize, i32)[0])
         if post_n is not None:
-            Rs = self._clamp_candidates(counts.ptr + 4 * B, Rs)[0]
-        return dict(B=B, counts=counts, cap=cap, p=mp, idx=mi, rect=mr, box=mb, row=row, pick=pick, fm=fm, fslot=fslot, fshape=fshape,
+            Rs = self._clamp_candidates(c_R, Rs)[0]
+        return dict(B=B, counts=counts, cap=cap, p=mp, idx=mi, rect=mr, box=mb, row=row, pick=pick, fm=fm, fshape=fshape,
                     ns=ns, Rs=Rs, matches=matches, key=(key_mode, key_col))
 
     def _records(self, st, more=None):
         """One _BatchRecord per frame of the chunk _first_stage returned st for (views of the chunk's buffers, kept = 0);
         more[b]: further device arrays of frame b (bbox, cls, pooled).  Host work only: _detect_chunk calls it with the whole
         chunk queued, in front of its second wait, not between read-back 1 and the launches that wait for it."""
-        cap, row, matches = st["cap"], st["row"], st["matches"]
+        row, matches = st["row"], st["matches"]
         records = []
         for b in range(st["B"]):
             n = st["ns"][b]
             R = st["Rs"][b] if n else 0  # :71
-            dev = dict(p=DeviceTensor(st["p"].ptr + 4 * b * cap, (n,), np.float32, owner=st["p"]),
-                       idx=DeviceTensor(st["idx"].ptr + 16 * b * cap, (n, 4), np.int32, owner=st["idx"]),
-                       rect=DeviceTensor(st["rect"].ptr + 32 * b * cap, (n, 4), np.float64, owner=st["rect"]),
-                       box=DeviceTensor(st["box"].ptr + 16 * b * cap, (n, 4), np.float32, owner=st["box"]),
-                       pick=DeviceTensor(st["pick"].ptr + 8 * b * cap, (R,), np.int64, owner=st["pick"]), **(more or {}).get(b, {}))
+            dev = dict({k: st[k].segment(b, n) for k in ("p", "idx", "rect", "box")}, pick=st["pick"].segment(b, R),
+                       **(more or {}).get(b, {}))
             if row is not None:   # the rows above are the selected ones: their 1-based original scan rows
-                dev.update(row=DeviceTensor(row.ptr + 4 * b * cap, (n,), np.int32, owner=row))
-            records.append(_BatchRecord(n, R, 0, dev, matches[b] if matches is not None else None))
+                dev.update(row=row.segment(b, n))
+            records.append(_BatchRecord(n, R, dev, matches[b] if matches is not None else None))
         return records
 
     def _detect_chunk(self, frames, shared, pre):
@@ -570,8 +568,7 @@ class Detector(object, metaclass=_DetectorType):
         cnet = model["cnet"]
         roi = self._roi_settings()
         kh, kw = roi[0], roi[1]
-        bgclass = cfg["class_count"] + 1
-        ncls = cfg["class_count"] + 1
+        ncls = cfg["class_count"] + 1     # the classes and, last, the background
         planes = model["layers"][-1]["filters"]
         s = stream_ptr()
         L = _lib.load()
@@ -580,7 +577,7 @@ class Detector(object, metaclass=_DetectorType):
         st = self._first_stage(frames, pre)   # :17-85
         B, counts, cap, mp, mi, mr, pick = st["B"], st["counts"], st["cap"], st["p"], st["idx"], st["rect"], st["pick"]
         ns, Rs, (key_mode, key_col) = st["ns"], st["Rs"], st["key"]
-        c_K, c_W = C.c_void_p(counts.ptr + 8 * B), C.c_void_p(counts.ptr + 12 * B)
+        c_K, c_W = counts.segment(2), ptr(counts.segment(3))
         Rmax = max([Rs[b] for b in range(B) if ns[b] > 0] + [0])
         if Rmax == 0:   # no frame has a match (:71)
             return [[] for _ in range(B)], self._records(st)
@@ -601,38 +598,37 @@ class Detector(object, metaclass=_DetectorType):
 
         def pooled(b):    # the region features of frame b's candidates (_pool) -> its input rows
             R = Rs[b]
-            cinput = DeviceTensor(cinput_buf.ptr + (4 * D * row0[b] if shared else 0), (R, D), np.float32, owner=cinput_buf)
-            self._pool(roi, C.c_void_p(st["fm"] + 4 * b * st["fslot"]), fmC, fmH, fmW, C.c_void_p(mr.ptr + 32 * b * cap),
-                       C.c_void_p(pick.ptr + 8 * b * cap), R, cinput, s, rows=Rmax)
+            cinput = cinput_buf.offset_view(D * row0[b] if shared else 0, (R, D))
+            self._pool(roi, ptr(st["fm"].segment(b)), fmC, fmH, fmW, ptr(mr.segment(b)), ptr(pick.segment(b)), R, cinput, s,
+                       rows=Rmax)
             return cinput
         for b in sorted(row0):
             if self.verbose:
                 print("candidates: %d" % Rs[b])
             # (the net writes into the frame's rows: its own output buffers are reused by the next pass)
-            more[b] = dict(bbox=DeviceTensor(bbox_all.ptr + 16 * row0[b], (Rs[b], 4), np.float32, owner=bbox_all),
-                           cls=DeviceTensor(cls_all.ptr + 4 * ncls * row0[b], (Rs[b], ncls), np.float32, owner=cls_all))
+            more[b] = dict(bbox=bbox_all.offset_view(4 * row0[b], (Rs[b], 4)),
+                           cls=cls_all.offset_view(ncls * row0[b], (Rs[b], ncls)))
             if shared:
                 more[b].update(pooled=pooled(b))
             else:
                 cnet.forward(pooled(b), out=(more[b]["bbox"], more[b]["cls"]))  # :101
         if shared:
-            cnet.forward(DeviceTensor(cinput_buf.ptr, (total, D), np.float32, owner=cinput_buf),
-                         out=(DeviceTensor(bbox_all.ptr, (total, 4), np.float32, owner=bbox_all),
-                              DeviceTensor(cls_all.ptr, (total, ncls), np.float32, owner=cls_all)))  # :101, all frames
+            cnet.forward(cinput_buf, out=(bbox_all.offset_view(0, (total, 4)),
+                                          cls_all.offset_view(0, (total, ncls))))  # :101, all frames
         # ---- then, per frame, the class test (:106-122) into the frame's segment: r2 = Anchors.anchorToInput(r, bbox) in double,
         #      survivors compacted in order
         bb = self._buf(pre + "bb", (B, Rmax, 5)); kc = self._buf(pre + "kc", (B, Rmax), i32)
         keep_row = self._buf(pre + "keep_row", (B, Rmax), i32); r2 = self._buf(pre + "r2", (B, Rmax, 4), np.float64)
         dcls = self._buf(pre + "cls", (Rmax,), i32); dconf = self._buf(pre + "conf", (Rmax,))
         for b in range(B):
+            c_Kb = c_K.offset_view(b, (1,))
             if ns[b] == 0:     # no candidates: an empty segment of the per-class NMS
-                _lib.call("frcnn_zero", C.c_void_p(counts.ptr + 4 * (2 * B + b)), 4, s)
+                _lib.call("frcnn_zero", ptr(c_Kb), c_Kb.dtype.itemsize, s)
                 continue
             _lib.call("frcnn_cnet_decode", ptr(more[b]["cls"]), Rs[b], ncls, ptr(dcls), ptr(dconf), s)  # :110-113
-            _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(more[b]["bbox"]), C.c_void_p(mr.ptr + 32 * b * cap),
-                      C.c_void_p(pick.ptr + 8 * b * cap), Rs[b], bgclass, 0.2, C.c_void_p(bb.ptr + 20 * b * Rmax),
-                      C.c_void_p(kc.ptr + 4 * b * Rmax), C.c_void_p(keep_row.ptr + 4 * b * Rmax), C.c_void_p(r2.ptr + 32 * b * Rmax),
-                      C.c_void_p(counts.ptr + 4 * (2 * B + b)), s)
+            _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(more[b]["bbox"]), ptr(mr.segment(b)), ptr(pick.segment(b)),
+                      Rs[b], ncls, 0.2, ptr(bb.segment(b)), ptr(kc.segment(b)), ptr(keep_row.segment(b)), ptr(r2.segment(b)),
+                      ptr(c_Kb), s)
         # ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame, rows only suppress rows of their own class: a stable
         #         partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
         #         column under order = "score"), the survivor counts read from device memory; ONE gather of every frame's winner
@@ -647,32 +643,29 @@ class Detector(object, metaclass=_DetectorType):
             if Rmax > 16384:
                 raise _lib.FrcnnError("Detector: %d candidates in a frame, more than the 16384 a soft per-class NMS takes" % Rmax)
             bb_win = self._buf(pre + "bb_soft", (B, Rmax, 5))
-            _lib.call("frcnn_memcpy_d2d", ptr(bb_win), ptr(bb), 20 * B * Rmax, s)
+            _lib.call("frcnn_memcpy_d2d", ptr(bb_win), ptr(bb), bb.nbytes, s)
             wsb2 = L.frcnn_soft_nms_workspace_bytes(B, Rmax)
             ws2 = self._buf(pre + "soft_nms_ws", (wsb2,), np.uint8)
             log_min = float(math.log(self.nms_min_score)) if self.nms_min_score > 0.0 else -math.inf
-            _lib.call("frcnn_soft_nms_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, 5, NMS_METHODS.index(self.nms_method),
+            _lib.call("frcnn_soft_nms_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, 5, SOFT_NMS_METHODS.index(self.nms_method),
                       C.c_float(self.nms_overlap), C.c_float(self.nms_sigma), C.c_float(log_min), 1, ptr(kc), ptr(wpick), c_W,
-                      C.c_void_p(bb_win.ptr + 16), 5, ptr(ws2), wsb2, s)
+                      ptr(bb_win.offset_view(4, (1,))), 5, ptr(ws2), wsb2, s)      # (column 5 of the copy)
         else:
             wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
             ws2 = self._buf(pre + "nms_ws2", (wsb2,), np.uint8)
-            _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, c_K, 5, C.c_float(self.nms_overlap), key_mode, key_col, ptr(kc),
-                      ptr(wpick), c_W, ptr(ws2), wsb2, s)
+            _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, C.c_float(self.nms_overlap), key_mode, key_col,
+                      ptr(kc), ptr(wpick), c_W, ptr(ws2), wsb2, s)
         out = self._buf(pre + "winners", (B, Rmax + 1, 16), np.float64)
         _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2), ptr(pick),
                   cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
         records = self._records(st, more)
-        raw = self._read(out.ptr, B * (Rmax + 1) * 128, np.float64).reshape(B, Rmax + 1, 16)   # ---- read-back 2 of 2
+        raw = self._read(out.ptr, out.nbytes, np.float64).reshape(out.shape)   # ---- read-back 2 of 2
         results = []
         for b in range(B):
             hdr = raw[b, 0].view(i32)
-            records[b]._v.update(kept=int(hdr[2]))
-            if soft:    # the class test's survivors as the pass read them (views of the chunk's buffers until detach())
-                K = int(hdr[2])
-                records[b]._dev.update(bb=DeviceTensor(bb.ptr + 20 * b * Rmax, (K, 5), np.float32, owner=bb),
-                                       kc=DeviceTensor(kc.ptr + 4 * b * Rmax, (K,), np.int32, owner=kc))
-                records[b]._KEYS = records[b]._KEYS + ("bb", "kc")
+            K = int(hdr[2])
+            # (soft: the class test's survivors as the pass read them, views of the chunk's buffers until detach())
+            records[b].finish(K, bb.segment(b, K) if soft else None, kc.segment(b, K) if soft else None)
             if ns[b] == 0:
                 results.append([])
                 continue

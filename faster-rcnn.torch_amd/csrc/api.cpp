@@ -167,6 +167,7 @@ int frcnn_nms_device_batch(const float* boxes, int B, long long row_stride, int 
                            int key_mode, int key_col, const int* cls, long long* pick, int* count, void* ws, size_t ws_bytes,
                            void* stream) {
   FR_CHECK(B <= 0 || (boxes && pick && count), "frcnn_nms_device_batch: NULL argument");
+  FR_CHECK(B <= 0 || n_cap <= 0 || n_dev, "frcnn_nms_device_batch: NULL device counts");
   return nms_device_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, overlap, key_mode, key_col, cls, pick, count, ws,
                           ws_bytes, S(stream));
 }
@@ -204,11 +205,6 @@ int frcnn_roi_windows(const double* rect, const long long* pick, int k, const in
 int frcnn_detect_post(const int* cls, const float* conf, const float* bbox, const double* rect, const long long* pick, int R,
                       int bgclass, double min_conf, float* bb, int* kc, int* keep_row, double* r2, int* K_dev, void* stream) {
   return detect_post(cls, conf, bbox, rect, pick, R, bgclass, min_conf, bb, kc, keep_row, r2, K_dev, S(stream));
-}
-int frcnn_detect_gather(const long long* wpick, const int* nwin_dev, int cap, const int* keep_row, const int* kc, const float* bb,
-                        const double* r2, const long long* pick, const float* match_p, const double* match_rect,
-                        const int* match_idx, double* rec, void* stream) {
-  return detect_gather(wpick, nwin_dev, cap, keep_row, kc, bb, r2, pick, match_p, match_rect, match_idx, rec, S(stream));
 }
 int frcnn_nms_host(const float* boxes_host, int n, int ncols, float overlap, int key_mode, int key_col,
                    long long* pick_host, int* count_host) {

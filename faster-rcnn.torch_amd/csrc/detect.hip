@@ -5,7 +5,8 @@
 //   detect_post   Detector.lua:106-122: class test (class != background and p > 0.2), r2 = Anchors.anchorToInput(r, bbox)
 //                 in double, ORDERED compaction of the survivors into the box / class arrays the per-class NMS reads;
 //                 the survivor count stays on the device (frcnn_nms_device_n reads it there)
-//   detect_gather one record per winner (class, candidate row, confidence, p, anchor rect, decoded rect, anchor index)
+//   detect_gather_batch  one table per frame: its counts, then one record per winner (class, candidate row, confidence, p,
+//                 anchor rect, decoded rect, anchor index)
 // Gather / scan work on a few thousand rows: latency-bound, no MFMA.  Double arithmetic follows the host mirror
 // operation by operation; FMA contraction is off for this translation unit (products and sums separately rounded, as
 // Lua numbers are).  exp() is the device library's double exp: it may differ from the host libm in the last bit (both
@@ -119,38 +120,14 @@ int detect_post(const int* cls, const float* conf, const float* bbox, const doub
   return FRCNN_OK;
 }
 
-// rec[q][16] (double) for winner q < *nwin_dev (pick order of the per-class NMS):
+// The winner tables of B frames in one launch (Detector:detect_batch; Detector:detect is B = 1), all in ONE buffer: frame b's table
+// is rec + b * (row_stride + 1) * 16 doubles -- a 128-byte header whose first four ints are the frame's counts (matches,
+// candidates, survivors of the class test, winners: counts[k * B + b]), then one record of 16 doubles per winner, in the pick
+// order of the per-class NMS:
 //   0 class, 1 candidate row (1-based, among the NMS candidates), 2 confidence (log-prob), 3 p (log-prob of the anchor),
 //   4-7 anchor rect, 8-11 r2, 12-15 anchor index {layer, aspect, y, x}
-__global__ void detect_gather_kernel(const long long* __restrict__ wpick, const int* __restrict__ nwin_dev, int cap,
-                                     const int* __restrict__ keep_row, const int* __restrict__ kc, const float* __restrict__ bb,
-                                     const double* __restrict__ r2, const long long* __restrict__ pick,
-                                     const float* __restrict__ mp, const double* __restrict__ rect, const int* __restrict__ midx,
-                                     double* __restrict__ rec) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= min(*nwin_dev, cap)) return;
-  const int j = (int)(wpick[q] - 1);
-  const int r = keep_row[j];
-  const size_t i = (size_t)(pick[r] - 1);
-  double* o = rec + 16 * (size_t)q;
-  o[0] = kc[j]; o[1] = r + 1; o[2] = bb[5 * (size_t)j + 4]; o[3] = mp[i];
-  for (int t = 0; t < 4; ++t) { o[4 + t] = rect[4 * i + t]; o[8 + t] = r2[4 * (size_t)j + t]; o[12 + t] = midx[4 * i + t]; }
-}
-
-int detect_gather(const long long* wpick, const int* nwin_dev, int cap, const int* keep_row, const int* kc, const float* bb,
-                  const double* r2, const long long* pick, const float* mp, const double* rect, const int* midx, double* rec,
-                  hipStream_t s) {
-  if (cap <= 0) return FRCNN_OK;
-  FR_LAUNCH(KC_ELEMWISE, 0, cap * 128.0, s, detect_gather_kernel, dim3(cdiv(cap, 64)), dim3(64), 0, wpick, nwin_dev, cap, keep_row,
-            kc, bb, r2, pick, mp, rect, midx, rec);
-  FR_LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-// The same for B frames in one launch (Detector:detect_batch), the winner tables of all frames in ONE buffer: frame b's table is
-// rec + b * (row_stride + 1) * 16 doubles -- a 128-byte header whose first four ints are the frame's counts (matches,
-// candidates, survivors of the class test, winners: counts[k * B + b]), then one record per winner.  The per-candidate arrays
-// (wpick, keep_row, kc, bb, r2) hold row_stride rows per frame, the match arrays (pick, mp, rect, midx) match_stride rows.
+// The per-candidate arrays (wpick, keep_row, kc, bb, r2) hold row_stride rows per frame, the match arrays (pick, mp, rect, midx)
+// match_stride rows.
 __global__ void detect_gather_batch_kernel(const long long* __restrict__ wpick, const int* __restrict__ counts, int B, int row_stride,
                                            const int* __restrict__ keep_row, const int* __restrict__ kc, const float* __restrict__ bb,
                                            const double* __restrict__ r2, const long long* __restrict__ pick, long match_stride,

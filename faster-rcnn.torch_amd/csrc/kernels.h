@@ -257,16 +257,17 @@ struct RpnLayers {
   const float* map[4];
   int H[4], W[4];
 };
-int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, double img_w,
-             double img_h, double p_threshold, int cap, float* match_p, int* match_idx,
-             double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
-             hipStream_t s);
-size_t rpn_scan_workspace_bytes(const RpnLayers& L);
 // B frames' head maps (slot b of map l at L.map[l] + b * slot_stride floats) in one pass; outputs at b * cap rows, count[b]
 int rpn_scan_batch(const RpnLayers& L, int B, long slot_stride, const float* anchor_w, const float* anchor_h, double img_w,
                    double img_h, double p_threshold, int cap, float* match_p, int* match_idx, double* match_rect,
                    float* match_box, int* count, void* ws, size_t ws_bytes, hipStream_t s);
 size_t rpn_scan_batch_workspace_bytes(const RpnLayers& L, int B);
+// the single frame: rpn_scan_batch with B = 1
+int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, double img_w,
+             double img_h, double p_threshold, int cap, float* match_p, int* match_idx,
+             double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
+             hipStream_t s);
+size_t rpn_scan_workspace_bytes(const RpnLayers& L);
 int rpn_loss(const RpnLayers& L, float* const* delta, const int* ex_idx, const double* ex_anchor,
              const double* ex_roi, const int* ex_class, int npos, int nneg, int bgclass,
              double* ex_loss, float* crtarget, float* cctarget, hipStream_t s);
@@ -274,15 +275,17 @@ int rpn_loss(const RpnLayers& L, float* const* delta, const int* ex_idx, const d
 int loss_accumulate(const double* ex_loss, int E, double* acc, hipStream_t s);
 
 // ---------------------------------------------------------------- nms (nms.hip)
-size_t nms_workspace_bytes(int n);
-// cls (optional, int[n]): rows only suppress rows of the same class (Detector.lua:125-136 in one pass)
-int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode, int key_col,
-               long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s, const int* cls = nullptr,
-               const int* n_dev = nullptr);   // n_dev: the row count is read from device memory (<= n)
-// B independent problems (segments of row_stride rows, counts n_dev[b] <= n in device memory) in one pass
+// B independent problems (segments of row_stride rows) in one pass.  cls (optional, int rows like boxes): rows only suppress rows
+// of the same class (Detector.lua:125-136 in one pass).  n_dev (optional): segment b's row count is read from device memory
+// (n_dev[b] <= n); NULL: n rows each.
 size_t nms_batch_workspace_bytes(int B, int n);
 int nms_device_batch(const float* boxes, int B, long row_stride, int n, const int* n_dev, int ncols, float overlap, int key_mode,
                      int key_col, const int* cls, long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+// the single problem: nms_device_batch with B = 1, row_stride = n
+size_t nms_workspace_bytes(int n);
+int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode, int key_col,
+               long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s, const int* cls = nullptr,
+               const int* n_dev = nullptr);
 // ---- Soft-NMS for the per-class pass (soft_nms.hip): B segments, one workgroup each; semantics in include/frcnn_hip.h
 size_t soft_nms_workspace_bytes(int B, int n_cap);
 int soft_nms_batch(const float* boxes, int B, long row_stride, int n_cap, const int* n_dev, int ncols, int score_col, int method,
@@ -300,9 +303,6 @@ int roi_windows(const double* rect, const long long* pick, int k, const int* lay
                 hipStream_t s);
 int detect_post(const int* cls, const float* conf, const float* bbox, const double* rect, const long long* pick, int R,
                 int bgclass, double min_conf, float* bb, int* kc, int* keep_row, double* r2, int* K_dev, hipStream_t s);
-int detect_gather(const long long* wpick, const int* nwin_dev, int cap, const int* keep_row, const int* kc, const float* bb,
-                  const double* r2, const long long* pick, const float* mp, const double* rect, const int* midx, double* rec,
-                  hipStream_t s);
 int detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                         const float* bb, const double* r2, const long long* pick, long match_stride, const float* mp,
                         const double* rect, const int* midx, double* rec, hipStream_t s);

@@ -20,8 +20,8 @@ namespace frcnn {
 // n_dev (optional, every kernel): the row count lives in device memory (the match count a scan just produced, the
 // number of candidates that passed the class test): n = min(*n_dev, n) -- the launch is sized for the host-side bound
 // and the pipeline that feeds it never waits for a read-back (Detector.lua:39-85 without a host round trip).
-// (Every stage's code is a body shared by two kernels: the single-problem kernel, launched as before, and the segmented
-// kernel of nms_device_batch further down, which takes the segment from a grid dimension and offsets the pointers.)
+// (Every stage's code is a body; its kernel, further down with nms_device_batch, takes the segment from a grid dimension and
+// offsets the pointers.  A single problem is the launch of one segment.)
 __device__ __forceinline__ void nms_prep_body(const float* __restrict__ boxes, int n, const int* __restrict__ n_dev, int ncols,
                                               int key_mode, int key_col, float* __restrict__ area, float* __restrict__ key) {
   if (n_dev) n = min(*n_dev, n);
@@ -36,14 +36,10 @@ __device__ __forceinline__ void nms_prep_body(const float* __restrict__ boxes, i
   area[i] = a;
   key[i] = key_mode == 2 ? b[key_col - 1] : (key_mode == 1 ? a : b[3]);
 }
-__global__ void nms_prep_kernel(const float* __restrict__ boxes, int n, const int* __restrict__ n_dev, int ncols, int key_mode,
-                                int key_col, float* __restrict__ area, float* __restrict__ key) {
-  nms_prep_body(boxes, n, n_dev, ncols, key_mode, key_col, area, key);
-}
 
 // rank[i] = #{ j : key[j] < key[i]  or (key[j] == key[i] and j < i) }; sorted[n-1-rank] = i.
 // 2-D grid: block (x, y) counts, for its 256 keys i, the 256 keys j of slice y (one LDS image, one barrier, 64 broadcast reads of
-// four keys); partial counts meet in an integer atomic (exact, order-independent), then nms_scatter_kernel writes the permutation.
+// four keys); partial counts meet in an integer atomic (exact, order-independent), then nms_scatter_batch_kernel writes the permutation.
 // Off the diagonal the tie rule is a constant (j < i for every pair of a block below the diagonal, never above it).  Round 6:
 // slices of 256 instead of 1024 keys -- a thread's 1 024 dependent compare steps were the whole 30 us of the launch at any n,
 // with one block per compute unit.
@@ -79,16 +75,10 @@ __device__ __forceinline__ void nms_rank_body(const float* __restrict__ key, int
   }
   if (i < n && r) atomicAdd(rank + i, r);
 }
-__global__ __launch_bounds__(256) void nms_rank_kernel(const float* __restrict__ key, int n, const int* __restrict__ n_dev, int* __restrict__ rank) {
-  nms_rank_body(key, n, n_dev, rank);
-}
 __device__ __forceinline__ void nms_scatter_body(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
   if (n_dev) n = min(*n_dev, n);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) sorted[n - 1 - rank[i]] = i;
-}
-__global__ void nms_scatter_kernel(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
-  nms_scatter_body(rank, n, n_dev, sorted);
 }
 
 // mask[a][w] bit b: box at sorted position a suppresses box at sorted position w*64+b (b > a)
@@ -140,7 +130,7 @@ __device__ __forceinline__ void nms_mask_body(const float* __restrict__ boxes, i
   }
   mask[(size_t)rpos * nw + cb] = bits;
   // diagonal tile: the block transposed as well -- diagT[pos] bit u: the box at sorted position 64 rb + u (u before pos in its
-  // group) suppresses the box at pos.  The scan resolves a group from these columns in a few wave-wide rounds (nms_reduce_kernel).
+  // group) suppresses the box at pos.  The scan resolves a group from these columns in a few wave-wide rounds (nms_reduce_batch_kernel).
   if (rb == cb) {
     unsigned long long col = 0ull;
     for (int c = 0; c < 64; ++c) {
@@ -149,12 +139,6 @@ __device__ __forceinline__ void nms_mask_body(const float* __restrict__ boxes, i
     }
     diagT[rpos] = col;
   }
-}
-__global__ void nms_mask_kernel(const float* __restrict__ boxes, int ncols, const float* __restrict__ area,
-                                const int* __restrict__ sorted, int n, const int* __restrict__ n_dev, int nw, float thr,
-                                const int* __restrict__ cls, unsigned long long* __restrict__ mask,
-                                unsigned long long* __restrict__ diagT) {
-  nms_mask_body(boxes, ncols, area, sorted, n, n_dev, nw, thr, cls, mask, diagT);
 }
 
 // OR of a 64-bit value over the 64 lanes of a wave, returned wave-uniform: data-parallel-primitive moves inside the vector ALU
@@ -388,41 +372,36 @@ __device__ __forceinline__ void nms_reduce_body(const unsigned long long* __rest
   if (tid == 0) *count = cnt_all;
 }
 #undef NMS_STEP_BARRIER
-__global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_kernel(const unsigned long long* __restrict__ mask,
-                                                                     const unsigned long long* __restrict__ diagT,
-                                                                     const int* __restrict__ sorted, int n,
-                                                                     const int* __restrict__ n_dev, int nwp,
-                                                                     long long* __restrict__ pick, int* __restrict__ count) {
-  nms_reduce_body(mask, diagT, sorted, n, n_dev, nwp, pick, count);
-}
 
 // ---- B independent problems in one pass (Detector:detect_batch): segment b = a grid dimension of every stage.  Its boxes are
 // rows [b * row_stride, b * row_stride + n_b) of `boxes` (cls likewise), n_b = min(n_dev[b], n), its work arrays slice b of
 // arrays of n entries per segment, its mask B_b = mask + b * n * nw words, its picks pick + b * row_stride (1-based rows WITHIN
-// the segment), its survivor count count[b].  The bodies above run unchanged on the offset pointers, so a segment's result
-// is that of the single-problem kernels on its rows; nothing is shared between segments (no tie rule across them).
+// the segment), its survivor count count[b].  The bodies above run on the offset pointers, so a segment's result is that of a
+// launch of that segment alone; nothing is shared between segments (no tie rule across them).  n_dev == NULL: every segment
+// holds n rows.
 __global__ void nms_prep_batch_kernel(const float* __restrict__ boxes, long row_stride, int n, const int* __restrict__ n_dev,
                                       int ncols, int key_mode, int key_col, float* __restrict__ area, float* __restrict__ key) {
   const int b = blockIdx.y;
-  nms_prep_body(boxes + (size_t)b * row_stride * ncols, n, n_dev + b, ncols, key_mode, key_col, area + (size_t)b * n,
-                key + (size_t)b * n);
+  nms_prep_body(boxes + (size_t)b * row_stride * ncols, n, n_dev ? n_dev + b : nullptr, ncols, key_mode, key_col,
+                area + (size_t)b * n, key + (size_t)b * n);
 }
 __global__ __launch_bounds__(256) void nms_rank_batch_kernel(const float* __restrict__ key, int n, const int* __restrict__ n_dev,
                                                              int* __restrict__ rank) {
   const int b = blockIdx.z;
-  nms_rank_body(key + (size_t)b * n, n, n_dev + b, rank + (size_t)b * n);
+  nms_rank_body(key + (size_t)b * n, n, n_dev ? n_dev + b : nullptr, rank + (size_t)b * n);
 }
 __global__ void nms_scatter_batch_kernel(const int* __restrict__ rank, int n, const int* __restrict__ n_dev, int* __restrict__ sorted) {
   const int b = blockIdx.y;
-  nms_scatter_body(rank + (size_t)b * n, n, n_dev + b, sorted + (size_t)b * n);
+  nms_scatter_body(rank + (size_t)b * n, n, n_dev ? n_dev + b : nullptr, sorted + (size_t)b * n);
 }
 __global__ void nms_mask_batch_kernel(const float* __restrict__ boxes, long row_stride, int ncols, const float* __restrict__ area,
                                       const int* __restrict__ sorted, int n, const int* __restrict__ n_dev, int nw, float thr,
                                       const int* __restrict__ cls, unsigned long long* __restrict__ mask,
                                       unsigned long long* __restrict__ diagT) {
   const int b = blockIdx.z;
-  nms_mask_body(boxes + (size_t)b * row_stride * ncols, ncols, area + (size_t)b * n, sorted + (size_t)b * n, n, n_dev + b, nw, thr,
-                cls ? cls + (size_t)b * row_stride : nullptr, mask + (size_t)b * n * nw, diagT + (size_t)b * n);
+  nms_mask_body(boxes + (size_t)b * row_stride * ncols, ncols, area + (size_t)b * n, sorted + (size_t)b * n, n,
+                n_dev ? n_dev + b : nullptr, nw, thr, cls ? cls + (size_t)b * row_stride : nullptr, mask + (size_t)b * n * nw,
+                diagT + (size_t)b * n);
 }
 // one workgroup per segment: B greedy scans side by side on B compute units, the pass as long as the longest of them
 __global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_batch_kernel(const unsigned long long* __restrict__ mask,
@@ -431,54 +410,8 @@ __global__ __launch_bounds__(NMS_RED_THREADS) void nms_reduce_batch_kernel(const
                                                                            const int* __restrict__ n_dev, int nwp, long row_stride,
                                                                            long long* __restrict__ pick, int* __restrict__ count) {
   const int b = blockIdx.x;
-  nms_reduce_body(mask + (size_t)b * n * nwp, diagT + (size_t)b * n, sorted + (size_t)b * n, n, n_dev + b, nwp,
-                  pick + (size_t)b * row_stride, count + b);
-}
-
-size_t nms_workspace_bytes(int n) {
-  size_t nw = (size_t)cdiv(n, 64);
-  size_t b = 0;
-  b += (size_t)n * 4 * 4;          // area, key, sorted, rank
-  b = (b + 255) / 256 * 256;
-  b += (size_t)n * nw * 8;         // mask
-  b = (b + 255) / 256 * 256;
-  b += (size_t)n * 8;              // the diagonal blocks transposed
-  return b + 256;
-}
-
-int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode, int key_col,
-               long long* pick, int* count, void* ws, size_t ws_bytes, hipStream_t s, const int* cls, const int* n_dev) {
-  if (n <= 0) {  // nms.lua:26-28
-    FR_HIP(hipMemsetAsync(count, 0, sizeof(int), s));
-    return FRCNN_OK;
-  }
-  FR_CHECK(ncols >= 4, "nms: boxes need >= 4 columns (got %d)", ncols);
-  FR_CHECK(key_mode >= 0 && key_mode <= 2, "nms: bad key_mode %d", key_mode);
-  FR_CHECK(key_mode != 2 || (key_col >= 1 && key_col <= ncols), "nms: key column %d out of range", key_col);
-  FR_CHECK(ws_bytes >= nms_workspace_bytes(n), "nms: workspace too small (%zu < %zu)", ws_bytes,
-           nms_workspace_bytes(n));
-  const int nw = cdiv(n, 64);
-  FR_CHECK((size_t)(nw + NMS_NU + 1) * 8 <= 64 * 1024, "nms: n=%d too large (max 523968)", n);
-  char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-  float* area = (float*)base;
-  float* key = area + n;
-  int* sorted = (int*)(key + n);
-  int* rank = sorted + n;
-  size_t off = ((size_t)n * 16 + 255) / 256 * 256;
-  unsigned long long* mask = (unsigned long long*)(base + off);
-  unsigned long long* diagT = (unsigned long long*)(base + (off + (size_t)n * nw * 8 + 255) / 256 * 256);
-  double pair_bytes = 20.0 * n;
-  FR_LAUNCH(KC_NMS, 0, pair_bytes, s, nms_prep_kernel, dim3(cdiv(n, 256)), dim3(256), 0, boxes, n, n_dev, ncols,
-            key_mode, key_col, area, key);
-  FR_HIP(hipMemsetAsync(rank, 0, (size_t)n * 4, s));
-  FR_LAUNCH(KC_NMS, 0, 8.0 * n, s, nms_rank_kernel, dim3(cdiv(n, 256), cdiv(n, NMS_RANK_SLICE)), dim3(256), 0, key, n, n_dev, rank);
-  FR_LAUNCH(KC_NMS, 0, 8.0 * n, s, nms_scatter_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (const int*)rank, n, n_dev, sorted);
-  FR_LAUNCH(KC_NMS, 3.5 * n * (double)n, 8.0 * n * nw / 2, s, nms_mask_kernel, dim3(nw, nw), dim3(64), 0,
-            boxes, ncols, area, sorted, n, n_dev, nw, overlap, cls, mask, diagT);
-  FR_LAUNCH(KC_NMS, 0, 8.0 * n * nw / 2, s, nms_reduce_kernel, dim3(1), dim3(NMS_RED_THREADS), (size_t)(nw + NMS_NU + 1) * 8, mask,
-            (const unsigned long long*)diagT, sorted, n, n_dev, nw, pick, count);
-  FR_LAUNCH_CHECK();
-  return FRCNN_OK;
+  nms_reduce_body(mask + (size_t)b * n * nwp, diagT + (size_t)b * n, sorted + (size_t)b * n, n, n_dev ? n_dev + b : nullptr,
+                  nwp, pick + (size_t)b * row_stride, count + b);
 }
 
 // Workspace of nms_device_batch: the work arrays of all segments side by side ([4][B][n] area, key, sorted, rank -- so that the
@@ -502,7 +435,6 @@ int nms_device_batch(const float* boxes, int B, long row_stride, int n, const in
     FR_HIP(hipMemsetAsync(count, 0, sizeof(int) * (size_t)B, s));
     return FRCNN_OK;
   }
-  FR_CHECK(n_dev, "nms_batch: NULL device counts");
   FR_CHECK(B <= 65535, "nms_batch: %d segments (at most 65535)", B);
   FR_CHECK(row_stride >= n, "nms_batch: row stride %ld < %d rows per segment", row_stride, n);
   FR_CHECK(ncols >= 4, "nms: boxes need >= 4 columns (got %d)", ncols);
@@ -535,6 +467,13 @@ int nms_device_batch(const float* boxes, int B, long row_stride, int n, const in
             count);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
+}
+
+// The single problem (nms(), frcnn_nms_device[_classes|_n], frcnn_nms_host): one segment of n rows.
+size_t nms_workspace_bytes(int n) { return nms_batch_workspace_bytes(1, n); }
+int nms_device(const float* boxes, int n, int ncols, float overlap, int key_mode, int key_col, long long* pick, int* count,
+               void* ws, size_t ws_bytes, hipStream_t s, const int* cls, const int* n_dev) {
+  return nms_device_batch(boxes, 1, n, n, n_dev, ncols, overlap, key_mode, key_col, cls, pick, count, ws, ws_bytes, s);
 }
 
 }  // namespace frcnn

@@ -19,8 +19,8 @@ struct ScanArgs {
   int start[5];  // prefix of 3*H*W per layer
 };
 
-// (the code of both kernels is a body shared with the batched forms below, which take the frame from a grid dimension: the maps
-// of frame b lie map_off floats behind a.map[]; first / step: the kernel's grid-stride loop over the anchors)
+// (the code of both kernels is a body; the kernels below take the frame from a grid dimension: the maps of frame b lie map_off
+// floats behind a.map[]; first / step: the kernel's grid-stride loop over the anchors)
 __device__ __forceinline__ void rpn_scan_body(const ScanArgs& a, size_t map_off, int first, int step, const float* __restrict__ aw,
                                               const float* __restrict__ ah, double img_w, double img_h, double thr,
                                               unsigned char* __restrict__ flag, float* __restrict__ dp, double* __restrict__ drect) {
@@ -60,11 +60,6 @@ __device__ __forceinline__ void rpn_scan_body(const ScanArgs& a, size_t map_off,
     }
     flag[n] = f;
   }
-}
-__global__ void rpn_scan_kernel(ScanArgs a, const float* __restrict__ aw, const float* __restrict__ ah,
-                                double img_w, double img_h, double thr, unsigned char* __restrict__ flag,
-                                float* __restrict__ dp, double* __restrict__ drect) {
-  rpn_scan_body(a, 0, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, aw, ah, img_w, img_h, thr, flag, dp, drect);
 }
 
 // single workgroup, ordered compaction by wave ballots
@@ -112,17 +107,9 @@ __device__ __forceinline__ void rpn_compact_body(const ScanArgs& a, const unsign
   }
   if (threadIdx.x == 0) *count = base_sh;
 }
-__global__ __launch_bounds__(1024) void rpn_compact_kernel(ScanArgs a, const unsigned char* __restrict__ flag,
-                                                           const float* __restrict__ dp,
-                                                           const double* __restrict__ drect, int cap,
-                                                           float* __restrict__ match_p, int* __restrict__ match_idx,
-                                                           double* __restrict__ match_rect,
-                                                           float* __restrict__ match_box, int* __restrict__ count) {
-  rpn_compact_body(a, flag, dp, drect, cap, match_p, match_idx, match_rect, match_box, count);
-}
 
 // ---- B frames in one pass (Detector:detect_batch).  Frame b's head maps are a.map[l] + b * slot_stride floats, its scratch
-// slice b of the workspace (ws_stride bytes apart, laid out like the single-frame workspace), its matches rows
+// slice b of the workspace (ws_stride bytes apart: rects, p, flags), its matches rows
 // [b * cap, b * cap + count[b]) of the match arrays.  The threshold test is one launch with the frame as grid dimension y, the
 // ordered compaction one launch of one workgroup per frame.
 struct ScanSlice { double* drect; float* dp; unsigned char* flag; };
@@ -159,38 +146,6 @@ static void fill_scan_args(const RpnLayers& L, ScanArgs* a) {
   }
 }
 
-size_t rpn_scan_workspace_bytes(const RpnLayers& L) {
-  ScanArgs a;
-  fill_scan_args(L, &a);
-  size_t n = (size_t)a.start[4];
-  return 256 + n * 40 + ((n + 255) / 256) * 256;
-}
-
-int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, double img_w,
-             double img_h, double p_threshold, int cap, float* match_p, int* match_idx,
-             double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
-             hipStream_t s) {
-  ScanArgs a;
-  fill_scan_args(L, &a);
-  for (int l = 0; l < 4; ++l)
-    FR_CHECK(L.H[l] <= 200 && L.W[l] <= 200, "rpn_scan: head map %d is %dx%d, anchor tables hold 200 (Anchors.lua:15)",
-             l + 1, L.H[l], L.W[l]);
-  const size_t n = (size_t)a.start[4];
-  FR_CHECK(ws_bytes >= rpn_scan_workspace_bytes(L), "rpn_scan: workspace too small");
-  char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-  double* drect = (double*)base;
-  float* dp = (float*)(base + n * 32);
-  unsigned char* flag = (unsigned char*)(base + n * 36 + 64);
-  int grid = (int)std::min<size_t>((n + 255) / 256, 1024);
-  FR_LAUNCH(KC_RPN, 0, n * 24.0, s, rpn_scan_kernel, dim3(grid), dim3(256), 0, a, anchor_w, anchor_h, img_w,
-            img_h, p_threshold, flag, dp, drect);
-  FR_LAUNCH(KC_RPN, 0, n * 1.0, s, rpn_compact_kernel, dim3(1), dim3(1024), 0, a,
-            (const unsigned char*)flag, (const float*)dp, (const double*)drect, cap, match_p, match_idx,
-            match_rect, match_box, count);
-  FR_LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
 static size_t rpn_scan_slice_bytes(size_t n) { return (n * 40 + ((n + 255) / 256) * 256 + 255) / 256 * 256; }
 size_t rpn_scan_batch_workspace_bytes(const RpnLayers& L, int B) {
   ScanArgs a;
@@ -220,6 +175,15 @@ int rpn_scan_batch(const RpnLayers& L, int B, long slot_stride, const float* anc
             match_idx, match_rect, match_box, count);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
+}
+
+// The single frame (frcnn_rpn_scan): one slot.  (cap < 0 holds no row, like cap == 0.)
+size_t rpn_scan_workspace_bytes(const RpnLayers& L) { return rpn_scan_batch_workspace_bytes(L, 1); }
+int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, double img_w, double img_h, double p_threshold,
+             int cap, float* match_p, int* match_idx, double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
+             hipStream_t s) {
+  return rpn_scan_batch(L, 1, 0, anchor_w, anchor_h, img_w, img_h, p_threshold, std::max(cap, 0), match_p, match_idx, match_rect,
+                        match_box, count, ws, ws_bytes, s);
 }
 
 // ------------------------------------------------------------------------------------------

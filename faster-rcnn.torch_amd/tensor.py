@@ -2,6 +2,7 @@
 (what `torch.CudaTensor` is to the reference's Lua code).  PyTorch tensors are accepted wherever a
 device pointer is needed (`.data_ptr()`); nothing here computes anything."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -93,6 +94,15 @@ class DeviceTensor(object):
 
     def offset_view(self, elem_offset, shape):
         return DeviceTensor(self.ptr + elem_offset * self.dtype.itemsize, shape, self.dtype, owner=self)
+
+    def segment(self, b, rows=None):
+        """Segment b of a tensor of shape (B, S, ...): the view of its S rows, or of the first `rows` of them.  The offset
+        follows from this tensor's shape and dtype (plain ints: hosts build these views between a read-back and a launch)."""
+        B, S = self.shape[:2]
+        if not 0 <= b < B or not (rows is None or 0 <= rows <= S):
+            raise IndexError("segment %r (rows %r) of a tensor of shape %r" % (b, rows, self.shape))
+        tail = self.shape[2:]
+        return self.offset_view(b * S * math.prod(tail), ((S if rows is None else rows),) + tail)
 
     def zero_(self, stream=None):
         _lib.call("frcnn_zero", C.c_void_p(self.ptr), self.nbytes, stream_ptr(stream))

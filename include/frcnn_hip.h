@@ -145,12 +145,12 @@ int frcnn_nms_device_classes(const float *boxes, int n, int ncols, float overlap
 int frcnn_nms_device_n(const float *boxes, int n_cap, const int *n_dev, int ncols, float overlap, int key_mode, int key_col,
                        const int *cls, long long *pick, int *count, void *workspace, size_t workspace_bytes, void *stream);
 /* B independent problems in ONE pass (Detector:detect_batch, and :detect with B = 1; every stage one launch with the segment
- * as a grid dimension, the
- * greedy scans as B workgroups side by side).  Segment b: rows boxes + b*row_stride*ncols, count min(n_dev[b], n_cap) (device
- * int[B], required), cls + b*row_stride (optional), picks pick + b*row_stride (1-based rows WITHIN the segment), survivor
- * count count[b].  row_stride >= n_cap.  Per segment the result is bit for bit frcnn_nms_device_n on that segment; a segment
- * with count 0 writes count[b] = 0 and nothing else.  Workspace: frcnn_nms_batch_workspace_bytes(B, n_cap) -- the masks are
- * n_cap^2 / 8 bytes per segment (33.5 MB at 16 384). */
+ * as a grid dimension, the greedy scans as B workgroups side by side; the entry points above are this pass with B = 1).
+ * Segment b: rows boxes + b*row_stride*ncols, count min(n_dev[b], n_cap) (device int[B], required), cls + b*row_stride
+ * (optional), picks pick + b*row_stride (1-based rows WITHIN the segment), survivor count count[b].  row_stride >= n_cap.
+ * Per segment the result is bit for bit frcnn_nms_device_n on that segment; a segment with count 0 writes count[b] = 0 and
+ * nothing else.  Workspace: frcnn_nms_batch_workspace_bytes(B, n_cap) -- the masks are n_cap^2 / 8 bytes per segment
+ * (33.5 MB at 16 384). */
 size_t frcnn_nms_batch_workspace_bytes(int B, int n_cap);
 int frcnn_nms_device_batch(const float *boxes, int B, long long row_stride, int n_cap, const int *n_dev, int ncols, float overlap,
                            int key_mode, int key_col, const int *cls, long long *pick, int *count, void *workspace,
@@ -205,17 +205,13 @@ int frcnn_roi_windows(const double *rect, const long long *pick, int k, const in
  * kc[K] = class, keep_row[K] = r (0-based); *K_dev = their number (device).  All outputs need room for R rows. */
 int frcnn_detect_post(const int *cls, const float *conf, const float *bbox, const double *rect, const long long *pick, int R,
                       int bgclass, double min_conf, float *bb, int *kc, int *keep_row, double *r2, int *K_dev, void *stream);
-/* frcnn_detect_gather: one record of 16 doubles per winner q < min(*nwin_dev, cap), in the pick order wpick of the
- * per-class NMS over bb/kc: {class, candidate row (1-based), confidence (log-prob), p (anchor log-prob), anchor rect x4,
- * r2 x4, anchor index {layer,aspect,y,x}} -- everything Detector.lua:116-122 puts into a detection's table. */
-int frcnn_detect_gather(const long long *wpick, const int *nwin_dev, int cap, const int *keep_row, const int *kc,
-                        const float *bb, const double *r2, const long long *pick, const float *match_p,
-                        const double *match_rect, const int *match_idx, double *rec, void *stream);
-/* frcnn_detect_gather for B frames in one launch (Detector:detect_batch, and Detector:detect with B = 1), all winner tables in
- * ONE buffer (one read-back): frame b's table starts at
- * rec + b*(row_stride + 1)*16 doubles -- a 128-byte header whose first four ints are the frame's counts, then one record per
- * winner q < min(winners, row_stride).  counts: device int[4][B] = {matches, candidates, survivors of the class test,
- * winners} per frame.  wpick / keep_row / kc / bb / r2 hold row_stride rows per frame, pick / match_* match_stride rows. */
+/* frcnn_detect_gather_batch: the winner tables of B frames in one launch (Detector:detect_batch, and Detector:detect with
+ * B = 1), all in ONE buffer (one read-back): frame b's table starts at rec + b*(row_stride + 1)*16 doubles -- a 128-byte header
+ * whose first four ints are the frame's counts, then one record of 16 doubles per winner q < min(winners, row_stride), in the
+ * pick order wpick of the per-class NMS over bb/kc: {class, candidate row (1-based), confidence (log-prob), p (anchor
+ * log-prob), anchor rect x4, r2 x4, anchor index {layer,aspect,y,x}} -- everything Detector.lua:116-122 puts into a
+ * detection's table.  counts: device int[4][B] = {matches, candidates, survivors of the class test, winners} per frame.
+ * wpick / keep_row / kc / bb / r2 hold row_stride rows per frame, pick / match_* match_stride rows. */
 int frcnn_detect_gather_batch(const long long *wpick, const int *counts, int B, int row_stride, const int *keep_row,
                               const int *kc, const float *bb, const double *r2, const long long *pick, long long match_stride,
                               const float *match_p, const double *match_rect, const int *match_idx, double *rec, void *stream);
@@ -343,7 +339,7 @@ int frcnn_rpn_scan(const float *const *maps_host, const int *H_host, const int *
  * frame 0, frame b's are slot_stride
  * floats further (every map); one launch for the threshold test, one for the ordered compaction with one workgroup per
  * frame.  Frame b's matches are rows [b*cap, b*cap + min(count[b], cap)) of the match arrays, count: device int[B].  Per
- * frame bit-identical to frcnn_rpn_scan. */
+ * frame bit-identical to frcnn_rpn_scan, which is this pass with B = 1. */
 size_t frcnn_rpn_scan_batch_workspace_bytes(const int *H_host, const int *W_host, int B);
 int frcnn_rpn_scan_batch(const float *const *maps_host, const int *H_host, const int *W_host, int B, long long slot_stride,
                          const float *anchor_w, const float *anchor_h, double img_w, double img_h, double p_threshold,
@@ -377,7 +373,7 @@ int frcnn_topk_select(const float *score, int B, long long stride, int n_cap, co
  * j < min(k_dev[b], k_cap) of segment b comes from source row sel_row[b*sel_stride + j] (0-based, as frcnn_topk_select wrote
  * it; sel_row NULL: row j itself, k_dev then being the scan's own count).  Destinations, any of which may be NULL: dst_p,
  * dst_idx[4], dst_rect[4] (double), dst_box[4], box5[5] = {box, p} (the first NMS's input under order = "score"), row = the
- * 1-based original scan row.  frcnn_roi_windows, frcnn_detect_post and frcnn_detect_gather[_batch] then run unchanged on the
+ * 1-based original scan row.  frcnn_roi_windows, frcnn_detect_post and frcnn_detect_gather_batch then run unchanged on the
  * compact arrays; with sel_row NULL the call only builds box5 for all matches -- no host round trip between scan and NMS in
  * any mode.  The 16-byte rows (idx, box, rect) must be 16-byte aligned. */
 int frcnn_rpn_gather_rows(const float *match_p, const int *match_idx, const double *match_rect, const float *match_box, int B,

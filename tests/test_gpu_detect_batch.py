@@ -162,7 +162,11 @@ def test_rpn_scan_batch_equals_rpn_scan_per_slot(F, small_cfg):
     for k in got:
         assert np.all(got[k][B * cap:] == SENTINEL), k
     wsb1 = L.frcnn_rpn_scan_workspace_bytes(Hs, Ws)
-    ws1 = F.DeviceTensor.empty((wsb1,), np.uint8)
+    # (the single call runs on one slice of the batch layout, rounded up to 256 bytes -- 26 544 x 40 is no multiple: nothing may be
+    # stored behind the size the library asked for)
+    assert wsb1 == L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, 1) and (cap * 40) % 256 != 0
+    guard = np.full(wsb1 + 256, 0xA5, np.uint8)
+    ws1 = F.DeviceTensor.from_numpy(guard)
     for b in range(B):
         s = outputs(cap)
         c1 = F.DeviceTensor.zeros((1,), np.int32)
@@ -175,6 +179,7 @@ def test_rpn_scan_batch_equals_rpn_scan_per_slot(F, small_cfg):
             seg = got[k][b * cap:(b + 1) * cap]
             assert np.array_equal(seg[:n], s[k].numpy()[:n]), "slot %d: %s" % (b, k)
             assert np.all(seg[n:] == SENTINEL), "slot %d: stray stores behind the matches of %s" % (b, k)
+    assert np.all(ws1.numpy()[wsb1:] == 0xA5), "frcnn_rpn_scan stored behind its workspace"
     print("scan batch: matches per slot", counts[:B].tolist())
     assert counts[0] == 0 and counts[1] == cap
     assert all(0 < c < cap for c in counts[2:B])

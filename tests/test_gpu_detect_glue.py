@@ -99,15 +99,38 @@ def test_detect_post_and_gather(F):
     assert np.array_equal(got_r2[:, :2], want_r2[:, :2])               # no exp involved: bit for bit
     gb = bb.numpy()[:k]
     assert np.allclose(gb[:, :4], want_r2.astype(np.float32), rtol=2e-7, atol=0) and np.array_equal(gb[:, 4], conf[keep])
-    # winner records for an arbitrary pick list over the survivors
+    # winner tables (frcnn_detect_gather_batch) for an arbitrary pick list over the survivors: the frame alone; as frame 0 of two
+    # with strides beyond the row counts and an empty frame 1 (all four counts 0) behind it; and as frames 0 and 2 of three around
+    # an empty one, frame 2 with its winners in reverse order (there every stride multiplies a frame that holds data)
     wp = (rng.permutation(k)[:min(k, 300)] + 1).astype(np.int64)
-    dwp = F.DeviceTensor.from_numpy(wp); nw = F.DeviceTensor.from_numpy(np.array([len(wp)], np.int32))
-    rec = F.DeviceTensor.empty((R, 16), np.float64)
-    F._lib.call("frcnn_detect_gather", F.ptr(dwp), F.ptr(nw), R, F.ptr(kr), F.ptr(kc), F.ptr(bb), F.ptr(r2), F.ptr(d["pick"]),
-                F.ptr(d["mp"]), F.ptr(d["rect"]), F.ptr(d["midx"]), F.ptr(rec), F.stream_ptr())
-    g = rec.numpy()[:len(wp)]
-    j = wp - 1
-    i = pick[keep[j]] - 1
-    assert np.array_equal(g[:, 0], cls[keep[j]]) and np.array_equal(g[:, 1], keep[j] + 1)
-    assert np.array_equal(g[:, 2], conf[keep[j]].astype(np.float64)) and np.array_equal(g[:, 3], mp[i].astype(np.float64))
-    assert np.array_equal(g[:, 4:8], rect[i]) and np.array_equal(g[:, 8:12], got_r2[j]) and np.array_equal(g[:, 12:16], midx[i])
+    SENTINEL = -12345.0
+
+    def strided(per_frame, B, stride):    # frame b = the rows of per_frame[b], everything else zero
+        a0 = next(iter(per_frame.values()))
+        out = np.zeros((B, stride) + a0.shape[1:], a0.dtype)
+        for b, a in per_frame.items():
+            out[b, :len(a)] = a
+        return F.DeviceTensor.from_numpy(out)
+    for B, row_stride, match_stride, full in ((1, R, nm, (0,)), (2, R + 5, nm + 3, (0,)), (3, R + 5, nm + 3, (0, 2))):
+        wps = {b: wp[::-1].copy() if b else wp for b in full}
+        counts = np.zeros((4, B), np.int32)
+        counts[:, list(full)] = np.array([[nm, R, k, len(wp)]]).T
+        per_row = [strided(wps, B, row_stride)] + [strided({b: a for b in full}, B, row_stride)
+                                                   for a in (kr.numpy(), kc.numpy(), bb.numpy(), r2.numpy())]
+        per_match = [strided({b: a for b in full}, B, match_stride) for a in (pick, mp, rect, midx)]
+        rec, dcounts = F.DeviceTensor.from_numpy(np.full((B, row_stride + 1, 16), SENTINEL)), F.DeviceTensor.from_numpy(counts)
+        F._lib.call("frcnn_detect_gather_batch", F.ptr(per_row[0]), F.ptr(dcounts), B, row_stride,
+                    *[F.ptr(t) for t in per_row[1:]], F.ptr(per_match[0]), match_stride, *[F.ptr(t) for t in per_match[1:]],
+                    F.ptr(rec), F.stream_ptr())
+        tab = rec.numpy()
+        for b in full:
+            g = tab[b, 1:1 + len(wp)]
+            j = wps[b] - 1
+            i = pick[keep[j]] - 1
+            assert np.array_equal(g[:, 0], cls[keep[j]]) and np.array_equal(g[:, 1], keep[j] + 1)
+            assert np.array_equal(g[:, 2], conf[keep[j]].astype(np.float64)) and np.array_equal(g[:, 3], mp[i].astype(np.float64))
+            assert np.array_equal(g[:, 4:8], rect[i]) and np.array_equal(g[:, 8:12], got_r2[j]) and np.array_equal(g[:, 12:16], midx[i])
+        for b in range(B):   # the header: the frame's four counts, nothing else; no row behind the last winner is written
+            assert tab[b, 0].view(np.int32)[:4].tolist() == counts[:, b].tolist()
+            assert np.all(tab[b, 0, 2:] == SENTINEL)
+            assert np.all(tab[b, 1 + counts[3, b]:] == SENTINEL)

@@ -21,7 +21,7 @@ def test_nms_known_answer_quirk(F):
     assert F.nms(boxes[:1], 0.25).tolist() == [1]
 
 
-@pytest.mark.parametrize("n", [2, 63, 64, 65, 129, 300, 2000, 6000])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 129, 300, 2000, 6000])
 @pytest.mark.parametrize("thr", [0.25, 0.1])
 def test_nms_matches_oracle(F, O, n, thr):
     rng = np.random.RandomState(n)

@@ -207,8 +207,9 @@ def test_lua_binding_declares_and_the_drop_in_calls_them():
 def test_python_detector_surface(F):
     import inspect
     sig = inspect.signature(F.Detector.__init__)
-    assert list(sig.parameters)[1:] == ["model", "static_weights", "proposals"]
+    assert list(sig.parameters)[1:] == ["model", "static_weights", "proposals", "nms"]
     assert sig.parameters["static_weights"].default is False and sig.parameters["proposals"].default is None
+    assert sig.parameters["nms"].default is None
     assert callable(F.Detector.proposals) and callable(F.Detector.set_proposals)
     assert "topk" == F._lib.KC_NAMES[-1]
     for name in ("frcnn_topk_select", "frcnn_topk_select_workspace_bytes", "frcnn_rpn_gather_rows"):
