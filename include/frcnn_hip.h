@@ -393,7 +393,10 @@ int frcnn_rpn_loss(const float *const *maps_host, float *const *deltas_host, con
                    double *ex_loss, float *crtarget, float *cctarget, void *stream);
 
 /* acc[0] += sum_e ex_loss[e][0]; acc[1] += sum_e ex_loss[e][1] (device fp64; the Lua accumulators
- * cls_loss / reg_loss of objective.lua:52, summed in example order). */
+ * cls_loss / reg_loss of objective.lua:52).  The order of the sum is FIXED but is not example order: 64 partial sums
+ * (partial k: examples k, k + 64, ... in that order), folded pairwise (k with k + 32, then + 16, ... + 1), and the total added
+ * to acc last.  Two runs give the same bits; the result is within E * 2^-53 * (|acc| + sum_e |ex_loss[e]|) of the exact sum.
+ * E <= 0: no launch, acc is not touched. */
 int frcnn_loss_accumulate(const double *ex_loss, int E, double *acc, void *stream);
 
 /* ---- nn.Linear (models/model_utilities.lua:82,99,103) -------------------------------- */
