@@ -15,31 +15,15 @@
 #include <vector>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 
 #include "kernels.h"
+#include "own.h"
 
 namespace frcnn {
 
 static const int HEAD_OUT = 18;  // 3 * (2 + 4), model_utilities.lua:33
 static const int SPARSE_MAX_POS = 512;  // above this the dense head backward is used
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  bool owned = true;
-  void view(void* ptr, size_t n) { p = ptr; bytes = n; owned = false; }  // slice of an arena
-  int ensure(size_t need) {
-    if (need <= bytes) return FRCNN_OK;
-    if (p && owned) (void)hipFree(p);
-    owned = true;
-    p = nullptr; bytes = 0;
-    FR_HIP(hipMalloc(&p, need + 64));   // (64 bytes of slack: conv_wgradx's unaligned 16-byte segment loads may read 12 bytes past a tensor)
-    bytes = need;
-    return FRCNN_OK;
-  }
-  void release() { if (p && owned) (void)hipFree(p); p = nullptr; bytes = 0; owned = true; }
-  float* f() const { return (float*)p; }
-};
 
 struct Conv {
   int Cin, Cout, k, pad;
@@ -85,8 +69,8 @@ struct Head {
   DevBuf spD, spHX, spHY, spGH, spCol, spDX;  // scratch of the sparse backward pass (per anchor net: they run concurrently)
   DevBuf spOut, spSlab;       // sparse training path (heads.hip): the 18 output planes at the sampled positions; K-split partial sums of HX
   hipStream_t stream = nullptr;  // this anchor net's own stream (forward and sparse backward beside the other anchor nets)
-  hipEvent_t done = nullptr;     // last work queued on `stream`
-  hipEvent_t gin_done = nullptr; // sparse backward: this net's contribution to the pooled map's gradient has been added (the
+  Event done;                    // last work queued on `stream`
+  Event gin_done;                // sparse backward: this net's contribution to the pooled map's gradient has been added (the
                                  // backbone's backward pass waits for THIS; the parameter gradients behind it are joined at its end)
   bool gin_recorded = false;
 };
@@ -111,9 +95,15 @@ struct ClsLayer {
 
 using namespace frcnn;
 
+// an on/off switch of the environment (FRCNN_*): unset = dflt, otherwise whether it reads as a non-zero number
+static bool env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) != 0 : dflt;
+}
+
 static int g_drop_compact = -1;   // option "drop_compact" (environment FRCNN_DROP_COMPACT), default on
 static int drop_compact_on() {
-  if (g_drop_compact < 0) g_drop_compact = getenv("FRCNN_DROP_COMPACT") ? (atoi(getenv("FRCNN_DROP_COMPACT")) != 0) : 1;
+  if (g_drop_compact < 0) g_drop_compact = env_flag("FRCNN_DROP_COMPACT", true);
   return g_drop_compact;
 }
 // The library's streams are the PROCESS's, not a model's: the runtime multiplexes every stream onto four hardware queues
@@ -122,6 +112,8 @@ static int drop_compact_on() {
 // Slot 0: the side stream (weight gradients), 1: the classification net's weight gradients / the update stream, 2..6: anchor nets.
 static int pool_stream(int slot, hipStream_t* out) {
   static hipStream_t pool[8] = {};
+  static std::mutex mu;   // (two host threads may drive two models)
+  std::lock_guard<std::mutex> lock(mu);
   if (!pool[slot]) FR_HIP(hipStreamCreateWithFlags(&pool[slot], hipStreamNonBlocking));
   *out = pool[slot];
   return FRCNN_OK;
@@ -130,7 +122,7 @@ static int pool_stream(int slot, hipStream_t* out) {
 // ---- the anchor nets' sparse training path (heads.hip) ---------------------------------------------------------------------
 static int g_sparse_heads = -1;   // option "sparse_heads" (environment FRCNN_SPARSE_HEADS), default on
 static int sparse_heads_on() {
-  if (g_sparse_heads < 0) g_sparse_heads = getenv("FRCNN_SPARSE_HEADS") ? (atoi(getenv("FRCNN_SPARSE_HEADS")) != 0) : 1;
+  if (g_sparse_heads < 0) g_sparse_heads = env_flag("FRCNN_SPARSE_HEADS", true);
   return g_sparse_heads;
 }
 static int g_static_weights = 0;   // option "static_weights" (see forward_impl)
@@ -185,23 +177,23 @@ struct frcnn_model {
   // per-step tables of the compact blocks (see Block::dc_on): a ring of page-locked host slots and device slots, one
   // asynchronous copy per step: [PackXJob table of the step][kept-channel tables of the blocks]
   static const int DC_RING = 4;
-  char* dc_pin = nullptr; DevBuf dc_dev; size_t dc_slot_bytes = 0, dc_idx_off = 0; unsigned dc_step = 0;
-  hipEvent_t dc_ev[DC_RING] = {};             // slot s's copy to the device has run (a host that queues more than DC_RING passes ahead waits here)
+  PinBuf dc_pin; DevBuf dc_dev; size_t dc_slot_bytes = 0, dc_idx_off = 0; unsigned dc_step = 0;
+  Event dc_ev[DC_RING];                       // slot s's copy to the device has run (a host that queues more than DC_RING passes ahead waits here)
   std::vector<PackXJob> x3_host, x3_host16;   // the model's training pack jobs as built by ensure_shapes (plain | fp16 form), host copies
   std::vector<int> x3_conv;                   // ... the convolution each job belongs to (index into convs, -1: an anchor net)
   DevBuf dbg_expand;                          // frcnn_model_debug_buffer: a compact tensor laid out dense
-  std::vector<hipEvent_t> block_rd_ev;   // block b's weights and packs have been read for the last time (caller's stream, frcnn_pnet_backward)
+  std::vector<Event> block_rd_ev;   // block b's weights and packs have been read for the last time (caller's stream, frcnn_pnet_backward)
   hipStream_t side = nullptr;      // accGradParameters stream (runs beside the updateGradInput chain)
   hipStream_t cw = nullptr;        // the classification net's weight gradients / bias sums (beside its input-gradient chain)
-  hipEvent_t cw_fork = nullptr, cw_done = nullptr;
+  Event cw_done;                   // last work queued on `cw`
   bool cw_pending = false;         // work on `cw` that no stream has been made to wait for yet
-  std::vector<hipEvent_t> cw_ev;   // one fork point per layer + one for the two heads
-  std::vector<hipEvent_t> fork_ev;
-  hipEvent_t join_ev = nullptr;
+  std::vector<Event> cw_ev;        // one fork point per layer + one for the two heads
+  std::vector<Event> fork_ev;      // fork points of the side stream and the anchor nets' streams (fork_to)
+  Event join_ev;                   // join point of the side stream (join_side_now)
   bool update_armed = false;       // a host has asked for the update stream (frcnn_model_update_stream): the passes record the
                                    // events its waits need (bwd_ev, block_rd_ev) -- each costs the caller's stream a marker packet
-  hipEvent_t bwd_ev = nullptr;     // the backbone's backward pass has begun on the caller's stream (anchor nets joined)
-  hipEvent_t upd_ev = nullptr, upd_join_ev = nullptr;   // fork / join points of the update stream (frcnn_model_update_*)
+  Event bwd_ev;                    // the backbone's backward pass has begun on the caller's stream (anchor nets joined)
+  Event upd_ev, upd_join_ev;       // fork / join points of the update stream (frcnn_model_update_*)
   bool head_x3_fresh = true;       // the anchor nets' split-operand packs and weight magnitudes match the last forward pass's weights
   int am_bb_off = 0, am_bb_n = 0, am_bb_grid = 0;   // AmaxJob sub-table: the backbone's weight tensors only
   int pk_bb_off = 0, pk_bb_n = 0, pk_bb_grid = 0;   // PackJob sub-table: the backbone's training packs only
@@ -209,14 +201,14 @@ struct frcnn_model {
                                    // leaves it to the call that knows the sampled positions: heads.hip)
   bool heads_sparse_fwd = false;   // ... and was then computed at the sampled positions only
   const float* last_w = nullptr;   // weight vector of the last forward pass
-  hipEvent_t heads_gin_ev = nullptr;   // sparse path: the anchor nets' contributions to the pooled maps' gradients have been added (side stream)
+  Event heads_gin_ev;              // sparse path: the anchor nets' contributions to the pooled maps' gradients have been added (side stream)
   bool heads_gin = false;
   bool heads_begun = false;        // anchor-net backward already running on the side stream
   bool heads_joined = false;       // ... and the caller's stream already waits for it
   bool side_busy = false;          // work was forked to the side stream and not joined yet
-  hipEvent_t loss_ev = nullptr;    // anchor losses of frcnn_pnet_anchor_loss_begin are final (side stream)
-  hipEvent_t chain_ev = nullptr;   // ... and the pooled-map gradient buffers are zeroed: the anchor nets' backward may start
-  std::vector<hipEvent_t> block_ev;   // block b's parameter gradients are final (recorded by frcnn_pnet_backward)
+  Event loss_ev;                   // anchor losses of frcnn_pnet_anchor_loss_begin are final (side stream)
+  Event chain_ev;                  // ... and the pooled-map gradient buffers are zeroed: the anchor nets' backward may start
+  std::vector<Event> block_ev;     // block b's parameter gradients are final (recorded by frcnn_pnet_backward)
   bool block_ev_valid = false;
   bool loss_pending = false;
   DevBuf wg_ws;                // split-K slab workspace of the weight-gradient kernels
@@ -315,6 +307,12 @@ static void build_layout(frcnn_model* m) {
   m->table.push_back({m->clsb_off, nc, 4, in});
   off += (long)in * nc + nc;
   m->total_params = off;
+  // the events by index (none is made before its first record: see Event)
+  m->block_ev.resize(m->blocks.size());
+  m->block_rd_ev.resize(m->blocks.size());
+  m->cw_ev.resize(m->cls.size() + 1);
+  // (fork_ev: one per backbone convolution in frcnn_pnet_backward, nblocks + 1 for the anchor nets' backward, 16 + i for anchor net i)
+  m->fork_ev.resize(std::max({m->convs.size(), m->blocks.size() + 2, 16 + m->heads.size()}));
 }
 
 static int ensure_conv(Conv& c, int H, int W, bool need_dgrad) {
@@ -528,11 +526,10 @@ static int ensure_shapes(frcnn_model* m, int H, int W) {
       for (size_t b = 0; b < m->blocks.size(); ++b) chans += (size_t)m->d.filters[b];
       m->dc_idx_off = (all.size() * sizeof(PackXJob) + 255) / 256 * 256;
       const size_t slot = (m->dc_idx_off + chans * 4 + 255) / 256 * 256;
-      if (slot != m->dc_slot_bytes) {
-        if (m->dc_pin) (void)hipHostFree(m->dc_pin);
-  for (auto e : m->dc_ev) if (e) (void)hipEventDestroy(e);
-        m->dc_pin = nullptr;
-        FR_HIP(hipHostMalloc((void**)&m->dc_pin, slot * frcnn_model::DC_RING, hipHostMallocDefault));
+      if (slot != m->dc_slot_bytes) {   // a new ring: no slot has a copy in flight, the first pass takes slot 0
+        for (auto& e : m->dc_ev) e.reset();
+        m->dc_step = 0;
+        FR_TRY(m->dc_pin.alloc(slot * frcnn_model::DC_RING));
         m->dc_dev.release();
         FR_TRY(m->dc_dev.ensure(slot * frcnn_model::DC_RING));
         m->dc_slot_bytes = slot;
@@ -606,41 +603,7 @@ int frcnn_model_create(const frcnn_model_desc* desc, frcnn_model** out) {
 
 int frcnn_model_destroy(frcnn_model* m) {
   if (!m) return FRCNN_OK;
-  auto rel = [](Conv& c) { c.wf.release(); c.wd.release(); c.wx.release(); c.wxd.release(); c.x.release(); c.gx.release(); };
-  for (auto& c : m->convs) rel(c);
-  for (auto& b : m->blocks) { b.scale.release(); b.pooled.release(); b.gpooled.release(); b.pidx.release(); b.dc_bias.release(); }
-  if (m->dc_pin) (void)hipHostFree(m->dc_pin);
-  for (auto e : m->dc_ev) if (e) (void)hipEventDestroy(e);
-  m->dc_dev.release(); m->dbg_expand.release();
-  for (auto& h : m->heads) {
-    rel(h.c3); rel(h.c1); h.delta.release(); h.spOut.release(); h.spSlab.release();
-    h.spD.release(); h.spHX.release(); h.spHY.release(); h.spGH.release(); h.spCol.release(); h.spDX.release();
-  }
-  for (auto& l : m->cls) {
-    l.lin.release(); l.pre.release(); l.post.release(); l.xhat.release(); l.invstd.release();
-    l.mask.release(); l.g.release(); l.xp.release(); l.xpT.release(); l.gp.release(); l.gpT.release(); l.am.release();
-  }
-  m->img.release(); m->wg_ws.release(); m->wg_ws_first.release(); m->pack_jobs.release(); m->x3_jobs.release(); m->zero_arena.release(); m->amax.release(); m->amax_ws.release(); m->amax_jobs.release();
-  for (auto e : m->fork_ev) (void)hipEventDestroy(e);
-  for (auto& h : m->heads) {
-    if (h.done) (void)hipEventDestroy(h.done);
-    if (h.gin_done) (void)hipEventDestroy(h.gin_done);
-  }
-  if (m->chain_ev) (void)hipEventDestroy(m->chain_ev);
-  if (m->join_ev) (void)hipEventDestroy(m->join_ev);
-  if (m->bwd_ev) (void)hipEventDestroy(m->bwd_ev);
-  if (m->heads_gin_ev) (void)hipEventDestroy(m->heads_gin_ev);
-  if (m->upd_ev) (void)hipEventDestroy(m->upd_ev);
-  if (m->upd_join_ev) (void)hipEventDestroy(m->upd_join_ev);
-  for (auto e : m->block_rd_ev) (void)hipEventDestroy(e);
-  for (auto e : m->cw_ev) (void)hipEventDestroy(e);
-  if (m->cw_fork) (void)hipEventDestroy(m->cw_fork);
-  if (m->cw_done) (void)hipEventDestroy(m->cw_done);
-  if (m->loss_ev) (void)hipEventDestroy(m->loss_ev);
-  for (auto e : m->block_ev) (void)hipEventDestroy(e);
-  m->delta_last.release(); m->feat_g.release(); m->logits.release(); m->lsm.release(); m->glog.release();
-  m->gtmp.release();
-  delete m;
+  delete m;   // (every buffer and event is given back by its field's type)
   return FRCNN_OK;
 }
 
@@ -700,7 +663,7 @@ int frcnn_model_localizer_layers(const frcnn_model* m, int output_index, int* la
 // ------------------------------------------------------------------------------------ pnet
 static int g_side_stream = -1;   // -1: not decided yet (environment FRCNN_SIDE_STREAM, default on)
 static bool side_enabled() {
-  if (g_side_stream < 0) g_side_stream = !(getenv("FRCNN_SIDE_STREAM") && atoi(getenv("FRCNN_SIDE_STREAM")) == 0) ? 1 : 0;
+  if (g_side_stream < 0) g_side_stream = env_flag("FRCNN_SIDE_STREAM", true);
   return g_side_stream != 0;
 }
 
@@ -708,11 +671,19 @@ static bool side_enabled() {
 // the cnet slice): with the option on (default) frcnn_cnet_backward queues them on a stream of their own, beside the
 // input-gradient chain that the ROI-pooling backward and the backbone wait for, and returns with that stream still busy --
 // frcnn_pnet_backward, the next frcnn_cnet_forward and frcnn_cnet_backward_join make the caller's stream wait for it.
-static int g_cnet_wgrad_async = getenv("FRCNN_CNET_WGRAD_ASYNC") ? (atoi(getenv("FRCNN_CNET_WGRAD_ASYNC")) != 0) : 1;
+static int g_cnet_wgrad_async = env_flag("FRCNN_CNET_WGRAD_ASYNC", true);
+
+// stream `to` waits for everything enqueued on `from` so far (event ev is re-recorded: its previous waiters are queued already).
+// The one place that pairs a record with a wait.
+static int chain(hipStream_t from, hipStream_t to, Event& ev) {
+  if (from == to) return FRCNN_OK;
+  FR_TRY(ev.record(from));
+  return ev.wait(to);
+}
 
 static int cw_join(frcnn_model* m, hipStream_t s) {
   if (m->cw_pending) {
-    FR_HIP(hipStreamWaitEvent(s, m->cw_done, 0));
+    FR_TRY(m->cw_done.wait(s));
     m->cw_pending = false;
   }
   return FRCNN_OK;
@@ -727,15 +698,7 @@ int frcnn_cnet_backward_join(frcnn_model* m, void* stream) {
 // the renewal of the packs made from it) while the caller's stream is still busy with the rest of the backward pass.  It is the
 // stream the classification net's weight gradients run on -- idle from the end of that stage to the end of the step -- so a
 // slice update queued on it is ordered behind those gradients by itself.
-static int ensure_update_stream(frcnn_model* m) {
-  if (!m->cw) {
-    FR_TRY(pool_stream(1, &m->cw));
-    FR_HIP(hipEventCreateWithFlags(&m->cw_done, hipEventDisableTiming));
-  }
-  if (!m->upd_ev) FR_HIP(hipEventCreateWithFlags(&m->upd_ev, hipEventDisableTiming));
-  if (!m->upd_join_ev) FR_HIP(hipEventCreateWithFlags(&m->upd_join_ev, hipEventDisableTiming));
-  return FRCNN_OK;
-}
+static int ensure_update_stream(frcnn_model* m) { return m->cw ? FRCNN_OK : pool_stream(1, &m->cw); }
 int frcnn_model_update_stream(frcnn_model* m, void** stream) {
   FR_CHECK(m && stream, "model_update_stream: null argument");
   FR_TRY(ensure_update_stream(m));
@@ -747,17 +710,13 @@ int frcnn_model_update_stream(frcnn_model* m, void** stream) {
 int frcnn_model_update_fork(frcnn_model* m, void* stream) {
   FR_CHECK(m != nullptr, "model_update_fork: null model");
   FR_TRY(ensure_update_stream(m));
-  FR_HIP(hipEventRecord(m->upd_ev, S(stream)));
-  FR_HIP(hipStreamWaitEvent(m->cw, m->upd_ev, 0));
-  return FRCNN_OK;
+  return chain(S(stream), m->cw, m->upd_ev);
 }
 // `stream` waits for everything queued on the update stream so far (before the next pass reads the weights and the packs)
 int frcnn_model_update_join(frcnn_model* m, void* stream) {
   FR_CHECK(m != nullptr, "model_update_join: null model");
   FR_TRY(ensure_update_stream(m));
-  FR_HIP(hipEventRecord(m->upd_join_ev, m->cw));
-  FR_HIP(hipStreamWaitEvent(S(stream), m->upd_join_ev, 0));
-  return FRCNN_OK;
+  return chain(m->cw, S(stream), m->upd_join_ev);
 }
 
 int frcnn_get_option(const char* name, int* value) {
@@ -792,30 +751,20 @@ int frcnn_set_option(const char* name, int value) {
   return FRCNN_OK;
 }
 
-static int ensure_head_streams(frcnn_model* m);
-static int ensure_side(frcnn_model* m) {
-  if (!m->side) {
-    FR_TRY(pool_stream(0, &m->side));
-    FR_HIP(hipEventCreateWithFlags(&m->join_ev, hipEventDisableTiming));
-    FR_HIP(hipEventCreateWithFlags(&m->loss_ev, hipEventDisableTiming));
-    FR_HIP(hipEventCreateWithFlags(&m->chain_ev, hipEventDisableTiming));
-    // FRCNN_HEAD_STREAMS=1: one stream per anchor net (the four nets are independent of each other: forward a k x k and
-    // a 1 x 1 convolution on a pooled map; backward on the sampled anchors ~17 small launches each), so that their chains
-    // run beside each other instead of one after the other.  Measured on the training step: the anchor nets' backward
-    // chains shrink from 670 to 310 us, but the classification net's chain on the caller's stream, which runs beside them,
-    // slows down by as much: 223.6 against 225.4 images/s (round 2).  Round 4: the two chains of the middle phase -- the
-    // anchor nets' and the classification net's -- are about equally long, so shortening ONE of them changes nothing; with
-    // the classification net's weight gradients off its chain as well (g_cnet_wgrad_async) the step goes from 3.11 to
-    // 3.02 ms, with either change alone it stays at 3.11.  On by default since then.
-    for (auto& h : m->heads) FR_HIP(hipEventCreateWithFlags(&h.done, hipEventDisableTiming));
-  }
-  return FRCNN_OK;
-}
+static int ensure_side(frcnn_model* m) { return m->side ? FRCNN_OK : pool_stream(0, &m->side); }
 
 // The anchor nets' own streams, made when the DENSE path first needs them (round 6): a stream that exists takes a share of a
 // hardware queue whether it is used or not, and the sparse training path (heads.hip) runs every anchor net on the side stream.
 static int ensure_head_streams(frcnn_model* m) {
-  static const int head_streams = getenv("FRCNN_HEAD_STREAMS") ? atoi(getenv("FRCNN_HEAD_STREAMS")) : 1;
+  // FRCNN_HEAD_STREAMS=1: one stream per anchor net (the four nets are independent of each other: forward a k x k and
+  // a 1 x 1 convolution on a pooled map; backward on the sampled anchors ~17 small launches each), so that their chains
+  // run beside each other instead of one after the other.  Measured on the training step: the anchor nets' backward
+  // chains shrink from 670 to 310 us, but the classification net's chain on the caller's stream, which runs beside them,
+  // slows down by as much: 223.6 against 225.4 images/s (round 2).  Round 4: the two chains of the middle phase -- the
+  // anchor nets' and the classification net's -- are about equally long, so shortening ONE of them changes nothing; with
+  // the classification net's weight gradients off its chain as well (g_cnet_wgrad_async) the step goes from 3.11 to
+  // 3.02 ms, with either change alone it stays at 3.11.  On by default since then.
+  static const bool head_streams = env_flag("FRCNN_HEAD_STREAMS", true);
   size_t hi = 0;
   for (auto& h : m->heads) {
     // (five workspace slots for streams of their own, head_slot(): a sixth anchor net shares the side stream and its slot)
@@ -830,58 +779,33 @@ static hipStream_t head_stream(frcnn_model* m, size_t i) { return m->heads[i].st
 // caller's and the side stream); build_layout gives streams of their own to at most five anchor nets
 static int head_slot(frcnn_model* m, size_t i) { return m->heads[i].stream ? 2 + (int)(i % 5) : 1; }
 
-// the caller's stream waits for everything queued on the side stream so far
+// stream s waits for everything queued on the anchor nets' own streams so far
 static int join_heads(frcnn_model* m, hipStream_t s) {
-  for (auto& h : m->heads) {
-    if (!h.stream) continue;
-    FR_HIP(hipEventRecord(h.done, h.stream));
-    FR_HIP(hipStreamWaitEvent(s, h.done, 0));
-  }
+  for (auto& h : m->heads)
+    if (h.stream) FR_TRY(chain(h.stream, s, h.done));
   return FRCNN_OK;
 }
+// ... for everything queued on the side stream so far
+static int join_side_now(frcnn_model* m, hipStream_t s) { return chain(m->side, s, m->join_ev); }
+// the caller's stream waits for whatever was forked off it and not joined yet: the anchor nets' streams and the side stream
 static int join_side(frcnn_model* m, hipStream_t s) {
   if (!m->side || !m->side_busy) return FRCNN_OK;
   FR_TRY(join_heads(m, s));
-  FR_HIP(hipEventRecord(m->join_ev, m->side));
-  FR_HIP(hipStreamWaitEvent(s, m->join_ev, 0));
+  FR_TRY(join_side_now(m, s));
   m->side_busy = false;
-  return FRCNN_OK;
-}
-
-// stream `to` waits for everything enqueued on `from` so far (event ev is re-recorded: its previous waiters are queued already)
-static int chain(hipStream_t from, hipStream_t to, hipEvent_t ev) {
-  if (from == to) return FRCNN_OK;
-  FR_HIP(hipEventRecord(ev, from));
-  FR_HIP(hipStreamWaitEvent(to, ev, 0));
-  return FRCNN_OK;
-}
-
-// side stream waits for everything enqueued on `s` so far
-static int fork_side(frcnn_model* m, hipStream_t s, size_t idx) {
-  FR_TRY(ensure_side(m));
-  while (m->fork_ev.size() <= idx) {
-    hipEvent_t e;
-    FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    m->fork_ev.push_back(e);
-  }
-  FR_HIP(hipEventRecord(m->fork_ev[idx], s));
-  FR_HIP(hipStreamWaitEvent(m->side, m->fork_ev[idx], 0));
-  m->side_busy = true;
   return FRCNN_OK;
 }
 
 // stream `to` (the side stream or an anchor net's own) waits for everything enqueued on `s` so far
 static int fork_to(frcnn_model* m, hipStream_t s, hipStream_t to, size_t idx) {
   FR_TRY(ensure_side(m));
-  while (m->fork_ev.size() <= idx) {
-    hipEvent_t e;
-    FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    m->fork_ev.push_back(e);
-  }
-  FR_HIP(hipEventRecord(m->fork_ev[idx], s));
-  FR_HIP(hipStreamWaitEvent(to, m->fork_ev[idx], 0));
+  FR_TRY(chain(s, to, m->fork_ev[idx]));
   m->side_busy = true;
   return FRCNN_OK;
+}
+static int fork_side(frcnn_model* m, hipStream_t s, size_t idx) {
+  FR_TRY(ensure_side(m));
+  return fork_to(m, s, m->side, idx);
 }
 
 // one anchor net: k x k conv -> PReLU (fused into the 1x1 loader) -> 1x1 conv (models/model_utilities.lua:31-34)
@@ -904,7 +828,7 @@ static bool any_compact(const frcnn_model* m) {
   for (auto& b : m->blocks) if (b.dc_on) return true;
   return false;
 }
-static bool fuse_act_on() { return !deterministic() && !(getenv("FRCNN_FUSE_ACT") && atoi(getenv("FRCNN_FUSE_ACT")) == 0); }
+static bool fuse_act_on() { return !deterministic() && env_flag("FRCNN_FUSE_ACT", true); }   // (read per call: the tests switch it)
 
 // Decides, block by block, whether this training pass runs compact, from the keep vectors -- drawn here with the very hash the
 // device kernel uses (common.h frcnn_keep_mask: the vectors on the device and on the host are the same), or read back from the
@@ -912,10 +836,10 @@ static bool fuse_act_on() { return !deterministic() && !(getenv("FRCNN_FUSE_ACT"
 // channels.  The job table follows in pack_compact.
 static int plan_compact(frcnn_model* m, int training, const float* const* drop_masks, unsigned long long seed) {
   for (auto& b : m->blocks) { b.dc_on = false; b.dc_idx = nullptr; }
-  if (!training || !drop_compact_on() || !fuse_act_on() || !m->dc_pin) return FRCNN_OK;
+  if (!training || !drop_compact_on() || !fuse_act_on() || !m->dc_pin.p) return FRCNN_OK;
   const unsigned slot = m->dc_step % frcnn_model::DC_RING;
-  if (m->dc_ev[slot]) FR_HIP(hipEventSynchronize(m->dc_ev[slot]));   // (the slot's previous copy, DC_RING passes ago: long done unless the host never looks back)
-  int* idx_host = (int*)(m->dc_pin + (size_t)slot * m->dc_slot_bytes + m->dc_idx_off);
+  FR_TRY(m->dc_ev[slot].sync());   // (the slot's previous copy, DC_RING passes ago: long done unless the host never looks back)
+  int* idx_host = (int*)(m->dc_pin.p + (size_t)slot * m->dc_slot_bytes + m->dc_idx_off);
   const int* idx_dev = (const int*)((char*)m->dc_dev.p + (size_t)slot * m->dc_slot_bytes + m->dc_idx_off);
   size_t at = 0;
   std::vector<float> keep;
@@ -956,7 +880,7 @@ static int plan_compact(frcnn_model* m, int training, const float* const* drop_m
 static int pack_compact(frcnn_model* m, const float* w, bool f16, hipStream_t s) {
   const unsigned slot = m->dc_step % frcnn_model::DC_RING;
   ++m->dc_step;
-  char* hslot = m->dc_pin + (size_t)slot * m->dc_slot_bytes;
+  char* hslot = m->dc_pin.p + (size_t)slot * m->dc_slot_bytes;
   char* dslot = (char*)m->dc_dev.p + (size_t)slot * m->dc_slot_bytes;
   const std::vector<PackXJob>& src = f16 ? m->x3_host16 : m->x3_host;
   PackXJob* jobs = (PackXJob*)hslot;
@@ -990,8 +914,7 @@ static int pack_compact(frcnn_model* m, const float* w, bool f16, hipStream_t s)
   }
   const int grid = conv_x3_pack_assign_blocks(jobs, n);
   FR_HIP(hipMemcpyAsync(dslot, hslot, m->dc_slot_bytes, hipMemcpyHostToDevice, s));
-  if (!m->dc_ev[slot]) FR_HIP(hipEventCreateWithFlags(&m->dc_ev[slot], hipEventDisableTiming));
-  FR_HIP(hipEventRecord(m->dc_ev[slot], s));
+  FR_TRY(m->dc_ev[slot].record(s));
   FR_TRY(conv_x3_pack_multi(w, (const PackXJob*)dslot, n, grid, s));
   return FRCNN_OK;
 }
@@ -1307,8 +1230,7 @@ static int backward_head(frcnn_model* m, Head& h, const float* w, float* grad, h
       FR_TRY(col2im_positions_add(DX, a.Cin, a.H, a.W, a.k, a.Wo, pos, P, in.gpooled.f(), s));
     }
     if (h.stream && s == h.stream) {   // (on its own stream: see Head::gin_done)
-      if (!h.gin_done) FR_HIP(hipEventCreateWithFlags(&h.gin_done, hipEventDisableTiming));
-      FR_HIP(hipEventRecord(h.gin_done, s));
+      FR_TRY(h.gin_done.record(s));
       h.gin_recorded = true;
     }
     // 1x1 conv: gW1[18][n] += D[18][P] * HY[n][P]^T ; gb1 += rowsum(D)
@@ -1354,7 +1276,7 @@ static int backward_heads(frcnn_model* m, const float* w, float* grad, hipStream
 static int backward_heads_fanout(frcnn_model* m, const float* w, float* grad) {
   FR_TRY(ensure_head_streams(m));
   if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
-  FR_HIP(hipEventRecord(m->chain_ev, m->side));
+  FR_TRY(m->chain_ev.record(m->side));
   for (auto& h : m->heads) h.gin_recorded = false;
   std::vector<char> own(m->heads.size(), 0);   // (the hint is consumed by backward_head: decide before calling it)
   for (size_t i = 0; i < m->heads.size(); ++i) own[i] = m->heads[i].stream && head_is_sparse(m->heads[i]);
@@ -1369,7 +1291,7 @@ static int backward_heads_fanout(frcnn_model* m, const float* w, float* grad) {
   for (size_t i = 0; i < m->heads.size(); ++i) {
     Head& h = m->heads[i];
     if (!own[i]) continue;
-    FR_HIP(hipStreamWaitEvent(h.stream, m->chain_ev, 0));
+    FR_TRY(m->chain_ev.wait(h.stream));
     FR_TRY(backward_head(m, h, w, grad, h.stream, head_slot(m, i)));
   }
   for (size_t i = 0; i < m->heads.size(); ++i)
@@ -1489,8 +1411,7 @@ static int heads_sparse_backward(frcnn_model* m, const float* w, float* grad, co
     FR_TRY(gemm_f32_group(q, gi.n, s));
     FR_TRY(heads_col2im(gi, s));                       // the pooled maps' gradients
   }
-  if (!m->heads_gin_ev) FR_HIP(hipEventCreateWithFlags(&m->heads_gin_ev, hipEventDisableTiming));
-  FR_HIP(hipEventRecord(m->heads_gin_ev, s));          // what the backbone's backward pass waits for; the parameter gradients follow
+  FR_TRY(m->heads_gin_ev.record(s));                   // what the backbone's backward pass waits for; the parameter gradients follow
   m->heads_gin = true;
   for (int i = 0; i < g.n; ++i) {                      // gW1[18][n] += D[18][P] HY[n][P]^T
     const HeadJob& j = g.j[i]; const Head* hd = head_of(j);
@@ -1559,7 +1480,7 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
     m->heads_deferred = false; m->heads_sparse_fwd = true;
     FR_TRY(rpn_loss(L, deltas, ex_idx, ex_anchor, ex_roi, ex_class, npos, nneg, bgclass, ex_loss, crtarget, cctarget, m->side));
     FR_TRY(loss_accumulate(ex_loss, E, acc, m->side));
-    FR_HIP(hipEventRecord(m->loss_ev, m->side));
+    FR_TRY(m->loss_ev.record(m->side));
     m->loss_pending = true;
     if (!m->train_heads) return heads_frozen_begun(m);   // staged training: the chain stops after the losses
     if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
@@ -1572,7 +1493,7 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
   FR_TRY(join_heads(m, m->side));                  // the anchor nets' outputs (each on its own stream) are final
   FR_TRY(rpn_loss(L, deltas, ex_idx, ex_anchor, ex_roi, ex_class, npos, nneg, bgclass, ex_loss, crtarget, cctarget, m->side));
   FR_TRY(loss_accumulate(ex_loss, E, acc, m->side));
-  FR_HIP(hipEventRecord(m->loss_ev, m->side));
+  FR_TRY(m->loss_ev.record(m->side));
   m->loss_pending = true;
   if (!m->train_heads) return heads_frozen_begun(m);
   FR_TRY(backward_heads_fanout(m, w, grad));
@@ -1582,7 +1503,7 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
 
 int frcnn_pnet_anchor_loss_wait(frcnn_model* m, void* stream) {
   if (m->loss_pending) {
-    FR_HIP(hipStreamWaitEvent(S(stream), m->loss_ev, 0));
+    FR_TRY(m->loss_ev.wait(S(stream)));
     m->loss_pending = false;
   }
   return FRCNN_OK;
@@ -1594,8 +1515,7 @@ int frcnn_pnet_backward_heads_join(frcnn_model* m, void* stream, int* joined) {
   if (!m->heads_begun) return FRCNN_OK;   // nothing was started: frcnn_pnet_backward computes the anchor nets' part
   if (!m->heads_joined) {
     FR_TRY(join_heads(m, s));
-    FR_HIP(hipEventRecord(m->join_ev, m->side));
-    FR_HIP(hipStreamWaitEvent(s, m->join_ev, 0));
+    FR_TRY(join_side_now(m, s));
     m->heads_joined = true;   // frcnn_pnet_backward will not wait again
   }
   if (joined) *joined = 1;
@@ -1606,10 +1526,9 @@ int frcnn_pnet_backward_heads_join(frcnn_model* m, void* stream, int* joined) {
 // backbone's backward pass -- the stretch of the step that is bound by the matrix cores, beside which bandwidth-bound work
 // (the update of slices that are final already) costs least.  Everything the caller's stream ran before it is final too.
 int frcnn_pnet_wait_backward_begun(frcnn_model* m, void* stream) {
-  FR_CHECK(m->update_armed && m->bwd_ev && m->block_ev_valid,
+  FR_CHECK(m->update_armed && m->bwd_ev.recorded() && m->block_ev_valid,
            "pnet_wait_backward_begun: call frcnn_model_update_stream before the pass and frcnn_pnet_backward first");
-  FR_HIP(hipStreamWaitEvent(S(stream), m->bwd_ev, 0));
-  return FRCNN_OK;
+  return m->bwd_ev.wait(S(stream));
 }
 
 // After frcnn_pnet_backward has been queued: `stream` waits until the anchor nets' whole backward pass -- their parameter
@@ -1617,7 +1536,7 @@ int frcnn_pnet_wait_backward_begun(frcnn_model* m, void* stream) {
 int frcnn_pnet_wait_heads_done(frcnn_model* m, void* stream) {
   FR_CHECK(m->block_ev_valid, "pnet_wait_heads_done: call frcnn_pnet_backward first");
   for (auto& h : m->heads)
-    if (h.stream && h.done) FR_HIP(hipStreamWaitEvent(S(stream), h.done, 0));
+    if (h.stream) FR_TRY(h.done.wait(S(stream)));
   if (m->side) {   // (the sparse training path runs the anchor nets on the side stream: everything queued there so far)
     FR_TRY(ensure_update_stream(m));
     FR_TRY(chain(m->side, S(stream), m->upd_ev));
@@ -1630,11 +1549,11 @@ int frcnn_pnet_wait_heads_done(frcnn_model* m, void* stream) {
 // packs or its weight-magnitude scalars (the input-gradient launch of the block's first convolution).
 int frcnn_pnet_wait_block_done(frcnn_model* m, int block, void* stream) {
   FR_CHECK(block >= 1 && block <= (int)m->blocks.size(), "pnet_wait_block_done: block %d out of range", block);
-  FR_CHECK(m->update_armed && m->block_ev_valid && (size_t)block <= m->block_ev.size() && (size_t)block <= m->block_rd_ev.size(),
+  // (the read events are recorded by a pass that found the update stream armed)
+  FR_CHECK(m->update_armed && m->block_ev_valid && m->block_rd_ev[block - 1].recorded(),
            "pnet_wait_block_done: call frcnn_model_update_stream before the pass and frcnn_pnet_backward first");
-  FR_HIP(hipStreamWaitEvent(S(stream), m->block_ev[block - 1], 0));
-  FR_HIP(hipStreamWaitEvent(S(stream), m->block_rd_ev[block - 1], 0));
-  return FRCNN_OK;
+  FR_TRY(m->block_ev[block - 1].wait(S(stream)));
+  return m->block_rd_ev[block - 1].wait(S(stream));
 }
 
 // Renews the training packs of one owner (group = 0-based backbone block, or the number of blocks for the anchor nets) from the
@@ -1668,51 +1587,43 @@ int frcnn_pnet_invalidate_packs(frcnn_model* m) {
 
 int frcnn_pnet_wait_block_gradients(frcnn_model* m, int block, void* stream) {
   FR_CHECK(block >= 1 && block <= (int)m->blocks.size(), "pnet_wait_block_gradients: block %d out of range", block);
-  FR_CHECK(m->block_ev_valid && (size_t)block <= m->block_ev.size(), "pnet_wait_block_gradients: call frcnn_pnet_backward first");
-  FR_HIP(hipStreamWaitEvent(S(stream), m->block_ev[block - 1], 0));
-  return FRCNN_OK;
+  FR_CHECK(m->block_ev_valid, "pnet_wait_block_gradients: call frcnn_pnet_backward first");
+  return m->block_ev[block - 1].wait(S(stream));
 }
 
+// block b's weights, packs and weight magnitudes have had their last reader on the caller's stream s
 static int record_block_read(frcnn_model* m, int b, hipStream_t s) {
-  if (!m->update_armed) return FRCNN_OK;
-  while (m->block_rd_ev.size() < m->blocks.size()) {
-    hipEvent_t e;
-    FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    m->block_rd_ev.push_back(e);
-  }
-  FR_HIP(hipEventRecord(m->block_rd_ev[b], s));
-  return FRCNN_OK;
+  return m->update_armed ? m->block_rd_ev[b].record(s) : FRCNN_OK;
+}
+// block b's parameter gradients are final at this point of stream s, and its weights have been read for the last time there
+static int mark_block_done(frcnn_model* m, int b, hipStream_t s) {
+  FR_TRY(m->block_ev[b].record(s));
+  return record_block_read(m, b, s);
 }
 
-int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* stream) {
-  hipStream_t s = S(stream);
-  FR_CHECK(m->H > 0 && m->training, "pnet_backward: needs a preceding training-mode forward "
-                                    "(nn.SpatialDropout: backprop only defined while training)");
-  const int nb = (int)m->blocks.size();
-  for (auto& c : m->convs) m->am_live[c.am + 1] = 0;
-  bool heads_tail = false;   // anchor nets still computing their parameter gradients on their own streams: joined at the end
+// The anchor nets' part of frcnn_pnet_backward: the caller's stream s waits for what the backbone's pass needs from them (or
+// computes it, when nobody has started it).  *heads_tail: anchor nets are still computing their parameter gradients on streams
+// of their own, to be joined at the end of the pass.
+static int join_anchor_nets_for_backbone(frcnn_model* m, const float* w, float* grad, hipStream_t s, bool* heads_tail) {
+  *heads_tail = false;
   if (m->heads_begun) {   // started by frcnn_pnet_backward_heads_begin: wait for the side stream
     if (!m->heads_joined) {
       // What the backbone's pass needs from an anchor net is its contribution to the pooled map's gradient; a net on a stream
       // of its own marks that point (Head::gin_done) and goes on with its parameter gradients beside the backbone's pass.
       if (m->heads_gin) {   // the sparse path's one chain on the side stream: its input-gradient part, the rest at the end
-        FR_HIP(hipStreamWaitEvent(s, m->heads_gin_ev, 0));
-        heads_tail = true;
+        FR_TRY(m->heads_gin_ev.wait(s));
+        *heads_tail = true;
       }
       for (auto& h : m->heads) {
         if (!h.stream || m->heads_gin) continue;
         if (h.gin_recorded) {
-          FR_HIP(hipStreamWaitEvent(s, h.gin_done, 0));
-          heads_tail = true;
+          FR_TRY(h.gin_done.wait(s));
+          *heads_tail = true;
         } else {
-          FR_HIP(hipEventRecord(h.done, h.stream));
-          FR_HIP(hipStreamWaitEvent(s, h.done, 0));
+          FR_TRY(chain(h.stream, s, h.done));
         }
       }
-      if (!m->heads_gin) {
-        FR_HIP(hipEventRecord(m->join_ev, m->side));
-        FR_HIP(hipStreamWaitEvent(s, m->join_ev, 0));
-      }
+      if (!m->heads_gin) FR_TRY(join_side_now(m, s));
     }
     m->heads_begun = false; m->heads_joined = false; m->side_busy = false;
   } else if (!m->train_heads) {   // staged training, anchor nets frozen: their deltas are not back-propagated
@@ -1730,6 +1641,55 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
     if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, s));
     FR_TRY(backward_heads(m, w, grad, s, 0));
   }
+  return FRCNN_OK;
+}
+
+// What the weight-gradient launch of convolution (b, st) takes besides its output gradient
+struct WgradArgs {
+  const float* in; const float* in_slope = nullptr; const float* in_scale = nullptr;   // the input tensor, its pending PReLU / SpatialDropout
+  int cin, o;                                             // channels / filters of the launch
+  WgradMap map; bool mapped = false;                      // compact block: where the gathered channels / filters belong
+  const float* wa_in = nullptr; const float* wa_g = nullptr;   // fp16 form: magnitude records of the input / the output gradient
+};
+static WgradArgs wgrad_args(const frcnn_model* m, const float* w, int b, int st) {
+  const Block& blk = m->blocks[b];
+  const Conv& c = m->convs[blk.first_conv + st];
+  WgradArgs a;
+  // accGradParameters: the input is the previous conv's x (activation fused) or a pooled map / image
+  if (st > 0) {
+    const Conv& pc = m->convs[blk.first_conv + st - 1];
+    a.in = pc.x.f(); a.in_slope = w + pc.a_off;
+    a.in_scale = (st - 1 == 0 && blk.has_drop) ? blk.scale.f() : nullptr;
+  } else {
+    a.in = b == 0 ? m->img.f() : m->blocks[b - 1].pooled.f();
+  }
+  // compact block (Block::dc_on): the second convolution's weight gradient is computed for the kept input channels (its
+  // input IS the compact tensor; their dropout scale is 1), the first one's for the kept filters (its output gradient is
+  // compact); the fold scatters both into the full tensors, the bias gradient follows the filter map
+  a.cin = c.Cin; a.o = c.Cout;
+  a.mapped = blk.dc_on && st <= 1;
+  if (a.mapped) {
+    a.map.Cfull = c.Cin;
+    if (st == 1) { a.cin = blk.nkM; a.map.cmap = blk.dc_idx; a.in_scale = nullptr; }
+    else { a.o = blk.nkM; a.map.omap = blk.dc_idx; }
+  }
+  // fp16 form of the weight-gradient launch: the records of both tensors exist when the forward launch that wrote `in` and
+  // the backward launch that wrote c.gx kept them (the same two tensors feed c's forward and c's input gradient)
+  if (m->f16_packed && c.x_f && c.x_d && (st > 0 || b > 0)) {
+    a.wa_in = st > 0 ? m->rec(m->convs[blk.first_conv + st - 1].am) : m->rec(m->blocks[b - 1].am);
+    a.wa_g = m->rec(c.am + 1);
+  }
+  return a;
+}
+
+int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* stream) {
+  hipStream_t s = S(stream);
+  FR_CHECK(m->H > 0 && m->training, "pnet_backward: needs a preceding training-mode forward "
+                                    "(nn.SpatialDropout: backprop only defined while training)");
+  const int nb = (int)m->blocks.size();
+  for (auto& c : m->convs) m->am_live[c.am + 1] = 0;
+  bool heads_tail = false;   // anchor nets still computing their parameter gradients on their own streams: joined at the end
+  FR_TRY(join_anchor_nets_for_backbone(m, w, grad, s, &heads_tail));
   // staged training (frcnn_model_set_trainable): blocks 0..fb-1 are frozen; the chain stops at block fb, whose first convolution
   // computes its weight gradient and no input gradient
   const int fb = m->frozen_blocks;
@@ -1740,20 +1700,9 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
     FR_TRY(add_inplace(last.gpooled.f(), m->delta_last.f(), (long)m->d.filters[nb - 1] * last.Hp * last.Wp, s));
   }
   // from here on the caller's stream is busy with matrix-core work for the rest of the pass (frcnn_pnet_wait_backward_begun)
-  if (m->update_armed) {
-    if (!m->bwd_ev) FR_HIP(hipEventCreateWithFlags(&m->bwd_ev, hipEventDisableTiming));
-    FR_HIP(hipEventRecord(m->bwd_ev, s));
-  }
+  if (m->update_armed) FR_TRY(m->bwd_ev.record(s));
   // a frozen block's gradients are final and its weights free at once: its events mark this point of the caller's stream
-  for (int b = 0; b < fb; ++b) {
-    while (m->block_ev.size() < (size_t)nb) {
-      hipEvent_t e;
-      FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      m->block_ev.push_back(e);
-    }
-    FR_HIP(hipEventRecord(m->block_ev[b], s));
-    FR_TRY(record_block_read(m, b, s));
-  }
+  for (int b = 0; b < fb; ++b) FR_TRY(mark_block_done(m, b, s));
   // The weight gradient of a layer and the input gradient that feeds the next act_backward are independent:
   // accGradParameters goes to a side stream, so its blocks fill the CUs that the tail of the updateGradInput
   // kernel (one wave of blocks, retiring unevenly) leaves idle, and the ~4 us dispatch gaps of one chain
@@ -1767,7 +1716,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
   // slope gradient; the bias gradient of st - 1 rides on its weight-gradient launch (conv_wgrad's gbias).  act_backward --
   // a read-read-write pass over the tensor on the dependent chain -- is then not launched for st - 1.  (Not in deterministic
   // mode: the sums leave through atomics.)
-  const bool fuse_act = !deterministic() && !(getenv("FRCNN_FUSE_ACT") && atoi(getenv("FRCNN_FUSE_ACT")) == 0);
+  const bool fuse_act = fuse_act_on();
   bool act_done = false;   // the gradient tensor of the convolution being visited already went through its activation
   for (int b = nb - 1; b >= fb; --b) {
     Block& blk = m->blocks[b];
@@ -1778,7 +1727,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
       act_done = false;
       // the very first convolution when it is its block's only one: its input gradient is not needed, so the pooling + PReLU
       // backward is computed inside its weight-gradient launch and the full-resolution gradient never exists
-      static const bool first_pooled_on = !(getenv("FRCNN_FIRST_POOLED") && atoi(getenv("FRCNN_FIRST_POOLED")) == 0);
+      static const bool first_pooled_on = env_flag("FRCNN_FIRST_POOLED", true);
       const bool first_pooled = fuse_act && first_pooled_on && b == 0 && st == 0 && blk.nconv == 1 && scale == nullptr &&
                                 conv_wgrad_first_pooled_eligible(c.Cin, c.Cout, c.k, c.Wo);
       if (first_pooled) {
@@ -1786,13 +1735,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
         FR_TRY(conv_wgrad_first_pooled(m->img.f(), c.Cin, c.H, c.W, blk.gpooled.f(), (const unsigned char*)blk.pidx.p, c.x.f(),
                                        w + c.a_off, c.Cout, c.pad, grad + c.w_off, grad + c.b_off, grad + c.a_off,
                                        m->wg_ws_first.p, m->wg_ws_first.bytes, s));
-        while (m->block_ev.size() < (size_t)nb) {
-          hipEvent_t e;
-          FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          m->block_ev.push_back(e);
-        }
-        FR_HIP(hipEventRecord(m->block_ev[b], s));
-        FR_TRY(record_block_read(m, b, s));
+        FR_TRY(mark_block_done(m, b, s));
         break;
       }
       if (fused_here) {
@@ -1805,56 +1748,21 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
         FR_TRY(act_backward(c.gx.f(), c.x.f(), c.Cout, (long)c.Ho * c.Wo, w + c.a_off, scale, c.gx.f(),
                             grad + c.b_off, grad + c.a_off, s, (c.x_d && m->f16_packed) ? m->rec_w(c.am + 1) : nullptr));
       }
-      // accGradParameters: the input is the previous conv's x (activation fused) or a pooled map / image
-      const float* in; const float* in_slope = nullptr; const float* in_scale = nullptr;
-      if (st > 0) {
-        Conv& pc = m->convs[blk.first_conv + st - 1];
-        in = pc.x.f(); in_slope = w + pc.a_off;
-        in_scale = (st - 1 == 0 && blk.has_drop) ? blk.scale.f() : nullptr;
-      } else {
-        in = b == 0 ? m->img.f() : m->blocks[b - 1].pooled.f();
-      }
-      // compact block (Block::dc_on): the second convolution's weight gradient is computed for the kept input channels (its
-      // input IS the compact tensor; their dropout scale is 1), the first one's for the kept filters (its output gradient is
-      // compact); the fold scatters both into the full tensors, the bias gradient follows the filter map
-      const bool dc = blk.dc_on && st <= 1;
-      int wg_cin = c.Cin, wg_o = c.Cout;
-      WgradMap wmap;
-      if (dc) {
-        wmap.Cfull = c.Cin;
-        if (st == 1) { wg_cin = blk.nkM; wmap.cmap = blk.dc_idx; in_scale = nullptr; }
-        else { wg_o = blk.nkM; wmap.omap = blk.dc_idx; }
-      }
-      // fp16 form of the weight-gradient launch: the records of both tensors exist when the forward launch that wrote `in` and
-      // the backward launch that wrote c.gx kept them (the same two tensors feed c's forward and c's input gradient)
-      const float* wa_in = nullptr; const float* wa_g = nullptr;
-      if (m->f16_packed && c.x_f && c.x_d && (st > 0 || b > 0)) {
-        wa_in = st > 0 ? m->rec(m->convs[blk.first_conv + st - 1].am) : m->rec(m->blocks[b - 1].am);
-        wa_g = m->rec(c.am + 1);
-      }
+      const WgradArgs wa = wgrad_args(m, w, b, st);
+      const bool dc = wa.mapped;
       // The first layer's weight gradient ends the pass and the caller's stream has nothing left to do (no input gradient for
       // the image): it runs THERE, with a slab workspace of its own, beside the side stream's last launches instead of
       // behind them (the optimiser waited ~80 us for the side stream's tail).
       const bool on_caller = use_side && b == 0 && st == 0;
       if (use_side && !on_caller) FR_TRY(fork_side(m, s, n_fork++));   // c.gx is final here
-      if (on_caller) {
-        FR_TRY(conv_wgrad(in, wg_cin, c.H, c.W, in_slope, in_scale, c.gx.f(), wg_o, c.k, c.pad, grad + c.w_off, m->wg_ws_first.p,
-                          m->wg_ws_first.bytes, s, fused_here ? grad + c.b_off : nullptr, wa_in, wa_g, dc ? &wmap : nullptr));
-        FR_HIP(hipEventRecord(m->join_ev, ws));          // (block 0's other convolutions, if any, are on the side stream)
-        FR_HIP(hipStreamWaitEvent(s, m->join_ev, 0));
-      } else {
-        FR_TRY(conv_wgrad(in, wg_cin, c.H, c.W, in_slope, in_scale, c.gx.f(), wg_o, c.k, c.pad, grad + c.w_off, m->wg_ws.p, m->wg_ws.bytes, ws,
-                          fused_here ? grad + c.b_off : nullptr, wa_in, wa_g, dc ? &wmap : nullptr));
-      }
-      if (st == 0) {   // every gradient of block b's parameters is final once this launch has run (its fork also
-                       // covers the bias / slope sums that act_backward accumulates on the caller's stream)
-        while (m->block_ev.size() < (size_t)nb) {
-          hipEvent_t e;
-          FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          m->block_ev.push_back(e);
-        }
-        FR_HIP(hipEventRecord(m->block_ev[b], on_caller ? s : ws));
-      }
+      const hipStream_t wgs = on_caller ? s : ws;
+      const DevBuf& slabs = on_caller ? m->wg_ws_first : m->wg_ws;
+      FR_TRY(conv_wgrad(wa.in, wa.cin, c.H, c.W, wa.in_slope, wa.in_scale, c.gx.f(), wa.o, c.k, c.pad, grad + c.w_off, slabs.p, slabs.bytes, wgs,
+                        fused_here ? grad + c.b_off : nullptr, wa.wa_in, wa.wa_g, dc ? &wa.map : nullptr));
+      if (on_caller) FR_TRY(join_side_now(m, s));   // (block 0's other convolutions, if any, are on the side stream)
+      // every gradient of block b's parameters is final once this launch has run (its fork also covers the bias / slope sums
+      // that act_backward accumulates on the caller's stream)
+      if (st == 0) FR_TRY(m->block_ev[b].record(wgs));
       if (b == fb && st == 0) {   // gradInput of the first conv is unused (objective.lua:189), so is a frozen block's
         FR_TRY(record_block_read(m, b, s));
         break;
@@ -1889,8 +1797,7 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
   if (heads_tail && !m->heads_gin) FR_TRY(join_heads(m, s));   // the anchor nets' parameter gradients (see above; the sparse path's are on the side stream, joined below)
   FR_TRY(cw_join(m, s));   // the classification net's weight gradients (frcnn_cnet_backward) belong to the same gradient vector
   if (use_side) {   // the caller's stream continues after every weight gradient has landed
-    FR_HIP(hipEventRecord(m->join_ev, ws));
-    FR_HIP(hipStreamWaitEvent(s, m->join_ev, 0));
+    FR_TRY(join_side_now(m, s));
     m->side_busy = false;
   }
   return FRCNN_OK;
@@ -1898,13 +1805,10 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
 
 // ------------------------------------------------------------------------------------ cnet
 // the row-wise layers fused with the folds of the products around them (cnet.hip: "fused forms"); FRCNN_CNET_FUSE=0: one launch each
-static bool cnet_fuse() {
-  const char* e = getenv("FRCNN_CNET_FUSE");   // (read per call: the tests switch it)
-  return !(e && atoi(e) == 0);
-}
+static bool cnet_fuse() { return env_flag("FRCNN_CNET_FUSE", true); }   // (read per call: the tests switch it)
 // the classification net's large products in the two-plane fp16 form: with option x3_f16 (FRCNN_GEMM_F16=0: these stay three-plane)
 static bool gemm_f16_on() {
-  static const bool env_on = !(getenv("FRCNN_GEMM_F16") && atoi(getenv("FRCNN_GEMM_F16")) == 0);
+  static const bool env_on = env_flag("FRCNN_GEMM_F16", true);
   return env_on && get_x3_f16();
 }
 static int ensure_cnet(frcnn_model* m, int R) {
@@ -2036,24 +1940,12 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
   // bias sums go to `ws`: a stream of their own (see g_cnet_wgrad_async), or `s` itself
   FR_TRY(cw_join(m, s));
   const bool async = g_cnet_wgrad_async && !deterministic();
-  if (async && !m->cw) {
-    FR_TRY(pool_stream(1, &m->cw));
-    FR_HIP(hipEventCreateWithFlags(&m->cw_done, hipEventDisableTiming));
-  }
-  while (async && m->cw_ev.size() < m->cls.size() + 1) {
-    hipEvent_t e;
-    FR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    m->cw_ev.push_back(e);
-  }
+  if (async) FR_TRY(ensure_update_stream(m));
   hipStream_t ws = async ? m->cw : s;
   const int wslot = async ? 7 : 0;     // split-K workspace of the products on `ws`
   size_t nfork = 0;
   auto fork = [&]() -> int {           // everything queued on `s` so far is final for `ws`
-    if (!async) return FRCNN_OK;
-    FR_HIP(hipEventRecord(m->cw_ev[nfork], s));
-    FR_HIP(hipStreamWaitEvent(ws, m->cw_ev[nfork], 0));
-    ++nfork;
-    return FRCNN_OK;
+    return async ? chain(s, ws, m->cw_ev[nfork++]) : FRCNN_OK;
   };
   // heads: LogSoftMax backward first, then the two input gradients on the chain, the two weight gradients beside it
   bool top_act_done = false;   // the last hidden layer's Dropout + PReLU backward was applied by the heads' launch (L.g is final)
@@ -2121,7 +2013,7 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
       FR_TRY(gemm_f32(L.g.f(), L.n, 1, w + L.w_off, L.in, 1, gin, L.in, R, L.in, L.n, OUT_STORE, nullptr, s, 0, gdefer));
     }
     // beside it: the weight gradient (planes in the transposed orientation) and the bias sums
-    static const bool wgrad_f16 = !(getenv("FRCNN_GEMM_WGRAD_F16") && atoi(getenv("FRCNN_GEMM_WGRAD_F16")) == 0);
+    static const bool wgrad_f16 = env_flag("FRCNN_GEMM_WGRAD_F16", true);
     if (xw && wgrad_f16 && gemm_f16_on() && L.am.bytes >= (size_t)5 * AMAX_REC * 4) {
       // two fp16 planes per operand here too (round 6; three products instead of six): both tensors' magnitudes are taken on this
       // stream (records 3 and 4 of the layer: the weight-gradient stream forked before the chain took its own)
@@ -2144,7 +2036,7 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
   }
   if (m->cls.empty() && gx) FR_HIP(hipMemcpyAsync(gx, g, (size_t)R * m->D * 4, hipMemcpyDeviceToDevice, s));
   if (async) {
-    FR_HIP(hipEventRecord(m->cw_done, ws));
+    FR_TRY(m->cw_done.record(ws));
     m->cw_pending = true;
   }
   return FRCNN_OK;
