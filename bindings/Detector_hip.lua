@@ -14,6 +14,8 @@
 -- (main.lua calls Detector(model) unchanged, so the settings ride on the model's cfg; Detector.proposal_settings).
 -- Likewise cfg.nms = { method = 'hard' | 'linear' | 'gaussian', overlap, sigma, min_score } (Detector.nms_settings): Soft-NMS in
 -- the per-class pass.  Under 'linear' or 'gaussian' a winner's confidence is its DECAYED log-score, the one it was ranked by.
+-- And cfg.box_voting = { overlap = 0.5, weight = 'score' | 'uniform' } (Detector.box_voting_settings): behind the per-class pass a
+-- winner's r2 becomes the weighted mean of the r2 of its class's survivors that overlap it; nothing else about a winner changes.
 --
 --   main.lua:  require 'Detector'  ->  require 'Detector_hip'
 local ffi = require 'ffi'
@@ -39,6 +41,30 @@ function Detector:__init(model)                                         -- Detec
   self.scratch = hip.scratch()
   self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n = Detector.proposal_settings(self.model.cfg.proposals)
   self.nms_method, self.nms_overlap, self.nms_sigma, self.nms_min_score = Detector.nms_settings(self.model.cfg.nms)
+  self.vote_overlap, self.vote_weight = Detector.box_voting_settings(self.model.cfg.box_voting)
+end
+
+-- cfg.box_voting -> nil (the key is absent: no voting, the reference's r2) or overlap, weight (validated on the host, before any
+-- device call).  Voting runs behind the per-class pass and changes a winner's r2 only: it becomes the weighted mean of the r2 of
+-- every survivor of the class test that has the winner's class and overlaps it by an IoU >= overlap, the winner included.
+--   overlap  in (0, 1]; default 0.5
+--   weight   'score' (default: a voter weighs its confidence as a probability -- the undecayed one, also under a soft per-class
+--            NMS) or 'uniform' (every voter weighs 1)
+-- An empty table turns voting on with the defaults.
+function Detector.box_voting_settings(t)
+  if t == nil then return nil end
+  if type(t) ~= 'table' then error('cfg.box_voting must be a table of {overlap, weight}') end
+  for k, _ in pairs(t) do
+    if k ~= 'overlap' and k ~= 'weight' then error('cfg.box_voting: unknown key ' .. tostring(k)) end
+  end
+  local weight = t.weight
+  if weight == nil then weight = 'score' end
+  if weight ~= 'score' and weight ~= 'uniform' then error('cfg.box_voting.weight must be "score" or "uniform"') end
+  local overlap = t.overlap
+  if overlap == nil then overlap = 0.5 end
+  if type(overlap) ~= 'number' then error('cfg.box_voting.overlap is not a number') end
+  if not (overlap > 0 and overlap <= 1) then error('cfg.box_voting.overlap must be in (0, 1]') end
+  return overlap, weight
 end
 
 -- cfg.nms -> method, overlap, sigma, min_score (validated on the host, before any device call).  The setting governs the
@@ -431,8 +457,20 @@ function Detector:detect_chunk(frames, shared, prefix)
     check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, self.nms_overlap, key_mode, key_col, dkc, cpick, cnt + 3 * B,
                                    cws.ptr, cwsb, nil))
   end
+  --         Under box voting (cfg.box_voting): ONE frcnn_box_vote_batch launch over the class test's survivors -- rows bb (the
+  --         UNDECAYED log-confidences, also under a soft method: weight_mode 2), classes, coordinates the fp64 r2, winners cpick
+  --         with the device winner counts -- writes the winners' voted rects into a buffer of their own, which the gather reads
+  --         in place of r2
+  local dr2_win = dr2
+  if self.vote_overlap ~= nil then
+    dr2_win = ffi.cast('double*', scratch(prefix .. 'r2_voted', 32 * B * Rmax).ptr)
+    local weight_mode = 2
+    if self.vote_weight == 'uniform' then weight_mode = 0 end
+    check(C.frcnn_box_vote_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 5, weight_mode, self.vote_overlap, dkc, dr2, cpick, cnt + 3 * B,
+                                 dr2_win, nil, nil))
+  end
   local out = ffi.cast('double*', scratch(prefix .. 'winners', 128 * B * (Rmax + 1)).ptr)
-  check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb_win, dr2, dpick, cap, mp, mr, mi, out, nil))
+  check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb_win, dr2_win, dpick, cap, mp, mr, mi, out, nil))
   local h = ffi.new('double[?]', 16 * B * (Rmax + 1))
   check(C.frcnn_memcpy_d2h(h, out, 128 * B * (Rmax + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table
   check(C.frcnn_stream_sync(nil))

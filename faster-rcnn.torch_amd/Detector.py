@@ -25,7 +25,12 @@ Not in the reference either, off by default (cfg["nms"] / Detector(..., nms=...)
 pass (step 5 of _detect_chunk; the first NMS is untouched).  Under method "linear" or "gaussian" the neighbours of a winner keep
 living with a lowered confidence instead of being deleted (frcnn_soft_nms_batch in place of frcnn_nms_device_batch, on the
 log-probabilities the class test produced: log_domain 1).  A winner's `confidence` is then its DECAYED log-score, the one it
-was ranked by; the undecayed one remains last_cnet["cls"][candidate - 1, class - 1]."""
+was ranked by; the undecayed one remains last_cnet["cls"][candidate - 1, class - 1].
+
+Nor is box voting (Gidaris & Komodakis 2015), off by default (cfg["box_voting"] / Detector(..., box_voting=...), see
+box_voting_settings): behind the per-class pass ONE frcnn_box_vote_batch launch replaces every winner's r2 by the weighted mean
+of the r2 of the class test's survivors of its class that overlap it by at least `overlap` (weights: the confidences, always the
+UNDECAYED ones).  Which rows win, their order and every other field of a winner are those of the same Detector without the key."""
 import ctypes as C
 import math
 
@@ -128,6 +133,38 @@ def nms_settings(cfg_or_table):
     return method, overlap, sigma, min_score, "overlap" in t
 
 
+BOX_VOTING_DEFAULTS = dict(overlap=0.5, weight="score")
+BOX_VOTING_WEIGHTS = dict(uniform=0, score=2)   # weight_mode of frcnn_box_vote_batch: bb's column 5 is a log-probability
+
+
+def box_voting_settings(cfg_or_table):
+    """cfg["box_voting"] -- or the table itself, or None -- -> None (the key is absent: no voting, the reference's r2) or
+    (overlap, weight), validated on the host.  Voting runs behind the per-class pass (step 5 of _detect_chunk) and changes a
+    winner's r2 only: it becomes the weighted mean of the r2 of every survivor of the class test that has the winner's class
+    and overlaps it (IoU of the fp32 boxes, the per-class NMS's own arithmetic) by at least `overlap`, the winner included.
+      overlap  in (0, 1]; default 0.5
+      weight   "score" (default: a voter weighs its confidence as a probability, exp of the log-confidence -- the undecayed
+               one, also under a soft per-class NMS) or "uniform" (every voter weighs 1)
+    An empty table turns voting on with the defaults.  Raises ValueError (before any device call) for an unknown key, an
+    unknown weight, a bool or a non-number, and an overlap outside (0, 1]."""
+    t = cfg_or_table
+    if isinstance(t, dict) and ("box_voting" in t or "class_count" in t):     # a model's cfg
+        t = t.get("box_voting")
+    if t is None:
+        return None
+    t = _settings_table(t, "box_voting", BOX_VOTING_DEFAULTS)
+    weight = t.get("weight", BOX_VOTING_DEFAULTS["weight"])
+    if not isinstance(weight, str) or weight not in BOX_VOTING_WEIGHTS:
+        raise ValueError("cfg.box_voting.weight = %r (\"score\" or \"uniform\")" % (weight,))
+    v = t.get("overlap", BOX_VOTING_DEFAULTS["overlap"])
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("cfg.box_voting.overlap = %r is not a number" % (v,))
+    overlap = float(v)
+    if not (0.0 < overlap <= 1.0):
+        raise ValueError("cfg.box_voting.overlap = %r (in (0, 1])" % (overlap,))
+    return overlap, weight
+
+
 class _Detections(object):
     """The list Detector:detect returns (Detector.lua:138-140): one table {p, a, r, l, r2, class, confidence} per winner,
     classes ascending (pairs() order is unspecified in Lua), pick order within a class.  Backed by the winner records the
@@ -177,7 +214,11 @@ class _BatchRecord(object):
     The arrays stay on the device and are fetched when they are looked at, like last_scan / last_pick / last_cnet of detect().
     Under pre_nms_top_n the scan rows are the SELECTED rows (n of them) and two more keys exist: row (their 1-based original
     scan rows) and matches (the frame's match count before the cap).  Under a soft per-class NMS (cfg["nms"]) two more: bb (K x 5:
-    the class test's survivors {x1 y1 x2 y2 log-confidence} as the pass read them) and kc (K: their classes)."""
+    the class test's survivors {x1 y1 x2 y2 log-confidence} as the pass read them) and kc (K: their classes).  Under box voting
+    (cfg["box_voting"]) those two and r2 (K x 4 float64: the survivors' UNVOTED decoded rects), keep_row (K: their 0-based
+    candidate positions) and votes (K: the voter count of every row that won, 0 for the others): what it takes to recompute
+    every winner's box."""
+    _EXTRA = ("bb", "kc", "r2", "keep_row", "votes")    # of a soft pass (the first two) or of box voting (all)
     _KEYS = ("n", "idx", "box", "rect", "p", "pick", "cnet", "kept", "pooled")   # of every record
 
     def __init__(self, n, R, dev, matches=None):
@@ -187,12 +228,11 @@ class _BatchRecord(object):
         if matches is not None:
             self._v["matches"] = matches
 
-    def finish(self, kept, bb=None, kc=None):
-        """What read-back 2 brings: the class test's survivor count, and -- a soft per-class NMS -- its rows as the pass read
-        them (device arrays of `kept` rows)."""
+    def finish(self, kept, **extra):
+        """What read-back 2 brings: the class test's survivor count, and -- a soft per-class NMS, box voting -- its rows as
+        the pass read them (extra: device arrays of `kept` rows, names of _EXTRA)."""
         self._v["kept"] = kept
-        if bb is not None:
-            self._dev.update(bb=bb, kc=kc)
+        self._dev.update(extra)
 
     def detach(self):
         """A private device copy of the frame's arrays (one allocation; the copies are queued on the stream, no wait): the
@@ -220,13 +260,12 @@ class _BatchRecord(object):
         return out
 
     def keys(self):
-        """The keys of every record, then those of what this one holds: row, matches (pre_nms_top_n); bb, kc (a soft pass)."""
+        """The keys of every record, then those of what this one holds: row, matches (pre_nms_top_n); bb, kc (a soft pass);
+        bb, kc, r2, keep_row, votes (box voting)."""
         ks = list(self._KEYS)
         if "matches" in self._v:
             ks += ["row", "matches"]
-        if "bb" in self._dev:
-            ks += ["bb", "kc"]
-        return ks
+        return ks + [k for k in self._EXTRA if k in self._dev]
 
     def get(self, k, default=None):
         return self[k] if k in self else default
@@ -248,9 +287,24 @@ class _BatchRecord(object):
         return v[k]
 
 
-class Detector(object):
+class _DetectorType(type):
+    """Detector(model, ..., box_voting=table): the voting setting is a keyword of the class call, not of __init__, whose
+    parameter list stays what it was.  The table is validated before anything is built -- before the model is looked at, let
+    alone the device -- and set on the finished object; without it __init__ has read model["cfg"]["box_voting"]."""
+
+    def __call__(cls, *args, box_voting=None, **kw):
+        if box_voting is not None:
+            box_voting_settings(box_voting)
+        d = super().__call__(*args, **kw)
+        if box_voting is not None:
+            d.set_box_voting(box_voting)
+        return d
+
+
+class Detector(object, metaclass=_DetectorType):
     proposal_settings = staticmethod(proposal_settings)
     nms_settings = staticmethod(nms_settings)
+    box_voting_settings = staticmethod(box_voting_settings)
 
     def __init__(self, model, static_weights=False, proposals=None, nms=None):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
@@ -258,11 +312,14 @@ class Detector(object):
         another Detector(..., static_weights=...) drops the packs).
         proposals: a table as proposal_settings takes it; None: model["cfg"]["proposals"] (absent: the reference's behaviour).
         nms: the per-class NMS, a table as nms_settings takes it -- validated first, before the model is looked at; None:
-        model["cfg"]["nms"] (absent: the reference's hard cut at 0.1)."""
+        model["cfg"]["nms"] (absent: the reference's hard cut at 0.1).
+        Box voting is model["cfg"]["box_voting"] (absent: none) unless the call names one: Detector(model, box_voting=table), a
+        table as box_voting_settings takes it (see _DetectorType)."""
         if nms is not None:
             nms_settings(nms)
         self.set_proposals(proposals if proposals is not None else model["cfg"])
         self.set_nms(model["cfg"])
+        self.set_box_voting(model["cfg"])
         if nms is not None:
             self.set_nms(nms)
         self.model = model
@@ -292,6 +349,11 @@ class Detector(object):
     def set_nms(self, cfg_or_table):
         """Validates a table as nms_settings takes it and makes it this Detector's per-class NMS from the next frame on."""
         self.nms_method, self.nms_overlap, self.nms_sigma, self.nms_min_score, _ = nms_settings(cfg_or_table)
+
+    def set_box_voting(self, cfg_or_table):
+        """Validates a table as box_voting_settings takes it and makes it this Detector's setting from the next frame on (None,
+        or a cfg without the key: no voting)."""
+        self.box_voting = box_voting_settings(cfg_or_table)
 
     def __del__(self):
         if getattr(self, "_host", None):
@@ -655,17 +717,32 @@ class Detector(object):
             ws2 = self._buf(pre + "nms_ws2", (wsb2,), np.uint8)
             _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, C.c_float(self.nms_overlap), key_mode, key_col,
                       ptr(kc), ptr(wpick), c_W, ptr(ws2), wsb2, s)
+        #         Under box voting (cfg["box_voting"]): ONE frcnn_box_vote_batch launch over the class test's survivors -- rows bb
+        #         (the UNDECAYED log-confidences, also under a soft method: weight_mode 2), classes kc, coordinates the fp64 r2,
+        #         winners wpick with the device winner counts -- writes the winners' voted rects into a buffer of their own, which
+        #         the gather reads in place of r2.  Nothing else changes
+        voting = self.box_voting is not None
+        r2_win = r2
+        if voting:
+            r2_win = self._buf(pre + "r2_voted", (B, Rmax, 4), np.float64)
+            votes = self._buf(pre + "votes", (B, Rmax), i32)
+            _lib.call("frcnn_zero", ptr(votes), votes.nbytes, s)      # (a record shows 0 votes for the rows that did not win)
+            _lib.call("frcnn_box_vote_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, 5, BOX_VOTING_WEIGHTS[self.box_voting[1]],
+                      C.c_float(self.box_voting[0]), ptr(kc), ptr(r2), ptr(wpick), c_W, ptr(r2_win), ptr(votes), s)
         out = self._buf(pre + "winners", (B, Rmax + 1, 16), np.float64)
-        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2), ptr(pick),
-                  cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
+        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2_win),
+                  ptr(pick), cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
         records = self._records(st, more)
         raw = self._read(out.ptr, out.nbytes, np.float64).reshape(out.shape)   # ---- read-back 2 of 2
         results = []
         for b in range(B):
             hdr = raw[b, 0].view(i32)
             K = int(hdr[2])
-            # (soft: the class test's survivors as the pass read them, views of the chunk's buffers until detach())
-            records[b].finish(K, bb.segment(b, K) if soft else None, kc.segment(b, K) if soft else None)
+            # (soft, voting: the class test's survivors as the pass read them, views of the chunk's buffers until detach())
+            extra = dict(bb=bb.segment(b, K), kc=kc.segment(b, K)) if soft or voting else {}
+            if voting:
+                extra.update(r2=r2.segment(b, K), keep_row=keep_row.segment(b, K), votes=votes.segment(b, K))
+            records[b].finish(K, **extra)
             if ns[b] == 0:
                 results.append([])
                 continue

@@ -63,6 +63,8 @@ _SIGS = {
     "frcnn_soft_nms_workspace_bytes": ([C.c_int, C.c_int], C.c_size_t),
     "frcnn_soft_nms_batch": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
                              vp, vp, vp, vp, C.c_longlong, vp, C.c_size_t, vp], C.c_int),
+    "frcnn_box_vote_batch": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp, vp, vp, vp],
+                             C.c_int),
     "frcnn_topk_select_workspace_bytes": ([C.c_int, C.c_int], C.c_size_t),
     "frcnn_topk_select": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, C.c_longlong, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_rpn_gather_rows": ([vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_longlong, vp, C.c_int, vp, vp, vp, vp, vp, vp,

@@ -178,6 +178,12 @@ int frcnn_soft_nms_batch(const float* boxes, int B, long long row_stride, int n_
   return soft_nms_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, score_col, method, overlap, sigma, min_score, log_domain,
                         cls, pick, count, score_out, (long)score_stride, ws, ws_bytes, S(stream));
 }
+int frcnn_box_vote_batch(const float* boxes, int B, long long row_stride, int n_cap, const int* n_dev, int ncols, int score_col,
+                         int weight_mode, float overlap, const int* cls, const double* rect, const long long* pick,
+                         const int* count, double* rect_out, int* votes_out, void* stream) {
+  return box_vote_batch(boxes, B, (long)row_stride, n_cap, n_dev, ncols, score_col, weight_mode, overlap, cls, rect, pick, count,
+                        rect_out, votes_out, S(stream));
+}
 size_t frcnn_topk_select_workspace_bytes(int B, int n_cap) { return topk_select_workspace_bytes(B, n_cap); }
 int frcnn_topk_select(const float* score, int B, long long stride, int n_cap, const int* n_dev, int K, int* sel_row,
                       long long sel_stride, int* k_dev, void* ws, size_t ws_bytes, void* stream) {

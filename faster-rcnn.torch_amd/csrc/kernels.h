@@ -291,6 +291,10 @@ size_t soft_nms_workspace_bytes(int B, int n_cap);
 int soft_nms_batch(const float* boxes, int B, long row_stride, int n_cap, const int* n_dev, int ncols, int score_col, int method,
                    float overlap, float sigma, float min_score, int log_domain, const int* cls, long long* pick, int* count,
                    float* score_out, long score_stride, void* ws, size_t ws_bytes, hipStream_t s);
+// ---- box voting behind the per-class pass (box_vote.hip): B segments, one wave per winner; semantics in include/frcnn_hip.h
+int box_vote_batch(const float* boxes, int B, long row_stride, int n_cap, const int* n_dev, int ncols, int score_col,
+                   int weight_mode, float overlap, const int* cls, const double* rect, const long long* pick, const int* count,
+                   double* rect_out, int* votes_out, hipStream_t s);
 // ---- proposal selection in front of the first NMS (topk.hip): the K best-scoring rows of a segment, in scan order
 size_t topk_select_workspace_bytes(int B, int n_cap);
 int topk_select(const float* score, int B, long stride, int n_cap, const int* n_dev, int K, int* sel_row, long sel_stride,

@@ -6,6 +6,8 @@ PASCAL-VOC style mean average precision over `BatchIterator:nextValidation` (Bat
       objective.lua:202-205 on `count` validation images, forward only, networks in evaluate() mode (SpatialDropout x(1-p),
       Dropout identity, BatchNormalization running statistics); the examples of an image are assembled exactly like the
       training ones (BatchIterator.lua:198-225) from a generator of their own, so the training stream is not disturbed.
+  mean_average_precision_range(detections, ground_truth, iou_thresholds) -> {mAP, by_iou}: the same at several IoU thresholds
+      (0.5 ... 0.95 by default) and their mean; evaluate_detections(..., iou_threshold=<a sequence>) routes to it.
   evaluate_detections(detector, batch_iterator, count) -> {mAP, ap: {class: AP}, ...}: Detector:detect on `count`
       validation images against their ground-truth boxes.  A detection (class c, box r2, confidence) is a true positive when
       its Rect.IoU (Rect.lua:138-141) with a not yet matched ground-truth box of class c in the same image is >= iou_threshold
@@ -167,8 +169,23 @@ def mean_average_precision(detections, ground_truth, iou_threshold=0.5, use_07_m
     return dict(mAP=float(np.mean(list(ap.values()))) if ap else float("nan"), ap=ap, npos=npos_of, tp=tp_total, fp=fp_total)
 
 
+IOU_RANGE = tuple(round(0.5 + 0.05 * i, 2) for i in range(10))     # 0.5, 0.55, ... 0.95
+
+
+def mean_average_precision_range(detections, ground_truth, iou_thresholds=IOU_RANGE, use_07_metric=False):
+    """mean_average_precision at several IoU thresholds (default 0.5, 0.55, ... 0.95: the average that rewards localisation, where
+    a setting such as cfg["box_voting"] shows; at 0.5 alone it barely does).
+    -> dict(mAP = the mean of the thresholds' mAP, by_iou = {t: the dict mean_average_precision returns at t})."""
+    ts = [float(t) for t in iou_thresholds]
+    if not ts:
+        raise ValueError("mean_average_precision_range: no IoU threshold")
+    by_iou = dict((t, mean_average_precision(detections, ground_truth, t, use_07_metric)) for t in ts)
+    return dict(mAP=float(np.mean([by_iou[t]["mAP"] for t in ts])), by_iou=by_iou)
+
+
 def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False, batch=1):
     """Detector:detect on `count` validation images (main.lua:198-206) scored against their ground truth.
+    iou_threshold: a number, or a sequence of them -> the dict of mean_average_precision_range (mAP, by_iou).
     batch > 1: up to that many consecutive frames of one size go through Detector.detect_batch in one call (same detections,
     two host waits per chunk instead of two per frame); 1 is the frame-by-frame loop of the reference."""
     detections, ground_truth = [], []
@@ -197,7 +214,10 @@ def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_
                 detections.append((image_id, int(w["class"]), float(w["confidence"]), w["r2"]))
     if pending:
         flush()
-    res = mean_average_precision(detections, ground_truth, iou_threshold, use_07_metric)
+    if isinstance(iou_threshold, (tuple, list, np.ndarray)):
+        res = mean_average_precision_range(detections, ground_truth, iou_threshold, use_07_metric)
+    else:
+        res = mean_average_precision(detections, ground_truth, iou_threshold, use_07_metric)
     res.update(images=images, detections=len(detections), ground_truth=len(ground_truth))
     return res
 

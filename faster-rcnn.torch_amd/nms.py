@@ -101,3 +101,66 @@ def soft_nms(boxes, overlap, score_col, method="gaussian", sigma=0.5, min_score=
     k = int(host[n + 1:].view(np.int32)[0])
     pick = host[1:1 + k].copy()
     return pick, out.numpy()[pick - 1].copy()
+
+
+BOX_VOTE_WEIGHTS = ("uniform", "score", "log_score")   # the C ABI's weight_mode 0, 1, 2
+
+
+def _on_device(x):
+    return isinstance(x, DeviceTensor) or (hasattr(x, "is_cuda") and x.is_cuda)
+
+
+def _device_array(x, dtype, shape, what):
+    """x where it is when it is on the device, else uploaded as a contiguous array of dtype; shape: the shape a host array must have"""
+    if _on_device(x):
+        return x
+    a = np.ascontiguousarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x).astype(dtype)
+    if a.shape != shape:
+        raise ValueError("box_vote: %s of shape %r, expected %r" % (what, a.shape, shape))
+    return DeviceTensor.from_numpy(a)
+
+
+def box_vote(boxes, picks, overlap=0.5, score_col=5, weights="score", classes=None, rects=None):
+    """Bounding-box voting (Gidaris & Komodakis 2015; not in the reference) over frcnn_box_vote_batch: for every winner -- the
+    1-based rows `picks` of boxes (n x ncols fp32, columns 1-4 = x1 y1 x2 y2), e.g. what nms() or soft_nms() returned -- the
+    weighted mean of the rows of its class that overlap it by an IoU >= overlap -> (rects: k x 4 float64, votes: k int32), in
+    the order of picks.
+      weights   "score": column score_col (1-based, >= 5) is a plain score and the weight; "log_score": it is a log-probability,
+                the weight is its exp; "uniform": every voter weighs 1 (score_col is ignored).  A row whose weight is not a
+                finite number > 0 does not vote
+      classes   optional n integers: only rows of the winner's class vote
+      rects     optional n x 4 float64: the coordinates that are averaged (membership is always decided on the fp32 boxes)
+    A winner with fewer than two voters keeps its own coordinates bit for bit.  Host arrays are uploaded; device tensors are
+    used where they are.  Runs on the device: there is no host twin (semantics: include/frcnn_hip.h)."""
+    if weights not in BOX_VOTE_WEIGHTS:
+        raise ValueError("box_vote: weights = %r (one of %s)" % (weights, ", ".join(BOX_VOTE_WEIGHTS)))
+    empty = (np.zeros((0, 4), dtype=np.float64), np.zeros(0, dtype=np.int32))
+    if not _on_device(boxes):
+        b = np.ascontiguousarray(boxes.detach().cpu().numpy() if hasattr(boxes, "detach") else boxes, dtype=np.float32)
+        if b.size == 0:
+            return empty
+        if b.ndim != 2:
+            raise ValueError("box_vote: boxes must be n x ncols")
+        boxes = DeviceTensor.from_numpy(b)
+    shape = tuple(int(v) for v in boxes.shape)
+    if len(shape) != 2 or int(np.prod(shape)) == 0:
+        return empty
+    n, ncols = shape
+    hp = picks.numpy() if isinstance(picks, DeviceTensor) else (picks.detach().cpu().numpy() if hasattr(picks, "detach") else picks)
+    hp = np.ascontiguousarray(hp).astype(np.int64).reshape(-1)
+    k = int(hp.size)
+    if k == 0:
+        return empty
+    if k > n or hp.min() < 1 or hp.max() > n:
+        raise ValueError("box_vote: picks are 1-based rows of boxes, at most one per row (%d picks in [%d, %d], %d rows)"
+                         % (k, hp.min(), hp.max(), n))
+    dpick = picks if _on_device(picks) else DeviceTensor.from_numpy(hp)
+    cls = None if classes is None else _device_array(classes, np.int32, (n,), "classes")
+    rect = None if rects is None else _device_array(rects, np.float64, (n, 4), "rects")
+    ctl = DeviceTensor.from_numpy(np.array([n, k], np.int32))          # the row count and the winner count
+    out = DeviceTensor.empty((n, 4), np.float64)
+    votes = DeviceTensor.empty((n,), np.int32)
+    _lib.call("frcnn_box_vote_batch", ptr(boxes), 1, n, n, ptr(ctl), ncols, int(score_col), BOX_VOTE_WEIGHTS.index(weights),
+              C.c_float(overlap), ptr(cls) if cls is not None else None, ptr(rect) if rect is not None else None, ptr(dpick),
+              C.c_void_p(ctl.ptr + 4), ptr(out), ptr(votes), stream_ptr())
+    return out.numpy()[hp - 1].copy(), votes.numpy()[hp - 1].copy()

@@ -191,6 +191,37 @@ int frcnn_soft_nms_batch(const float *boxes, int B, long long row_stride, int n_
                          int method, float overlap, float sigma, float min_score, int log_domain, const int *cls,
                          long long *pick, int *count, float *score_out, long long score_stride, void *workspace,
                          size_t workspace_bytes, void *stream);
+/* ---- Bounding-box voting (Gidaris & Komodakis 2015; not in the reference; csrc/box_vote.hip) -------------------------------
+ * A winner of the per-class pass carries the one regressed box of the candidate that won; the other survivors of its class
+ * that sit on the same object are dropped (or re-scored by Soft-NMS).  Voting replaces the winner's box by the weighted mean
+ * of all of them (cfg.box_voting = { overlap, weight }; default: off).  One SEGMENT is one frame's rows: n rows of ncols fp32
+ * columns, columns 1-4 = x1 y1 x2 y2, column score_col (1-based, 5 .. ncols; ignored under weight_mode 0) the score, cls[i] an
+ * optional integer class, rect[i][0..3] optional fp64 coordinates.
+ * Winners of a segment: the 1-based rows pick[0 .. min(count, n)).  For a winner row m:
+ *   VOTERS   row j of the segment votes iff cls[j] == cls[m] (every row when cls is NULL) AND iou(j, m) >= overlap AND its
+ *            weight w_j is finite and > 0.  iou is frcnn_nms_device's fp32 arithmetic, every operation rounded on its own:
+ *            area = (x2-x1+1)*(y2-y1+1), w = max(0, (xx2 + (-1)*xx1) + 1), iou = (w*h) / ((area_j + area_m) - w*h).  A NaN IoU
+ *            is not a vote; m itself goes through the same test.  Who votes is a function of the inputs' bits: EXACT.
+ *   WEIGHTS  fp64.  weight_mode 0: 1.  1: (double)score_j, a plain score.  2: exp((double)score_j), a log-probability (what
+ *            frcnn_detect_post puts in bb[:,4]); within the math library's error of exp.
+ *   COORDS   c_j = rect[j][0..3] when rect is given, else (double)boxes[j][0..3].
+ *   RESULT   rect_out[m][t] = (sum w_j c_j[t]) / (sum w_j) over the voters, in fp64: one rounded product per term, the sums in a
+ *            fixed order (lane l of a 64-lane wave adds rows l, l+64, ... ascending; a butterfly 32 .. 1 adds the lanes), one
+ *            division.  No atomics: the value is a function of the segment's data alone -- not of the slot, of B, of the
+ *            neighbours or of the run.  votes_out[m] (optional) = the number of voters.  With FEWER THAN TWO voters
+ *            rect_out[m] = c_m bit for bit: an isolated detection is unchanged by voting (a lone voter other than m exists only
+ *            when m itself is barred by its weight or a NaN IoU; it does not move m either).
+ * Nothing is stored for rows that are not winners, for an empty segment or for a segment with count[b] == 0; a pick outside
+ * [1, n] is skipped.  Inputs are only read.
+ * Segments as in frcnn_nms_device_batch: segment b = boxes + b*row_stride*ncols, n = min(n_dev[b], n_cap) read on the device,
+ * row_stride >= n_cap; cls, rect, pick, rect_out and votes_out are offset by b*row_stride rows; count is a device int[B].  One
+ * wave per winner; no limit on n_cap beyond int (up to 2048 rows a segment is staged in LDS, beyond that read from global
+ * memory).  No workspace.  Errors (before any launch): B < 1 (or > 65535), n_cap < 0, row_stride < n_cap, ncols < 4, score_col
+ * outside [5, ncols] under weight_mode 1 / 2, bad weight_mode, overlap not in (0, 1] or NaN, NULL boxes / n_dev / pick / count /
+ * rect_out.  Counted under FRCNN_KC_NMS. */
+int frcnn_box_vote_batch(const float *boxes, int B, long long row_stride, int n_cap, const int *n_dev, int ncols, int score_col,
+                         int weight_mode, float overlap, const int *cls, const double *rect, const long long *pick,
+                         const int *count, double *rect_out, int *votes_out, void *stream);
 /* ---- Detector:detect glue kept on the device (Detector.lua:88-136; csrc/detect.hip) ------------------------------
  * frcnn_roi_windows: extract_roi_pooling_input (objective.lua:5-13) for k ROIs at once -- Localizer:inputToFeatureRect
  * (Localizer.lua:41-67, the reference's double arithmetic incl. its dH/dW mix-ups) over layers_host[nlayers][6] =
