@@ -4,8 +4,9 @@
 -- Lua loop of Detector.lua:39-66 is one scan + compaction kernel (frcnn_rpn_scan_batch), the per-candidate pooling loop
 -- (:94-98) one batched kernel, and the first NMS runs on the device.  Both NMS calls of the reference pass a tensor as
 -- `scores`, which nms.lua:37-43 ignores: boxes are processed by descending max-y.  That behaviour is reproduced.
--- There is ONE pipeline, written for a chunk of B frames of one size (first_stage + detect_chunk: frcnn_rpn_scan_batch,
--- frcnn_nms_device_batch twice, frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound):
+-- There is ONE pipeline, written for a chunk of B frames (first_stage + detect_chunk: frcnn_rpn_scan_batch -- or, for a chunk
+-- that mixes frame sizes under detect_batch's opts.mixed_sizes, frcnn_rpn_scan_ragged --, frcnn_nms_device_batch twice,
+-- frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound):
 -- detect_batch runs it on chunks of Detector.BATCH frames, detect(input) on the chunk { input }, which reads the proposal
 -- net's outputs where the net left them (no device copies); proposals(input) runs its first stage.
 -- 1:1 with the tested Python host mirror (faster-rcnn.torch_amd/Detector.py); checked statically, not executed here.
@@ -175,16 +176,17 @@ function Detector:clamp_candidates(dev, count, B)
   if changed then check(C.frcnn_memcpy_h2d(dev, count, 4 * B, nil)) end
 end
 
--- The ONE pipeline, for a chunk of B frames of one size; Detector:detect(input) is the chunk { input }.
+-- The ONE pipeline, for a chunk of B frames (of one size unless `ragged`); Detector:detect(input) is the chunk { input }.
 Detector.BATCH = 8              -- frames per chunk of detect_batch
 Detector.NMS_FIRST_CAP = 16384  -- rows the first NMS launch is sized for (see first_stage)
 
 -- Detector.lua:17-85 for a chunk: the proposal net frame by frame, ONE scan, (selection or score rows), ONE segmented first
 -- NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> a table { B, cnt (device int[4][B]),
 -- cap (rows a frame in mp, mi, mr, dpick: the match arrays the rest of the chunk reads, the selected rows under
--- pre_nms_top_n), fm, fslot, fs (frame b's last feature map at fm + b * fslot), count (host int[2][B]: rows and candidates per
--- frame), key_mode, key_col (of both NMS passes) }.  prefix: of the scratch names ('' for detect and proposals, 'b_' for
--- detect_batch: neither overwrites what the other left behind)
+-- pre_nms_top_n), fm, fslot, fs (frame b's last feature map at fm + b * fslot, its size fs[b]), count (host int[2][B]: rows and
+-- candidates per frame), key_mode, key_col (of both NMS passes) }.  prefix: of the scratch names ('' for detect and proposals,
+-- 'b_' for detect_batch: neither overwrites what the other left behind).  A chunk that really mixes sizes (detect_batch with
+-- opts.mixed_sizes) takes first_stage_ragged instead: steps 1 and 2 are ragged_front; from step 3 on nothing differs
 function Detector:first_stage(frames, prefix)
   local pnet = self.model.pnet
   local scratch = self.scratch
@@ -197,7 +199,7 @@ function Detector:first_stage(frames, prefix)
   -- ---- 1. per frame: the proposal net; its head maps and last feature map are copied to the frame's slot (the net reuses its
   --         output buffers).  A chunk of ONE frame reads the net's buffers where they are: no copies
   local Hs, Ws, maps, hoff = ffi.new('int[4]'), ffi.new('int[4]'), ffi.new('const float*[4]'), { 0 }
-  local slot, fslot, heads, fm, fs
+  local slot, fslot, heads, fm, fs1
   for b = 0, B - 1 do
     local outputs = pnet:forward(hip.to_device(frames[b + 1]))          -- :32-33
     if b == 0 then
@@ -207,8 +209,8 @@ function Detector:first_stage(frames, prefix)
         hoff[i + 1] = hoff[i] + math.floor((s[1] * s[2] * s[3] + 63) / 64) * 64
       end
       slot = hoff[5]
-      fs = outputs[self.nheads + 1]:size()
-      fslot = math.floor((fs[1] * fs[2] * fs[3] + 63) / 64) * 64
+      fs1 = outputs[self.nheads + 1]:size()
+      fslot = math.floor((fs1[1] * fs1[2] * fs1[3] + 63) / 64) * 64
       if B == 1 then
         for i = 1, 4 do maps[i - 1] = outputs[i].ptr end
         fm = ffi.cast('float*', outputs[self.nheads + 1].ptr)
@@ -222,7 +224,7 @@ function Detector:first_stage(frames, prefix)
       for i = 1, 4 do
         check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[i], outputs[i].ptr, 4 * 18 * Hs[i - 1] * Ws[i - 1], nil))
       end
-      check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[self.nheads + 1].ptr, 4 * fs[1] * fs[2] * fs[3], nil))
+      check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[self.nheads + 1].ptr, 4 * fs1[1] * fs1[2] * fs1[3], nil))
     end
   end
   -- ---- 2. ONE scan over the B slots (:39-66 on the device: log-softmax of every anchor's two logits, p > 0.95, decode,
@@ -237,6 +239,102 @@ function Detector:first_stage(frames, prefix)
   local mb = ffi.cast('float*', scratch(prefix .. 'match_box', 16 * B * cap).ptr)
   check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap,
                                mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
+  local fs, anchors = {}, {}
+  for b = 0, B - 1 do fs[b], anchors[b] = fs1, cap end
+  return self:first_nms({ B = B, cnt = cnt, cap = cap, mp = mp, mi = mi, mr = mr, mb = mb, fm = fm, fslot = fslot, fs = fs,
+                          anchors = anchors }, prefix)
+end
+
+-- (h, w) of the output a Localizer's layer list yields for an H x W input: per layer ceil((n + 2 pad - k) / d) + 1, the native
+-- model's arithmetic (stride-1 convolutions, ceil-mode 2x2 pooling)
+local function map_hw(layers, H, W)
+  local h, w = H, W
+  for _, l in ipairs(layers) do
+    h = math.ceil((h + 2 * l.padH - l.kH) / l.dH) + 1
+    w = math.ceil((w + 2 * l.padW - l.kW) / l.dW) + 1
+  end
+  return h, w
+end
+
+-- Steps 1 and 2 of first_stage for a chunk of B > 1 frames of DIFFERENT sizes.  The map sizes of every frame follow from its
+-- size on the host (map_hw over the layer lists Localizer.lua walks; checked against what the net hands back), so the slots --
+-- strided by the chunk's largest frame -- are sized before the first pass.  Frame b's four head maps lie packed at the start of
+-- slot b of `heads`, its last feature map at the start of slot b of `fm`.  ONE frcnn_rpn_scan_ragged with per-frame sizes,
+-- offsets and image sizes; cap, the row stride of the match arrays, is the largest frame's anchor count, anchors[b] frame b's own
+function Detector:ragged_front(frames, prefix, cnt)
+  local pnet = self.model.pnet
+  local scratch = self.scratch
+  local B = #frames
+  local nout = self.nheads + 1
+  if self.out_layers == nil then
+    self.out_layers = {}
+    for i = 1, nout do self.out_layers[i] = Localizer.new(pnet.outnode.children[i]).layers end
+  end
+  local Hs, Ws = ffi.new('int[?]', 4 * B), ffi.new('int[?]', 4 * B)
+  local map_off, img_wh = ffi.new('long long[?]', 4 * B), ffi.new('double[?]', 2 * B)
+  local fs, anchors, hoff = {}, {}, {}
+  local planes = self.model.layers[#self.model.layers].filters              -- of the last feature map
+  local slot, fslot, cap = 0, 0, 0
+  for b = 0, B - 1 do
+    local size = frames[b + 1]:size()
+    img_wh[2 * b], img_wh[2 * b + 1] = size[3], size[2]
+    hoff[b] = { 0 }
+    anchors[b] = 0
+    for i = 1, 4 do
+      local h, w = map_hw(self.out_layers[i], size[2], size[3])
+      Hs[4 * b + i - 1], Ws[4 * b + i - 1] = h, w
+      hoff[b][i + 1] = hoff[b][i] + math.floor((18 * h * w + 63) / 64) * 64
+      anchors[b] = anchors[b] + ASPECTS * h * w
+    end
+    local fh, fw = map_hw(self.out_layers[nout], size[2], size[3])
+    fs[b] = { planes, fh, fw }
+    slot = math.max(slot, hoff[b][5])
+    fslot = math.max(fslot, math.floor((planes * fh * fw + 63) / 64) * 64)
+    cap = math.max(cap, anchors[b])
+  end
+  local heads = ffi.cast('float*', scratch(prefix .. 'heads', 4 * B * slot).ptr)
+  local fm = ffi.cast('float*', scratch(prefix .. 'fm', 4 * B * fslot).ptr)
+  for b = 0, B - 1 do
+    local outputs = pnet:forward(hip.to_device(frames[b + 1]))          -- :32-33
+    for i = 1, 4 do
+      local s = outputs[i]:size()
+      if s[2] ~= Hs[4 * b + i - 1] or s[3] ~= Ws[4 * b + i - 1] then
+        error(string.format('Detector: head map %d of frame %d is %dx%d, expected %dx%d', i, b + 1, s[2], s[3],
+                            Hs[4 * b + i - 1], Ws[4 * b + i - 1]))
+      end
+      map_off[4 * b + i - 1] = b * slot + hoff[b][i]
+      check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[b][i], outputs[i].ptr, 4 * 18 * s[2] * s[3], nil))
+    end
+    local s = outputs[nout]:size()
+    if s[1] ~= planes or s[2] ~= fs[b][2] or s[3] ~= fs[b][3] then
+      error(string.format('Detector: the last feature map of frame %d is %dx%dx%d, expected %dx%dx%d', b + 1, s[1], s[2], s[3],
+                          planes, fs[b][2], fs[b][3]))
+    end
+    check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[nout].ptr, 4 * s[1] * s[2] * s[3], nil))
+  end
+  local wsb = tonumber(C.frcnn_rpn_scan_ragged_workspace_bytes(Hs, Ws, B))
+  local ws = scratch(prefix .. 'scan_ws', wsb)
+  local mp = ffi.cast('float*', scratch(prefix .. 'match_p', 4 * B * cap).ptr)
+  local mi = ffi.cast('int*', scratch(prefix .. 'match_idx', 16 * B * cap).ptr)
+  local mr = ffi.cast('double*', scratch(prefix .. 'match_rect', 32 * B * cap).ptr)
+  local mb = ffi.cast('float*', scratch(prefix .. 'match_box', 16 * B * cap).ptr)
+  check(C.frcnn_rpn_scan_ragged(heads, map_off, Hs, Ws, img_wh, B, self.aw.ptr, self.ah.ptr, 0.95, cap, mp, mi, mr, mb, cnt, ws.ptr,
+                                wsb, nil))
+  return { B = B, cnt = cnt, cap = cap, mp = mp, mi = mi, mr = mr, mb = mb, fm = fm, fslot = fslot, fs = fs, anchors = anchors }
+end
+
+-- first_stage for a chunk of B > 1 frames of different sizes
+function Detector:first_stage_ragged(frames, prefix)
+  local cnt = ffi.cast('int*', self.scratch(prefix .. 'counts', 16 * #frames).ptr)
+  self.model.pnet:evaluate()                                            -- :31
+  return self:first_nms(self:ragged_front(frames, prefix, cnt), prefix)
+end
+
+-- Steps 3 and on of first_stage, on what its front (one size: first_stage itself; mixed sizes: ragged_front) scanned
+function Detector:first_nms(front, prefix)
+  local scratch = self.scratch
+  local B, cnt, cap, mp, mi, mr, mb = front.B, front.cnt, front.cap, front.mp, front.mi, front.mr, front.mb
+  local fm, fslot, fs, anchors = front.fm, front.fslot, front.fs, front.anchors
   -- ---- 3. ONE segmented NMS (:74-85) on the device, the match counts read from DEVICE memory (no round trip between scan
   --         and NMS); the score tensor is ignored by nms.lua -> key = max-y.  Launch and workspace are sized for a bound on
   --         the matches, not for every anchor of the maps; a frame with more matches repeats the pass alone, sized by the
@@ -246,7 +344,6 @@ function Detector:first_stage(frames, prefix)
   local order, pre, post = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
   local key_mode, key_col = 0, 0
   if order == 'score' then key_mode, key_col = 2, 5 end
-  local anchors = cap
   local ncap = math.min(cap, Detector.NMS_FIRST_CAP)
   local ndev, boxes, ncols = cnt, mb, 4
   if order == 'score' and pre == nil then boxes, ncols = self:score_rows(mp, mb, B, cap, cnt, prefix), 5 end
@@ -264,8 +361,8 @@ function Detector:first_stage(frames, prefix)
   check(C.frcnn_memcpy_d2h(count, cnt, 8 * B, nil))                      -- ---- read-back 1 of 2: B pairs of counts
   check(C.frcnn_stream_sync(nil))
   for b = 0, B - 1 do
-    if count[b] > anchors then
-      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], anchors))
+    if count[b] > anchors[b] then
+      error(string.format('Detector: %d anchors pass p > 0.95, more than the %d the maps hold', count[b], anchors[b]))
     end
     if pre ~= nil then count[b] = math.min(count[b], pre) end           -- rows of the (compact) match arrays from here on
     if count[b] > ncap then
@@ -309,29 +406,45 @@ function Detector:detect(input)                                         -- Detec
   return self:detect_chunk({ input }, false, '')[1]
 end
 
--- Detector:detect_batch(inputs, shared_cnet) -- detect() for a list of frames of ONE size: a list with one entry per frame,
--- in order, each what detect(frame) returns.  Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
+-- Detector:detect_batch(inputs, opts) -- detect() for a list of frames -- of ONE size, or (opts.mixed_sizes) of any sizes: a list
+-- with one entry per frame, in order, each what detect(frame) returns.  opts: a table { shared_cnet = bool, mixed_sizes = bool },
+-- or (as before) the boolean shared_cnet itself.  Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
 -- head maps and last feature map are copied to the frame's slot), then ONE scan, ONE segmented NMS, per frame with
 -- candidates the pooling / classification net / class test, ONE segmented per-class NMS and ONE gather; the host waits
 -- twice per chunk instead of twice per frame.  Bit-identical to detect() frame by frame: detect() is a chunk of one.
 -- shared_cnet = true: ONE classification-net pass over the candidates of all frames of a chunk (frame b's rows at the prefix
 -- sum of the candidate counts); everything up to the pooled rows stays bit-identical, the net's outputs agree with detect()'s
 -- within the net's own error only (input scale and Linear form depend on the whole tensor / the row count).
+-- mixed_sizes = false (default): frames of different sizes are refused before anything is queued.  true: the chunks are the
+-- consecutive Detector.BATCH frames whatever their sizes; a chunk of one size (or of one frame) runs as it always did
+-- (frcnn_rpn_scan_batch), a chunk that mixes sizes keeps per-frame map sizes and image sizes, strides its slots by its largest
+-- frame and scans them with ONE frcnn_rpn_scan_ragged call (ragged_front); everything behind the scan reads per-frame device
+-- counts already, so nothing else changes and every frame's result stays what detect(frame) returns.
 -- 1:1 with Detector.detect_batch of the Python host mirror.
-function Detector:detect_batch(inputs, shared_cnet)
+function Detector:detect_batch(inputs, opts)
+  local shared_cnet, mixed_sizes = opts, false
+  if type(opts) == 'table' then shared_cnet, mixed_sizes = opts.shared_cnet, opts.mixed_sizes end
   local nframes = #inputs
-  for i = 2, nframes do                                                 -- refused before anything is queued
-    local a, b = inputs[1]:size(), inputs[i]:size()
-    if a[1] ~= b[1] or a[2] ~= b[2] or a[3] ~= b[3] then
+  local function same_size(i, j)
+    local a, b = inputs[i]:size(), inputs[j]:size()
+    return a[1] == b[1] and a[2] == b[2] and a[3] == b[3]
+  end
+  for i = 1, nframes do                                                 -- refused before anything is queued
+    if mixed_sizes then       -- (:dim() and indexing what :size() returns: both host and device tensors have them)
+      if inputs[i]:dim() ~= 3 or inputs[i]:size()[1] ~= 3 then error('Detector:detect_batch: expected 3xHxW frames') end
+    elseif not same_size(1, i) then
       error('Detector:detect_batch: frames of different sizes in one call')
     end
   end
   local results = {}
   local lo = 1
   while lo <= nframes do
-    local chunk = {}
-    for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do chunk[#chunk + 1] = inputs[i] end
-    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet, 'b_')) do results[#results + 1] = winners end
+    local chunk, ragged = {}, false
+    for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do
+      chunk[#chunk + 1] = inputs[i]
+      if not same_size(lo, i) then ragged = true end
+    end
+    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet, 'b_', ragged)) do results[#results + 1] = winners end
     lo = lo + Detector.BATCH
   end
   return results
@@ -339,7 +452,7 @@ end
 
 -- detect() of a chunk of frames -> one list of winners per frame: first_stage, then -- unless no frame has a match -- per
 -- frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather, read-back 2 of 2
-function Detector:detect_chunk(frames, shared, prefix)
+function Detector:detect_chunk(frames, shared, prefix, ragged)
   local model = self.model
   local cfg = model.cfg
   local cnet = model.cnet
@@ -351,9 +464,10 @@ function Detector:detect_chunk(frames, shared, prefix)
   local D = kh * kw * model.layers[#model.layers].filters
   local scratch = self.scratch
 
-  local st = self:first_stage(frames, prefix)                           -- :17-85
+  local st                                                              -- :17-85
+  if ragged then st = self:first_stage_ragged(frames, prefix) else st = self:first_stage(frames, prefix) end
   local B, cnt, cap, mp, mi, mr, dpick, count = st.B, st.cnt, st.cap, st.mp, st.mi, st.mr, st.dpick, st.count
-  local fm, fslot, fs, key_mode, key_col = st.fm, st.fslot, st.fs, st.key_mode, st.key_col
+  local fm, fslot, key_mode, key_col = st.fm, st.fslot, st.key_mode, st.key_col
   local Rmax = 0
   for b = 0, B - 1 do
     if count[b] > 0 then Rmax = math.max(Rmax, count[B + b]) end
@@ -392,6 +506,7 @@ function Detector:detect_chunk(frames, shared, prefix)
   -- kernel) and one pooling launch (no indices: there is no backward pass), or one RoIAlign launch
   local function pooled(b)
     local R = count[B + b]
+    local fs = st.fs[b]                                                 -- (the frame's own feature-map size)
     local cinput = hip.view(shared and (cbuf + row0[b] * D) or cbuf, { R, D })
     if method == 'align' then
       check(C.frcnn_roi_align_forward(fm + b * fslot, fs[1], fs[2], fs[3], mr + 4 * b * cap, dpick + b * cap, R, inv_sx, inv_sy,

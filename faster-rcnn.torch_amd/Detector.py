@@ -10,8 +10,9 @@ device memory), ONE read-back of two counts (the cnet's row count sizes its laun
 -> cnet -> class test + rect decode + ordered compaction -> per-class NMS -> one record per winner, and ONE read-back
 of the winner table.  The list detect() returns builds its {p, a, r, l, r2, class, confidence} tables on access.
 
-There is ONE pipeline, written for a chunk of B frames of one size (_first_stage + _detect_chunk: frcnn_rpn_scan_batch,
-frcnn_nms_device_batch twice, frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound).
+There is ONE pipeline, written for a chunk of B frames (_first_stage + _detect_chunk: frcnn_rpn_scan_batch -- or, for a chunk
+that mixes frame sizes under detect_batch(mixed_sizes=True), frcnn_rpn_scan_ragged --, frcnn_nms_device_batch twice,
+frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound).
 detect_batch(frames) runs it on chunks of BATCH frames, detect(input) on the chunk [input], proposals(input) runs its first
 stage on [input].  A chunk of one frame reads the proposal net's outputs where the model left them: no device copies.
 
@@ -205,6 +206,17 @@ def _frame_shape(x):
     if len(shp) != 3 or shp[0] != 3:
         raise ValueError("detect_batch: expected 3xHxW frames, got %r" % (shp,))
     return shp
+
+
+def _map_hw(layers, H, W):
+    """(h, w) of the output a layer list (rows kW, kH, dW, dH, padW, padH: a Localizer's) yields for an H x W input: per layer
+    ceil((n + 2 pad - k) / d) + 1 -- the native model's arithmetic (stride-1 convolutions, ceil-mode 2x2 pooling)."""
+    h, w = int(H), int(W)
+    for l in layers:
+        kW, kH, dW, dH, pW, pH = (int(v) for v in l[:6])
+        h = -((h + 2 * pH - kH) // -dH) + 1
+        w = -((w + 2 * pW - kW) // -dW) + 1
+    return h, w
 
 
 class _BatchRecord(object):
@@ -479,11 +491,12 @@ class Detector(object, metaclass=_DetectorType):
 
     BATCH = 8   # frames per chunk of detect_batch: bounds the memory of a call
 
-    def detect_batch(self, inputs, shared_cnet=False):
-        """detect() for a sequence of frames of one size: a list with one entry per frame, in order, each exactly what
-        detect(frame) returns.  The frames are processed in chunks of BATCH: the proposal net runs frame by frame, everything
-        between and after those passes once per chunk -- one scan, one segmented NMS, (per frame: pooling, classification net,
-        class test), one segmented per-class NMS, one gather -- and the host waits twice per chunk instead of twice per frame.
+    def detect_batch(self, inputs, shared_cnet=False, mixed_sizes=False):
+        """detect() for a sequence of frames -- of one size, or (mixed_sizes=True) of any sizes: a list with one entry per frame,
+        in order, each exactly what detect(frame) returns.  The frames are processed in chunks of BATCH: the proposal net runs
+        frame by frame, everything between and after those passes once per chunk -- one scan, one segmented NMS, (per frame:
+        pooling, classification net, class test), one segmented per-class NMS, one gather -- and the host waits twice per chunk
+        instead of twice per frame.
         Results are bit-identical to detect(), which is this pipeline on a chunk of one frame: every stage of a frame sees the
         inputs it sees there, through the same kernels, and a segment of a kernel computes what a one-segment launch computes.
         last_batch holds one record per frame (_BatchRecord).
@@ -491,30 +504,39 @@ class Detector(object, metaclass=_DetectorType):
         prefix sum of the candidate counts) instead of one per frame -- the large Linear streams its weights once per chunk.
         Everything up to the pooled rows stays bit-identical to detect(); the net's outputs do NOT (the two-plane form scales
         its input by the largest magnitude of the whole tensor, the Linear picks tile shape and arithmetic form by row
-        count): they agree with detect()'s within the net's own error (1e-3 bar), and winners follow from them."""
+        count): they agree with detect()'s within the net's own error (1e-3 bar), and winners follow from them.
+        mixed_sizes=False (default): frames of different sizes are refused (ValueError) before anything is queued.  True: the
+        chunks are the consecutive BATCH frames whatever their sizes.  A chunk of one size (or of one frame) runs as it always
+        did; a chunk that mixes sizes keeps per-frame map shapes and image sizes, strides its head-map and feature-map slots by
+        its largest frame and scans them with ONE frcnn_rpn_scan_ragged call (_ragged_front).  Everything behind the scan reads
+        per-frame device counts already, so nothing else changes, the two waits per chunk included, and every frame's result
+        and record stay bit-identical to detect(frame)."""
         frames = list(inputs)
         shapes = [_frame_shape(f) for f in frames]
-        if any(shp != shapes[0] for shp in shapes):
+        if not mixed_sizes and any(shp != shapes[0] for shp in shapes):
             raise ValueError("detect_batch: frames of different sizes in one call: %s" % sorted(set(shapes)))
         results, records = [], []
         step = max(int(self.BATCH), 1)
         for lo in range(0, len(frames), step):
             for r in records:     # (the records of the previous chunk view buffers this chunk writes)
                 r.detach()
-            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet), "b_")
+            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet), "b_", len(set(shapes[lo:lo + step])) > 1)
             results += res
             records += rec
         self.last_batch = records
         return results
 
-    def _first_stage(self, frames, pre):
-        """Detector.lua:17-85 for a chunk of B frames of one size: the proposal net frame by frame, ONE scan, (selection or score
-        rows), ONE segmented first NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> dict(B,
-        counts (device int32[4][B]), cap (rows a frame in p, idx, rect, pick: the match arrays the rest of the chunk reads, the
-        selected rows under pre_nms_top_n), fm, fshape (frame b's last feature map is fm.segment(b)), ns, Rs (rows and
-        candidates per frame), key (key_mode, key_col of both NMS passes), and box, row, matches for _records).
+    def _first_stage(self, frames, pre, ragged=False):
+        """Detector.lua:17-85 for a chunk of B frames (of one size unless `ragged`): the proposal net frame by frame, ONE scan,
+        (selection or score rows), ONE segmented first NMS, read-back 1 of 2, alone again every frame over the bound, the
+        post-NMS clamp -> dict(B, counts (device int32[4][B]), cap (rows a frame in p, idx, rect, pick: the match arrays the
+        rest of the chunk reads, the selected rows under pre_nms_top_n), fm, fshapes (frame b's last feature map is
+        fm.segment(b), its shape fshapes[b]), ns, Rs (rows and candidates per frame), key (key_mode, key_col of both NMS passes), and box, row, matches for _records).
         pre: prefix of the buffer names ("" for detect() and proposals(), "b_" for detect_batch: neither overwrites what the other
-        left behind)."""
+        left behind).
+        ragged (detect_batch(mixed_sizes=True) on a chunk that really mixes sizes): steps 1 and 2 are _ragged_front -- per-frame
+        map shapes and image sizes, ONE frcnn_rpn_scan_ragged -- and `cap` is the largest frame's anchor count; from step 3 on
+        nothing differs."""
         pnet = self.model["pnet"]
         s = stream_ptr()
         L = _lib.load()
@@ -524,43 +546,48 @@ class Detector(object, metaclass=_DetectorType):
         # ---- 1. per frame: the proposal net; its head maps and last feature map go to the frame's slot (the model owns and
         #         reuses its output buffers).  A chunk of ONE frame reads the model's buffers where they are: no copies.
         pnet.evaluate()  # :31
-        for b, f in enumerate(frames):
-            inp = to_device(f)
-            _, H, W = inp.shape
-            outputs = pnet.forward(inp)  # :33
-            if b == 0:
-                hshape = [o.shape for o in outputs[:4]]
-                hoff = [0]
-                for shp in hshape:
-                    hoff.append(hoff[-1] + (int(np.prod(shp)) + 63) // 64 * 64)
-                slot = hoff[4]
-                fshape = outputs[-1].shape
-                fslot = (int(np.prod(fshape)) + 63) // 64 * 64
-                if B == 1:
-                    heads, fm = [ptr(o) for o in outputs[:4]], outputs[-1].view(1, *fshape)
-                    break
-                heads_buf, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
-                heads = [ptr(heads_buf.offset_view(hoff[i], hshape[i])) for i in range(4)]
-            for i in range(4):
-                _lib.call("frcnn_memcpy_d2d", ptr(heads_buf.segment(b).offset_view(hoff[i], hshape[i])), ptr(outputs[i]),
-                          outputs[i].nbytes, s)
-            _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
         # counts (device int32[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
         counts = self._buf(pre + "counts", (4, B), i32)
         c_n, c_R = ptr(counts.segment(0)), counts.segment(1)
-        # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b).  Every anchor
-        #         of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is ever truncated
-        Hs = (C.c_int * 4)(*[shp[1] for shp in hshape])
-        Ws = (C.c_int * 4)(*[shp[2] for shp in hshape])
-        maps = (C.c_void_p * 4)(*[h.value for h in heads])
-        cap = ASPECTS * sum(shp[1] * shp[2] for shp in hshape)
-        wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B)
-        ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
-        mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
-        mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
         threshold = 0.95
-        _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, B, slot, ptr(self._aw), ptr(self._ah), float(W), float(H), threshold, cap,
-                  ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
+        if ragged:     # frames of different sizes: per-frame shapes, slots strided by the largest frame, ONE ragged scan
+            fm, fshapes, anchors, cap, (mp, mi, mr, mb) = self._ragged_front(frames, pre, c_n, threshold)
+        else:
+            for b, f in enumerate(frames):
+                inp = to_device(f)
+                _, H, W = inp.shape
+                outputs = pnet.forward(inp)  # :33
+                if b == 0:
+                    hshape = [o.shape for o in outputs[:4]]
+                    hoff = [0]
+                    for shp in hshape:
+                        hoff.append(hoff[-1] + (int(np.prod(shp)) + 63) // 64 * 64)
+                    slot = hoff[4]
+                    fshape = outputs[-1].shape
+                    fslot = (int(np.prod(fshape)) + 63) // 64 * 64
+                    if B == 1:
+                        heads, fm = [ptr(o) for o in outputs[:4]], outputs[-1].view(1, *fshape)
+                        break
+                    heads_buf, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
+                    heads = [ptr(heads_buf.offset_view(hoff[i], hshape[i])) for i in range(4)]
+                for i in range(4):
+                    _lib.call("frcnn_memcpy_d2d", ptr(heads_buf.segment(b).offset_view(hoff[i], hshape[i])), ptr(outputs[i]),
+                              outputs[i].nbytes, s)
+                _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
+            # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b).  Every
+            #         anchor of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is
+            #         ever truncated
+            Hs = (C.c_int * 4)(*[shp[1] for shp in hshape])
+            Ws = (C.c_int * 4)(*[shp[2] for shp in hshape])
+            maps = (C.c_void_p * 4)(*[h.value for h in heads])
+            cap = ASPECTS * sum(shp[1] * shp[2] for shp in hshape)
+            wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B)
+            ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
+            mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
+            mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
+            _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, B, slot, ptr(self._aw), ptr(self._ah), float(W), float(H), threshold,
+                      cap, ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
+            fshapes, anchors = [fshape] * B, [cap] * B
         # ---- 3. ONE segmented NMS (:74-85) on the device, the match counts read from device memory; the score tensor is ignored
         #         by nms.lua -> key = max-y.  The launch and its workspace are sized for a BOUND on the matches, not for every
         #         anchor of the maps (vgg_large: 45 015 anchors -> 253 MB of masks and a 704 x 704 tile grid per frame for a few
@@ -570,7 +597,7 @@ class Detector(object, metaclass=_DetectorType):
         order, pre_n, post_n = self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n
         key_mode, key_col = (2, 5) if order == "score" else (0, 0)
         ncap = min(cap, self.NMS_FIRST_CAP)
-        c_first, boxes, ncols, row, matches, anchors = c_n, mb, 4, None, None, cap
+        c_first, boxes, ncols, row, matches = c_n, mb, 4, None, None
         if order == "score" and pre_n is None:
             boxes, ncols = self._box5(mp, mb, B, cap, c_n, pre), 5
         if pre_n is not None:
@@ -588,8 +615,9 @@ class Detector(object, metaclass=_DetectorType):
         nR = self._read(counts.ptr, counts.nbytes // 2, i32)                   # ---- read-back 1 of 2: B pairs of counts
         ns, Rs = [int(v) for v in nR[:B]], [int(v) for v in nR[B:]]
         for b in range(B):
-            if ns[b] > anchors:
-                raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold" % (ns[b], threshold, anchors))
+            if ns[b] > anchors[b]:
+                raise _lib.FrcnnError("Detector: %d anchors pass p > %g, more than the %d the maps hold"
+                                      % (ns[b], threshold, anchors[b]))
         if pre_n is not None:
             matches, ns = ns, [min(n, pre_n) for n in ns]
         for b in range(B):
@@ -602,8 +630,59 @@ class Detector(object, metaclass=_DetectorType):
                 Rs[b] = int(self._read(c_Rb.ptr, c_Rb.dtype.itemsize, i32)[0])
         if post_n is not None:
             Rs = self._clamp_candidates(c_R, Rs)[0]
-        return dict(B=B, counts=counts, cap=cap, p=mp, idx=mi, rect=mr, box=mb, row=row, pick=pick, fm=fm, fshape=fshape,
+        return dict(B=B, counts=counts, cap=cap, p=mp, idx=mi, rect=mr, box=mb, row=row, pick=pick, fm=fm, fshapes=fshapes,
                     ns=ns, Rs=Rs, matches=matches, key=(key_mode, key_col))
+
+    def _ragged_front(self, frames, pre, c_n, threshold):
+        """Steps 1 and 2 of _first_stage for a chunk of B > 1 frames of different sizes -> (fm, fshapes, anchors, cap, (match_p,
+        match_idx, match_rect, match_box)).  The map shapes of every frame follow from its size on the host (_map_hw over the
+        layer lists the Localizer walks; checked against what the net hands back), so the slots -- strided by the chunk's
+        largest frame -- are sized before the first pass.  Frame b's four head maps lie packed at the start of slot b of
+        `heads`, its last feature map at the start of slot b of `fm` (fm.segment(b), fshapes[b]).  ONE frcnn_rpn_scan_ragged
+        with per-frame sizes, offsets and image sizes; cap, the row stride of the match arrays, is the largest frame's anchor
+        count, anchors[b] frame b's own."""
+        pnet = self.model["pnet"]
+        s = stream_ptr()
+        B = len(frames)
+        i32 = np.int32
+        nodes = pnet.outnode.children
+        sizes = [_frame_shape(f)[1:] for f in frames]
+        hw = [[_map_hw(n.layers, H, W) for n in nodes] for H, W in sizes]      # per frame: 4 head maps, the last feature map
+        heads_buf = fm = None
+        hoffs, fshapes = [], []
+        for b, f in enumerate(frames):
+            outputs = pnet.forward(to_device(f))  # :33
+            got = [tuple(o.shape[1:]) for o in outputs]
+            if got != hw[b]:
+                raise _lib.FrcnnError("Detector: a %dx%d frame gives maps %r, expected %r" % (sizes[b] + (got, hw[b])))
+            if b == 0:    # (the planes of every output: the same for every frame)
+                planes = [o.shape[0] for o in outputs]
+                for t in hw:
+                    off = [0]
+                    for i in range(4):
+                        off.append(off[-1] + (planes[i] * t[i][0] * t[i][1] + 63) // 64 * 64)
+                    hoffs.append(off)
+                slot = max(off[4] for off in hoffs)
+                fslot = max((planes[-1] * t[-1][0] * t[-1][1] + 63) // 64 * 64 for t in hw)
+                heads_buf, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
+            for i in range(4):
+                _lib.call("frcnn_memcpy_d2d", ptr(heads_buf.segment(b).offset_view(hoffs[b][i], outputs[i].shape)), ptr(outputs[i]),
+                          outputs[i].nbytes, s)
+            _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
+            fshapes.append(tuple(outputs[-1].shape))
+        Hs = (C.c_int * (4 * B))(*[t[i][0] for t in hw for i in range(4)])
+        Ws = (C.c_int * (4 * B))(*[t[i][1] for t in hw for i in range(4)])
+        map_off = (C.c_longlong * (4 * B))(*[b * slot + hoffs[b][i] for b in range(B) for i in range(4)])
+        img_wh = (C.c_double * (2 * B))(*[float(v) for H, W in sizes for v in (W, H)])
+        anchors = [ASPECTS * sum(h * w for h, w in t[:4]) for t in hw]
+        cap = max(anchors)
+        wsb = _lib.load().frcnn_rpn_scan_ragged_workspace_bytes(Hs, Ws, B)
+        ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
+        mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
+        mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
+        _lib.call("frcnn_rpn_scan_ragged", ptr(heads_buf), map_off, Hs, Ws, img_wh, B, ptr(self._aw), ptr(self._ah), threshold, cap,
+                  ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
+        return fm, fshapes, anchors, cap, (mp, mi, mr, mb)
 
     def _records(self, st, more=None):
         """One _BatchRecord per frame of the chunk _first_stage returned st for (views of the chunk's buffers, kept = 0);
@@ -621,7 +700,7 @@ class Detector(object, metaclass=_DetectorType):
             records.append(_BatchRecord(n, R, dev, matches[b] if matches is not None else None))
         return records
 
-    def _detect_chunk(self, frames, shared, pre):
+    def _detect_chunk(self, frames, shared, pre, ragged=False):
         """detect() of a chunk of frames -> (one result per frame, their records): _first_stage, then -- unless no frame has a match
         -- per frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather and
         read-back 2 of 2."""
@@ -636,7 +715,7 @@ class Detector(object, metaclass=_DetectorType):
         L = _lib.load()
         i32 = np.int32
 
-        st = self._first_stage(frames, pre)   # :17-85
+        st = self._first_stage(frames, pre, ragged)   # :17-85
         B, counts, cap, mp, mi, mr, pick = st["B"], st["counts"], st["cap"], st["p"], st["idx"], st["rect"], st["pick"]
         ns, Rs, (key_mode, key_col) = st["ns"], st["Rs"], st["key"]
         c_K, c_W = counts.segment(2), ptr(counts.segment(3))
@@ -646,7 +725,7 @@ class Detector(object, metaclass=_DetectorType):
         # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) into the frame's rows.  These launches come first:
         #         the device has been idle since read-back 1, and whatever else the host prepares it prepares while they run
         cnet.evaluate()
-        fmC, fmH, fmW = st["fshape"]
+        fshapes = st["fshapes"]
         D = kh * kw * planes
         # first row of frame b in the net's input / output arrays: its own segment (Rmax rows per frame), or (shared pass) the
         # prefix sum of R
@@ -660,6 +739,7 @@ class Detector(object, metaclass=_DetectorType):
 
         def pooled(b):    # the region features of frame b's candidates (_pool) -> its input rows
             R = Rs[b]
+            fmC, fmH, fmW = fshapes[b]
             cinput = cinput_buf.offset_view(D * row0[b] if shared else 0, (R, D))
             self._pool(roi, ptr(st["fm"].segment(b)), fmC, fmH, fmW, ptr(mr.segment(b)), ptr(pick.segment(b)), R, cinput, s,
                        rows=Rmax)

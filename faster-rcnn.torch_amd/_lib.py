@@ -99,6 +99,9 @@ _SIGS = {
     "frcnn_rpn_scan_batch_workspace_bytes": ([vp, vp, C.c_int], C.c_size_t),
     "frcnn_rpn_scan_batch": ([vp, vp, vp, C.c_int, C.c_longlong, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp,
                              vp, C.c_size_t, vp], C.c_int),
+    "frcnn_rpn_scan_ragged_workspace_bytes": ([vp, vp, C.c_int], C.c_size_t),
+    "frcnn_rpn_scan_ragged": ([vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp, C.c_size_t, vp],
+                              C.c_int),
     "frcnn_rpn_loss": ([vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp], C.c_int),
     "frcnn_loss_accumulate": ([vp, C.c_int, vp, vp], C.c_int),
     "frcnn_linear_forward": ([vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp], C.c_int),

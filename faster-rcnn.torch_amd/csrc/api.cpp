@@ -467,6 +467,16 @@ int frcnn_rpn_scan_batch(const float* const* maps, const int* H, const int* W, i
   return rpn_scan_batch(L, B, (long)slot_stride, anchor_w, anchor_h, img_w, img_h, p_threshold, cap, match_p, match_idx,
                         match_rect, match_box, count, ws, ws_bytes, S(stream));
 }
+size_t frcnn_rpn_scan_ragged_workspace_bytes(const int* Hs, const int* Ws, int B) {
+  return rpn_scan_ragged_workspace_bytes(Hs, Ws, B);
+}
+int frcnn_rpn_scan_ragged(const float* heads, const long long* map_off, const int* Hs, const int* Ws, const double* img_wh, int B,
+                          const float* anchor_w, const float* anchor_h, double p_threshold, int cap, float* match_p,
+                          int* match_idx, double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
+                          void* stream) {
+  return rpn_scan_ragged(heads, map_off, Hs, Ws, img_wh, B, anchor_w, anchor_h, p_threshold, cap, match_p, match_idx, match_rect,
+                         match_box, count, ws, ws_bytes, S(stream));
+}
 int frcnn_rpn_loss(const float* const* maps, float* const* deltas, const int* H, const int* W, const int* ex_idx,
                    const double* ex_anchor, const double* ex_roi, const int* ex_class, int npos, int nneg,
                    int bgclass, double* ex_loss, float* crtarget, float* cctarget, void* stream) {

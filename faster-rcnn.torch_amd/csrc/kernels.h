@@ -268,6 +268,12 @@ int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, d
              double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes,
              hipStream_t s);
 size_t rpn_scan_workspace_bytes(const RpnLayers& L);
+// B frames of different sizes in one pass: frame b's sizes Hs / Ws[4b ... 4b+3], its maps at heads + map_off[4b + l] floats, its
+// image size img_wh[2b], [2b+1] (host arrays); one workspace slice per frame, sized by the frame's own anchor count
+int rpn_scan_ragged(const float* heads, const long long* map_off, const int* Hs, const int* Ws, const double* img_wh, int B,
+                    const float* anchor_w, const float* anchor_h, double p_threshold, int cap, float* match_p, int* match_idx,
+                    double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes, hipStream_t s);
+size_t rpn_scan_ragged_workspace_bytes(const int* Hs, const int* Ws, int B);
 int rpn_loss(const RpnLayers& L, float* const* delta, const int* ex_idx, const double* ex_anchor,
              const double* ex_roi, const int* ex_class, int npos, int nneg, int bgclass,
              double* ex_loss, float* crtarget, float* cctarget, hipStream_t s);

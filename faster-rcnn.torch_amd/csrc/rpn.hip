@@ -186,6 +186,111 @@ int rpn_scan(const RpnLayers& L, const float* anchor_w, const float* anchor_h, d
                         match_box, count, ws, ws_bytes, s);
 }
 
+// ---- B frames of DIFFERENT sizes in one pass (Detector:detect_batch with mixed_sizes).  Every frame has a descriptor of its
+// own: head-map sizes, their prefix, the four maps (the call's float offsets from `heads`, resolved to addresses on the host), the
+// image size and the byte offset of its workspace slice (sized by its own anchor count, at prefix offsets).  The descriptors
+// travel BY VALUE as a kernel argument, in groups of at most RAGGED_GROUP frames: no device table, no copy, no host memory that
+// has to outlive the call, no wait.  The first three live in the descriptor AS a ScanArgs, which both passes hand to the bodies
+// above where it lies (in the kernel-argument segment, like the batch kernels' own: indexing it by layer needs no private copy),
+// so a frame is bit for bit what a one-slot launch computes.  The threshold pass takes the frame from grid dimension y with
+// grid.x sized for the group's largest frame (a block whose first anchor lies behind its frame's total leaves through the body's
+// loop condition); the compaction runs one workgroup per frame.
+constexpr int RAGGED_GROUP = 16;
+struct RaggedFrame {
+  ScanArgs a;           // map[l] = heads + map_off[l]
+  double img_w, img_h;
+  size_t ws_off;        // bytes from the (aligned) workspace base to the frame's slice
+};
+struct RaggedGroup { RaggedFrame f[RAGGED_GROUP]; };
+static_assert(sizeof(RaggedGroup) <= 2048, "the descriptors of a group travel as a kernel argument (limit 4 KB)");
+
+__global__ void rpn_scan_ragged_kernel(RaggedGroup g, const float* __restrict__ aw, const float* __restrict__ ah, double thr,
+                                       char* __restrict__ ws) {
+  const RaggedFrame& d = g.f[blockIdx.y];
+  const ScanSlice v = rpn_scan_slice(ws + d.ws_off, 0, 0, d.a.start[4]);
+  rpn_scan_body(d.a, 0, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, aw, ah, d.img_w, d.img_h, thr, v.flag, v.dp,
+                v.drect);
+}
+// (b0: the group's first frame, for the rows of the match arrays and the count)
+__global__ __launch_bounds__(1024) void rpn_compact_ragged_kernel(RaggedGroup g, int b0, char* __restrict__ ws, int cap,
+                                                                  float* __restrict__ match_p, int* __restrict__ match_idx,
+                                                                  double* __restrict__ match_rect, float* __restrict__ match_box,
+                                                                  int* __restrict__ count) {
+  const RaggedFrame& d = g.f[blockIdx.x];
+  const ScanSlice v = rpn_scan_slice(ws + d.ws_off, 0, 0, d.a.start[4]);
+  const int b = b0 + blockIdx.x;
+  const size_t o = (size_t)b * cap;
+  rpn_compact_body(d.a, v.flag, v.dp, v.drect, cap, match_p + o, match_idx + 4 * o, match_rect + 4 * o, match_box + 4 * o, count + b);
+}
+
+// (host) frame b's sizes Hs[4b..], Ws[4b..] -> its anchor count, or -1 when a size lies outside 1 ... 200
+static long ragged_frame_anchors(const int* Hs, const int* Ws, int b) {
+  long n = 0;
+  for (int l = 0; l < 4; ++l) {
+    const int H = Hs[4 * b + l], W = Ws[4 * b + l];
+    if (H < 1 || H > 200 || W < 1 || W > 200) return -1;
+    n += 3L * H * W;
+  }
+  return n;
+}
+size_t rpn_scan_ragged_workspace_bytes(const int* Hs, const int* Ws, int B) {
+  size_t bytes = 256;
+  if (!Hs || !Ws) return bytes;
+  for (int b = 0; b < B; ++b) bytes += rpn_scan_slice_bytes((size_t)std::max(ragged_frame_anchors(Hs, Ws, b), 0L));
+  return bytes;
+}
+
+int rpn_scan_ragged(const float* heads, const long long* map_off, const int* Hs, const int* Ws, const double* img_wh, int B,
+                    const float* anchor_w, const float* anchor_h, double p_threshold, int cap, float* match_p, int* match_idx,
+                    double* match_rect, float* match_box, int* count, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (B == 0) return FRCNN_OK;
+  FR_CHECK(B > 0 && B <= 65535, "rpn_scan_ragged: %d frames (0 ... 65535)", B);
+  FR_CHECK(heads && map_off && Hs && Ws && img_wh && anchor_w && anchor_h && match_p && match_idx && match_rect && match_box &&
+               count && ws,
+           "rpn_scan_ragged: NULL argument");
+  FR_CHECK(cap >= 0, "rpn_scan_ragged: negative cap");
+  // everything is checked before the first launch: a refused call has written nothing
+  for (int b = 0; b < B; ++b) {
+    for (int l = 0; l < 4; ++l) {
+      FR_CHECK(Hs[4 * b + l] >= 1 && Hs[4 * b + l] <= 200 && Ws[4 * b + l] >= 1 && Ws[4 * b + l] <= 200,
+               "rpn_scan_ragged: head map %d of frame %d is %dx%d (1 ... 200: the anchor tables hold 200, Anchors.lua:15)", l + 1, b,
+               Hs[4 * b + l], Ws[4 * b + l]);
+      FR_CHECK(map_off[4 * b + l] >= 0, "rpn_scan_ragged: negative offset of map %d of frame %d", l + 1, b);
+    }
+  }
+  FR_CHECK(ws_bytes >= rpn_scan_ragged_workspace_bytes(Hs, Ws, B), "rpn_scan_ragged: workspace too small");
+  char* base = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+  size_t ws_off = 0;
+  for (int b0 = 0; b0 < B; b0 += RAGGED_GROUP) {
+    const int nb = std::min(B - b0, RAGGED_GROUP);
+    RaggedGroup g;
+    memset(&g, 0, sizeof(g));
+    size_t n_max = 0, n_sum = 0;
+    for (int i = 0; i < nb; ++i) {
+      const int b = b0 + i;
+      RaggedFrame& d = g.f[i];
+      d.a.start[0] = 0;
+      for (int l = 0; l < 4; ++l) {
+        d.a.H[l] = Hs[4 * b + l]; d.a.W[l] = Ws[4 * b + l];
+        d.a.start[l + 1] = d.a.start[l] + 3 * d.a.H[l] * d.a.W[l];
+        d.a.map[l] = heads + map_off[4 * b + l];
+      }
+      d.img_w = img_wh[2 * b]; d.img_h = img_wh[2 * b + 1];
+      d.ws_off = ws_off;
+      const size_t n = (size_t)d.a.start[4];
+      ws_off += rpn_scan_slice_bytes(n);
+      n_max = std::max(n_max, n); n_sum += n;
+    }
+    const int grid = (int)std::min<size_t>((n_max + 255) / 256, 1024);
+    FR_LAUNCH(KC_RPN, 0, n_sum * 24.0, s, rpn_scan_ragged_kernel, dim3(grid, nb), dim3(256), 0, g, anchor_w, anchor_h, p_threshold,
+              base);
+    FR_LAUNCH(KC_RPN, 0, n_sum * 1.0, s, rpn_compact_ragged_kernel, dim3(nb), dim3(1024), 0, g, b0, base, cap, match_p, match_idx,
+              match_rect, match_box, count);
+  }
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // sparse RPN loss.  One thread per example.  ex_idx[e] = {layer, aspect, y, x} (1-based).
 // Positives first (e < npos), then negatives.

@@ -183,17 +183,21 @@ def mean_average_precision_range(detections, ground_truth, iou_thresholds=IOU_RA
     return dict(mAP=float(np.mean([by_iou[t]["mAP"] for t in ts])), by_iou=by_iou)
 
 
-def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False, batch=1):
+def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False, batch=1, mixed_sizes=False):
     """Detector:detect on `count` validation images (main.lua:198-206) scored against their ground truth.
     iou_threshold: a number, or a sequence of them -> the dict of mean_average_precision_range (mAP, by_iou).
     batch > 1: up to that many consecutive frames of one size go through Detector.detect_batch in one call (same detections,
-    two host waits per chunk instead of two per frame); 1 is the frame-by-frame loop of the reference."""
+    two host waits per chunk instead of two per frame); 1 is the frame-by-frame loop of the reference.
+    mixed_sizes=True (with batch > 1): a change of size no longer ends a chunk -- `batch` consecutive frames, whatever their
+    sizes, go through detect_batch(..., mixed_sizes=True) (a data set whose every file has a size of its own)."""
     detections, ground_truth = [], []
     images = 0
-    pending = []     # (image id, frame) of one size, waiting for detect_batch
+    pending = []     # (image id, frame) -- of one size unless mixed_sizes -- waiting for detect_batch
 
     def flush():
-        for (image_id, _), winners in zip(pending, detector.detect_batch([img for _, img in pending])):
+        imgs = [img for _, img in pending]
+        results = detector.detect_batch(imgs, mixed_sizes=True) if mixed_sizes else detector.detect_batch(imgs)
+        for (image_id, _), winners in zip(pending, results):
             for w in winners:
                 detections.append((image_id, int(w["class"]), float(w["confidence"]), w["r2"]))
         del pending[:]
@@ -204,7 +208,7 @@ def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_
             for roi in x["rois"]:
                 ground_truth.append((image_id, int(roi.class_index), roi.rect))
             if batch > 1:
-                if pending and tuple(pending[0][1].shape) != tuple(x["img"].shape):
+                if not mixed_sizes and pending and tuple(pending[0][1].shape) != tuple(x["img"].shape):
                     flush()
                 pending.append((image_id, x["img"]))
                 if len(pending) >= batch:

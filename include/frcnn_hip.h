@@ -376,6 +376,22 @@ int frcnn_rpn_scan_batch(const float *const *maps_host, const int *H_host, const
                          const float *anchor_w, const float *anchor_h, double img_w, double img_h, double p_threshold,
                          int cap, float *match_p, int *match_idx, double *match_rect, float *match_box, int *count,
                          void *workspace, size_t workspace_bytes, void *stream);
+/* The same for B frames of DIFFERENT sizes (Detector:detect_batch with mixed_sizes).  Host arrays, read before the call
+ * returns: H_host / W_host [B][4] (frame b's head-map sizes), map_off_host [B][4] (floats from `heads` to frame b's map l),
+ * img_wh_host [B][2] = {img_w, img_h}.  Per frame exactly frcnn_rpn_scan on that frame's maps, sizes and image size, bit for
+ * bit: frame b's matches are rows [b*cap, b*cap + min(count[b], cap)) of the match arrays, count (device int[B]) holds the
+ * full numbers, nothing is stored behind a frame's matches.  Two launches per group of at most 16 frames (the frames'
+ * descriptors travel as a kernel argument: no device table, no copy, no wait).  The workspace holds one slice per frame,
+ * sized by that frame's anchors: for frames of one size the byte count is frcnn_rpn_scan_batch_workspace_bytes', for B = 1
+ * frcnn_rpn_scan_workspace_bytes'.  Refused on the host before any launch: B < 0 or > 65535, an H or W outside 1 ... 200, a
+ * negative cap or offset, a workspace that is too small, a NULL array with B > 0.  B == 0 does nothing.
+ * The size query validates nothing: it counts a frame with an H or W outside 1 ... 200 as no anchors and returns the 256-byte
+ * head alone for NULL arrays or B <= 0; the scan call checks the sizes before it looks at the workspace. */
+size_t frcnn_rpn_scan_ragged_workspace_bytes(const int *H_host, const int *W_host, int B);
+int frcnn_rpn_scan_ragged(const float *heads, const long long *map_off_host, const int *H_host, const int *W_host,
+                          const double *img_wh_host, int B, const float *anchor_w, const float *anchor_h, double p_threshold,
+                          int cap, float *match_p, int *match_idx, double *match_rect, float *match_box, int *count,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- score-ordered proposals with pre- and post-NMS caps (not in the reference; csrc/topk.hip) -----------------------
  * Detector.lua:39-85 hands every anchor with exp(p) > 0.95 to nms(), which ignores the scores it is given (key = max-y).  A

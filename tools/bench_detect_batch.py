@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import frcnn_amd as F  # noqa: E402
+from detect_bench_model import amplified_vgg_small  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--frames", type=int, default=208, help="frames per measurement (>= 200; a multiple of 16)")
@@ -36,19 +37,7 @@ ap.add_argument("--gain", type=float, default=30.0)
 ap.add_argument("--shared", action="store_true", help="with --trace-chunks: shared_cnet=True")
 args = ap.parse_args()
 
-cfg = dict(F.duplo_cfg)
-model = F.vgg_small(cfg)
-weights, gradient = F.combine_and_flatten_parameters(model["pnet"], model["cnet"], seed=42)
-nat = model["native"]
-w = weights.cpu().numpy().copy()
-for off, cnt, kind, aux in nat.param_table:
-    if kind == 0 and aux == 18:
-        v = w[off:off + cnt].reshape(18, -1)
-        for a in range(3):
-            v[a * 6:a * 6 + 2] *= args.gain
-    if kind == 3 and cnt == 512 * (cfg["class_count"] + 1):
-        w[off:off + cnt] *= 200.0
-weights.copy_(torch.from_numpy(w))
+cfg, model, weights, gradient = amplified_vgg_small(F, args.gain)
 imgs = [F.to_device(F.synthetic_image(450, 800, i)) for i in range(4)]
 has_batch = hasattr(F.Detector, "detect_batch")
 batches = [int(b) for b in args.batches.split(",")] if has_batch and args.only != "detect" else []
