@@ -4,9 +4,11 @@
 -- Lua loop of Detector.lua:39-66 is one scan + compaction kernel (frcnn_rpn_scan_batch), the per-candidate pooling loop
 -- (:94-98) one batched kernel, and the first NMS runs on the device.  Both NMS calls of the reference pass a tensor as
 -- `scores`, which nms.lua:37-43 ignores: boxes are processed by descending max-y.  That behaviour is reproduced.
--- There is ONE pipeline, written for a chunk of B frames (first_stage + detect_chunk: frcnn_rpn_scan_batch -- or, for a chunk
--- that mixes frame sizes under detect_batch's opts.mixed_sizes, frcnn_rpn_scan_ragged --, frcnn_nms_device_batch twice,
--- frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound):
+-- There is ONE pipeline, written for a chunk of B frames (first_stage + detect_chunk: ONE scan, frcnn_nms_device_batch twice,
+-- frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound), with ONE front: every frame's slot
+-- offsets, feature-map size and anchor count come from its size's layout (Detector:layout, host arithmetic, cached per size),
+-- the chunk's strides are those of its largest frame, and the sizes pick the scan -- frcnn_rpn_scan_batch for a chunk of one
+-- size, frcnn_rpn_scan_ragged for one that mixes sizes under detect_batch's opts.mixed_sizes:
 -- detect_batch runs it on chunks of Detector.BATCH frames, detect(input) on the chunk { input }, which reads the proposal
 -- net's outputs where the net left them (no device copies); proposals(input) runs its first stage.
 -- 1:1 with the tested Python host mirror (faster-rcnn.torch_amd/Detector.py); checked statically, not executed here.
@@ -176,74 +178,9 @@ function Detector:clamp_candidates(dev, count, B)
   if changed then check(C.frcnn_memcpy_h2d(dev, count, 4 * B, nil)) end
 end
 
--- The ONE pipeline, for a chunk of B frames (of one size unless `ragged`); Detector:detect(input) is the chunk { input }.
+-- The ONE pipeline, for a chunk of B frames, of one size or not; Detector:detect(input) is the chunk { input }.
 Detector.BATCH = 8              -- frames per chunk of detect_batch
 Detector.NMS_FIRST_CAP = 16384  -- rows the first NMS launch is sized for (see first_stage)
-
--- Detector.lua:17-85 for a chunk: the proposal net frame by frame, ONE scan, (selection or score rows), ONE segmented first
--- NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> a table { B, cnt (device int[4][B]),
--- cap (rows a frame in mp, mi, mr, dpick: the match arrays the rest of the chunk reads, the selected rows under
--- pre_nms_top_n), fm, fslot, fs (frame b's last feature map at fm + b * fslot, its size fs[b]), count (host int[2][B]: rows and
--- candidates per frame), key_mode, key_col (of both NMS passes) }.  prefix: of the scratch names ('' for detect and proposals,
--- 'b_' for detect_batch: neither overwrites what the other left behind).  A chunk that really mixes sizes (detect_batch with
--- opts.mixed_sizes) takes first_stage_ragged instead: steps 1 and 2 are ragged_front; from step 3 on nothing differs
-function Detector:first_stage(frames, prefix)
-  local pnet = self.model.pnet
-  local scratch = self.scratch
-  local B = #frames
-
-  -- counts (device int[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
-  local cnt = ffi.cast('int*', scratch(prefix .. 'counts', 16 * B).ptr)
-  local input_size = frames[1]:size()
-  pnet:evaluate()                                                       -- :31
-  -- ---- 1. per frame: the proposal net; its head maps and last feature map are copied to the frame's slot (the net reuses its
-  --         output buffers).  A chunk of ONE frame reads the net's buffers where they are: no copies
-  local Hs, Ws, maps, hoff = ffi.new('int[4]'), ffi.new('int[4]'), ffi.new('const float*[4]'), { 0 }
-  local slot, fslot, heads, fm, fs1
-  for b = 0, B - 1 do
-    local outputs = pnet:forward(hip.to_device(frames[b + 1]))          -- :32-33
-    if b == 0 then
-      for i = 1, 4 do
-        local s = outputs[i]:size()
-        Hs[i - 1], Ws[i - 1] = s[2], s[3]
-        hoff[i + 1] = hoff[i] + math.floor((s[1] * s[2] * s[3] + 63) / 64) * 64
-      end
-      slot = hoff[5]
-      fs1 = outputs[self.nheads + 1]:size()
-      fslot = math.floor((fs1[1] * fs1[2] * fs1[3] + 63) / 64) * 64
-      if B == 1 then
-        for i = 1, 4 do maps[i - 1] = outputs[i].ptr end
-        fm = ffi.cast('float*', outputs[self.nheads + 1].ptr)
-      else
-        heads = ffi.cast('float*', scratch(prefix .. 'heads', 4 * B * slot).ptr)
-        fm = ffi.cast('float*', scratch(prefix .. 'fm', 4 * B * fslot).ptr)
-        for i = 0, 3 do maps[i] = heads + hoff[i + 1] end
-      end
-    end
-    if B > 1 then
-      for i = 1, 4 do
-        check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[i], outputs[i].ptr, 4 * 18 * Hs[i - 1] * Ws[i - 1], nil))
-      end
-      check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[self.nheads + 1].ptr, 4 * fs1[1] * fs1[2] * fs1[3], nil))
-    end
-  end
-  -- ---- 2. ONE scan over the B slots (:39-66 on the device: log-softmax of every anchor's two logits, p > 0.95, decode,
-  --         overlap test, compaction): frame b's matches at rows [b * cap, b * cap + n_b)
-  local cap = 0   -- every anchor of the four maps may pass: the buffers hold them all (vgg_large 1000x600: 45 015)
-  for i = 0, 3 do cap = cap + ASPECTS * Hs[i] * Ws[i] end
-  local wsb = tonumber(C.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B))
-  local ws = scratch(prefix .. 'scan_ws', wsb)
-  local mp = ffi.cast('float*', scratch(prefix .. 'match_p', 4 * B * cap).ptr)
-  local mi = ffi.cast('int*', scratch(prefix .. 'match_idx', 16 * B * cap).ptr)
-  local mr = ffi.cast('double*', scratch(prefix .. 'match_rect', 32 * B * cap).ptr)
-  local mb = ffi.cast('float*', scratch(prefix .. 'match_box', 16 * B * cap).ptr)
-  check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, input_size[3], input_size[2], 0.95, cap,
-                               mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
-  local fs, anchors = {}, {}
-  for b = 0, B - 1 do fs[b], anchors[b] = fs1, cap end
-  return self:first_nms({ B = B, cnt = cnt, cap = cap, mp = mp, mi = mi, mr = mr, mb = mb, fm = fm, fslot = fslot, fs = fs,
-                          anchors = anchors }, prefix)
-end
 
 -- (h, w) of the output a Localizer's layer list yields for an H x W input: per layer ceil((n + 2 pad - k) / d) + 1, the native
 -- model's arithmetic (stride-1 convolutions, ceil-mode 2x2 pooling)
@@ -256,85 +193,126 @@ local function map_hw(layers, H, W)
   return h, w
 end
 
--- Steps 1 and 2 of first_stage for a chunk of B > 1 frames of DIFFERENT sizes.  The map sizes of every frame follow from its
--- size on the host (map_hw over the layer lists Localizer.lua walks; checked against what the net hands back), so the slots --
--- strided by the chunk's largest frame -- are sized before the first pass.  Frame b's four head maps lie packed at the start of
--- slot b of `heads`, its last feature map at the start of slot b of `fm`.  ONE frcnn_rpn_scan_ragged with per-frame sizes,
--- offsets and image sizes; cap, the row stride of the match arrays, is the largest frame's anchor count, anchors[b] frame b's own
-function Detector:ragged_front(frames, prefix, cnt)
+-- What a frame of H x W occupies in a chunk, from the layer lists Localizer.lua walks -- host arithmetic only, no pass, worked
+-- out once per size: hw (the four head maps' { h, w }), fshape ({ planes, fh, fw } of the last feature map), hoff (the 5-entry
+-- prefix of the head maps' float counts, 18 planes each, every one rounded up to 64: where map i lies in the frame's slot,
+-- hoff[5] what the frame needs of it), fslot (likewise, the feature map) and anchors (of the four maps)
+function Detector:layout(H, W)
+  self.layouts = self.layouts or {}
+  local key = H .. 'x' .. W
+  local t = self.layouts[key]
+  if t == nil then
+    local function ceil64(n) return math.floor((n + 63) / 64) * 64 end
+    local children = self.model.pnet.outnode.children
+    local planes = self.model.layers[#self.model.layers].filters
+    t = { hw = {}, hoff = { 0 }, anchors = 0 }
+    for i = 1, 4 do
+      local h, w = map_hw(Localizer.new(children[i]).layers, H, W)
+      t.hw[i] = { h, w }
+      t.hoff[i + 1] = t.hoff[i] + ceil64(ASPECTS * 6 * h * w)
+      t.anchors = t.anchors + ASPECTS * h * w
+    end
+    local fh, fw = map_hw(Localizer.new(children[self.nheads + 1]).layers, H, W)
+    t.fshape, t.fslot = { planes, fh, fw }, ceil64(planes * fh * fw)
+    self.layouts[key] = t
+  end
+  return t
+end
+
+-- Detector.lua:17-85 for a chunk: the proposal net frame by frame, ONE scan, (selection or score rows), ONE segmented first
+-- NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp -> a table { B, cnt (device int[4][B]),
+-- cap (rows a frame in mp, mi, mr, dpick: the match arrays the rest of the chunk reads, the selected rows under
+-- pre_nms_top_n), fm, fslot, fs (frame b's last feature map at fm + b * fslot, its size fs[b]), count (host int[2][B]: rows and
+-- candidates per frame), key_mode, key_col (of both NMS passes) }.  prefix: of the scratch names ('' for detect and proposals,
+-- 'b_' for detect_batch: neither overwrites what the other left behind)
+function Detector:first_stage(frames, prefix)
   local pnet = self.model.pnet
   local scratch = self.scratch
   local B = #frames
   local nout = self.nheads + 1
-  if self.out_layers == nil then
-    self.out_layers = {}
-    for i = 1, nout do self.out_layers[i] = Localizer.new(pnet.outnode.children[i]).layers end
-  end
-  local Hs, Ws = ffi.new('int[?]', 4 * B), ffi.new('int[?]', 4 * B)
-  local map_off, img_wh = ffi.new('long long[?]', 4 * B), ffi.new('double[?]', 2 * B)
-  local fs, anchors, hoff = {}, {}, {}
-  local planes = self.model.layers[#self.model.layers].filters              -- of the last feature map
+
+  -- ---- 1. per frame: the proposal net; its head maps and last feature map are copied to the frame's slot (the net reuses its
+  --         output buffers).  Where they lie follows from the frame's size on the host (layout, checked against what the net
+  --         hands back), so the slots -- strided by the chunk's largest frame -- are sized before the first pass: frame b's four
+  --         head maps lie packed at hoff[i] of slot b of `heads`, its last feature map at the start of slot b of `fm`.  A chunk
+  --         of ONE frame reads the net's buffers where they are: no copies
+  pnet:evaluate()                                                       -- :31
+  -- counts (device int[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
+  local cnt = ffi.cast('int*', scratch(prefix .. 'counts', 16 * B).ptr)
+  local size1 = frames[1]:size()
+  local lay, fs, anchors, one_size = {}, {}, {}, true
   local slot, fslot, cap = 0, 0, 0
   for b = 0, B - 1 do
     local size = frames[b + 1]:size()
-    img_wh[2 * b], img_wh[2 * b + 1] = size[3], size[2]
-    hoff[b] = { 0 }
-    anchors[b] = 0
-    for i = 1, 4 do
-      local h, w = map_hw(self.out_layers[i], size[2], size[3])
-      Hs[4 * b + i - 1], Ws[4 * b + i - 1] = h, w
-      hoff[b][i + 1] = hoff[b][i] + math.floor((18 * h * w + 63) / 64) * 64
-      anchors[b] = anchors[b] + ASPECTS * h * w
-    end
-    local fh, fw = map_hw(self.out_layers[nout], size[2], size[3])
-    fs[b] = { planes, fh, fw }
-    slot = math.max(slot, hoff[b][5])
-    fslot = math.max(fslot, math.floor((planes * fh * fw + 63) / 64) * 64)
-    cap = math.max(cap, anchors[b])
+    if size[2] ~= size1[2] or size[3] ~= size1[3] then one_size = false end
+    local t = self:layout(size[2], size[3])
+    lay[b], fs[b], anchors[b] = t, t.fshape, t.anchors
+    slot, fslot, cap = math.max(slot, t.hoff[5]), math.max(fslot, t.fslot), math.max(cap, t.anchors)
   end
-  local heads = ffi.cast('float*', scratch(prefix .. 'heads', 4 * B * slot).ptr)
-  local fm = ffi.cast('float*', scratch(prefix .. 'fm', 4 * B * fslot).ptr)
+  local maps, heads, fm = ffi.new('const float*[4]')
+  if B > 1 then
+    heads = ffi.cast('float*', scratch(prefix .. 'heads', 4 * B * slot).ptr)
+    fm = ffi.cast('float*', scratch(prefix .. 'fm', 4 * B * fslot).ptr)
+  end
   for b = 0, B - 1 do
+    local t = lay[b]
     local outputs = pnet:forward(hip.to_device(frames[b + 1]))          -- :32-33
-    for i = 1, 4 do
+    for i = 1, nout do
       local s = outputs[i]:size()
-      if s[2] ~= Hs[4 * b + i - 1] or s[3] ~= Ws[4 * b + i - 1] then
-        error(string.format('Detector: head map %d of frame %d is %dx%d, expected %dx%d', i, b + 1, s[2], s[3],
-                            Hs[4 * b + i - 1], Ws[4 * b + i - 1]))
+      local want = t.fshape
+      if i < nout then want = { ASPECTS * 6, t.hw[i][1], t.hw[i][2] } end
+      if s[1] ~= want[1] or s[2] ~= want[2] or s[3] ~= want[3] then
+        error(string.format('Detector: output %d of frame %d is %dx%dx%d, expected %dx%dx%d', i, b + 1, s[1], s[2], s[3],
+                            want[1], want[2], want[3]))
       end
-      map_off[4 * b + i - 1] = b * slot + hoff[b][i]
-      check(C.frcnn_memcpy_d2d(heads + b * slot + hoff[b][i], outputs[i].ptr, 4 * 18 * s[2] * s[3], nil))
     end
-    local s = outputs[nout]:size()
-    if s[1] ~= planes or s[2] ~= fs[b][2] or s[3] ~= fs[b][3] then
-      error(string.format('Detector: the last feature map of frame %d is %dx%dx%d, expected %dx%dx%d', b + 1, s[1], s[2], s[3],
-                          planes, fs[b][2], fs[b][3]))
+    if B == 1 then
+      for i = 1, 4 do maps[i - 1] = outputs[i].ptr end
+      fm = ffi.cast('float*', outputs[nout].ptr)
+    else
+      for i = 1, 4 do
+        check(C.frcnn_memcpy_d2d(heads + b * slot + t.hoff[i], outputs[i].ptr, 4 * ASPECTS * 6 * t.hw[i][1] * t.hw[i][2], nil))
+      end
+      check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[nout].ptr, 4 * t.fshape[1] * t.fshape[2] * t.fshape[3], nil))
     end
-    check(C.frcnn_memcpy_d2d(fm + b * fslot, outputs[nout].ptr, 4 * s[1] * s[2] * s[3], nil))
   end
-  local wsb = tonumber(C.frcnn_rpn_scan_ragged_workspace_bytes(Hs, Ws, B))
+  -- ---- 2. ONE scan over the B slots (:39-66 on the device: log-softmax of every anchor's two logits, p > 0.95, decode,
+  --         overlap test, compaction): frame b's matches at rows [b * cap, b * cap + n_b).  Every anchor of the four maps may
+  --         pass (vgg_large 1000x600: 45 015): the buffers hold them all; cap is the largest frame's anchor count.  A chunk of
+  --         one size takes frcnn_rpn_scan_batch (the four maps of slot 0 -- or the net's own --, the slot stride, that size), a
+  --         chunk that mixes sizes frcnn_rpn_scan_ragged (per-frame map sizes, offsets and image sizes): the same bodies, 3 %
+  --         dearer a call
+  local Hs, Ws = ffi.new('int[?]', 4 * B), ffi.new('int[?]', 4 * B)
+  for b = 0, B - 1 do
+    for i = 1, 4 do Hs[4 * b + i - 1], Ws[4 * b + i - 1] = lay[b].hw[i][1], lay[b].hw[i][2] end
+  end
+  local wsb
+  if one_size then
+    wsb = tonumber(C.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B))
+  else
+    wsb = tonumber(C.frcnn_rpn_scan_ragged_workspace_bytes(Hs, Ws, B))
+  end
   local ws = scratch(prefix .. 'scan_ws', wsb)
   local mp = ffi.cast('float*', scratch(prefix .. 'match_p', 4 * B * cap).ptr)
   local mi = ffi.cast('int*', scratch(prefix .. 'match_idx', 16 * B * cap).ptr)
   local mr = ffi.cast('double*', scratch(prefix .. 'match_rect', 32 * B * cap).ptr)
   local mb = ffi.cast('float*', scratch(prefix .. 'match_box', 16 * B * cap).ptr)
-  check(C.frcnn_rpn_scan_ragged(heads, map_off, Hs, Ws, img_wh, B, self.aw.ptr, self.ah.ptr, 0.95, cap, mp, mi, mr, mb, cnt, ws.ptr,
-                                wsb, nil))
-  return { B = B, cnt = cnt, cap = cap, mp = mp, mi = mi, mr = mr, mb = mb, fm = fm, fslot = fslot, fs = fs, anchors = anchors }
-end
-
--- first_stage for a chunk of B > 1 frames of different sizes
-function Detector:first_stage_ragged(frames, prefix)
-  local cnt = ffi.cast('int*', self.scratch(prefix .. 'counts', 16 * #frames).ptr)
-  self.model.pnet:evaluate()                                            -- :31
-  return self:first_nms(self:ragged_front(frames, prefix, cnt), prefix)
-end
-
--- Steps 3 and on of first_stage, on what its front (one size: first_stage itself; mixed sizes: ragged_front) scanned
-function Detector:first_nms(front, prefix)
-  local scratch = self.scratch
-  local B, cnt, cap, mp, mi, mr, mb = front.B, front.cnt, front.cap, front.mp, front.mi, front.mr, front.mb
-  local fm, fslot, fs, anchors = front.fm, front.fslot, front.fs, front.anchors
+  if one_size then
+    if B > 1 then
+      for i = 0, 3 do maps[i] = heads + lay[0].hoff[i + 1] end
+    end
+    check(C.frcnn_rpn_scan_batch(maps, Hs, Ws, B, slot, self.aw.ptr, self.ah.ptr, size1[3], size1[2], 0.95, cap,
+                                 mp, mi, mr, mb, cnt, ws.ptr, wsb, nil))
+  else
+    local map_off, img_wh = ffi.new('long long[?]', 4 * B), ffi.new('double[?]', 2 * B)
+    for b = 0, B - 1 do
+      local size = frames[b + 1]:size()
+      img_wh[2 * b], img_wh[2 * b + 1] = size[3], size[2]
+      for i = 1, 4 do map_off[4 * b + i - 1] = b * slot + lay[b].hoff[i] end
+    end
+    check(C.frcnn_rpn_scan_ragged(heads, map_off, Hs, Ws, img_wh, B, self.aw.ptr, self.ah.ptr, 0.95, cap, mp, mi, mr, mb, cnt,
+                                  ws.ptr, wsb, nil))
+  end
   -- ---- 3. ONE segmented NMS (:74-85) on the device, the match counts read from DEVICE memory (no round trip between scan
   --         and NMS); the score tensor is ignored by nms.lua -> key = max-y.  Launch and workspace are sized for a bound on
   --         the matches, not for every anchor of the maps; a frame with more matches repeats the pass alone, sized by the
@@ -416,10 +394,11 @@ end
 -- sum of the candidate counts); everything up to the pooled rows stays bit-identical, the net's outputs agree with detect()'s
 -- within the net's own error only (input scale and Linear form depend on the whole tensor / the row count).
 -- mixed_sizes = false (default): frames of different sizes are refused before anything is queued.  true: the chunks are the
--- consecutive Detector.BATCH frames whatever their sizes; a chunk of one size (or of one frame) runs as it always did
--- (frcnn_rpn_scan_batch), a chunk that mixes sizes keeps per-frame map sizes and image sizes, strides its slots by its largest
--- frame and scans them with ONE frcnn_rpn_scan_ragged call (ragged_front); everything behind the scan reads per-frame device
--- counts already, so nothing else changes and every frame's result stays what detect(frame) returns.
+-- consecutive Detector.BATCH frames whatever their sizes.  Every chunk takes the one front of first_stage: each frame lies in
+-- its slot by its own size's layout, the slots are strided by the chunk's largest frame, and ONE scan follows --
+-- frcnn_rpn_scan_batch when the chunk has one size (then the strides are that size's own), else frcnn_rpn_scan_ragged with
+-- per-frame map sizes and image sizes; everything behind the scan reads per-frame device counts already, so nothing else
+-- changes and every frame's result stays what detect(frame) returns.
 -- 1:1 with Detector.detect_batch of the Python host mirror.
 function Detector:detect_batch(inputs, opts)
   local shared_cnet, mixed_sizes = opts, false
@@ -439,12 +418,9 @@ function Detector:detect_batch(inputs, opts)
   local results = {}
   local lo = 1
   while lo <= nframes do
-    local chunk, ragged = {}, false
-    for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do
-      chunk[#chunk + 1] = inputs[i]
-      if not same_size(lo, i) then ragged = true end
-    end
-    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet, 'b_', ragged)) do results[#results + 1] = winners end
+    local chunk = {}
+    for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do chunk[#chunk + 1] = inputs[i] end
+    for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet, 'b_')) do results[#results + 1] = winners end
     lo = lo + Detector.BATCH
   end
   return results
@@ -452,7 +428,7 @@ end
 
 -- detect() of a chunk of frames -> one list of winners per frame: first_stage, then -- unless no frame has a match -- per
 -- frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather, read-back 2 of 2
-function Detector:detect_chunk(frames, shared, prefix, ragged)
+function Detector:detect_chunk(frames, shared, prefix)
   local model = self.model
   local cfg = model.cfg
   local cnet = model.cnet
@@ -464,8 +440,7 @@ function Detector:detect_chunk(frames, shared, prefix, ragged)
   local D = kh * kw * model.layers[#model.layers].filters
   local scratch = self.scratch
 
-  local st                                                              -- :17-85
-  if ragged then st = self:first_stage_ragged(frames, prefix) else st = self:first_stage(frames, prefix) end
+  local st = self:first_stage(frames, prefix)                           -- :17-85
   local B, cnt, cap, mp, mi, mr, dpick, count = st.B, st.cnt, st.cap, st.mp, st.mi, st.mr, st.dpick, st.count
   local fm, fslot, key_mode, key_col = st.fm, st.fslot, st.key_mode, st.key_col
   local Rmax = 0

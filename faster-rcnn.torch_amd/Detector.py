@@ -10,9 +10,11 @@ device memory), ONE read-back of two counts (the cnet's row count sizes its laun
 -> cnet -> class test + rect decode + ordered compaction -> per-class NMS -> one record per winner, and ONE read-back
 of the winner table.  The list detect() returns builds its {p, a, r, l, r2, class, confidence} tables on access.
 
-There is ONE pipeline, written for a chunk of B frames (_first_stage + _detect_chunk: frcnn_rpn_scan_batch -- or, for a chunk
-that mixes frame sizes under detect_batch(mixed_sizes=True), frcnn_rpn_scan_ragged --, frcnn_nms_device_batch twice,
-frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound).
+There is ONE pipeline, written for a chunk of B frames (_first_stage + _detect_chunk: ONE scan, frcnn_nms_device_batch twice,
+frcnn_detect_gather_batch; frcnn_nms_device for a frame over the first NMS's bound), with ONE front: every frame's slot
+offsets, feature-map shape and anchor count come from its size's layout (_layout, host arithmetic, cached per size), the
+chunk's strides are those of its largest frame, and the shapes pick the scan -- frcnn_rpn_scan_batch for a chunk of one size,
+frcnn_rpn_scan_ragged for one that mixes sizes under detect_batch(mixed_sizes=True).
 detect_batch(frames) runs it on chunks of BATCH frames, detect(input) on the chunk [input], proposals(input) runs its first
 stage on [input].  A chunk of one frame reads the proposal net's outputs where the model left them: no device copies.
 
@@ -32,6 +34,7 @@ Nor is box voting (Gidaris & Komodakis 2015), off by default (cfg["box_voting"] 
 box_voting_settings): behind the per-class pass ONE frcnn_box_vote_batch launch replaces every winner's r2 by the weighted mean
 of the r2 of the class test's survivors of its class that overlap it by at least `overlap` (weights: the confidences, always the
 UNDECAYED ones).  Which rows win, their order and every other field of a winner are those of the same Detector without the key."""
+import collections
 import ctypes as C
 import math
 
@@ -204,7 +207,7 @@ def _frame_shape(x):
     """(3, H, W) of a frame as detect() accepts it, without touching the device."""
     shp = tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
     if len(shp) != 3 or shp[0] != 3:
-        raise ValueError("detect_batch: expected 3xHxW frames, got %r" % (shp,))
+        raise ValueError("Detector: expected 3xHxW frames, got %r" % (shp,))
     return shp
 
 
@@ -217,6 +220,29 @@ def _map_hw(layers, H, W):
         h = -((h + 2 * pH - kH) // -dH) + 1
         w = -((w + 2 * pW - kW) // -dW) + 1
     return h, w
+
+
+_Layout = collections.namedtuple("_Layout", "hw fshape hoff fslot anchors")
+
+
+def _layout(layer_lists, planes, H, W):
+    """What a frame of H x W occupies in a chunk, from the layer lists of the proposal net's outputs (the four head maps, then
+    the last feature map, of `planes` planes) -- host arithmetic only, no pass: hw (the head maps' (h, w)), fshape (planes, fh,
+    fw), hoff (the 5-entry prefix of the head maps' float counts, 18 planes each, every one rounded up to 64: where map i lies
+    in the frame's slot, hoff[4] what the frame needs of it), fslot (likewise, the feature map) and anchors (of the four maps)."""
+    hw = [_map_hw(l, H, W) for l in layer_lists]
+    ceil64 = lambda n: (n + 63) // 64 * 64
+    hoff = [0]
+    for h, w in hw[:4]:
+        hoff.append(hoff[-1] + ceil64(ASPECTS * 6 * h * w))
+    fh, fw = hw[-1]
+    return _Layout(hw[:4], (planes, fh, fw), hoff, ceil64(planes * fh * fw), ASPECTS * sum(h * w for h, w in hw[:4]))
+
+
+def _chunk_slots(layouts):
+    """(slot, fslot, cap) of a chunk: the strides (floats) of its head-map and feature-map slots and the row stride of its match
+    arrays are those of its largest frame.  For a chunk of one size slot == hoff[4]."""
+    return max(t.hoff[4] for t in layouts), max(t.fslot for t in layouts), max(t.anchors for t in layouts)
 
 
 class _BatchRecord(object):
@@ -347,6 +373,7 @@ class Detector(object, metaclass=_DetectorType):
         self._aw = DeviceTensor.from_numpy(self.anchors.w)
         self._ah = DeviceTensor.from_numpy(self.anchors.h)
         self._bufs = {}
+        self._layouts = {}           # (H, W) -> _Layout: a frame size is worked out once (_layout_of)
         self._host = None            # page-locked landing buffer of the two read-backs
         self._host_bytes = 0
         self.verbose = False
@@ -506,11 +533,12 @@ class Detector(object, metaclass=_DetectorType):
         its input by the largest magnitude of the whole tensor, the Linear picks tile shape and arithmetic form by row
         count): they agree with detect()'s within the net's own error (1e-3 bar), and winners follow from them.
         mixed_sizes=False (default): frames of different sizes are refused (ValueError) before anything is queued.  True: the
-        chunks are the consecutive BATCH frames whatever their sizes.  A chunk of one size (or of one frame) runs as it always
-        did; a chunk that mixes sizes keeps per-frame map shapes and image sizes, strides its head-map and feature-map slots by
-        its largest frame and scans them with ONE frcnn_rpn_scan_ragged call (_ragged_front).  Everything behind the scan reads
-        per-frame device counts already, so nothing else changes, the two waits per chunk included, and every frame's result
-        and record stay bit-identical to detect(frame)."""
+        chunks are the consecutive BATCH frames whatever their sizes.  Every chunk takes the one front of _first_stage: each
+        frame lies in its slot by its own size's layout, the slots are strided by the chunk's largest frame, and ONE scan
+        follows -- frcnn_rpn_scan_batch when the chunk has one size (then the strides are that size's own), else
+        frcnn_rpn_scan_ragged with per-frame map shapes and image sizes.  Everything behind the scan reads per-frame device
+        counts already, so nothing else changes, the two waits per chunk included, and every frame's result and record stay
+        bit-identical to detect(frame)."""
         frames = list(inputs)
         shapes = [_frame_shape(f) for f in frames]
         if not mixed_sizes and any(shp != shapes[0] for shp in shapes):
@@ -520,23 +548,29 @@ class Detector(object, metaclass=_DetectorType):
         for lo in range(0, len(frames), step):
             for r in records:     # (the records of the previous chunk view buffers this chunk writes)
                 r.detach()
-            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet), "b_", len(set(shapes[lo:lo + step])) > 1)
+            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet), "b_")
             results += res
             records += rec
         self.last_batch = records
         return results
 
-    def _first_stage(self, frames, pre, ragged=False):
-        """Detector.lua:17-85 for a chunk of B frames (of one size unless `ragged`): the proposal net frame by frame, ONE scan,
-        (selection or score rows), ONE segmented first NMS, read-back 1 of 2, alone again every frame over the bound, the
-        post-NMS clamp -> dict(B, counts (device int32[4][B]), cap (rows a frame in p, idx, rect, pick: the match arrays the
-        rest of the chunk reads, the selected rows under pre_nms_top_n), fm, fshapes (frame b's last feature map is
-        fm.segment(b), its shape fshapes[b]), ns, Rs (rows and candidates per frame), key (key_mode, key_col of both NMS passes), and box, row, matches for _records).
+    def _layout_of(self, H, W):
+        """_layout of an H x W frame under this Detector's model, worked out once per size."""
+        t = self._layouts.get((H, W))
+        if t is None:
+            t = self._layouts[H, W] = _layout([n.layers for n in self.model["pnet"].outnode.children],
+                                              self.model["layers"][-1]["filters"], H, W)
+        return t
+
+    def _first_stage(self, frames, pre):
+        """Detector.lua:17-85 for a chunk of B frames, of one size or not: the proposal net frame by frame, ONE scan, (selection or
+        score rows), ONE segmented first NMS, read-back 1 of 2, alone again every frame over the bound, the post-NMS clamp ->
+        dict(B, counts (device int32[4][B]), cap (rows a frame in p, idx, rect, pick: the match arrays the rest of the chunk
+        reads, the selected rows under pre_nms_top_n), fm, fshapes (frame b's last feature map is fm.segment(b), its shape
+        fshapes[b]), ns, Rs (rows and candidates per frame), key (key_mode, key_col of both NMS passes), and box, row, matches
+        for _records).
         pre: prefix of the buffer names ("" for detect() and proposals(), "b_" for detect_batch: neither overwrites what the other
-        left behind).
-        ragged (detect_batch(mixed_sizes=True) on a chunk that really mixes sizes): steps 1 and 2 are _ragged_front -- per-frame
-        map shapes and image sizes, ONE frcnn_rpn_scan_ragged -- and `cap` is the largest frame's anchor count; from step 3 on
-        nothing differs."""
+        left behind)."""
         pnet = self.model["pnet"]
         s = stream_ptr()
         L = _lib.load()
@@ -544,50 +578,56 @@ class Detector(object, metaclass=_DetectorType):
         i32 = np.int32
 
         # ---- 1. per frame: the proposal net; its head maps and last feature map go to the frame's slot (the model owns and
-        #         reuses its output buffers).  A chunk of ONE frame reads the model's buffers where they are: no copies.
+        #         reuses its output buffers).  Where they lie follows from the frame's size on the host (_layout, checked against
+        #         what the net hands back), so the slots -- strided by the chunk's largest frame -- are sized before the first
+        #         pass: frame b's four head maps lie packed at hoff[i] of slot b of `heads`, its last feature map at the start of
+        #         slot b of `fm`.  A chunk of ONE frame reads the model's buffers where they are: no copies.
         pnet.evaluate()  # :31
         # counts (device int32[4][B]): per frame matches, NMS candidates, candidates that pass the class test, winners
         counts = self._buf(pre + "counts", (4, B), i32)
         c_n, c_R = ptr(counts.segment(0)), counts.segment(1)
         threshold = 0.95
-        if ragged:     # frames of different sizes: per-frame shapes, slots strided by the largest frame, ONE ragged scan
-            fm, fshapes, anchors, cap, (mp, mi, mr, mb) = self._ragged_front(frames, pre, c_n, threshold)
-        else:
-            for b, f in enumerate(frames):
-                inp = to_device(f)
-                _, H, W = inp.shape
-                outputs = pnet.forward(inp)  # :33
-                if b == 0:
-                    hshape = [o.shape for o in outputs[:4]]
-                    hoff = [0]
-                    for shp in hshape:
-                        hoff.append(hoff[-1] + (int(np.prod(shp)) + 63) // 64 * 64)
-                    slot = hoff[4]
-                    fshape = outputs[-1].shape
-                    fslot = (int(np.prod(fshape)) + 63) // 64 * 64
-                    if B == 1:
-                        heads, fm = [ptr(o) for o in outputs[:4]], outputs[-1].view(1, *fshape)
-                        break
-                    heads_buf, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
-                    heads = [ptr(heads_buf.offset_view(hoff[i], hshape[i])) for i in range(4)]
-                for i in range(4):
-                    _lib.call("frcnn_memcpy_d2d", ptr(heads_buf.segment(b).offset_view(hoff[i], hshape[i])), ptr(outputs[i]),
-                              outputs[i].nbytes, s)
-                _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
-            # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b).  Every
-            #         anchor of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is
-            #         ever truncated
-            Hs = (C.c_int * 4)(*[shp[1] for shp in hshape])
-            Ws = (C.c_int * 4)(*[shp[2] for shp in hshape])
-            maps = (C.c_void_p * 4)(*[h.value for h in heads])
-            cap = ASPECTS * sum(shp[1] * shp[2] for shp in hshape)
+        sizes = [_frame_shape(f)[1:] for f in frames]
+        lay = [self._layout_of(H, W) for H, W in sizes]
+        slot, fslot, cap = _chunk_slots(lay)
+        if B > 1:
+            heads, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
+        for b, (f, t) in enumerate(zip(frames, lay)):
+            outputs = pnet.forward(to_device(f))  # :33
+            got, want = [tuple(o.shape) for o in outputs], [(ASPECTS * 6,) + m for m in t.hw] + [t.fshape]
+            if got != want:
+                raise _lib.FrcnnError("Detector: a %dx%d frame gives maps %r, expected %r" % (sizes[b] + (got, want)))
+            if B == 1:
+                maps, fm = [ptr(o) for o in outputs[:4]], outputs[-1].view(1, *t.fshape)
+                break
+            for i in range(4):
+                _lib.call("frcnn_memcpy_d2d", ptr(heads.segment(b).offset_view(t.hoff[i], outputs[i].shape)), ptr(outputs[i]),
+                          outputs[i].nbytes, s)
+            _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
+        # ---- 2. ONE scan over the B slots (Detector.lua:39-66): frame b's matches at rows [b * cap, b * cap + n_b).  Every
+        #         anchor of the four maps may pass (vgg_large 1000x600 scans 45 015): the buffers hold them all, nothing is
+        #         ever truncated; cap is the largest frame's anchor count.  A chunk of one size takes frcnn_rpn_scan_batch (the
+        #         four maps of slot 0 -- or the model's own --, the slot stride, that size), a chunk that mixes sizes
+        #         frcnn_rpn_scan_ragged (per-frame map sizes, offsets and image sizes): the same bodies, 3 % dearer a call
+        Hs = (C.c_int * (4 * B))(*[h for t in lay for h, _ in t.hw])
+        Ws = (C.c_int * (4 * B))(*[w for t in lay for _, w in t.hw])
+        if len(set(sizes)) == 1:
+            H, W = sizes[0]
+            if B > 1:
+                maps = [ptr(heads.offset_view(lay[0].hoff[i], (1,))) for i in range(4)]
             wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, B)
-            ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
-            mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
-            mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
-            _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, B, slot, ptr(self._aw), ptr(self._ah), float(W), float(H), threshold,
-                      cap, ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
-            fshapes, anchors = [fshape] * B, [cap] * B
+            scan = ("frcnn_rpn_scan_batch", (C.c_void_p * 4)(*[m.value for m in maps]), Hs, Ws, B, slot, ptr(self._aw),
+                    ptr(self._ah), float(W), float(H))
+        else:
+            map_off = (C.c_longlong * (4 * B))(*[b * slot + t.hoff[i] for b, t in enumerate(lay) for i in range(4)])
+            img_wh = (C.c_double * (2 * B))(*[float(v) for H, W in sizes for v in (W, H)])
+            wsb = L.frcnn_rpn_scan_ragged_workspace_bytes(Hs, Ws, B)
+            scan = ("frcnn_rpn_scan_ragged", ptr(heads), map_off, Hs, Ws, img_wh, B, ptr(self._aw), ptr(self._ah))
+        ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
+        mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
+        mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
+        _lib.call(*scan, threshold, cap, ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
+        fshapes, anchors = [t.fshape for t in lay], [t.anchors for t in lay]
         # ---- 3. ONE segmented NMS (:74-85) on the device, the match counts read from device memory; the score tensor is ignored
         #         by nms.lua -> key = max-y.  The launch and its workspace are sized for a BOUND on the matches, not for every
         #         anchor of the maps (vgg_large: 45 015 anchors -> 253 MB of masks and a 704 x 704 tile grid per frame for a few
@@ -633,57 +673,6 @@ class Detector(object, metaclass=_DetectorType):
         return dict(B=B, counts=counts, cap=cap, p=mp, idx=mi, rect=mr, box=mb, row=row, pick=pick, fm=fm, fshapes=fshapes,
                     ns=ns, Rs=Rs, matches=matches, key=(key_mode, key_col))
 
-    def _ragged_front(self, frames, pre, c_n, threshold):
-        """Steps 1 and 2 of _first_stage for a chunk of B > 1 frames of different sizes -> (fm, fshapes, anchors, cap, (match_p,
-        match_idx, match_rect, match_box)).  The map shapes of every frame follow from its size on the host (_map_hw over the
-        layer lists the Localizer walks; checked against what the net hands back), so the slots -- strided by the chunk's
-        largest frame -- are sized before the first pass.  Frame b's four head maps lie packed at the start of slot b of
-        `heads`, its last feature map at the start of slot b of `fm` (fm.segment(b), fshapes[b]).  ONE frcnn_rpn_scan_ragged
-        with per-frame sizes, offsets and image sizes; cap, the row stride of the match arrays, is the largest frame's anchor
-        count, anchors[b] frame b's own."""
-        pnet = self.model["pnet"]
-        s = stream_ptr()
-        B = len(frames)
-        i32 = np.int32
-        nodes = pnet.outnode.children
-        sizes = [_frame_shape(f)[1:] for f in frames]
-        hw = [[_map_hw(n.layers, H, W) for n in nodes] for H, W in sizes]      # per frame: 4 head maps, the last feature map
-        heads_buf = fm = None
-        hoffs, fshapes = [], []
-        for b, f in enumerate(frames):
-            outputs = pnet.forward(to_device(f))  # :33
-            got = [tuple(o.shape[1:]) for o in outputs]
-            if got != hw[b]:
-                raise _lib.FrcnnError("Detector: a %dx%d frame gives maps %r, expected %r" % (sizes[b] + (got, hw[b])))
-            if b == 0:    # (the planes of every output: the same for every frame)
-                planes = [o.shape[0] for o in outputs]
-                for t in hw:
-                    off = [0]
-                    for i in range(4):
-                        off.append(off[-1] + (planes[i] * t[i][0] * t[i][1] + 63) // 64 * 64)
-                    hoffs.append(off)
-                slot = max(off[4] for off in hoffs)
-                fslot = max((planes[-1] * t[-1][0] * t[-1][1] + 63) // 64 * 64 for t in hw)
-                heads_buf, fm = self._buf(pre + "heads", (B, slot)), self._buf(pre + "fm", (B, fslot))
-            for i in range(4):
-                _lib.call("frcnn_memcpy_d2d", ptr(heads_buf.segment(b).offset_view(hoffs[b][i], outputs[i].shape)), ptr(outputs[i]),
-                          outputs[i].nbytes, s)
-            _lib.call("frcnn_memcpy_d2d", ptr(fm.segment(b)), ptr(outputs[-1]), outputs[-1].nbytes, s)
-            fshapes.append(tuple(outputs[-1].shape))
-        Hs = (C.c_int * (4 * B))(*[t[i][0] for t in hw for i in range(4)])
-        Ws = (C.c_int * (4 * B))(*[t[i][1] for t in hw for i in range(4)])
-        map_off = (C.c_longlong * (4 * B))(*[b * slot + hoffs[b][i] for b in range(B) for i in range(4)])
-        img_wh = (C.c_double * (2 * B))(*[float(v) for H, W in sizes for v in (W, H)])
-        anchors = [ASPECTS * sum(h * w for h, w in t[:4]) for t in hw]
-        cap = max(anchors)
-        wsb = _lib.load().frcnn_rpn_scan_ragged_workspace_bytes(Hs, Ws, B)
-        ws = self._buf(pre + "scan_ws", (wsb,), np.uint8)
-        mp = self._buf(pre + "match_p", (B, cap)); mi = self._buf(pre + "match_idx", (B, cap, 4), i32)
-        mr = self._buf(pre + "match_rect", (B, cap, 4), np.float64); mb = self._buf(pre + "match_box", (B, cap, 4))
-        _lib.call("frcnn_rpn_scan_ragged", ptr(heads_buf), map_off, Hs, Ws, img_wh, B, ptr(self._aw), ptr(self._ah), threshold, cap,
-                  ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(ws), wsb, s)
-        return fm, fshapes, anchors, cap, (mp, mi, mr, mb)
-
     def _records(self, st, more=None):
         """One _BatchRecord per frame of the chunk _first_stage returned st for (views of the chunk's buffers, kept = 0);
         more[b]: further device arrays of frame b (bbox, cls, pooled).  Host work only: _detect_chunk calls it with the whole
@@ -700,7 +689,7 @@ class Detector(object, metaclass=_DetectorType):
             records.append(_BatchRecord(n, R, dev, matches[b] if matches is not None else None))
         return records
 
-    def _detect_chunk(self, frames, shared, pre, ragged=False):
+    def _detect_chunk(self, frames, shared, pre):
         """detect() of a chunk of frames -> (one result per frame, their records): _first_stage, then -- unless no frame has a match
         -- per frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather and
         read-back 2 of 2."""
@@ -715,7 +704,7 @@ class Detector(object, metaclass=_DetectorType):
         L = _lib.load()
         i32 = np.int32
 
-        st = self._first_stage(frames, pre, ragged)   # :17-85
+        st = self._first_stage(frames, pre)   # :17-85
         B, counts, cap, mp, mi, mr, pick = st["B"], st["counts"], st["cap"], st["p"], st["idx"], st["rect"], st["pick"]
         ns, Rs, (key_mode, key_col) = st["ns"], st["Rs"], st["key"]
         c_K, c_W = counts.segment(2), ptr(counts.segment(3))

@@ -3,7 +3,8 @@ tests/scan_ragged_cases.py -- per frame BIT FOR BIT frcnn_rpn_scan on that frame
 of tests/anchor_ops_ref.py, nothing stored behind a frame's matches, behind B * cap rows, behind count[B - 1] or behind the
 workspace size the library asked for; truncation; frames of one size against frcnn_rpn_scan_batch; every refusal.  Detector
 level: detect_batch(frames, mixed_sizes=True) against [detect(f)] bit for bit under the Detector's settings, the number of host
-waits, chunks of one size inside a mixed call, the default call's refusal, evaluate_detections(mixed_sizes=True)."""
+waits, chunks of one size inside a mixed call, the default call's refusal, evaluate_detections(mixed_sizes=True).  The one
+front: its copies and its scan for a chunk of one size and for a mixed one, the layout cache, the shape check."""
 import ctypes as C
 
 import numpy as np
@@ -455,3 +456,80 @@ def test_evaluate_detections_mixed_sizes(F, amplified):
     assert one["detections"] > 0 and one["tp"] > 0
     got = evaluate_detections(F.Detector(s["model"]), _Val(items), len(items), batch=4, mixed_sizes=True)
     assert got == one
+
+
+# ================================================================================================ the one front
+SCANS = ("frcnn_rpn_scan_batch", "frcnn_rpn_scan_ragged")
+
+
+def _counted(F, monkeypatch):
+    """the names of the library calls made through _lib.call from here on"""
+    calls = []
+    orig_call = F._lib.call
+    monkeypatch.setattr(F._lib, "call", lambda name, *a, **kw: calls.append(name) or orig_call(name, *a, **kw))
+    return calls
+
+
+@pytest.mark.parametrize("sizes,scan", [([(128, 176)] * 3, SCANS[0]), ([(128, 176), (144, 176), (176, 128)], SCANS[1])])
+def test_front_copies_and_scan(F, amplified, monkeypatch, sizes, scan):
+    """a chunk of 3 frames: five copies a frame in front of ONE scan -- the batch scan for one size, the ragged scan for three"""
+    frames = [F.synthetic_image(h, w, k) for (h, w), k in zip(sizes, SEEDS)]
+    d = F.Detector(amplified["model"])
+    calls = _counted(F, monkeypatch)
+    got = d.detect_batch(frames, mixed_sizes=len(set(sizes)) > 1)
+    seen = list(calls)
+    assert len(got) == 3 and [n for n in seen if n in SCANS] == [scan]
+    assert seen[:seen.index(scan)].count("frcnn_memcpy_d2d") == 15
+
+
+def _snapshot(d, win):
+    """what detect() returned and left behind, as _detect_reference keeps it"""
+    m = d.last_scan
+    return dict(n=m["n"], idx=m["idx"].numpy(), p=m["p"].numpy(), rect=m["rect"].numpy(), box=m["box"].numpy(),
+                pick=d.last_pick.copy(), cnet=d.last_cnet if m["n"] else None, kept=d._last.get("kept", 0),
+                winners=_winner_rows(win), nwin=len(win), empty_list=(win == []))
+
+
+def test_layout_is_worked_out_once_per_size(F, amplified, monkeypatch):
+    """detect(a), detect(b) of another size, detect(a): the layer lists are walked once per size, and the third call is the first"""
+    import sys
+    mod = sys.modules[F.Detector.__module__]
+    walks = []
+    orig = mod._map_hw
+    monkeypatch.setattr(mod, "_map_hw", lambda layers, H, W: walks.append((H, W)) or orig(layers, H, W))
+    a, b = F.synthetic_image(128, 176, 5), F.synthetic_image(144, 176, 7)
+    d = F.Detector(amplified["model"])
+    outputs = len(amplified["model"]["pnet"].outnode.children)
+    first = _snapshot(d, d.detect(a))
+    assert first["n"] > 0 and walks == [(128, 176)] * outputs
+    other = _snapshot(d, d.detect(b))
+    assert other["n"] > 0 and walks == [(128, 176)] * outputs + [(144, 176)] * outputs
+    win = d.detect(a)
+    assert len(walks) == 2 * outputs
+    _assert_same([d._last], [win], [first], "the first size again")
+    for k in ("idx", "p", "rect", "box"):
+        assert same_bits(d.last_scan[k].numpy(), first[k]), k
+
+
+def test_shape_check_guards_the_one_size_chunk(F, amplified, monkeypatch):
+    """a layout that reports a head map one row too tall: detect() and a one-size detect_batch raise on the host, in front of
+    the scan"""
+    d = F.Detector(amplified["model"])
+    orig = d._layout_of
+
+    def too_tall(H, W):
+        t = orig(H, W)
+        hw = list(t.hw)
+        hw[1] = (hw[1][0] + 1, hw[1][1])
+        return t._replace(hw=hw)
+    d._layout_of = too_tall
+    frames = [F.synthetic_image(128, 176, k) for k in (5, 6)]
+    calls = _counted(F, monkeypatch)
+    with pytest.raises(F._lib.FrcnnError, match="gives maps"):
+        d.detect(frames[0])
+    with pytest.raises(F._lib.FrcnnError, match="gives maps"):
+        d.detect_batch(frames)
+    assert not [n for n in calls if n.startswith("frcnn_rpn_scan")] and "frcnn_memcpy_d2d" not in calls
+    d._layout_of = orig      # the Detector is none the worse for it
+    d.detect(frames[0])
+    assert d.last_scan["n"] > 0

@@ -32,7 +32,7 @@ import torch  # noqa: E402
 import frcnn_amd as F  # noqa: E402
 from detect_bench_model import amplified_vgg_small  # noqa: E402
 from frcnn_amd.BatchIterator import find_target_size  # noqa: E402
-from frcnn_amd.Detector import _map_hw  # noqa: E402
+from frcnn_amd.Detector import _chunk_slots  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=6, help="passes over the 8 frames per measurement")
@@ -65,19 +65,13 @@ def spread(values, digits=4):
 def scan_bench():
     """device time per call of the scan entry points on random head maps (about a third of the anchors pass)"""
     L = F._lib.load()
-    nodes = model["pnet"].outnode.children
     rng = np.random.RandomState(0)
 
     def problem(sizes):     # sizes: (w, h) per frame -> the arguments of a ragged call and of a batch call (one size only)
-        hw = [[_map_hw(n.layers, h, w_) for n in nodes[:4]] for w_, h in sizes]
+        lay = [det._layout_of(h, w_) for w_, h in sizes]     # the Detector's own slot offsets, strides and anchor counts
         B = len(sizes)
-        hoffs = []
-        for t in hw:
-            off = [0]
-            for hh, ww in t:
-                off.append(off[-1] + (18 * hh * ww + 63) // 64 * 64)
-            hoffs.append(off)
-        slot = max(o[4] for o in hoffs)
+        hw, hoffs = [t.hw for t in lay], [t.hoff for t in lay]
+        slot, _, cap = _chunk_slots(lay)
         heads = np.zeros((B, slot), np.float32)
         for b, t in enumerate(hw):
             for i, (hh, ww) in enumerate(t):
@@ -86,8 +80,7 @@ def scan_bench():
                     m[a * 6] = rng.randn(hh, ww) * 3.0 + 2.0
                     m[a * 6 + 1] = rng.randn(hh, ww) * 3.0
                 heads[b, hoffs[b][i]:hoffs[b][i] + m.size] = m.ravel()
-        anchors = [3 * sum(hh * ww for hh, ww in t) for t in hw]
-        cap = max(anchors)
+        anchors = [t.anchors for t in lay]
         out = dict(heads=F.DeviceTensor.from_numpy(heads), B=B, slot=slot, cap=cap, anchors=anchors,
                    Hs=(C.c_int * (4 * B))(*[t[i][0] for t in hw for i in range(4)]),
                    Ws=(C.c_int * (4 * B))(*[t[i][1] for t in hw for i in range(4)]),
