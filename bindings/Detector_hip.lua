@@ -19,6 +19,8 @@
 -- the per-class pass.  Under 'linear' or 'gaussian' a winner's confidence is its DECAYED log-score, the one it was ranked by.
 -- And cfg.box_voting = { overlap = 0.5, weight = 'score' | 'uniform' } (Detector.box_voting_settings): behind the per-class pass a
 -- winner's r2 becomes the weighted mean of the r2 of its class's survivors that overlap it; nothing else about a winner changes.
+-- And cfg.scoring = { classes = 'top' | 'all', min_confidence = 0.2, max_detections = M } (Detector.scoring_settings): the class
+-- test as ONE frcnn_detect_classes_batch launch per chunk; 'all' scores a candidate under every foreground class over the threshold.
 --
 --   main.lua:  require 'Detector'  ->  require 'Detector_hip'
 local ffi = require 'ffi'
@@ -45,6 +47,54 @@ function Detector:__init(model)                                         -- Detec
   self.proposal_order, self.pre_nms_top_n, self.post_nms_top_n = Detector.proposal_settings(self.model.cfg.proposals)
   self.nms_method, self.nms_overlap, self.nms_sigma, self.nms_min_score = Detector.nms_settings(self.model.cfg.nms)
   self.vote_overlap, self.vote_weight = Detector.box_voting_settings(self.model.cfg.box_voting)
+  self:set_scoring(self.model.cfg.scoring)
+end
+
+-- cfg.scoring -> nil (the key is absent: the reference's class test, launch for launch) or classes, min_confidence,
+-- max_detections (validated on the host, before any device call).  The setting governs the class test between the classification
+-- net and the per-class NMS, which under it is ONE frcnn_detect_classes_batch launch per chunk.
+--   classes         'top' (default: the reference -- a candidate is scored under the arg-max of its log-probabilities only, and
+--                   dropped when that is the background) or 'all': one row per foreground class whose probability clears
+--                   min_confidence, whatever the arg-max is
+--   min_confidence  in [0, 1), a probability; default 0.2 (the reference's literal)
+--   max_detections  nil or M >= 1: a frame keeps the M winners of highest confidence (ties to the earlier pick), applied on the
+--                   host behind read-back 2
+-- An empty table is 'top' at 0.2: the results of the key absent, from one launch.
+function Detector.scoring_settings(t)
+  if t == nil then return nil end
+  if type(t) ~= 'table' then error('cfg.scoring must be a table of {classes, min_confidence, max_detections}') end
+  for k, _ in pairs(t) do
+    if k ~= 'classes' and k ~= 'min_confidence' and k ~= 'max_detections' then
+      error('cfg.scoring: unknown key ' .. tostring(k))
+    end
+  end
+  local classes = t.classes
+  if classes == nil then classes = 'top' end
+  if classes ~= 'top' and classes ~= 'all' then error('cfg.scoring.classes must be "top" or "all"') end
+  local min_confidence = t.min_confidence
+  if min_confidence == nil then min_confidence = 0.2 end
+  if type(min_confidence) ~= 'number' then error('cfg.scoring.min_confidence is not a number') end
+  if not (min_confidence >= 0 and min_confidence < 1) then error('cfg.scoring.min_confidence must be in [0, 1)') end
+  local M = t.max_detections
+  if M ~= nil then
+    if type(M) ~= 'number' or M ~= math.floor(M) then error('cfg.scoring.max_detections is not an integer') end
+    if M < 1 then error('cfg.scoring.max_detections must be at least 1') end
+  end
+  return classes, min_confidence, M
+end
+
+-- Makes a table as scoring_settings takes it this Detector's class test from the next frame on (nil: the reference's)
+function Detector:set_scoring(t)
+  self.scoring_classes, self.min_confidence, self.max_detections = Detector.scoring_settings(t)
+end
+
+-- m: the rows a candidate can emit, what the per-row buffers of a chunk are sized by (Rmax * m rows a frame).  'top': 1.  'all':
+-- min(ncls - 1, floor(1 / min_confidence) + 1) -- at most floor(1 / c) classes exceed c when the probabilities sum to 1, one more
+-- slot covers the rounding of an fp32 log-softmax; ncls - 1 at min_confidence = 0
+function Detector:scoring_rows(ncls)
+  if self.scoring_classes ~= 'all' then return 1 end
+  if self.min_confidence <= 0 then return ncls - 1 end
+  return math.min(ncls - 1, math.floor(1 / self.min_confidence) + 1)
 end
 
 -- cfg.box_voting -> nil (the key is absent: no voting, the reference's r2) or overlap, weight (validated on the host, before any
@@ -181,6 +231,7 @@ end
 -- The ONE pipeline, for a chunk of B frames, of one size or not; Detector:detect(input) is the chunk { input }.
 Detector.BATCH = 8              -- frames per chunk of detect_batch
 Detector.NMS_FIRST_CAP = 16384  -- rows the first NMS launch is sized for (see first_stage)
+Detector.CLASS_NMS_WORKSPACE = 2 * 2 ^ 30   -- bytes: under cfg.scoring a per-class NMS whose workspace would exceed them is refused
 
 -- (h, w) of the output a Localizer's layer list yields for an H x W input: per layer ceil((n + 2 pad - k) / d) + 1, the native
 -- model's arithmetic (stride-1 convolutions, ceil-mode 2x2 pooling)
@@ -385,8 +436,9 @@ function Detector:detect(input)                                         -- Detec
 end
 
 -- Detector:detect_batch(inputs, opts) -- detect() for a list of frames -- of ONE size, or (opts.mixed_sizes) of any sizes: a list
--- with one entry per frame, in order, each what detect(frame) returns.  opts: a table { shared_cnet = bool, mixed_sizes = bool },
--- or (as before) the boolean shared_cnet itself.  Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
+-- with one entry per frame, in order, each what detect(frame) returns.  opts: a table { shared_cnet = bool, mixed_sizes = bool,
+-- scoring = a table as Detector.scoring_settings takes it }, or (as before) the boolean shared_cnet itself.
+-- Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
 -- head maps and last feature map are copied to the frame's slot), then ONE scan, ONE segmented NMS, per frame with
 -- candidates the pooling / classification net / class test, ONE segmented per-class NMS and ONE gather; the host waits
 -- twice per chunk instead of twice per frame.  Bit-identical to detect() frame by frame: detect() is a chunk of one.
@@ -402,7 +454,10 @@ end
 -- 1:1 with Detector.detect_batch of the Python host mirror.
 function Detector:detect_batch(inputs, opts)
   local shared_cnet, mixed_sizes = opts, false
-  if type(opts) == 'table' then shared_cnet, mixed_sizes = opts.shared_cnet, opts.mixed_sizes end
+  if type(opts) == 'table' then
+    shared_cnet, mixed_sizes = opts.shared_cnet, opts.mixed_sizes
+    if opts.scoring ~= nil then self:set_scoring(opts.scoring) end     -- (validated before anything is queued; it stays set)
+  end
   local nframes = #inputs
   local function same_size(i, j)
     local a, b = inputs[i]:size(), inputs[j]:size()
@@ -464,10 +519,16 @@ function Detector:detect_chunk(frames, shared, prefix)
   local dwins = ffi.cast('int*', scratch('wins', 16 * Rmax).ptr)
   local dcls = ffi.cast('int*', scratch(prefix .. 'cls', 4 * Rmax).ptr)
   local dconf = ffi.cast('float*', scratch(prefix .. 'conf', 4 * Rmax).ptr)
-  local dbb = ffi.cast('float*', scratch(prefix .. 'bb5', 20 * B * Rmax).ptr)
-  local dkc = ffi.cast('int*', scratch(prefix .. 'bbcls', 4 * B * Rmax).ptr)
-  local dkeep = ffi.cast('int*', scratch(prefix .. 'keep_row', 4 * B * Rmax).ptr)
-  local dr2 = ffi.cast('double*', scratch(prefix .. 'r2', 32 * B * Rmax).ptr)
+  -- Under cfg.scoring the class test is ONE frcnn_detect_classes_batch launch behind the passes of all frames, which reads the
+  -- net's log-probabilities itself; 'all': a row per foreground class over min_confidence, so the per-row buffers and everything
+  -- behind hold `rows` = Rmax * m a frame
+  local scoring = self.scoring_classes ~= nil
+  local rows = Rmax
+  if scoring then rows = Rmax * self:scoring_rows(ncls) end
+  local dbb = ffi.cast('float*', scratch(prefix .. 'bb5', 20 * B * rows).ptr)
+  local dkc = ffi.cast('int*', scratch(prefix .. 'bbcls', 4 * B * rows).ptr)
+  local dkeep = ffi.cast('int*', scratch(prefix .. 'keep_row', 4 * B * rows).ptr)
+  local dr2 = ffi.cast('double*', scratch(prefix .. 'r2', 32 * B * rows).ptr)
   -- first row of frame b in the shared pass's input / output: the prefix sum of the candidate counts
   local row0, total = {}, 0
   for b = 0, B - 1 do
@@ -499,7 +560,11 @@ function Detector:detect_chunk(frames, shared, prefix)
     end
     local coutputs = cnet:forward(hip.view(cbuf, { total, D }))         -- :101, all frames
     all_bbox, all_cls = ffi.cast('float*', coutputs[1].ptr), ffi.cast('float*', coutputs[2].ptr)
+  elseif scoring then      -- the net reuses its outputs: every frame's are copied to its rows (b * Rmax) for the one launch
+    all_bbox = ffi.cast('float*', scratch(prefix .. 'bbox', 16 * B * Rmax).ptr)
+    all_cls = ffi.cast('float*', scratch(prefix .. 'cls_out', 4 * ncls * B * Rmax).ptr)
   end
+  local R_arg, row0_arg = ffi.new('int[?]', B), ffi.new('long long[?]', B)     -- (zeroed: a frame without matches has no rows)
   for b = 0, B - 1 do
     local R = count[B + b]
     if count[b] > 0 then
@@ -507,17 +572,31 @@ function Detector:detect_chunk(frames, shared, prefix)
       local bbox_ptr, cls_ptr
       if shared then
         bbox_ptr, cls_ptr = all_bbox + 4 * row0[b], all_cls + ncls * row0[b]
+        R_arg[b], row0_arg[b] = R, row0[b]
       else
         local coutputs = cnet:forward(pooled(b))                        -- :101
         bbox_ptr, cls_ptr = coutputs[1].ptr, coutputs[2].ptr
+        if scoring then
+          check(C.frcnn_memcpy_d2d(all_bbox + 4 * b * Rmax, bbox_ptr, 16 * R, nil))
+          check(C.frcnn_memcpy_d2d(all_cls + ncls * b * Rmax, cls_ptr, 4 * ncls * R, nil))
+          R_arg[b], row0_arg[b] = R, b * Rmax
+        end
       end
-      check(C.frcnn_cnet_decode(cls_ptr, R, ncls, dcls, dconf, nil))    -- :110-113 (arg-max of the log-probs)
-      -- :106-122 on the device: class test, r2 = Anchors.anchorToInput(r, bbox) in double, survivors compacted in order
-      check(C.frcnn_detect_post(dcls, dconf, bbox_ptr, mr + 4 * b * cap, dpick + b * cap, R, bgclass, 0.2,
-                                dbb + 5 * b * Rmax, dkc + b * Rmax, dkeep + b * Rmax, dr2 + 4 * b * Rmax, cnt + 2 * B + b, nil))
-    else
+      if not scoring then
+        check(C.frcnn_cnet_decode(cls_ptr, R, ncls, dcls, dconf, nil))  -- :110-113 (arg-max of the log-probs)
+        -- :106-122 on the device: class test, r2 = Anchors.anchorToInput(r, bbox) in double, survivors compacted in order
+        check(C.frcnn_detect_post(dcls, dconf, bbox_ptr, mr + 4 * b * cap, dpick + b * cap, R, bgclass, 0.2,
+                                  dbb + 5 * b * Rmax, dkc + b * Rmax, dkeep + b * Rmax, dr2 + 4 * b * Rmax, cnt + 2 * B + b, nil))
+      end
+    elseif not scoring then
       check(C.frcnn_zero(cnt + 2 * B + b, 4, nil))                      -- no candidates: an empty segment of the per-class NMS
     end
+  end
+  if scoring then
+    local mode = 0
+    if self.scoring_classes == 'all' then mode = 1 end
+    check(C.frcnn_detect_classes_batch(all_cls, all_bbox, R_arg, row0_arg, B, mr, dpick, cap, ncls, bgclass, self.min_confidence, mode,
+                                       dbb, dkc, dkeep, dr2, rows, cnt + 2 * B, nil, nil))
   end
   -- ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame), every class in ONE device pass: rows only suppress
   --         rows of their own class; a stable partition of the picks by class is, per class, exactly nms(bb, 0.1, bb[{{}, 5}])
@@ -527,24 +606,35 @@ function Detector:detect_chunk(frames, shared, prefix)
   --         Under a soft method (cfg.nms): ONE frcnn_soft_nms_batch launch instead, on the log-confidences (log_domain 1,
   --         min_score as a log), which writes every winner's decayed score into column 5 of a COPY of bb; the gather reads that
   --         copy, so a winner's confidence is the score it was picked at
-  local cpick = ffi.cast('long long*', scratch(prefix .. 'wpick', 8 * B * Rmax).ptr)
+  local cpick = ffi.cast('long long*', scratch(prefix .. 'wpick', 8 * B * rows).ptr)
   local dbb_win = dbb
+  -- (a frame's rows are its candidates times m: fewer candidates are the way out of either refusal)
+  local remedy = ''
+  if rows > Rmax then
+    remedy = string.format(' (%d candidates x %d rows each: lower cfg.proposals.post_nms_top_n)', Rmax, rows / Rmax)
+  end
   if self.nms_method ~= 'hard' then
-    if Rmax > 16384 then error('Detector: more candidates in a frame than the 16384 a soft per-class NMS takes') end
-    dbb_win = ffi.cast('float*', scratch(prefix .. 'bb_soft', 20 * B * Rmax).ptr)
-    check(C.frcnn_memcpy_d2d(dbb_win, dbb, 20 * B * Rmax, nil))
-    local swsb = tonumber(C.frcnn_soft_nms_workspace_bytes(B, Rmax))
+    if rows > 16384 then
+      error('Detector: more candidates in a frame than the 16384 a soft per-class NMS takes' .. remedy)
+    end
+    dbb_win = ffi.cast('float*', scratch(prefix .. 'bb_soft', 20 * B * rows).ptr)
+    check(C.frcnn_memcpy_d2d(dbb_win, dbb, 20 * B * rows, nil))
+    local swsb = tonumber(C.frcnn_soft_nms_workspace_bytes(B, rows))
     local sws = scratch(prefix .. 'soft_nms_ws', swsb)
     local log_min = -math.huge
     if self.nms_min_score > 0 then log_min = math.log(self.nms_min_score) end
     local method = 2
     if self.nms_method == 'linear' then method = 1 end
-    check(C.frcnn_soft_nms_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 5, method, self.nms_overlap, self.nms_sigma, log_min, 1, dkc,
+    check(C.frcnn_soft_nms_batch(dbb, B, rows, rows, cnt + 2 * B, 5, 5, method, self.nms_overlap, self.nms_sigma, log_min, 1, dkc,
                                  cpick, cnt + 3 * B, dbb_win + 4, 5, sws.ptr, swsb, nil))
   else
-    local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, Rmax))
+    local cwsb = tonumber(C.frcnn_nms_batch_workspace_bytes(B, rows))
+    if scoring and cwsb > Detector.CLASS_NMS_WORKSPACE then
+      error(string.format('Detector: the per-class NMS of %d frames of %d rows needs a workspace of %d bytes, more than the %d allowed',
+                          B, rows, cwsb, Detector.CLASS_NMS_WORKSPACE) .. remedy)
+    end
     local cws = scratch(prefix .. 'nms_ws2', cwsb)
-    check(C.frcnn_nms_device_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, self.nms_overlap, key_mode, key_col, dkc, cpick, cnt + 3 * B,
+    check(C.frcnn_nms_device_batch(dbb, B, rows, rows, cnt + 2 * B, 5, self.nms_overlap, key_mode, key_col, dkc, cpick, cnt + 3 * B,
                                    cws.ptr, cwsb, nil))
   end
   --         Under box voting (cfg.box_voting): ONE frcnn_box_vote_batch launch over the class test's survivors -- rows bb (the
@@ -553,23 +643,36 @@ function Detector:detect_chunk(frames, shared, prefix)
   --         in place of r2
   local dr2_win = dr2
   if self.vote_overlap ~= nil then
-    dr2_win = ffi.cast('double*', scratch(prefix .. 'r2_voted', 32 * B * Rmax).ptr)
+    dr2_win = ffi.cast('double*', scratch(prefix .. 'r2_voted', 32 * B * rows).ptr)
     local weight_mode = 2
     if self.vote_weight == 'uniform' then weight_mode = 0 end
-    check(C.frcnn_box_vote_batch(dbb, B, Rmax, Rmax, cnt + 2 * B, 5, 5, weight_mode, self.vote_overlap, dkc, dr2, cpick, cnt + 3 * B,
+    check(C.frcnn_box_vote_batch(dbb, B, rows, rows, cnt + 2 * B, 5, 5, weight_mode, self.vote_overlap, dkc, dr2, cpick, cnt + 3 * B,
                                  dr2_win, nil, nil))
   end
-  local out = ffi.cast('double*', scratch(prefix .. 'winners', 128 * B * (Rmax + 1)).ptr)
-  check(C.frcnn_detect_gather_batch(cpick, cnt, B, Rmax, dkeep, dkc, dbb_win, dr2_win, dpick, cap, mp, mr, mi, out, nil))
-  local h = ffi.new('double[?]', 16 * B * (Rmax + 1))
-  check(C.frcnn_memcpy_d2h(h, out, 128 * B * (Rmax + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table
+  local out = ffi.cast('double*', scratch(prefix .. 'winners', 128 * B * (rows + 1)).ptr)
+  check(C.frcnn_detect_gather_batch(cpick, cnt, B, rows, dkeep, dkc, dbb_win, dr2_win, dpick, cap, mp, mr, mi, out, nil))
+  local h = ffi.new('double[?]', 16 * B * (rows + 1))
+  check(C.frcnn_memcpy_d2h(h, out, 128 * B * (rows + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table
   check(C.frcnn_stream_sync(nil))
   for b = 0, B - 1 do
-    local tab = h + 16 * b * (Rmax + 1)
+    local tab = h + 16 * b * (rows + 1)
     local nwin = ffi.cast('int*', tab)[3]
     -- classes in ascending order (the reference iterates with pairs(): unspecified), pick order within a class
     local byclass, classes = {}, {}
-    for q = 1, nwin do
+    -- max_detections: the M winners of highest confidence (compared as fp32 values, ties to the earlier pick), still in pick order
+    local kept = nil
+    if self.max_detections ~= nil and nwin > self.max_detections then
+      local order = {}
+      for q = 1, nwin do order[q] = q end
+      local function conf(q) return tonumber(ffi.cast('float', tab[16 * q + 2])) end
+      table.sort(order, function(i, j)
+        if conf(i) ~= conf(j) then return conf(i) > conf(j) end
+        return i < j
+      end)
+      kept = {}
+      for i = 1, self.max_detections do kept[order[i]] = true end
+    end
+    for q = 1, nwin do if kept == nil or kept[q] then
       local v = tab + 16 * q
       local l, a, y, x = tonumber(v[12]), tonumber(v[13]), tonumber(v[14]), tonumber(v[15])
       local det = { p = v[3], a = self.anchors:get(l, a, y, x), l = l, r = Rect.new(v[4], v[5], v[6], v[7]),
@@ -579,7 +682,7 @@ function Detector:detect_chunk(frames, shared, prefix)
         classes[#classes + 1] = det.class
       end
       table.insert(byclass[det.class], det)
-    end
+    end end
     table.sort(classes)
     for _, ci in ipairs(classes) do
       for _, x in ipairs(byclass[ci]) do table.insert(results[b + 1], x) end

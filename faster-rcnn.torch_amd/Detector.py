@@ -33,7 +33,13 @@ was ranked by; the undecayed one remains last_cnet["cls"][candidate - 1, class -
 Nor is box voting (Gidaris & Komodakis 2015), off by default (cfg["box_voting"] / Detector(..., box_voting=...), see
 box_voting_settings): behind the per-class pass ONE frcnn_box_vote_batch launch replaces every winner's r2 by the weighted mean
 of the r2 of the class test's survivors of its class that overlap it by at least `overlap` (weights: the confidences, always the
-UNDECAYED ones).  Which rows win, their order and every other field of a winner are those of the same Detector without the key."""
+UNDECAYED ones).  Which rows win, their order and every other field of a winner are those of the same Detector without the key.
+
+Nor is scoring a candidate under more than its arg-max class, off by default (cfg["scoring"] / Detector(..., scoring=...), see
+scoring_settings): with the key the class test of a chunk is ONE frcnn_detect_classes_batch launch in place of two per frame, its
+threshold is min_confidence, and under classes = "all" a candidate yields one row per foreground class over the threshold -- the
+rows the per-class NMS, voting and the gather then work on; several winners may share a candidate (field `candidate`), with
+bit-identical r2 unless voted.  max_detections caps a frame's winners on the host."""
 import collections
 import ctypes as C
 import math
@@ -167,6 +173,67 @@ def box_voting_settings(cfg_or_table):
     if not (0.0 < overlap <= 1.0):
         raise ValueError("cfg.box_voting.overlap = %r (in (0, 1])" % (overlap,))
     return overlap, weight
+
+
+SCORING_DEFAULTS = dict(classes="top", min_confidence=0.2, max_detections=None)
+SCORING_MODES = dict(top=0, all=1)   # mode of frcnn_detect_classes_batch
+
+
+def scoring_settings(cfg_or_table):
+    """cfg["scoring"] -- or the table itself, or None -- -> None (the key is absent: the reference's class test, launch for
+    launch) or (classes, min_confidence, max_detections), validated on the host.  The setting governs the class test between the
+    classification net and the per-class NMS (step 4 of _detect_chunk), which under it is ONE frcnn_detect_classes_batch launch
+    per chunk.
+      classes         "top" (default: the reference -- a candidate is scored under the arg-max of its log-probabilities only, and
+                      dropped when that is the background) or "all": one row per foreground class whose probability clears
+                      min_confidence, whatever the arg-max is; the per-class NMS, voting and the records then work on those rows
+      min_confidence  in [0, 1), a probability; default 0.2 (the reference's literal).  A row needs exp(log-probability) > it
+      max_detections  None or M >= 1: a frame keeps the M winners of highest confidence (compared as fp32 values, ties to the
+                      earlier pick), applied on the host behind read-back 2
+    An empty table is "top" at 0.2: the results of the key absent, from one launch.  Raises ValueError (before any device call)
+    for an unknown key, an unknown classes, a bool or a non-number, a min_confidence outside [0, 1) and a max_detections that is
+    not an integer >= 1."""
+    t = cfg_or_table
+    if isinstance(t, dict) and ("scoring" in t or "class_count" in t):     # a model's cfg
+        t = t.get("scoring")
+    if t is None:
+        return None
+    t = _settings_table(t, "scoring", SCORING_DEFAULTS)
+    classes = t.get("classes", SCORING_DEFAULTS["classes"])
+    if not isinstance(classes, str) or classes not in SCORING_MODES:
+        raise ValueError("cfg.scoring.classes = %r (\"top\" or \"all\")" % (classes,))
+    v = t.get("min_confidence", SCORING_DEFAULTS["min_confidence"])
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("cfg.scoring.min_confidence = %r is not a number" % (v,))
+    min_confidence = float(v)
+    if not (0.0 <= min_confidence < 1.0):
+        raise ValueError("cfg.scoring.min_confidence = %r (in [0, 1))" % (min_confidence,))
+    M = t.get("max_detections")
+    if M is not None:
+        if isinstance(M, (bool, np.bool_)) or not isinstance(M, (int, np.integer)):
+            raise ValueError("cfg.scoring.max_detections = %r is not an integer" % (M,))
+        if M < 1:
+            raise ValueError("cfg.scoring.max_detections = %d (at least 1)" % M)
+        M = int(M)
+    return classes, min_confidence, M
+
+
+def scoring_rows(classes, min_confidence, ncls):
+    """m: the rows a candidate can emit under a scoring setting, what the per-row buffers of a chunk are sized by (Rmax * m rows a
+    frame).  "top": 1.  "all": min(ncls - 1, floor(1 / min_confidence) + 1) -- at most floor(1 / c) classes exceed c when the
+    probabilities sum to 1, and one more slot covers the rounding of an fp32 log-softmax, whose exp need not sum to 1 exactly;
+    ncls - 1 at min_confidence = 0."""
+    if classes != "all":
+        return 1
+    if min_confidence <= 0.0:
+        return ncls - 1
+    return min(ncls - 1, int(math.floor(1.0 / min_confidence)) + 1)
+
+
+def keep_best(conf, M):
+    """max_detections: the rows (ascending) of the M highest values of conf, compared as fp32 values, ties to the earlier row."""
+    c = np.asarray(conf).astype(np.float32)
+    return np.sort(np.argsort(-c, kind="stable")[:M])
 
 
 class _Detections(object):
@@ -326,16 +393,21 @@ class _BatchRecord(object):
 
 
 class _DetectorType(type):
-    """Detector(model, ..., box_voting=table): the voting setting is a keyword of the class call, not of __init__, whose
-    parameter list stays what it was.  The table is validated before anything is built -- before the model is looked at, let
-    alone the device -- and set on the finished object; without it __init__ has read model["cfg"]["box_voting"]."""
+    """Detector(model, ..., box_voting=table, scoring=table): the voting and scoring settings are keywords of the class call, not
+    of __init__, whose parameter list stays what it was.  A table is validated before anything is built -- before the model is
+    looked at, let alone the device -- and set on the finished object; without it __init__ has read model["cfg"]["box_voting"] /
+    model["cfg"]["scoring"]."""
 
-    def __call__(cls, *args, box_voting=None, **kw):
+    def __call__(cls, *args, box_voting=None, scoring=None, **kw):
         if box_voting is not None:
             box_voting_settings(box_voting)
+        if scoring is not None:
+            scoring_settings(scoring)
         d = super().__call__(*args, **kw)
         if box_voting is not None:
             d.set_box_voting(box_voting)
+        if scoring is not None:
+            d.set_scoring(scoring)
         return d
 
 
@@ -343,6 +415,7 @@ class Detector(object, metaclass=_DetectorType):
     proposal_settings = staticmethod(proposal_settings)
     nms_settings = staticmethod(nms_settings)
     box_voting_settings = staticmethod(box_voting_settings)
+    scoring_settings = staticmethod(scoring_settings)
 
     def __init__(self, model, static_weights=False, proposals=None, nms=None):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
@@ -352,12 +425,14 @@ class Detector(object, metaclass=_DetectorType):
         nms: the per-class NMS, a table as nms_settings takes it -- validated first, before the model is looked at; None:
         model["cfg"]["nms"] (absent: the reference's hard cut at 0.1).
         Box voting is model["cfg"]["box_voting"] (absent: none) unless the call names one: Detector(model, box_voting=table), a
-        table as box_voting_settings takes it (see _DetectorType)."""
+        table as box_voting_settings takes it (see _DetectorType).  Likewise the class test: model["cfg"]["scoring"] (absent: the
+        reference's) unless the call names one, Detector(model, scoring=table), a table as scoring_settings takes it."""
         if nms is not None:
             nms_settings(nms)
         self.set_proposals(proposals if proposals is not None else model["cfg"])
         self.set_nms(model["cfg"])
         self.set_box_voting(model["cfg"])
+        self.set_scoring(model["cfg"])
         if nms is not None:
             self.set_nms(nms)
         self.model = model
@@ -394,6 +469,11 @@ class Detector(object, metaclass=_DetectorType):
         or a cfg without the key: no voting)."""
         self.box_voting = box_voting_settings(cfg_or_table)
 
+    def set_scoring(self, cfg_or_table):
+        """Validates a table as scoring_settings takes it and makes it this Detector's class test from the next frame on (None,
+        or a cfg without the key: the reference's, launch for launch)."""
+        self.scoring = scoring_settings(cfg_or_table)
+
     def __del__(self):
         if getattr(self, "_host", None):
             try:
@@ -425,6 +505,8 @@ class Detector(object, metaclass=_DetectorType):
         return np.frombuffer(raw, dtype=dtype).copy()
 
     NMS_FIRST_CAP = 16384   # rows the first NMS launch is sized for (see _first_stage)
+    SOFT_NMS_ROWS = 16384   # rows of a frame a soft per-class NMS takes (frcnn_soft_nms_batch)
+    CLASS_NMS_WORKSPACE = 2 << 30   # bytes: under cfg["scoring"] a per-class NMS whose workspace would exceed them is refused
 
     @property
     def last_pick(self):
@@ -748,18 +830,29 @@ class Detector(object, metaclass=_DetectorType):
                                           cls_all.offset_view(0, (total, ncls))))  # :101, all frames
         # ---- then, per frame, the class test (:106-122) into the frame's segment: r2 = Anchors.anchorToInput(r, bbox) in double,
         #      survivors compacted in order
-        bb = self._buf(pre + "bb", (B, Rmax, 5)); kc = self._buf(pre + "kc", (B, Rmax), i32)
-        keep_row = self._buf(pre + "keep_row", (B, Rmax), i32); r2 = self._buf(pre + "r2", (B, Rmax, 4), np.float64)
-        dcls = self._buf(pre + "cls", (Rmax,), i32); dconf = self._buf(pre + "conf", (Rmax,))
-        for b in range(B):
-            c_Kb = c_K.offset_view(b, (1,))
-            if ns[b] == 0:     # no candidates: an empty segment of the per-class NMS
-                _lib.call("frcnn_zero", ptr(c_Kb), c_Kb.dtype.itemsize, s)
-                continue
-            _lib.call("frcnn_cnet_decode", ptr(more[b]["cls"]), Rs[b], ncls, ptr(dcls), ptr(dconf), s)  # :110-113
-            _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(more[b]["bbox"]), ptr(mr.segment(b)), ptr(pick.segment(b)),
-                      Rs[b], ncls, 0.2, ptr(bb.segment(b)), ptr(kc.segment(b)), ptr(keep_row.segment(b)), ptr(r2.segment(b)),
-                      ptr(c_Kb), s)
+        #      Under cfg["scoring"]: ONE frcnn_detect_classes_batch launch for the chunk, which reads the net's log-probabilities
+        #      itself (every frame's row count and first row are kernel arguments) -- "top": the same rows; "all": a row per
+        #      foreground class over min_confidence, so the per-row buffers and everything behind hold `rows` = Rmax * m a frame
+        scoring = self.scoring
+        rows = Rmax * (scoring_rows(scoring[0], scoring[1], ncls) if scoring else 1)
+        bb = self._buf(pre + "bb", (B, rows, 5)); kc = self._buf(pre + "kc", (B, rows), i32)
+        keep_row = self._buf(pre + "keep_row", (B, rows), i32); r2 = self._buf(pre + "r2", (B, rows, 4), np.float64)
+        if scoring:
+            R_arg = (C.c_int * B)(*[Rs[b] if b in row0 else 0 for b in range(B)])     # (a frame without matches: no rows)
+            row0_arg = (C.c_longlong * B)(*[row0.get(b, 0) for b in range(B)])
+            _lib.call("frcnn_detect_classes_batch", ptr(cls_all), ptr(bbox_all), R_arg, row0_arg, B, ptr(mr), ptr(pick), cap, ncls,
+                      ncls, scoring[1], SCORING_MODES[scoring[0]], ptr(bb), ptr(kc), ptr(keep_row), ptr(r2), rows, ptr(c_K), None, s)
+        else:
+            dcls = self._buf(pre + "cls", (Rmax,), i32); dconf = self._buf(pre + "conf", (Rmax,))
+            for b in range(B):
+                c_Kb = c_K.offset_view(b, (1,))
+                if ns[b] == 0:     # no candidates: an empty segment of the per-class NMS
+                    _lib.call("frcnn_zero", ptr(c_Kb), c_Kb.dtype.itemsize, s)
+                    continue
+                _lib.call("frcnn_cnet_decode", ptr(more[b]["cls"]), Rs[b], ncls, ptr(dcls), ptr(dconf), s)  # :110-113
+                _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(more[b]["bbox"]), ptr(mr.segment(b)),
+                          ptr(pick.segment(b)), Rs[b], ncls, 0.2, ptr(bb.segment(b)), ptr(kc.segment(b)),
+                          ptr(keep_row.segment(b)), ptr(r2.segment(b)), ptr(c_Kb), s)
         # ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame, rows only suppress rows of their own class: a stable
         #         partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
         #         column under order = "score"), the survivor counts read from device memory; ONE gather of every frame's winner
@@ -767,24 +860,30 @@ class Detector(object, metaclass=_DetectorType):
         #         Under a soft method (cfg["nms"]): ONE frcnn_soft_nms_batch launch instead, on the log-confidences (log_domain 1,
         #         min_score as a log), which writes every winner's decayed score into column 5 of a COPY of bb; the gather reads
         #         that copy, so a winner's confidence is the score it was picked at
-        wpick = self._buf(pre + "wpick", (B, Rmax), np.int64)
+        wpick = self._buf(pre + "wpick", (B, rows), np.int64)
         soft = self.nms_method != "hard"
+        # (a frame's rows are its candidates times m: fewer candidates are the way out of either refusal)
+        remedy = " (%d candidates x %d rows each: lower cfg.proposals.post_nms_top_n)" % (Rmax, rows // Rmax) if rows > Rmax else ""
         bb_win = bb
         if soft:
-            if Rmax > 16384:
-                raise _lib.FrcnnError("Detector: %d candidates in a frame, more than the 16384 a soft per-class NMS takes" % Rmax)
-            bb_win = self._buf(pre + "bb_soft", (B, Rmax, 5))
+            if rows > self.SOFT_NMS_ROWS:
+                raise _lib.FrcnnError("Detector: %d candidates in a frame, more than the %d a soft per-class NMS takes%s"
+                                      % (rows, self.SOFT_NMS_ROWS, remedy))
+            bb_win = self._buf(pre + "bb_soft", (B, rows, 5))
             _lib.call("frcnn_memcpy_d2d", ptr(bb_win), ptr(bb), bb.nbytes, s)
-            wsb2 = L.frcnn_soft_nms_workspace_bytes(B, Rmax)
+            wsb2 = L.frcnn_soft_nms_workspace_bytes(B, rows)
             ws2 = self._buf(pre + "soft_nms_ws", (wsb2,), np.uint8)
             log_min = float(math.log(self.nms_min_score)) if self.nms_min_score > 0.0 else -math.inf
-            _lib.call("frcnn_soft_nms_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, 5, SOFT_NMS_METHODS.index(self.nms_method),
+            _lib.call("frcnn_soft_nms_batch", ptr(bb), B, rows, rows, ptr(c_K), 5, 5, SOFT_NMS_METHODS.index(self.nms_method),
                       C.c_float(self.nms_overlap), C.c_float(self.nms_sigma), C.c_float(log_min), 1, ptr(kc), ptr(wpick), c_W,
                       ptr(bb_win.offset_view(4, (1,))), 5, ptr(ws2), wsb2, s)      # (column 5 of the copy)
         else:
-            wsb2 = L.frcnn_nms_batch_workspace_bytes(B, Rmax)
+            wsb2 = L.frcnn_nms_batch_workspace_bytes(B, rows)
+            if scoring and wsb2 > self.CLASS_NMS_WORKSPACE:
+                raise _lib.FrcnnError("Detector: the per-class NMS of %d frames of %d rows needs a workspace of %d bytes, more than "
+                                      "the %d allowed%s" % (B, rows, wsb2, self.CLASS_NMS_WORKSPACE, remedy))
             ws2 = self._buf(pre + "nms_ws2", (wsb2,), np.uint8)
-            _lib.call("frcnn_nms_device_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, C.c_float(self.nms_overlap), key_mode, key_col,
+            _lib.call("frcnn_nms_device_batch", ptr(bb), B, rows, rows, ptr(c_K), 5, C.c_float(self.nms_overlap), key_mode, key_col,
                       ptr(kc), ptr(wpick), c_W, ptr(ws2), wsb2, s)
         #         Under box voting (cfg["box_voting"]): ONE frcnn_box_vote_batch launch over the class test's survivors -- rows bb
         #         (the UNDECAYED log-confidences, also under a soft method: weight_mode 2), classes kc, coordinates the fp64 r2,
@@ -793,13 +892,13 @@ class Detector(object, metaclass=_DetectorType):
         voting = self.box_voting is not None
         r2_win = r2
         if voting:
-            r2_win = self._buf(pre + "r2_voted", (B, Rmax, 4), np.float64)
-            votes = self._buf(pre + "votes", (B, Rmax), i32)
+            r2_win = self._buf(pre + "r2_voted", (B, rows, 4), np.float64)
+            votes = self._buf(pre + "votes", (B, rows), i32)
             _lib.call("frcnn_zero", ptr(votes), votes.nbytes, s)      # (a record shows 0 votes for the rows that did not win)
-            _lib.call("frcnn_box_vote_batch", ptr(bb), B, Rmax, Rmax, ptr(c_K), 5, 5, BOX_VOTING_WEIGHTS[self.box_voting[1]],
+            _lib.call("frcnn_box_vote_batch", ptr(bb), B, rows, rows, ptr(c_K), 5, 5, BOX_VOTING_WEIGHTS[self.box_voting[1]],
                       C.c_float(self.box_voting[0]), ptr(kc), ptr(r2), ptr(wpick), c_W, ptr(r2_win), ptr(votes), s)
-        out = self._buf(pre + "winners", (B, Rmax + 1, 16), np.float64)
-        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, Rmax, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2_win),
+        out = self._buf(pre + "winners", (B, rows + 1, 16), np.float64)
+        _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, rows, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2_win),
                   ptr(pick), cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
         records = self._records(st, more)
         raw = self._read(out.ptr, out.nbytes, np.float64).reshape(out.shape)   # ---- read-back 2 of 2
@@ -816,6 +915,8 @@ class Detector(object, metaclass=_DetectorType):
                 results.append([])
                 continue
             w = raw[b, 1:1 + int(hdr[3])]
+            if scoring and scoring[2] is not None and len(w) > scoring[2]:   # max_detections: the best M, still in pick order
+                w = w[keep_best(w[:, 2], scoring[2])]
             # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
             results.append(_Detections(w[np.argsort(w[:, 0], kind="stable")].copy(), self.anchors))
         return results, records

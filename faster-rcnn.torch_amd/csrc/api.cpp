@@ -212,6 +212,13 @@ int frcnn_detect_post(const int* cls, const float* conf, const float* bbox, cons
                       int bgclass, double min_conf, float* bb, int* kc, int* keep_row, double* r2, int* K_dev, void* stream) {
   return detect_post(cls, conf, bbox, rect, pick, R, bgclass, min_conf, bb, kc, keep_row, r2, K_dev, S(stream));
 }
+int frcnn_detect_classes_batch(const float* cls_out, const float* bbox, const int* R_host, const long long* row0_host, int B,
+                               const double* rect, const long long* pick, long long match_stride, int ncls, int bgclass,
+                               double min_conf, int mode, float* bb, int* kc, int* keep_row, double* r2, int row_stride, int* K_dev,
+                               int* total_dev, void* stream) {
+  return detect_classes_batch(cls_out, bbox, R_host, row0_host, B, rect, pick, match_stride, ncls, bgclass, min_conf, mode, bb, kc,
+                              keep_row, r2, row_stride, K_dev, total_dev, S(stream));
+}
 int frcnn_nms_host(const float* boxes_host, int n, int ncols, float overlap, int key_mode, int key_col,
                    long long* pick_host, int* count_host) {
   if (n <= 0) { *count_host = 0; return FRCNN_OK; }

@@ -5,6 +5,9 @@
 //   detect_post   Detector.lua:106-122: class test (class != background and p > 0.2), r2 = Anchors.anchorToInput(r, bbox)
 //                 in double, ORDERED compaction of the survivors into the box / class arrays the per-class NMS reads;
 //                 the survivor count stays on the device (frcnn_nms_device_n reads it there)
+//   detect_classes_batch  the class test of a chunk of B frames in ONE launch, straight from the net's log-probabilities
+//                 (the arg-max of frcnn_cnet_decode folded in): mode 0 the rule above, one row per candidate at most; mode 1
+//                 one row per (candidate, foreground class) whose probability clears the threshold
 //   detect_gather_batch  one table per frame: its counts, then one record per winner (class, candidate row, confidence, p,
 //                 anchor rect, decoded rect, anchor index)
 // Gather / scan work on a few thousand rows: latency-bound, no MFMA.  Double arithmetic follows the host mirror
@@ -59,6 +62,16 @@ int roi_windows(const double* rect, const long long* pick, int k, const int* lay
   return FRCNN_OK;
 }
 
+// Anchors.anchorToInput (Anchors.lua:245-252) + Rect.fromXYWidthHeight: a = the anchor's input rect, t = the net's 4 deltas;
+// products and sums separately rounded, as Lua numbers are
+__device__ __forceinline__ void anchor_to_input(const double* __restrict__ a, const float* __restrict__ t, double* __restrict__ o) {
+  const double aw = a[2] - a[0], ah = a[3] - a[1];
+  double x0 = (double)t[0] * aw; x0 = x0 + a[0];
+  double y0 = (double)t[1] * ah; y0 = y0 + a[1];
+  const double ew = exp((double)t[2]) * aw, eh = exp((double)t[3]) * ah;
+  o[0] = x0; o[1] = y0; o[2] = x0 + ew; o[3] = y0 + eh;
+}
+
 // One block, ordered compaction.  For candidate r (row pick[r] of the match arrays): keep iff cls != bgclass and
 // exp(conf) > min_conf.  Survivor j (in candidate order): bb[j] = {float(r2), conf}, kc[j] = class, keep_row[j] = r,
 // r2[j] = decoded rect in double; *K_dev = number of survivors.
@@ -86,14 +99,9 @@ __global__ __launch_bounds__(DP_THREADS) void detect_post_kernel(const int* __re
     for (int w = 0; w < wave; ++w) off += wsum[w];
     if (keep) {
       const int j = off + before;
-      const double* a = rect + 4 * (size_t)(pick[r] - 1);   // the anchor's input rect (Detector.lua:106)
-      const double aw = a[2] - a[0], ah = a[3] - a[1];
-      const float* t = bbox + 4 * (size_t)r;
-      // Anchors.anchorToInput (Anchors.lua:245-252): products and sums separately rounded, as Lua numbers are
-      double x0 = (double)t[0] * aw; x0 = x0 + a[0];
-      double y0 = (double)t[1] * ah; y0 = y0 + a[1];
-      const double ew = exp((double)t[2]) * aw, eh = exp((double)t[3]) * ah;
-      const double x1 = x0 + ew, y1 = y0 + eh;     // Rect.fromXYWidthHeight
+      double q[4];
+      anchor_to_input(rect + 4 * (size_t)(pick[r] - 1), bbox + 4 * (size_t)r, q);   // the anchor's input rect (Detector.lua:106)
+      const double x0 = q[0], y0 = q[1], x1 = q[2], y1 = q[3];
       r2out[4 * (size_t)j] = x0; r2out[4 * (size_t)j + 1] = y0; r2out[4 * (size_t)j + 2] = x1; r2out[4 * (size_t)j + 3] = y1;
       float* b = bb + 5 * (size_t)j;               // r.r2:totensor() (FloatTensor) + the confidence column
       b[0] = (float)x0; b[1] = (float)y0; b[2] = (float)x1; b[3] = (float)y1; b[4] = conf[r];
@@ -116,6 +124,153 @@ int detect_post(const int* cls, const float* conf, const float* bbox, const doub
   if (R <= 0) { FR_HIP(hipMemsetAsync(K_dev, 0, sizeof(int), s)); return FRCNN_OK; }
   FR_LAUNCH(KC_ELEMWISE, 0, R * 64.0, s, detect_post_kernel, dim3(1), dim3(DP_THREADS), 0, cls, conf, bbox, rect, pick, R, bgclass,
             min_conf, bb, kc, keep_row, r2, K_dev);
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// ---- The class test of B frames in one launch (Detector:detect_batch under cfg.scoring), from the net's outputs as they lie:
+// frame b's R[b] candidates are rows row0[b] ... of lsm (ncls log-probabilities a row) and of bbox.  R and row0 are host values and
+// travel BY VALUE as a kernel argument, in groups of at most DC_GROUP frames (the way rpn_scan_ragged carries its descriptors): no
+// table upload, no copy, no wait.
+// One workgroup per frame, tiles of DC_THREADS candidates, one candidate per thread.  The 64 candidates of a wave own 64 * ncls
+// CONTIGUOUS floats; the wave moves them through its own LDS tile DC_CLS classes at a time -- DC_CLS consecutive lanes load the
+// DC_CLS consecutive floats of one candidate, so a load touches 8 runs of 32 bytes, not 64 rows, and every 128-byte line is used
+// up by the wave's next rounds -- and a lane then reads its own candidate's values from the tile (walk_row; rows of DC_CLS + 1
+// floats: no bank conflicts).  Two walks per tile of candidates: the first counts a candidate's rows (mode 0: the first maximum,
+// exactly cnet_decode_kernel, then the test of detect_post_kernel: 0 or 1; mode 1: every class c != bgclass with
+// exp(lp[c]) > min_conf: 0 ... ncls - 1); a wave prefix sum and the cross-wave sums in LDS turn the counts into row numbers
+// (ordered: candidate-major, c ascending); the second walk (mode 1) stores the rows.  r2 is decoded ONCE per candidate with a
+// row.  No atomics: a frame's output is a function of its own data.  Rows at and behind row_stride are counted, not stored.
+#define DC_THREADS 1024
+#define DC_CLS 8       // classes a round of walk_row
+constexpr int DC_GROUP = 32;
+struct ClassFrame { long long row0; int R; };
+struct ClassGroup { ClassFrame f[DC_GROUP]; };
+static_assert(sizeof(ClassGroup) <= 1024, "the descriptors of a group travel as a kernel argument");
+
+// f(c, v) for c = 0 ... ncls - 1, v = span[lane * ncls + c], in order, on the lanes < cands: `span` is the wave's part of lsm
+// (cands <= 64 candidates), `tile` its LDS tile.  Every wave of the block makes the same rounds (the barriers are the block's).
+template <class F>
+__device__ __forceinline__ void walk_row(const float* __restrict__ span, int cands, int ncls, int lane, float* tile, F f) {
+  for (int c0 = 0; c0 < ncls; c0 += DC_CLS) {
+    const int nc = min(DC_CLS, ncls - c0);
+    __syncthreads();
+    for (int i = lane; i < 64 * DC_CLS; i += 64) {
+      const int t = i / DC_CLS, cc = i % DC_CLS;
+      if (t < cands && cc < nc) tile[t * (DC_CLS + 1) + cc] = span[(size_t)t * ncls + c0 + cc];
+    }
+    __syncthreads();
+    if (lane < cands)
+      for (int cc = 0; cc < nc; ++cc) f(c0 + cc, tile[lane * (DC_CLS + 1) + cc]);
+  }
+}
+
+__global__ __launch_bounds__(DC_THREADS) void detect_classes_batch_kernel(
+    ClassGroup g, int b0, const float* __restrict__ lsm, const float* __restrict__ bbox, const double* __restrict__ rect,
+    const long long* __restrict__ pick, long long match_stride, int ncls, int bgclass, double min_conf, int mode,
+    float* __restrict__ bb, int* __restrict__ kc, int* __restrict__ keep_row, double* __restrict__ r2out, int row_stride,
+    int* __restrict__ K_dev, int* __restrict__ total_dev) {
+  __shared__ float tiles[DC_THREADS / 64][64 * (DC_CLS + 1)];
+  __shared__ int wsum[DC_THREADS / 64];
+  __shared__ int base;
+  const int b = b0 + blockIdx.x;
+  const int R = g.f[blockIdx.x].R;
+  const size_t first = (size_t)g.f[blockIdx.x].row0;
+  lsm += first * ncls; bbox += first * 4;
+  rect += (size_t)b * match_stride * 4; pick += (size_t)b * match_stride;
+  const size_t so = (size_t)b * row_stride;
+  bb += so * 5; kc += so; keep_row += so; r2out += so * 4;
+  if (threadIdx.x == 0) base = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* tile = tiles[wave];
+  for (int r0 = 0; r0 < R; r0 += DC_THREADS) {
+    const int r = r0 + threadIdx.x, rw = r0 + wave * 64;     // the thread's candidate, the wave's first
+    const float* span = lsm + (size_t)min(rw, R) * ncls;
+    const int cands = max(min(R - rw, 64), 0);
+    int cnt = 0, best = 0;
+    float bestv = 0.0f;
+    walk_row(span, cands, ncls, lane, tile, [&](int c, float v) {
+      if (mode == 0) {
+        if (c == 0 || v > bestv) { best = c; bestv = v; }      // torch.sort(cprob, 1, true)[1]: the first maximum
+      } else {
+        cnt += c + 1 != bgclass && exp((double)v) > min_conf;
+      }
+    });
+    if (mode == 0 && r < R) cnt = best + 1 != bgclass && exp((double)bestv) > min_conf;   // Detector.lua:115
+    // rows before this thread's: inclusive wave scan, then the waves before this one
+    int incl = cnt;
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += up;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int j = base + incl - cnt;
+    for (int w = 0; w < wave; ++w) j += wsum[w];
+    const bool stores = cnt > 0 && j < row_stride;
+    double q[4];
+    if (stores) anchor_to_input(rect + 4 * (size_t)(pick[r] - 1), bbox + 4 * (size_t)r, q);
+    auto emit = [&](int c, float v) {
+      if (j < row_stride) {
+        double* o = r2out + 4 * (size_t)j;
+        o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
+        float* x = bb + 5 * (size_t)j;
+        x[0] = (float)q[0]; x[1] = (float)q[1]; x[2] = (float)q[2]; x[3] = (float)q[3]; x[4] = v;
+        kc[j] = c + 1;
+        keep_row[j] = r;
+      }
+      ++j;
+    };
+    if (mode == 0) {
+      if (stores) emit(best, bestv);
+    } else {   // (the second walk: the rows come from cache)
+      walk_row(span, cands, ncls, lane, tile, [&](int c, float v) {
+        if (stores && c + 1 != bgclass && exp((double)v) > min_conf) emit(c, v);
+      });
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int tot = 0;
+      for (int w = 0; w < DC_THREADS / 64; ++w) tot += wsum[w];
+      base += tot;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    K_dev[b] = min(base, row_stride);
+    if (total_dev) total_dev[b] = base;
+  }
+}
+
+int detect_classes_batch(const float* cls_out, const float* bbox, const int* R, const long long* row0, int B, const double* rect,
+                         const long long* pick, long long match_stride, int ncls, int bgclass, double min_conf, int mode, float* bb,
+                         int* kc, int* keep_row, double* r2, int row_stride, int* K_dev, int* total_dev, hipStream_t s) {
+  if (B == 0) return FRCNN_OK;
+  // everything is checked before the first launch: a refused call has written nothing
+  FR_CHECK(B > 0 && B <= 65535, "detect_classes_batch: %d frames (0 ... 65535)", B);
+  FR_CHECK(ncls >= 2, "detect_classes_batch: %d classes (at least 2: one and the background)", ncls);
+  FR_CHECK(bgclass >= 1 && bgclass <= ncls, "detect_classes_batch: background class %d (1 ... %d)", bgclass, ncls);
+  FR_CHECK(mode == 0 || mode == 1, "detect_classes_batch: mode %d (0: top class, 1: all classes)", mode);
+  FR_CHECK(row_stride >= 0 && match_stride >= 0, "detect_classes_batch: negative stride (%d / %lld)", row_stride, match_stride);
+  FR_CHECK(R && row0 && K_dev, "detect_classes_batch: NULL argument");
+  double rows = 0;
+  for (int b = 0; b < B; ++b) {
+    FR_CHECK(R[b] >= 0 && row0[b] >= 0, "detect_classes_batch: frame %d has R %d, row0 %lld (negative)", b, R[b], row0[b]);
+    FR_CHECK((long long)R[b] * ncls <= 0x7fffffffLL, "detect_classes_batch: frame %d: %d x %d log-probabilities", b, R[b], ncls);
+    rows += R[b];
+  }
+  FR_CHECK(rows == 0 || (cls_out && bbox && rect && pick), "detect_classes_batch: NULL argument");
+  FR_CHECK(rows == 0 || row_stride == 0 || (bb && kc && keep_row && r2), "detect_classes_batch: NULL output");
+  for (int b0 = 0; b0 < B; b0 += DC_GROUP) {
+    const int nb = std::min(B - b0, DC_GROUP);
+    ClassGroup g;
+    memset(&g, 0, sizeof(g));
+    for (int i = 0; i < nb; ++i) { g.f[i].row0 = row0[b0 + i]; g.f[i].R = R[b0 + i]; }
+    FR_LAUNCH(KC_ELEMWISE, 0, rows * (ncls * 4.0 + 64.0), s, detect_classes_batch_kernel, dim3(nb), dim3(DC_THREADS), 0, g, b0,
+              cls_out, bbox, rect, pick, match_stride, ncls, bgclass, min_conf, mode, bb, kc, keep_row, r2, row_stride, K_dev,
+              total_dev);
+  }
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }

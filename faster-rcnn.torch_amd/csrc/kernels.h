@@ -313,6 +313,9 @@ int roi_windows(const double* rect, const long long* pick, int k, const int* lay
                 hipStream_t s);
 int detect_post(const int* cls, const float* conf, const float* bbox, const double* rect, const long long* pick, int R,
                 int bgclass, double min_conf, float* bb, int* kc, int* keep_row, double* r2, int* K_dev, hipStream_t s);
+int detect_classes_batch(const float* cls_out, const float* bbox, const int* R, const long long* row0, int B, const double* rect,
+                         const long long* pick, long long match_stride, int ncls, int bgclass, double min_conf, int mode, float* bb,
+                         int* kc, int* keep_row, double* r2, int row_stride, int* K_dev, int* total_dev, hipStream_t s);
 int detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                         const float* bb, const double* r2, const long long* pick, long match_stride, const float* mp,
                         const double* rect, const int* midx, double* rec, hipStream_t s);

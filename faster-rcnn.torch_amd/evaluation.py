@@ -189,7 +189,11 @@ def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_
     batch > 1: up to that many consecutive frames of one size go through Detector.detect_batch in one call (same detections,
     two host waits per chunk instead of two per frame); 1 is the frame-by-frame loop of the reference.
     mixed_sizes=True (with batch > 1): a change of size no longer ends a chunk -- `batch` consecutive frames, whatever their
-    sizes, go through detect_batch(..., mixed_sizes=True) (a data set whose every file has a size of its own)."""
+    sizes, go through detect_batch(..., mixed_sizes=True) (a data set whose every file has a size of its own).
+    The precision/recall curves are only as long as the detector's list: mAP is meant to be computed under a detector with
+    cfg["scoring"] = {classes = "all", min_confidence = a low value such as 0.05} (Detector.scoring_settings), which scores a
+    region under every class over the threshold; the reference's class test (arg-max only, p > 0.2) cuts the low-confidence
+    tail off every curve."""
     detections, ground_truth = [], []
     images = 0
     pending = []     # (image id, frame) -- of one size unless mixed_sizes -- waiting for detect_batch

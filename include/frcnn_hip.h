@@ -236,6 +236,24 @@ int frcnn_roi_windows(const double *rect, const long long *pick, int k, const in
  * kc[K] = class, keep_row[K] = r (0-based); *K_dev = their number (device).  All outputs need room for R rows. */
 int frcnn_detect_post(const int *cls, const float *conf, const float *bbox, const double *rect, const long long *pick, int R,
                       int bgclass, double min_conf, float *bb, int *kc, int *keep_row, double *r2, int *K_dev, void *stream);
+/* frcnn_detect_classes_batch: the class test of B frames in ONE launch (Detector under cfg.scoring), read from the net's outputs:
+ * frame b's R_host[b] candidates are rows row0_host[b] ... of cls_out (ncls fp32 log-probabilities a row) and of bbox (4 a row);
+ * both arrays are HOST values and travel as kernel arguments (no upload, no wait).  rect / pick: the match arrays, match_stride
+ * rows a frame.  Candidate r of frame b emits, in candidate order,
+ *   mode 0 (top class)    the row (r, c*), c* the first maximum of its log-probabilities (frcnn_cnet_decode), iff c* != bgclass and
+ *                         exp((double)lp[c*]) > min_conf: per frame exactly frcnn_cnet_decode + frcnn_detect_post, bit for bit;
+ *   mode 1 (all classes)  one row (r, c) for every class c != bgclass with exp((double)lp[c]) > min_conf, c ascending (a NaN emits
+ *                         nothing).
+ * A row j of frame b lies at row b*row_stride + j of the outputs: bb[5] = {float(r2), lp[c]}, kc = c (1-based), keep_row = r
+ * (0-based), r2[4] = Anchors.anchorToInput(anchor rect, bbox row) in double, decoded once per candidate (the rows of one candidate
+ * carry identical coordinates).  total_dev[b] (device int[B], optional) = the rows the rule emits, K_dev[b] (device int[B]) =
+ * min(total, row_stride): only the first row_stride rows are stored, nothing is written behind row K_dev[b].  A frame with
+ * R_host[b] = 0 writes its two counts (0) and nothing else.  Errors (B outside 0 ... 65535, ncls < 2, bgclass outside 1 ... ncls,
+ * mode, a negative stride, R or row0, a NULL required pointer) are returned before any launch. */
+int frcnn_detect_classes_batch(const float *cls_out, const float *bbox, const int *R_host, const long long *row0_host, int B,
+                               const double *rect, const long long *pick, long long match_stride, int ncls, int bgclass,
+                               double min_conf, int mode, float *bb, int *kc, int *keep_row, double *r2, int row_stride, int *K_dev,
+                               int *total_dev, void *stream);
 /* frcnn_detect_gather_batch: the winner tables of B frames in one launch (Detector:detect_batch, and Detector:detect with
  * B = 1), all in ONE buffer (one read-back): frame b's table starts at rec + b*(row_stride + 1)*16 doubles -- a 128-byte header
  * whose first four ints are the frame's counts, then one record of 16 doubles per winner q < min(winners, row_stride), in the
