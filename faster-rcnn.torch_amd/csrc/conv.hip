@@ -1226,11 +1226,11 @@ static void choose_wgrad_tile(int Ho, int Wo, int k, int tys, int* TH, int* TW) 
   *TH = bth; *TW = btw;
 }
 
-static bool g_wgrad_first_ok = true;  // cleared by conv_wgrad when the input carries a fused activation
-static bool wgrad_is_first(int Cin, int O, int k, int Wo) { return g_wgrad_first_ok && k == 3 && Cin * 9 <= 32 && O <= 64 && Wo >= 2; }
+// first_ok: the input carries no fused activation (the first-layer kernel has no activating loader)
+static bool wgrad_is_first(int Cin, int O, int k, int Wo, bool first_ok) { return first_ok && k == 3 && Cin * 9 <= 32 && O <= 64 && Wo >= 2; }
 
-static void wgrad_plan(WgradArgs& a, int k) {
-  if (wgrad_is_first(a.Cin, a.O, k, a.Wo)) {
+static void wgrad_plan(WgradArgs& a, int k, bool first_ok) {
+  if (wgrad_is_first(a.Cin, a.O, k, a.Wo, first_ok)) {
     a.TH = W1_TH; a.TW = W1_TW;
     a.tilesX = cdiv(a.Wo, W1_TW); a.tilesY = cdiv(a.Ho, W1_TH);
     a.oTiles = a.cTiles = a.kyGroups = 1;
@@ -1353,15 +1353,20 @@ size_t conv_wgrad_workspace_bytes(int Cin, int H, int W, int O, int k, int pad) 
   if (k == 3 && Cin % 64 == 0 && O % 64 == 0) {   // either form may run (option split_bf16): room for both
     WgradArgs b;
     b.Cin = Cin; b.H = H; b.W = W; b.O = O; b.pad = pad; b.Ho = H + 2 * pad - k + 1; b.Wo = W + 2 * pad - k + 1;
-    wgrad_plan(b, k);
+    wgrad_plan(b, k, false);
     return std::max((size_t)b.nSplit * k * k * O * Cin * 4 + 256, conv_wgradx_workspace_bytes(Cin, H, W, O, pad));
   }
   WgradArgs a;
   a.Cin = Cin; a.H = H; a.W = W; a.O = O; a.pad = pad;
   a.Ho = H + 2 * pad - k + 1; a.Wo = W + 2 * pad - k + 1;
-  wgrad_plan(a, k);
+  wgrad_plan(a, k, true);
   // (first-layer shapes: room for the bias / slope sums that conv_wgrad_first_pooled keeps behind every slab slice)
-  return (size_t)a.nSplit * (k * k * O * Cin + O + 1) * 4 + 256;
+  size_t need = (size_t)a.nSplit * (k * k * O * Cin + O + 1) * 4 + 256;
+  if (wgrad_is_first(Cin, O, k, a.Wo, true)) {   // a call with a fused activation takes the generic kernel: room for either plan
+    wgrad_plan(a, k, false);
+    need = std::max(need, (size_t)a.nSplit * k * k * O * Cin * 4 + 256);
+  }
+  return need;
 }
 
 template <int KS, int TYS, int PM>
@@ -1405,14 +1410,14 @@ int conv_wgrad(const float* in, int Cin, int H, int W, const float* in_slope, co
   FR_CHECK(!map || (!map->omap && !map->cmap), "conv_wgrad: a gathered weight gradient needs a conv_wgradx shape");
   if (gbias) FR_TRY(channel_sum(g, O, (long)a.Ho * a.Wo, gbias, s));   // the fp32 kernels leave the bias half to a pass of its own
   FR_CHECK((long)Cin * H * W < (1L << 31) && (long)O * a.Ho * a.Wo < (1L << 31), "conv_wgrad: tensor too large for 32-bit offsets");
-  g_wgrad_first_ok = (in_slope == nullptr && in_scale == nullptr);
-  wgrad_plan(a, k);
+  const bool first_ok = in_slope == nullptr && in_scale == nullptr;
+  wgrad_plan(a, k, first_ok);
   size_t need = (size_t)a.nSplit * k * k * O * Cin * 4 + 256;
   FR_CHECK(ws && ws_bytes >= need, "conv_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
   a.slab = (float*)(((uintptr_t)ws + 255) / 256 * 256);
   double flops = 2.0 * O * Cin * k * k * (double)a.Ho * a.Wo;
   int klass = k == 3 ? KC_CONV_WGRAD_K3 : KC_CONV_WGRAD_OTHER;
-  if (wgrad_is_first(Cin, O, k, a.Wo)) {
+  if (wgrad_is_first(Cin, O, k, a.Wo, first_ok)) {
     FR_CHECK((double)O * a.Ho * a.Wo * 4.0 < 4294967295.0 && (double)Cin * H * W * 4.0 < 4294967295.0,
              "conv_wgrad: first-layer tensors too large for 32-bit buffer resources");
     size_t lds = ((size_t)64 * W1_GP + W1_PATCH) * 4;

@@ -1,6 +1,11 @@
-"""nn.SpatialConvolution forward / updateGradInput / accGradParameters: HIP implicit-GEMM kernels
-(fp32 MFMA) through the C ABI vs the CPU oracle (fp64 accumulation).  Tolerance:
-|a-b| <= 1e-4 * max(1, |b|)."""
+"""nn.SpatialConvolution forward / updateGradInput / accGradParameters through the C ABI vs the CPU oracle (fp64
+accumulation).  Tolerance: |a-b| <= 1e-4 * max(1, |b|).
+
+Which kernels that is: with option split_bf16 at its default (on) the entry points send every eligible shape to the split
+operand forms -- forward and input gradient of 64 -> 128, 256 -> 512, 512 -> 512 (3x3) and 512 -> 256 (7x7) to convx.hip, the
+weight gradient of the first three to wgradx.hip -- and only the seven other CASES run the fp32 matrix-core kernels of
+conv.hip (tests/test_conv_plan.py::test_which_cases_of_test_gpu_conv_still_reach_conv_hip keeps this list in step).  Those
+kernels across their launch plans, with the option off: tests/test_gpu_conv_plans.py."""
 import ctypes as C
 
 import numpy as np
