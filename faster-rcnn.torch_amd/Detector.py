@@ -61,13 +61,16 @@ ASPECTS = 3   # anchors per map position (Anchors.lua:108-109)
 PROPOSAL_DEFAULTS = dict(order="y2", pre_nms_top_n=None, post_nms_top_n=None)
 
 
-def _settings_table(cfg_or_table, name, defaults):
-    """The table cfg[name] of a model's cfg -- or the table itself, or None (-> {}) -- refused (ValueError) unless it is a table
-    with keys of `defaults` only: the prologue of proposal_settings and nms_settings."""
+def _settings_table(cfg_or_table, name, defaults, optional=False):
+    """The table cfg[name] of a model's cfg -- or the table itself, or None -- refused (ValueError) unless it is a table with
+    keys of `defaults` only: the prologue of the four validators below.  An absent key or None is {} -- or, optional=True, None:
+    the feature is off."""
     t = cfg_or_table
     if isinstance(t, dict) and (name in t or "class_count" in t):     # a model's cfg
         t = t.get(name)
     if t is None:
+        if optional:
+            return None
         t = {}
     if not isinstance(t, dict):
         raise ValueError("cfg.%s must be a table of {%s}" % (name, ", ".join(defaults)))
@@ -75,6 +78,24 @@ def _settings_table(cfg_or_table, name, defaults):
     if unknown:
         raise ValueError("cfg.%s: unknown key(s) %s" % (name, ", ".join(map(str, unknown))))
     return t
+
+
+def _number(name, key, v):
+    """cfg.<name>.<key> = v as a float; refused (ValueError) when it is a bool or not a number."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError("cfg.%s.%s = %r is not a number" % (name, key, v))
+    return float(v)
+
+
+def _count(name, key, v):
+    """cfg.<name>.<key> = v as None or an int; refused (ValueError) unless it is None or an integer (no bool) of at least 1."""
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise ValueError("cfg.%s.%s = %r is not an integer" % (name, key, v))
+    if v < 1:
+        raise ValueError("cfg.%s.%s = %d (at least 1)" % (name, key, v))
+    return int(v)
 
 
 def proposal_settings(cfg_or_table):
@@ -93,19 +114,10 @@ def proposal_settings(cfg_or_table):
     order = t.get("order", "y2")
     if not isinstance(order, str) or order not in ("y2", "score"):
         raise ValueError("cfg.proposals.order = %r (\"y2\" or \"score\")" % (order,))
-    caps = []
-    for k in ("pre_nms_top_n", "post_nms_top_n"):
-        v = t.get(k)
-        if v is not None:
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError("cfg.proposals.%s = %r is not an integer" % (k, v))
-            if v < 1:
-                raise ValueError("cfg.proposals.%s = %d (at least 1)" % (k, v))
-            v = int(v)
-        caps.append(v)
-    if caps[1] is not None and order != "score":
+    pre_n, post_n = (_count("proposals", k, t.get(k)) for k in ("pre_nms_top_n", "post_nms_top_n"))
+    if post_n is not None and order != "score":
         raise ValueError("cfg.proposals.post_nms_top_n needs order = \"score\": the first picks in max-y order are not the best")
-    return order, caps[0], caps[1]
+    return order, pre_n, post_n
 
 
 NMS_DEFAULTS = dict(method="hard", overlap=0.1, sigma=0.5, min_score=0.001)
@@ -127,13 +139,7 @@ def nms_settings(cfg_or_table):
     method = t.get("method", NMS_DEFAULTS["method"])
     if not isinstance(method, str) or method not in SOFT_NMS_METHODS:
         raise ValueError("cfg.nms.method = %r (\"hard\", \"linear\" or \"gaussian\")" % (method,))
-    vals = []
-    for k in ("overlap", "sigma", "min_score"):
-        v = t.get(k, NMS_DEFAULTS[k])
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError("cfg.nms.%s = %r is not a number" % (k, v))
-        vals.append(float(v))
-    overlap, sigma, min_score = vals
+    overlap, sigma, min_score = (_number("nms", k, t.get(k, NMS_DEFAULTS[k])) for k in ("overlap", "sigma", "min_score"))
     if not (0.0 < overlap <= 1.0):
         raise ValueError("cfg.nms.overlap = %r (in (0, 1])" % (overlap,))
     if not (sigma > 0.0) or math.isinf(sigma):
@@ -157,19 +163,13 @@ def box_voting_settings(cfg_or_table):
                one, also under a soft per-class NMS) or "uniform" (every voter weighs 1)
     An empty table turns voting on with the defaults.  Raises ValueError (before any device call) for an unknown key, an
     unknown weight, a bool or a non-number, and an overlap outside (0, 1]."""
-    t = cfg_or_table
-    if isinstance(t, dict) and ("box_voting" in t or "class_count" in t):     # a model's cfg
-        t = t.get("box_voting")
+    t = _settings_table(cfg_or_table, "box_voting", BOX_VOTING_DEFAULTS, optional=True)
     if t is None:
         return None
-    t = _settings_table(t, "box_voting", BOX_VOTING_DEFAULTS)
     weight = t.get("weight", BOX_VOTING_DEFAULTS["weight"])
     if not isinstance(weight, str) or weight not in BOX_VOTING_WEIGHTS:
         raise ValueError("cfg.box_voting.weight = %r (\"score\" or \"uniform\")" % (weight,))
-    v = t.get("overlap", BOX_VOTING_DEFAULTS["overlap"])
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError("cfg.box_voting.overlap = %r is not a number" % (v,))
-    overlap = float(v)
+    overlap = _number("box_voting", "overlap", t.get("overlap", BOX_VOTING_DEFAULTS["overlap"]))
     if not (0.0 < overlap <= 1.0):
         raise ValueError("cfg.box_voting.overlap = %r (in (0, 1])" % (overlap,))
     return overlap, weight
@@ -193,29 +193,16 @@ def scoring_settings(cfg_or_table):
     An empty table is "top" at 0.2: the results of the key absent, from one launch.  Raises ValueError (before any device call)
     for an unknown key, an unknown classes, a bool or a non-number, a min_confidence outside [0, 1) and a max_detections that is
     not an integer >= 1."""
-    t = cfg_or_table
-    if isinstance(t, dict) and ("scoring" in t or "class_count" in t):     # a model's cfg
-        t = t.get("scoring")
+    t = _settings_table(cfg_or_table, "scoring", SCORING_DEFAULTS, optional=True)
     if t is None:
         return None
-    t = _settings_table(t, "scoring", SCORING_DEFAULTS)
     classes = t.get("classes", SCORING_DEFAULTS["classes"])
     if not isinstance(classes, str) or classes not in SCORING_MODES:
         raise ValueError("cfg.scoring.classes = %r (\"top\" or \"all\")" % (classes,))
-    v = t.get("min_confidence", SCORING_DEFAULTS["min_confidence"])
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError("cfg.scoring.min_confidence = %r is not a number" % (v,))
-    min_confidence = float(v)
+    min_confidence = _number("scoring", "min_confidence", t.get("min_confidence", SCORING_DEFAULTS["min_confidence"]))
     if not (0.0 <= min_confidence < 1.0):
         raise ValueError("cfg.scoring.min_confidence = %r (in [0, 1))" % (min_confidence,))
-    M = t.get("max_detections")
-    if M is not None:
-        if isinstance(M, (bool, np.bool_)) or not isinstance(M, (int, np.integer)):
-            raise ValueError("cfg.scoring.max_detections = %r is not an integer" % (M,))
-        if M < 1:
-            raise ValueError("cfg.scoring.max_detections = %d (at least 1)" % M)
-        M = int(M)
-    return classes, min_confidence, M
+    return classes, min_confidence, _count("scoring", "max_detections", t.get("max_detections"))
 
 
 def scoring_rows(classes, min_confidence, ncls):

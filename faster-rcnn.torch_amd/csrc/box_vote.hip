@@ -9,9 +9,8 @@
 //   rect_out[m][t] = (sum_j w_j c_j[t]) / (sum_j w_j) over the voters; votes_out[m] = their number;
 //   fewer than two voters: rect_out[m] = c_m, bit for bit (m votes for itself through the same test as every other row)
 //
-// Arithmetic.  Membership is fp32, every operation rounded on its own (no contraction), area and IoU those of nms.hip:4-6 and
-// soft_nms.hip:  area = (x2 - x1 + 1) * (y2 - y1 + 1);  w = max(0, (xx2 + (-1) * xx1) + 1), h likewise;
-// iou = (w*h) / ((area_j + area_m) - w*h): who votes is a function of the inputs' bits.  The means are fp64: one product per
+// Arithmetic.  Membership is fp32, every operation rounded on its own (no contraction), area and IoU the box_area and box_iou of
+// box_iou.h, which nms.hip and soft_nms.hip compute theirs with: who votes is a function of the inputs' bits.  The means are fp64: one product per
 // voter and coordinate, sums in a FIXED order -- lane l of the winner's wave adds its rows l, l + 64, ... in ascending order
 // into five accumulators (the four numerators and the denominator), then a __shfl_xor butterfly (32, 16, ... 1) adds the lanes
 // -- and one division.  No atomics: a winner's result depends on its segment's data alone, not on the slot, the number of
@@ -29,6 +28,7 @@
 // rows of a segment other than int.
 #pragma clang fp contract(off)
 #include "kernels.h"
+#include "box_iou.h"
 
 namespace frcnn {
 
@@ -38,33 +38,6 @@ namespace frcnn {
 #define BV_LDS_ROWS 2048                   // largest segment staged in LDS
 #define BV_LDS_ROW_BYTES 28                // weight 8, box 16, class 4
 #define BV_MAX_GRID_X 4096                 // blocks per segment; beyond it a block takes several winner groups
-
-__device__ __forceinline__ float bv_area(float x1, float y1, float x2, float y2) {
-  float dx = x2 - x1;
-  float dy = y2 - y1;
-  dx = dx + 1.0f;
-  dy = dy + 1.0f;
-  return dx * dy;
-}
-
-__device__ __forceinline__ float bv_iou(float jx1, float jy1, float jx2, float jy2, float mx1, float my1, float mx2, float my2,
-                                        float ma) {
-  const float ja = bv_area(jx1, jy1, jx2, jy2);
-  float xx1 = jx1 > mx1 ? jx1 : mx1;
-  float yy1 = jy1 > my1 ? jy1 : my1;
-  float xx2 = jx2 < mx2 ? jx2 : mx2;
-  float yy2 = jy2 < my2 ? jy2 : my2;
-  float w = xx2 + (-1.0f) * xx1;
-  w = w + 1.0f;
-  w = w > 0.0f ? w : 0.0f;
-  float h = yy2 + (-1.0f) * yy1;
-  h = h + 1.0f;
-  h = h > 0.0f ? h : 0.0f;
-  float inter = w * h;
-  float denom = ja + ma;
-  denom = denom - inter;
-  return inter / denom;
-}
 
 // the weight of a row; a row votes only when it is finite and > 0
 __device__ __forceinline__ double bv_weight(int weight_mode, const float* __restrict__ row, int score_col) {
@@ -126,7 +99,7 @@ __global__ __launch_bounds__(BV_THREADS) void box_vote_batch_kernel(const float*
       mx1 = r[0]; my1 = r[1]; mx2 = r[2]; my2 = r[3];
       mc = cls ? cls[m] : 0;
     }
-    const float ma = bv_area(mx1, my1, mx2, my2);
+    const float ma = box_area(mx1, my1, mx2, my2);
     double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     int votes = 0;
     for (long j = lane; j < (long)n; j += BV_LANES) {
@@ -139,7 +112,7 @@ __global__ __launch_bounds__(BV_THREADS) void box_vote_batch_kernel(const float*
         jc = cls ? cls[j] : 0;
       }
       if (jc != mc) continue;
-      const float iou = bv_iou(jx1, jy1, jx2, jy2, mx1, my1, mx2, my2, ma);
+      const float iou = box_iou(jx1, jy1, jx2, jy2, box_area(jx1, jy1, jx2, jy2), mx1, my1, mx2, my2, ma);
       if (!(iou >= overlap)) continue;
       const double w = staged ? lw[j] : bv_weight(weight_mode, r, score_col);
       if (!bv_votes(w)) continue;

@@ -1,11 +1,9 @@
 // nms.hip -- nms(boxes, overlap, scores) of the reference (nms.lua:23-102; callers
 // Detector.lua:82,133) as coalesced-HBM, wavefront-ballot kernels (no MFMA: this is compare /
-// gather work).  Survivor ids are BIT-EXACT with the reference's fp32 CPU arithmetic:
-//   area  = (x2 - x1 + 1) * (y2 - y1 + 1)                      nms.lua:35
-//   w     = max(0, (xx2 + (-1)*xx1) + 1), h likewise           nms.lua:85-86
-//   IoU   = (w*h) / ((area_j + area_i) - w*h), keep IoU <= t   nms.lua:89-96
-// every operation individually rounded to fp32 -- so FMA contraction is switched off for this
-// translation unit.  Sort key dispatch (nms.lua:37-43): column / 'area' / otherwise y2.
+// gather work).  Survivor ids are BIT-EXACT with the reference's fp32 CPU arithmetic: area and IoU
+// are box_area and box_iou of box_iou.h (shared with soft_nms.hip and box_vote.hip), keep IoU <= t
+// (nms.lua:89-96), every operation individually rounded to fp32 -- so FMA contraction is switched
+// off for this translation unit.  Sort key dispatch (nms.lua:37-43): column / 'area' / otherwise y2.
 // Tie rule (TH's quicksort is unstable, tie order unpinned by the reference): ascending key,
 // ties by ascending row id, picks taken from the end.
 //
@@ -14,6 +12,7 @@
 // resolves each 64-row group sequentially with readlane and ORs kept rows into the removed set.
 #pragma clang fp contract(off)
 #include "kernels.h"
+#include "box_iou.h"
 
 namespace frcnn {
 
@@ -28,11 +27,7 @@ __device__ __forceinline__ void nms_prep_body(const float* __restrict__ boxes, i
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* b = boxes + (size_t)i * ncols;
-  float dx = b[2] - b[0];
-  float dy = b[3] - b[1];
-  dx = dx + 1.0f;
-  dy = dy + 1.0f;
-  float a = dx * dy;
+  const float a = box_area(b[0], b[1], b[2], b[3]);
   area[i] = a;
   key[i] = key_mode == 2 ? b[key_col - 1] : (key_mode == 1 ? a : b[3]);
 }
@@ -112,20 +107,7 @@ __device__ __forceinline__ void nms_mask_body(const float* __restrict__ boxes, i
   const int lim = min(64, n - cb * 64);
   for (int c = 0; c < lim; ++c) {
     if (cb * 64 + c <= rpos) continue;
-    float xx1 = cx1[c] > ix1 ? cx1[c] : ix1;  // cmax, nms.lua:78
-    float yy1 = cy1[c] > iy1 ? cy1[c] : iy1;
-    float xx2 = cx2[c] < ix2 ? cx2[c] : ix2;  // cmin, nms.lua:80
-    float yy2 = cy2[c] < iy2 ? cy2[c] : iy2;
-    float w = xx2 + (-1.0f) * xx1;
-    w = w + 1.0f;
-    w = w > 0.0f ? w : 0.0f;
-    float h = yy2 + (-1.0f) * yy1;
-    h = h + 1.0f;
-    h = h > 0.0f ? h : 0.0f;
-    float inter = w * h;
-    float denom = car[c] + iar;
-    denom = denom - inter;
-    float iou = inter / denom;
+    const float iou = box_iou(cx1[c], cy1[c], cx2[c], cy2[c], car[c], ix1, iy1, ix2, iy2, iar);
     if (!(iou <= thr) && ccl[c] == icl) bits |= 1ull << c;
   }
   mask[(size_t)rpos * nw + cb] = bits;

@@ -15,9 +15,8 @@
 //             gaussian  (every j)     s[j] = s[j] * expf(-(iou * iou) / sigma)  log domain: s[j] - (iou * iou) / sigma
 //             then      !(s[j] >= min_score): j dies
 //
-// Arithmetic: fp32, every operation rounded on its own (no contraction, as in nms.hip), area and IoU those of nms.hip:4-6:
-//   area = (x2 - x1 + 1) * (y2 - y1 + 1);  w = max(0, (xx2 + (-1) * xx1) + 1), h likewise;  iou = (w*h) / ((area_j + area_m) - w*h).
-// hard, linear outside the log domain and gaussian inside it contain no transcendental: their results are a function of the
+// Arithmetic: fp32, every operation rounded on its own (no contraction, as in nms.hip), area and IoU the box_area and box_iou of
+// box_iou.h, which nms.hip computes its own with.  hard, linear outside the log domain and gaussian inside it contain no transcendental: their results are a function of the
 // inputs' bits alone.  The scores are plain loads, stores and arithmetic; there is no atomic of any kind in this file, and a
 // row's score is only ever read and written by the one thread that owns the row.
 //
@@ -40,6 +39,7 @@
 //                                 working scores in the workspace (owner-only, so no fence is needed).
 #pragma clang fp contract(off)
 #include "kernels.h"
+#include "box_iou.h"
 
 namespace frcnn {
 
@@ -76,31 +76,10 @@ __device__ __forceinline__ unsigned snms_wave_max(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-__device__ __forceinline__ float snms_area(float x1, float y1, float x2, float y2) {
-  float dx = x2 - x1;
-  float dy = y2 - y1;
-  dx = dx + 1.0f;
-  dy = dy + 1.0f;
-  return dx * dy;
-}
-
 // the score of row j (box j*, area ja) after the pick of box m*: the new working score, a NaN when the row dies
 __device__ __forceinline__ float snms_decay(const SnmsParams& P, float s, float jx1, float jy1, float jx2, float jy2, float ja,
                                             float mx1, float my1, float mx2, float my2, float ma) {
-  float xx1 = jx1 > mx1 ? jx1 : mx1;
-  float yy1 = jy1 > my1 ? jy1 : my1;
-  float xx2 = jx2 < mx2 ? jx2 : mx2;
-  float yy2 = jy2 < my2 ? jy2 : my2;
-  float w = xx2 + (-1.0f) * xx1;
-  w = w + 1.0f;
-  w = w > 0.0f ? w : 0.0f;
-  float h = yy2 + (-1.0f) * yy1;
-  h = h + 1.0f;
-  h = h > 0.0f ? h : 0.0f;
-  float inter = w * h;
-  float denom = ja + ma;
-  denom = denom - inter;
-  float iou = inter / denom;
+  const float iou = box_iou(jx1, jy1, jx2, jy2, ja, mx1, my1, mx2, my2, ma);
   const float dead = __builtin_nanf("");
   if (P.method == 2) {
     float t = iou * iou;
@@ -135,7 +114,7 @@ __device__ __forceinline__ void snms_wave_body(const float* __restrict__ boxes, 
     if (i < n) {
       const float* b = boxes + (size_t)i * ncols;
       x1[k] = b[0]; y1[k] = b[1]; x2[k] = b[2]; y2[k] = b[3];
-      ar[k] = snms_area(x1[k], y1[k], x2[k], y2[k]);
+      ar[k] = box_area(x1[k], y1[k], x2[k], y2[k]);
       cl[k] = cls ? cls[i] : 0;
       const float v = b[score_col - 1];
       s[k] = v >= P.min_score ? v : __builtin_nanf("");
@@ -237,7 +216,7 @@ __device__ __forceinline__ void snms_group_body(const float* __restrict__ boxes,
             const float* b = boxes + (size_t)i * ncols;
             jx1 = b[0]; jy1 = b[1]; jx2 = b[2]; jy2 = b[3];
           }
-          s = snms_decay(P, s, jx1, jy1, jx2, jy2, snms_area(jx1, jy1, jx2, jy2), mx1, my1, mx2, my2, ma);
+          s = snms_decay(P, s, jx1, jy1, jx2, jy2, box_area(jx1, jy1, jx2, jy2), mx1, my1, mx2, my2, ma);
           sc[i] = s;
           if (!(s == s)) continue;
         }
@@ -266,7 +245,7 @@ __device__ __forceinline__ void snms_group_body(const float* __restrict__ boxes,
       mx1 = b[0]; my1 = b[1]; mx2 = b[2]; my2 = b[3];
       mc = cls ? cls[m] : 0;
     }
-    ma = snms_area(mx1, my1, mx2, my2);
+    ma = box_area(mx1, my1, mx2, my2);
     if ((m & (SNMS_THREADS - 1)) == tid) {   // the owner: records the pick and retires the row
       pick[cnt] = (long long)m + 1;
       if (score_out) score_out[(size_t)m * score_stride] = sc[m];
