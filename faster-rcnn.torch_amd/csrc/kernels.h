@@ -239,6 +239,11 @@ int linear_x_wgrad(const void* GpT, const void* XpT, int R, int O, int I, float*
 
 
 // ---------------------------------------------------------------- roi (roi.hip)
+// wins: device int[R][4] {row_lo, row_hi, col_lo, col_hi}, 1-based inclusive.  Every window must lie inside the map
+// (1 <= lo <= hi <= H or W): the kernels do not clip, a window outside is an out-of-bounds read.  out / idx rows [C][kh][kw];
+// the first maximum in row-major order wins (strict >), idx = y * W + x in map coordinates, and idx = -1 where nothing exceeds
+// -FLT_MAX (backward skips such an entry, and a zero gout entry).  idx may be NULL (inference).  backward ACCUMULATES:
+// gmap += scatter(gout), the map already holds the anchor nets' contributions.  R <= 0: nothing is launched.
 int roi_pool_forward(const float* fmap, int C, int H, int W, const int* wins, int R, int kh, int kw,
                      float* out, int* idx, hipStream_t s);
 int roi_pool_backward(float* gmap, int C, int H, int W, const float* gout, const int* idx, int R,
