@@ -556,23 +556,26 @@ int frcnn_linear_backward(const float* x, const float* gy, int R, int I, const f
   return FRCNN_OK;
 }
 
+// optim.rmsprop (main.lua:122,133)
 int frcnn_rmsprop(float* x, const float* g, float* m, long long n, float lr, float alpha, float eps,
                   void* stream) {
-  return rmsprop_step(x, const_cast<float*>(g), m, n, lr, alpha, eps, 1.f, false, S(stream));
+  FR_CHECK(n >= 0, "frcnn_rmsprop: bad length %lld", n);
+  return rmsprop_update(x, const_cast<float*>(g), m, 0, n, false, 1.f, nullptr, lr, alpha, eps, S(stream));   // unscaled: g is only read
 }
-
 int frcnn_scale_rmsprop(float* x, float* g, float gscale, float* m, long long n, float lr, float alpha, float eps,
                         void* stream) {
-  return rmsprop_step(x, g, m, n, lr, alpha, eps, gscale, true, S(stream));
+  FR_CHECK(n >= 0, "frcnn_scale_rmsprop: bad length %lld", n);
+  return rmsprop_update(x, g, m, 0, n, false, gscale, nullptr, lr, alpha, eps, S(stream));
 }
 int frcnn_scale_rmsprop_slice(float* x, float* g, float gscale, float* m, long long lo, long long hi, float lr, float alpha,
                               float eps, void* stream) {
-  return rmsprop_slice(x, g, m, lo, hi, lr, alpha, eps, gscale, gscale != 1.0f, S(stream));
+  return rmsprop_update(x, g, m, lo, hi, true, gscale, nullptr, lr, alpha, eps, S(stream));
 }
 int frcnn_scale_rmsprop_dev(float* x, float* g, const double* gcount_dev, float* m, long long n, float lr, float alpha,
                             float eps, void* stream) {
   FR_CHECK(gcount_dev, "frcnn_scale_rmsprop_dev: NULL divisor");
-  return rmsprop_step(x, g, m, n, lr, alpha, eps, 1.f, true, S(stream), gcount_dev);
+  FR_CHECK(n >= 0, "frcnn_scale_rmsprop_dev: bad length %lld", n);
+  return rmsprop_update(x, g, m, 0, n, false, 1.f, gcount_dev, lr, alpha, eps, S(stream));
 }
 
 // optim.sgd / optim.nag (main.lua:122-124,134-135)
@@ -598,7 +601,7 @@ int frcnn_nag_slice(float* x, float* g, float* v, long long lo, long long hi, fl
 int frcnn_scale_rmsprop_slice_dev(float* x, float* g, const double* gcount_dev, float* m, long long lo, long long hi, float lr,
                                   float alpha, float eps, void* stream) {
   FR_CHECK(gcount_dev, "frcnn_scale_rmsprop_slice_dev: NULL divisor");
-  return rmsprop_slice(x, g, m, lo, hi, lr, alpha, eps, 1.f, true, S(stream), gcount_dev);
+  return rmsprop_update(x, g, m, lo, hi, true, 1.f, gcount_dev, lr, alpha, eps, S(stream));
 }
 int frcnn_sgd_slice_dev(float* x, float* g, float* v, long long lo, long long hi, const double* gcount_dev, float clr, float wd,
                         float mom, float one_minus_damp, int nesterov, int first, void* stream) {

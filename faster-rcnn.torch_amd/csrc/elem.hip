@@ -584,114 +584,33 @@ int dropout_mask(float* mask, long n, float p, unsigned long long seed, hipStrea
   return FRCNN_OK;
 }
 
-// ---------------------------------------------------------------- optim.rmsprop
-// m = alpha*m + (1-alpha)*g*g ; x -= lr * g / (sqrt(m) + eps).  5 streams of n floats: HBM-bound.
-// SCALE: g is first multiplied by gscale and written back (gradient:div(n), objective.lua:200, folded into the
-// optimiser's pass over the flat vectors: 6 streams instead of 2 + 5).
-// one element of the update: shared by the whole-vector kernel and the slice kernel, so that an update applied slice by slice
-// (frcnn_scale_rmsprop_slice: beside the backward pass, as slices of the gradient become final) leaves the same bits as one
-// pass over the whole vector wherever a slice boundary falls inside a 16-byte group
-template <bool SCALE>
-__device__ __forceinline__ void rmsprop_one(float& x, float& g, float& m, float lr, float alpha, float oma, float eps, float gscale) {
-#pragma clang fp contract(off)   // every operation rounded by itself: the same bits from either instantiation and either kernel
-  if (SCALE) g *= gscale;
-  m = alpha * m + oma * (g * g);
-  x = x - lr * g / (sqrtf(m) + eps);
-}
-template <bool SCALE>
-__device__ __forceinline__ void rmsprop_four(float4* x4, float4* g4, float4* m4, long i, float lr, float alpha, float oma, float eps, float gscale) {
-  float4 xv = x4[i], gv = g4[i], mv = m4[i];
-  rmsprop_one<SCALE>(xv.x, gv.x, mv.x, lr, alpha, oma, eps, gscale);
-  rmsprop_one<SCALE>(xv.y, gv.y, mv.y, lr, alpha, oma, eps, gscale);
-  rmsprop_one<SCALE>(xv.z, gv.z, mv.z, lr, alpha, oma, eps, gscale);
-  rmsprop_one<SCALE>(xv.w, gv.w, mv.w, lr, alpha, oma, eps, gscale);
-  if (SCALE) g4[i] = gv;
-  m4[i] = mv;
-  x4[i] = xv;
-}
-template <bool SCALE>
-__device__ __forceinline__ void rmsprop_scalar(float* x, float* g, float* m, long i, float lr, float alpha, float oma, float eps, float gscale) {
-  float xi = x[i], gi = g[i], mi = m[i];
-  rmsprop_one<SCALE>(xi, gi, mi, lr, alpha, oma, eps, gscale);
-  if (SCALE) g[i] = gi;
-  m[i] = mi;
-  x[i] = xi;
-}
-
-template <bool SCALE>
-__global__ void rmsprop_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ m,
-                               long n, float lr, float alpha, float eps, float gscale,
-                               const double* __restrict__ gcount) {
-  // gcount: the divisor of gradient:div (objective.lua:200) read from the device -- the all-reduced example count of a
-  // data-parallel step, which no host has seen yet (a count of 0 leaves the gradient as it is)
-  if (SCALE && gcount) { const double c = *gcount; gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }
-  const long n4 = n >> 2;
-  float4* x4 = reinterpret_cast<float4*>(x);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* m4 = reinterpret_cast<float4*>(m);
-  const float oma = 1.0f - alpha;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
-    rmsprop_four<SCALE>(x4, g4, m4, i, lr, alpha, oma, eps, gscale);
-  for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x)
-    rmsprop_scalar<SCALE>(x, g, m, i, lr, alpha, oma, eps, gscale);
-}
-
-// elements [lo, hi) of 16-byte aligned vectors: 16-byte groups where the slice covers them whole, the up to three elements
-// in front of the first and behind the last such group one by one (thread t < 8 of block 0)
-template <bool SCALE>
-__global__ void rmsprop_slice_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ m, long lo, long hi,
-                                     float lr, float alpha, float eps, float gscale, const double* __restrict__ gcount) {
-  if (SCALE && gcount) { const double c = *gcount; gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }   // as rmsprop_kernel
-  const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);   // [lo, a) ragged | [a, b) whole groups | [b, hi) ragged
-  const long n4 = (b - a) >> 2;
-  float4* x4 = reinterpret_cast<float4*>(x + a);
-  float4* g4 = reinterpret_cast<float4*>(g + a);
-  float4* m4 = reinterpret_cast<float4*>(m + a);
-  const float oma = 1.0f - alpha;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
-    rmsprop_four<SCALE>(x4, g4, m4, i, lr, alpha, oma, eps, gscale);
-  if (blockIdx.x == 0 && threadIdx.x < 8) {
-    const int t = threadIdx.x;
-    const long i = t < 4 ? lo + t : b + (t - 4);
-    if (t < 4 ? i < a : i < hi) rmsprop_scalar<SCALE>(x, g, m, i, lr, alpha, oma, eps, gscale);
-  }
-}
-int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, float alpha, float eps, float gscale, bool scale_first,
-                  hipStream_t s, const double* gcount_dev) {
-  FR_CHECK((((uintptr_t)x | (uintptr_t)g | (uintptr_t)m) & 15) == 0, "rmsprop_slice: the vectors must be 16-byte aligned");
-  FR_CHECK(lo >= 0 && lo <= hi, "rmsprop_slice: bad range [%ld, %ld)", lo, hi);
-  if (lo == hi) return FRCNN_OK;
-  const long n = hi - lo;
-  // half the wave slots at most: a slice update runs BESIDE other launches (the backward pass) and must not keep them waiting for slots
-  int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 1024);
-  if (scale_first)
-    FR_LAUNCH(KC_OPTIM, 0, n * 24.0, s, rmsprop_slice_kernel<true>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, gscale, gcount_dev);
-  else
-    FR_LAUNCH(KC_OPTIM, 0, n * 20.0, s, rmsprop_slice_kernel<false>, dim3(grid), dim3(256), 0, x, g, m, lo, hi, lr, alpha, eps, 1.f, (const double*)nullptr);
-  FR_LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-int rmsprop_step(float* x, float* g, float* m, long n, float lr, float alpha, float eps, float gscale,
-                 bool scale_first, hipStream_t s, const double* gcount_dev) {
-  FR_CHECK((((uintptr_t)x | (uintptr_t)g | (uintptr_t)m) & 15) == 0, "rmsprop_step: buffers must be 16-byte aligned");
-  int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 2048);
-  if (scale_first)
-    FR_LAUNCH(KC_OPTIM, 0, n * 24.0, s, rmsprop_kernel<true>, dim3(grid), dim3(256), 0, x, g, m, n, lr, alpha, eps, gscale, gcount_dev);
-  else
-    FR_LAUNCH(KC_OPTIM, 0, n * 20.0, s, rmsprop_kernel<false>, dim3(grid), dim3(256), 0, x, g, m, n, lr, alpha, eps, 1.f, (const double*)nullptr);
-  FR_LAUNCH_CHECK();
-  return FRCNN_OK;
-}
-
-// ---------------------------------------------------------------- optim.sgd / optim.nag
-// The two optimisers main.lua:122-124,134-135 keeps one comment away from optim.rmsprop, one element of each as one inline
-// function shared by the whole-vector kernel and the slice kernel (the same bit-for-bit contract as rmsprop_one), every Lua
-// statement one separately rounded fp32 operation.  x = weights, g = the gradient the objective returned, v = state.dfdx.
-// The variants are template parameters, not per-element branches; the gradient is written back only where Torch leaves
-// something else in it than it was handed (the scale of gradient:div, weight decay, Nesterov's look-ahead term).
+// ---------------------------------------------------------------- optim.rmsprop / optim.sgd / optim.nag
+// The three optimisers of main.lua:122-124,133-135 on the flat vectors: HBM-bound passes of 3 to 6 fp32 streams.
+// x = weights, g = the gradient the objective returned, v = the optimiser's state (rmsprop's m, state.dfdx of sgd and nag).
+// The contract, stated once:
+//   - one element of each update is ONE inline function (an Op's operator()), every Lua statement one separately rounded
+//     fp32 operation (fp contract off), its variants template parameters and not per-element branches;
+//   - ONE kernel, optim_kernel<Op>, applies it to any range [lo, hi) of 16-byte aligned vectors, and the whole vector is the
+//     range [0, n) of that kernel.  So an update applied slice by slice (beside the backward pass, as slices of the gradient
+//     become final) leaves the same bits as one pass over the whole vector, wherever a slice boundary falls.
+// kScale: g is first multiplied by gscale (gradient:div(n), objective.lua:200, folded into the optimiser's pass: 6 streams
+// instead of 2 + 5).  The gradient is written back only where Torch leaves something else in it than it was handed (that
+// scale, weight decay, Nesterov's look-ahead term).
 //
+// optim.rmsprop:  g *= gscale ; m = alpha*m + (1-alpha)*g*g ; x -= lr * g / (sqrt(m) + eps).  m travels as v.
+template <bool SCALE>
+struct RmspropOp {
+  static constexpr bool kScale = SCALE, kReadV = true, kWriteV = true, kWriteG = SCALE;
+  static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV;   // fp32 streams moved per element
+  float gscale, lr, alpha, oma, eps;   // oma = 1 - alpha
+  __device__ __forceinline__ void operator()(float& x, float& g, float& m) const {
+#pragma clang fp contract(off)   // every operation rounded by itself: the same bits from every instantiation
+    if (SCALE) g *= gscale;
+    m = alpha * m + oma * (g * g);
+    x = x - lr * g / (sqrtf(m) + eps);
+  }
+};
+
 // optim.sgd:  g *= gscale ; g += wd*x ; v = g (first step) | v = v*mom + (1-damp)*g ; g += mom*v (nesterov) ; x += -clr*dir
 // MOM: 0 = no momentum (v untouched, may be NULL), 1 = the first step (v = copy(g)), 2 = later steps
 template <bool SCALE, bool WD, int MOM, bool NEST>
@@ -753,27 +672,15 @@ __device__ __forceinline__ void optim_scalar(float* x, float* g, float* v, long 
   x[i] = xi;
 }
 
-// the whole vector: 16-byte groups grid-stride, then the up to three tail elements; gcount as in rmsprop_kernel
+// elements [lo, hi) of 16-byte aligned vectors: 16-byte groups grid-stride where the range covers them whole, the up to three
+// elements in front of the first and behind the last such group one by one (thread t < 8 of block 0)
 template <class Op>
-__global__ void optim_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long n, Op op,
+__global__ void optim_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long lo, long hi, Op op,
                              const double* __restrict__ gcount) {
+  // gcount: the divisor of gradient:div (objective.lua:200) read from the device -- the all-reduced example count of a
+  // data-parallel step, which no host has seen yet (a count of 0 leaves the gradient as it is)
   if (Op::kScale && gcount) { const double c = *gcount; op.gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }
-  const long n4 = n >> 2;
-  float4* x4 = reinterpret_cast<float4*>(x);
-  float4* g4 = reinterpret_cast<float4*>(g);
-  float4* v4 = reinterpret_cast<float4*>(v);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
-    optim_four(x4, g4, v4, i, op);
-  for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    optim_scalar(x, g, v, i, op);
-}
-
-// elements [lo, hi): the split of rmsprop_slice_kernel (whole 16-byte groups grid-stride, ragged ends by block 0)
-template <class Op>
-__global__ void optim_slice_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long lo, long hi, Op op,
-                                   const double* __restrict__ gcount) {
-  if (Op::kScale && gcount) { const double c = *gcount; op.gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }   // as optim_kernel
-  const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);
+  const long a = min(hi, (lo + 3) & ~3L), b = max(a, hi & ~3L);   // [lo, a) ragged | [a, b) whole groups | [b, hi) ragged
   const long n4 = (b - a) >> 2;
   float4* x4 = reinterpret_cast<float4*>(x + a);
   float4* g4 = reinterpret_cast<float4*>(g + a);
@@ -791,7 +698,7 @@ namespace {
 struct OptimRange {
   float* x; float* g; float* v;
   long lo, hi;
-  bool slice;             // slice kernel (grid capped: it runs beside the backward pass) or the whole vector [0, hi)
+  bool slice;             // a slice beside the backward pass (its grid capped lower) or the whole vector [0, hi)
   const double* gcount;   // the divisor on the device (NULL: the host's gscale)
   hipStream_t s;
 };
@@ -801,13 +708,9 @@ int optim_launch(const Op& op, const OptimRange& r) {
   const long n = r.hi - r.lo;
   if (n == 0) return FRCNN_OK;
   const double bytes = 4.0 * Op::kStreams * n;
-  if (r.slice) {
-    int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 1024);   // half the wave slots, as rmsprop_slice
-    FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_slice_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op, r.gcount);
-  } else {
-    int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), 2048);
-    FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, n, op, r.gcount);
-  }
+  // a slice takes half the wave slots at most: it runs BESIDE other launches (the backward pass) and must not keep them waiting for slots
+  const int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), r.slice ? 1024 : 2048);
+  FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op, r.gcount);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
@@ -836,6 +739,15 @@ int optim_check(const char* what, const OptimRange& r, bool uses_v) {
   return FRCNN_OK;
 }
 }  // namespace
+
+int rmsprop_update(float* x, float* g, float* m, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float lr,
+                   float alpha, float eps, hipStream_t s) {
+  const OptimRange r{x, g, m, lo, hi, slice, gcount_dev, s};
+  FR_TRY(optim_check("rmsprop", r, true));
+  const float oma = 1.0f - alpha;
+  if (r.gcount || gscale != 1.f) return optim_launch(RmspropOp<true>{gscale, lr, alpha, oma, eps}, r);
+  return optim_launch(RmspropOp<false>{1.f, lr, alpha, oma, eps}, r);
+}
 
 int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s) {
@@ -974,7 +886,7 @@ __global__ __launch_bounds__(256) void grad_clip_finish_kernel(const double* __r
   const double S = block_sum_d(v, sh);
   if (threadIdx.x == 0) {
     double D = divisor_dev ? *divisor_dev : divisor;
-    if (!(D > 0.0)) D = 1.0;                                 // (a count of 0 leaves the gradient as it is: rmsprop_kernel)
+    if (!(D > 0.0)) D = 1.0;                                 // (a count of 0 leaves the gradient as it is: optim_kernel)
     const double norm = __ddiv_rn(__dsqrt_rn(S), D);
     const bool finite = S < __builtin_huge_val();            // false for +inf and for NaN (S is a sum of squares: never negative)
     double Dc = D;

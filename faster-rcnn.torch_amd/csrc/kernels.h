@@ -152,14 +152,11 @@ int col2im_positions_add(const float* col, int C, int H, int W, int k, int Wo, c
 // per-channel Bernoulli keep mask (nn.SpatialDropout, model_utilities.lua:10-12): scale[c] in {0,1}
 int dropout_channel_mask(float* scale, int C, float p, unsigned long long seed, hipStream_t s);
 int fill_value(float* x, long n, float v, hipStream_t s);
-int rmsprop_step(float* x, float* g, float* m, long n, float lr, float alpha, float eps, float gscale,
-                 bool scale_first, hipStream_t s, const double* gcount_dev = nullptr);
-// the same step on elements [lo, hi) only (any bounds; the vectors' bases 16-byte aligned): bit-identical to what rmsprop_step
-// leaves in those elements
-int rmsprop_slice(float* x, float* g, float* m, long lo, long hi, float lr, float alpha, float eps, float gscale, bool scale_first,
-                  hipStream_t s, const double* gcount_dev = nullptr);
-// optim.sgd / optim.nag (main.lua:122-124,134-135) on elements [lo, hi) (slice: the slice kernel, any bounds) or on the whole
-// vector [0, hi) (lo = 0); gcount_dev: the divisor of gradient:div read on the device (either form).  gscale = 1 and no gcount_dev: g unscaled.
+// optim.rmsprop / optim.sgd / optim.nag (main.lua:122-124,133-135) on elements [lo, hi) of 16-byte aligned vectors, any bounds:
+// one kernel for every range, so a slice gets the bits the whole vector [0, hi) would give it.  slice: the update runs beside
+// the backward pass (a smaller grid).  gcount_dev: the divisor of gradient:div read on the device.  gscale = 1 and no gcount_dev: g unscaled.
+int rmsprop_update(float* x, float* g, float* m, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float lr,
+                   float alpha, float eps, hipStream_t s);
 int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s);
 int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,

@@ -476,7 +476,7 @@ int frcnn_rmsprop(float *x, const float *g, float *m, long long n, float lr, flo
                   float eps, void *stream);
 /* frcnn_scale(g, n, gscale) followed by frcnn_rmsprop in ONE pass over the flat vectors: gradient:div(n)
  * (objective.lua:200) folded into the optimiser step that follows it in main.lua:133.  g holds the scaled
- * gradient afterwards, exactly as after the two separate calls. */
+ * gradient afterwards, exactly as after the two separate calls (gscale = 1: the gradient is left unscaled). */
 int frcnn_scale_rmsprop(float *x, float *g, float gscale, float *m, long long n, float lr, float alpha,
                         float eps, void *stream);
 /* The same with the divisor read from the device: gscale = 1 / *gcount_dev (a count of 0 leaves g unscaled).  For the

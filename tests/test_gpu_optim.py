@@ -1,5 +1,6 @@
 """optim.sgd and optim.nag (main.lua:122-124 sgd_state / nag_state, main.lua:134-135) on the device: frcnn_sgd / frcnn_nag and
-their slice forms, the look-ahead, the folded gradient:div (objective.lua:200) and the Python optimisers F.sgd / F.nag.
+their slice forms, the look-ahead, the folded gradient:div (objective.lua:200) and the Python optimisers F.sgd / F.nag; and
+optim.rmsprop's kernel (main.lua:133), which runs through the same range kernel as those two.
 
 The reference is a numpy fp32 restatement of Torch's optim functions: one separately rounded numpy operation per Lua statement
 (numpy never contracts to FMA), host scalars in double as Lua computes them, passed as fp32.  Comparisons are bit for bit,
@@ -74,6 +75,18 @@ def ref_nag(x, g, v, gscale, s, first):
     return x, g, v
 
 
+RMS = dict(lr=1e-3, alpha=0.9, eps=1e-8)
+
+
+def ref_rmsprop(x, g, m, gscale, s, first=None):
+    """optim.rmsprop after opfunc: -> x, g, m (fp32 divide and square root are correctly rounded, here and on the device)"""
+    if gscale is not None:
+        g = g * f32(gscale)                          # gradient:div(n)
+    m = f32(s["alpha"]) * m + (f32(1) - f32(s["alpha"])) * (g * g)
+    x = x - f32(s["lr"]) * g / (np.sqrt(m) + f32(s["eps"]))
+    return x, g, m
+
+
 def same_bits(a, b):
     a = np.ascontiguousarray(a, dtype=np.float32); b = np.ascontiguousarray(b, dtype=np.float32)
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
@@ -106,6 +119,20 @@ def _nag_call(F, x, g, v, gscale, s, first, gcount=None, lo=None, hi=None):
         F._lib.call("frcnn_nag", F.ptr(x), F.ptr(g), F.ptr(v), x.numel(), gscale, F.ptr(gcount), s["clr"], *args, F.stream_ptr())
     else:
         F._lib.call("frcnn_nag_slice", F.ptr(x), F.ptr(g), F.ptr(v), lo, hi, gscale, s["clr"], *args, F.stream_ptr())
+
+
+def _rmsprop_call(F, x, g, m, gscale, s, first=None, gcount=None, lo=None, hi=None, unscaled_entry=False):
+    args = (s["lr"], s["alpha"], s["eps"], F.stream_ptr())
+    if unscaled_entry:
+        F._lib.call("frcnn_rmsprop", F.ptr(x), F.ptr(g), F.ptr(m), x.numel(), *args)
+    elif lo is None and gcount is None:
+        F._lib.call("frcnn_scale_rmsprop", F.ptr(x), F.ptr(g), gscale, F.ptr(m), x.numel(), *args)
+    elif lo is None:
+        F._lib.call("frcnn_scale_rmsprop_dev", F.ptr(x), F.ptr(g), F.ptr(gcount), F.ptr(m), x.numel(), *args)
+    elif gcount is None:
+        F._lib.call("frcnn_scale_rmsprop_slice", F.ptr(x), F.ptr(g), gscale, F.ptr(m), lo, hi, *args)
+    else:
+        F._lib.call("frcnn_scale_rmsprop_slice_dev", F.ptr(x), F.ptr(g), F.ptr(gcount), F.ptr(m), lo, hi, *args)
 
 
 def _host(t):
@@ -166,6 +193,61 @@ def test_nag_kernel_matches_the_restatement(F, name, gscale, n):
         assert same_bits(_host(v), v_ref), "v after step %d" % k
 
 
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1_000_003])
+@pytest.mark.parametrize("gscale", [1.0 / 41.0, 1.0])
+def test_rmsprop_kernel_matches_the_restatement(F, gscale, n):
+    """three consecutive steps from m = 0 (as optim.rmsprop creates it): x, g and m bit for bit from frcnn_scale_rmsprop, and
+    from frcnn_rmsprop where the gradient is unscaled; a scale of exactly 1 leaves g's bits alone"""
+    entries = (False,) if gscale != 1.0 else (False, True)      # frcnn_scale_rmsprop | frcnn_rmsprop
+    rng = np.random.RandomState(n % 1000 + 13)
+    x_ref = rng.randn(n).astype(np.float32)
+    m_ref = np.zeros(n, np.float32)
+    xs = [_dev(x_ref) for _ in entries]
+    ms = [_dev(m_ref) for _ in entries]
+    for k in range(3):
+        g_in = _gradient(rng, n)
+        x_ref, g_ref, m_ref = ref_rmsprop(x_ref, g_in, m_ref, gscale if gscale != 1.0 else None, RMS)
+        for x, m, unscaled_entry in zip(xs, ms, entries):
+            g = _dev(g_in)
+            _rmsprop_call(F, x, g, m, gscale, RMS, unscaled_entry=unscaled_entry)
+            what = "frcnn_rmsprop" if unscaled_entry else "frcnn_scale_rmsprop"
+            assert same_bits(_host(x), x_ref), "x after step %d of %s" % (k, what)
+            assert same_bits(_host(g), g_ref), "g after step %d of %s" % (k, what)
+            assert same_bits(_host(m), m_ref), "m after step %d of %s" % (k, what)
+            if gscale == 1.0:
+                assert same_bits(_host(g), g_in), "g changed by step %d of %s" % (k, what)
+
+
+@pytest.mark.parametrize("form", ["whole", "slice"])
+@pytest.mark.parametrize("opt", ["rmsprop", "sgd_main_lua"])
+def test_a_grid_that_wraps_matches_the_restatement(F, opt, form):
+    """the grid-stride loop takes a second turn: one block's worth of 16-byte groups above the grid's cap (2048 blocks for the
+    whole vector, 1024 for a slice), a three-element tail on the whole vector, ragged ends on both sides of the slice.
+    x, g and v bit for bit against the restatement inside the range, untouched outside it"""
+    n = 4 * (2048 * 256 + 256) + 3
+    lo, hi = (0, n) if form == "whole" else (5, 5 + 3 + 4 * (1024 * 256 + 256) + 2)
+    rng = np.random.RandomState(17)
+    x0 = rng.randn(n).astype(np.float32); g0 = _gradient(rng, n); v0 = rng.rand(n).astype(np.float32)
+    gscale = 1.0 / 41.0
+    if opt == "rmsprop":
+        s, call, ref = RMS, _rmsprop_call, ref_rmsprop
+    else:
+        s, call, ref = sgd_scalars(MAIN_SGD, 4), _sgd_call, ref_sgd
+    x, g, v = _dev(x0), _dev(g0), _dev(v0)
+    if form == "whole":
+        call(F, x, g, v, gscale, s, False)
+    else:
+        call(F, x, g, v, gscale, s, False, lo=lo, hi=hi)
+    want = [a.copy() for a in (x0, g0, v0)]
+    for w, r in zip(want, ref(x0[lo:hi], g0[lo:hi], v0[lo:hi], gscale, s, False)):
+        w[lo:hi] = r
+    for t, w, a0, what in zip((x, g, v), want, (x0, g0, v0), ("x", "g", "v")):
+        got = _host(t)
+        assert same_bits(got[lo:hi], w[lo:hi]), "%s differs from the restatement" % what
+        assert same_bits(got[:lo], a0[:lo]) and same_bits(got[hi:], a0[hi:]), "%s changed outside [%d, %d)" % (what, lo, hi)
+    assert not same_bits(_host(x)[lo:hi], x0[lo:hi])
+
+
 def test_nag_first_step_adds_to_a_literal_zero(F):
     """fill(0):add(-clr, dfdx): a zero gradient leaves +0 in v (0 + -0), never -0"""
     import torch
@@ -176,12 +258,12 @@ def test_nag_first_step_adds_to_a_literal_zero(F):
     assert same_bits(_host(v), np.zeros(8, np.float32)) and same_bits(_host(x), np.ones(8, np.float32))
 
 
-@pytest.mark.parametrize("opt", ["sgd_main_lua", "sgd_nesterov", "nag_main_lua", "nag_wd"])
+@pytest.mark.parametrize("opt", ["sgd_main_lua", "sgd_nesterov", "nag_main_lua", "nag_wd", "rmsprop"])
 def test_slices_tile_the_whole_vector_bit_for_bit(F, opt):
     """the slice form over a partition with ragged bounds (inside 16-byte groups, empty, shorter than a group) == the whole-vector
     form: x, g and v bit for bit, on the first step and on a later one, with and without the folded scale"""
     import torch
-    kind, name = opt.split("_", 1)
+    kind, _, name = opt.partition("_")
     n = 1_000_003
     rng = np.random.RandomState(5)
     x0 = _dev(rng.randn(n)); v0 = _dev(rng.rand(n))
@@ -191,8 +273,10 @@ def test_slices_tile_the_whole_vector_bit_for_bit(F, opt):
             g0 = _dev(_gradient(rng, n))
             if kind == "sgd":
                 s, call = sgd_scalars(SGD_CFGS[name], 0 if first else 4), _sgd_call
-            else:
+            elif kind == "nag":
                 s, call = nag_scalars(NAG_CFGS[name], 0 if first else 4), _nag_call
+            else:
+                s, call = RMS, _rmsprop_call         # (no first step of its own: both rounds are later steps)
             a = [t.clone() for t in (x0, g0, v0)]
             b = [t.clone() for t in (x0, g0, v0)]
             call(F, a[0], a[1], a[2], gscale, s, first)
@@ -224,6 +308,33 @@ def test_slice_and_whole_reject_bad_arguments(F):
     # mom = 0: no momentum vector needed
     F._lib.call("frcnn_sgd", F.ptr(x), F.ptr(g), None, 8, 1.0, None, 0.1, 0.0, 0.0, 1.0, 0, 0, F.stream_ptr())
     torch.cuda.synchronize()
+    # optim.rmsprop: every form refuses the same malformed calls, and refuses them before anything is written
+    rng = np.random.RandomState(2)
+    kept = [rng.randn(64).astype(np.float32), _gradient(rng, 64), rng.rand(64).astype(np.float32)]
+    x, g, m = (_dev(a) for a in kept)
+    cnt = torch.tensor([41.0], dtype=torch.float64, device="cuda")
+    off = C.c_void_p(x.data_ptr() + 4)
+    tail = (RMS["lr"], RMS["alpha"], RMS["eps"], F.stream_ptr())
+    whole = {"frcnn_rmsprop": lambda x_, m_, n: (x_, F.ptr(g), m_, n),
+             "frcnn_scale_rmsprop": lambda x_, m_, n: (x_, F.ptr(g), 1.0 / 41.0, m_, n),
+             "frcnn_scale_rmsprop_dev": lambda x_, m_, n: (x_, F.ptr(g), F.ptr(cnt), m_, n)}
+    sliced = {"frcnn_scale_rmsprop_slice": lambda x_, m_, lo, hi: (x_, F.ptr(g), 1.0 / 41.0, m_, lo, hi),
+              "frcnn_scale_rmsprop_slice_dev": lambda x_, m_, lo, hi: (x_, F.ptr(g), F.ptr(cnt), m_, lo, hi)}
+    bad = [(fn, args(off, F.ptr(m), 8)) for fn, args in whole.items()]                 # a misaligned x
+    bad += [(fn, args(F.ptr(x), None, 8)) for fn, args in whole.items()]              # a NULL m
+    bad += [(fn, args(F.ptr(x), F.ptr(m), -1)) for fn, args in whole.items()]         # n = -1
+    for fn, args in sliced.items():
+        bad += [(fn, args(off, F.ptr(m), 5, 9)), (fn, args(F.ptr(x), None, 5, 9)),    # a misaligned x, a NULL m
+                (fn, args(F.ptr(x), F.ptr(m), 5, 4)), (fn, args(F.ptr(x), F.ptr(m), -1, 4))]   # lo > hi, lo = -1
+    for fn, args in bad:
+        with pytest.raises(F.FrcnnError):
+            F._lib.call(fn, *args, *tail)
+    for fn, args in whole.items():                                                     # empty ranges: OK, nothing written
+        F._lib.call(fn, *args(F.ptr(x), F.ptr(m), 0), *tail)
+    for fn, args in sliced.items():
+        F._lib.call(fn, *args(F.ptr(x), F.ptr(m), 7, 7), *tail)
+    for t, a, what in zip((x, g, m), kept, ("x", "g", "m")):
+        assert same_bits(_host(t), a), "%s changed by a refused or an empty rmsprop call" % what
 
 
 @pytest.mark.parametrize("kind", ["sgd", "nag"])

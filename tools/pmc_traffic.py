@@ -1,7 +1,7 @@
 """Build profiles/pmc_traffic.json from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE: separate runs with
 --kernel-trace only, as MI355X_MICROARCH.md prescribes).  usage: python tools/pmc_traffic.py <fetch_dir> <write_dir> <out.json>
 Values are KB per dispatch (x1024).  gfx950 correction: FETCH_SIZE reports 1/2 of wide coalesced reads -> doubled
-(calibrated on rmsprop_kernel: 3 reads + 2 writes of the flat parameter vector)."""
+(calibrated on the rmsprop instance of optim_kernel: 3 reads + 2 writes of the flat parameter vector)."""
 import collections, csv, glob, json, re, sys
 
 
@@ -30,7 +30,7 @@ for key, prefix in (("conv_igemm_k3", "conv_igemm_kernel<3, 8"), ("conv_x3", "co
     n = sum(out["kernels"][k]["launches"] for k in ks)
     if n:
         out[key + "_bytes_per_launch"] = round(sum(out["kernels"][k]["launches"] * (out["kernels"][k]["fetch_bytes_per_launch_corrected"] + out["kernels"][k]["write_bytes_per_launch"]) for k in ks) / n)
-rm = next((v for k, v in out["kernels"].items() if k.startswith("rmsprop_kernel")), None)
+rm = next((v for k, v in out["kernels"].items() if k.startswith("optim_kernel") and "RmspropOp" in k), None)
 if rm:
     out["calibration_rmsprop"] = dict(fetch_corrected=rm["fetch_bytes_per_launch_corrected"], write=rm["write_bytes_per_launch"])
 # provenance: bench.py copies it into roofline.traffic_taken, so that a table from another tree is visible in the bench line.
