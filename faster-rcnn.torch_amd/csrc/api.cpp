@@ -370,16 +370,11 @@ int frcnn_conv2d_backward_weight(const float* in, int C, int H, int W, const flo
     rc = tensor_absmax(in, (long)C * H * W, am, S(stream));
     if (rc == FRCNN_OK) rc = tensor_absmax(gout, (long)O * (H + 2 * pad - k + 1) * (W + 2 * pad - k + 1), am + AMAX_REC, S(stream));
   }
-  if (rc == FRCNN_OK)
-    rc = conv_wgrad(in, C, H, W, in_slope, in_scale, gout, O, k, pad, gweight, ws, wsb, S(stream), nullptr, am, am ? am + AMAX_REC : nullptr);
+  if (rc == FRCNN_OK)   // gbias: the split form sums it from the staged gradient tiles, the fp32 kernels in a pass of their own (conv_wgrad)
+    rc = conv_wgrad(in, C, H, W, in_slope, in_scale, gout, O, k, pad, gweight, ws, wsb, S(stream), gbias, am, am ? am + AMAX_REC : nullptr);
   (void)hipStreamSynchronize(S(stream));
   (void)hipFree(ws); (void)hipFree(am);
-  FR_TRY(rc);
-  if (gbias) {
-    int Ho = H + 2 * pad - k + 1, Wo = W + 2 * pad - k + 1;
-    FR_TRY(channel_sum(gout, O, (long)Ho * Wo, gbias, S(stream)));
-  }
-  return FRCNN_OK;
+  return rc;
 }
 
 int frcnn_maxpool_act_forward(const float* x, int C, int H, int W, const float* slope, const float* scale,

@@ -1151,8 +1151,12 @@ int conv_x3(const float* in, int Cin, int H, int W, const float* in_slope, const
   a.nChunks = Cin / CX_CH;
   const long blocks = (long)a.tilesX * a.tilesY * a.mTiles;
   // split K until one round of blocks fills the CX_OCC x 256 resident slots, keeping >= 36 stages (4 chunks of a 3x3) per split
-  const int min_chunks = cdiv(36, k * k);
-  // (the 5x5 / 7x7 kernels hold two blocks per CU and have 25 / 49 stages per chunk: up to 24 splits of one chunk each)
+  // (the 5x5 / 7x7 kernels hold two blocks per CU and have 25 / 49 stages per chunk: up to 24 splits of one chunk each.  A 5x5
+  // launch used to keep TWO chunks per split (cdiv(36, 25)), against this comment: 800 products per slab where conv_igemm folds
+  // slabs of 200, and with six plane products per fp32 product the RMS rounding error came out 1.9 to 2.0 times that kernel's
+  // at 144 channels -- tests/test_gpu_convx_plans.py, forward / input_gradient nine_slabs_k5, is the test that showed it.  The
+  // 384-channel anchor net on the 29 x 50 map keeps its 12 splits of two chunks: its 24 blocks leave 21 slots each.)
+  const int min_chunks = k == 3 ? 4 : 1;
   const long slots = 256 * (k == 3 ? CX_OCC : 2);
   int splitK = (int)std::min<long>(std::min<long>(std::max<long>(1, slots / blocks), k == 3 ? 16 : 24), std::max(1, a.nChunks / min_chunks));
   a.chunksPerSplit = cdiv(a.nChunks, splitK);
