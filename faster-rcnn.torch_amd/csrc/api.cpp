@@ -528,17 +528,27 @@ int frcnn_linear_backward(const float* x, const float* gy, int R, int I, const f
     if (xw) { alloc(&gpT, (size_t)3 * O * Rp * 2); alloc(&xpT, (size_t)3 * I * Rp * 2); }
     float* am = nullptr;   // (two-plane fp16 form of the input-gradient product)
     if (rc == FRCNN_OK && xd) rc = x3_f16_records(&am);
+    // ... and of the weight-gradient product, as the model runs it (net.cpp frcnn_cnet_backward): records of gy and of x,
+    // of their own -- `am` holds gy and the weights
+    float* amw = nullptr;
+    if (xw && get_x3_f16()) alloc((void**)&amw, (size_t)2 * AMAX_REC * 4);
+    float* const rg = amw, * const rx = amw ? amw + AMAX_REC : nullptr;
+    if (rc == FRCNN_OK && amw) {
+      rc = tensor_absmax(gy, (long)R * O, rg, S(stream));
+      if (rc == FRCNN_OK) rc = tensor_absmax(x, (long)R * I, rx, S(stream));
+    }
     if (rc == FRCNN_OK && am) {
       rc = tensor_absmax(gy, (long)R * O, am, S(stream));
       if (rc == FRCNN_OK) rc = tensor_absmax(weight, (long)O * I, am + AMAX_REC, S(stream));
       if (rc == FRCNN_OK) rc = split_planes(gy, R, O, gp, nullptr, S(stream), am);
-      if (rc == FRCNN_OK && gpT) rc = split_planes(gy, R, O, nullptr, gpT, S(stream));
-    } else if (rc == FRCNN_OK) rc = split_planes(gy, R, O, gp, gpT, S(stream));
-    if (rc == FRCNN_OK && xw) rc = split_planes(x, R, I, nullptr, xpT, S(stream));
+      if (rc == FRCNN_OK && gpT) rc = split_planes(gy, R, O, nullptr, gpT, S(stream), rg);
+    } else if (rc == FRCNN_OK && amw) rc = split_planes(gy, R, O, nullptr, gpT, S(stream), rg);   // (the weight gradient alone)
+    else if (rc == FRCNN_OK) rc = split_planes(gy, R, O, gp, gpT, S(stream));
+    if (rc == FRCNN_OK && xw) rc = split_planes(x, R, I, nullptr, xpT, S(stream), rx);
     if (rc == FRCNN_OK && xd) rc = linear_x_dgrad(gp, R, O, weight, I, gx, OUT_STORE, S(stream), 0, nullptr, am, am ? am + AMAX_REC : nullptr);
-    if (rc == FRCNN_OK && xw) rc = linear_x_wgrad(gpT, xpT, R, O, I, gweight, S(stream));
+    if (rc == FRCNN_OK && xw) rc = linear_x_wgrad(gpT, xpT, R, O, I, gweight, S(stream), 0, rg, rx);
     (void)hipStreamSynchronize(S(stream));
-    (void)hipFree(gp); (void)hipFree(gpT); (void)hipFree(xpT); (void)hipFree(am);
+    (void)hipFree(gp); (void)hipFree(gpT); (void)hipFree(xpT); (void)hipFree(am); (void)hipFree(amw);
     FR_TRY(rc);
     if (gx && !xd) FR_TRY(gemm_f32(gy, O, 1, weight, I, 1, gx, I, R, I, O, OUT_STORE, nullptr, S(stream)));
     if (gweight && !xw) FR_TRY(gemm_f32(gy, 1, O, x, I, 1, gweight, I, O, I, R, OUT_ADD, nullptr, S(stream)));

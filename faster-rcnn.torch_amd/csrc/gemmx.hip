@@ -189,6 +189,7 @@ struct GxArgs {
 // LDS) is split in registers by the two waves that need it.  K step = 16; a ring of 3 - 4 LDS stages filled by LDS-DMA
 // ring - 1 steps ahead, counted vmcnt, one barrier per step; one block per CU.
 #define GX_TN 256
+#define GX_WGRAD_SLAB_ROWS 1024
 #define GX_LDS_MAX (160 * 1024)
 constexpr int gx_stage_bytes(int TM, int BMODE, int NP = 3) { return 32 * NP * TM + (BMODE == 0 ? 32 * NP * GX_TN : 64 * GX_TN); }
 // Tiles of up to 128 rows are laid out for TWO blocks per CU (<= 80 KB of LDS, <= 128 registers): two independent blocks
@@ -464,15 +465,19 @@ static int launch_gx(GxArgs& a, dim3 grid, double flops, double bytes, hipStream
 // step costs a block that is alone on its CU 768 cycles per 64 rows (12 MFMAs of 32 cycles on each of two waves per SIMD)
 // at ~80 % plus ~300 for the barrier, the fragment latency and the DMA issue; two co-resident blocks (tiles of <= 128 rows)
 // share the pipe at ~92 % and hide each other's fixed part; a block pays ~8000 cycles of prologue (first stages from HBM)
-// and epilogue; split-K slabs are written and folded at ~1500 B/clk.
-static void gx_plan(int M, int N, int K, int bmode, int splitK_max, int* TM, int* splitK) {
+// and epilogue; split-K slabs are written and folded at ~1500 B/clk.  splitK_min: the fewest splits the caller accepts (its
+// precision, not its speed: linear_x_wgrad).  FRCNN_GX_TM forces a tile height; a height the operand form does not have (256
+// rows with fp32 weights) forces nothing -- skipping every candidate would leave gx_run's 128 rows and ONE split of any K.
+static void gx_plan(int M, int N, int K, int bmode, int splitK_min, int splitK_max, int* TM, int* splitK) {
   double best = 1e300;
+  int forced = getenv("FRCNN_GX_TM") ? atoi(getenv("FRCNN_GX_TM")) : 0;
+  if (forced == 256 && bmode != 0) forced = 0;
   for (int tmv : {256, 192, 128, 64}) {
     if (tmv == 256 && bmode != 0) continue;
-    if (const char* e = getenv("FRCNN_GX_TM")) if (atoi(e) != tmv) continue;
+    if (forced && forced != tmv) continue;
     const long tiles = (long)cdiv(M, tmv) * cdiv(N, GX_TN);
     const int bpc = gx_blocks_per_cu(tmv);
-    for (int sk = 1; sk <= splitK_max; ++sk) {
+    for (int sk = splitK_min; sk <= splitK_max; ++sk) {
       const int kper = cdiv(cdiv(K, sk), 16) * 16;
       if (sk > 1 && kper < 256) break;
       const int sk_eff = cdiv(K, kper);
@@ -521,12 +526,12 @@ static int launch_gx_tm(int TM, GxArgs& a, dim3 grid, double flops, double bytes
   }
 }
 
-static int gx_run(GxArgs& a, int bmode, int splitK_max, float* user_C, const float* bias, int out_mode, hipStream_t s, int ws_slot,
+static int gx_run(GxArgs& a, int bmode, int splitK_min, int splitK_max, float* user_C, const float* bias, int out_mode, hipStream_t s, int ws_slot,
                   GemmFold* defer = nullptr) {
   if (defer) *defer = GemmFold{};
   FR_CHECK(a.K % 16 == 0, "gemm_planes: K = %d must be a multiple of 16", a.K);
   int TM = 128, splitK = 1;
-  gx_plan(a.M, a.N, a.K, bmode, splitK_max, &TM, &splitK);
+  gx_plan(a.M, a.N, a.K, bmode, splitK_min, splitK_max, &TM, &splitK);
   const int tm = cdiv(a.M, TM), tn = cdiv(a.N, GX_TN);
   a.kPerSplit = cdiv(cdiv(a.K, splitK), 16) * 16;
   splitK = cdiv(a.K, a.kPerSplit);
@@ -561,7 +566,7 @@ int linear_x_forward(const void* Xp, int R, int I, const float* W, const float* 
   a.Ap = (const unsigned short*)Xp; a.aPlane = (long)R * I; a.aLd = R;
   a.B = W; a.bPlane = 0; a.bLd = I;
   a.ldc = O; a.M = R; a.N = O; a.K = I;
-  return gx_run(a, 1, 32, y, bias, OUT_STORE, s, ws_slot, defer);
+  return gx_run(a, 1, 1, 32, y, bias, OUT_STORE, s, ws_slot, defer);
 }
 
 // gX[R][I] (= | +=) gY W ; Gp = planes of gY, [3][O/8][R][8]
@@ -574,7 +579,7 @@ int linear_x_dgrad(const void* Gp, int R, int O, const float* W, int I, float* g
   a.Ap = (const unsigned short*)Gp; a.aPlane = (long)R * O; a.aLd = R;
   a.B = W; a.bPlane = 0; a.bLd = I;
   a.ldc = I; a.M = R; a.N = I; a.K = O;
-  return gx_run(a, 2, 4, gx, nullptr, out_mode, s, ws_slot, defer);
+  return gx_run(a, 2, 1, 4, gx, nullptr, out_mode, s, ws_slot, defer);
 }
 
 // gW[O][I] += gY^T X ; GpT = planes of gY^T [3][Rp/8][O][8], XpT = planes of X^T [3][Rp/8][I][8] (k = r; r >= R zero)
@@ -587,7 +592,13 @@ int linear_x_wgrad(const void* GpT, const void* XpT, int R, int O, int I, float*
   a.Ap = (const unsigned short*)GpT; a.aPlane = (long)O * Rp; a.aLd = O;
   a.B = XpT; a.bPlane = (long)I * Rp; a.bLd = I;
   a.ldc = I; a.M = O; a.N = I; a.K = Rp;
-  return gx_run(a, 0, 1, gw, nullptr, OUT_ADD, s, ws_slot);
+  // One slab up to 1024 rows of k (every training step: the slabs of this product are the size of the weight matrix), then as
+  // many as keep a slab at 1024 rows: the rounding error of an fp32 accumulation grows with the square root of the roundings
+  // per slab -- 0.375 per product in the three-plane form, 0.5 in gemm_f32, which splits K down to 256 values per slab where
+  // it has few tiles: 2000 rows in one slab measured 2.24 times gemm_f32's RMS error (tests/test_gpu_gemm_plans.py), 1024
+  // rows are sqrt(384 / 128) = 1.73 at the worst.
+  const int splits = cdiv(Rp, GX_WGRAD_SLAB_ROWS);
+  return gx_run(a, 0, splits, splits, gw, nullptr, OUT_ADD, s, ws_slot);
 }
 
 }  // namespace frcnn

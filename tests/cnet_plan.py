@@ -130,14 +130,22 @@ FB_CB, FB_RG, FB_KEEP = 4, 256, 4   # cnet.hip: the fused kernels' block and the
 BN_CB, BN_RG = 16, 64               # cnet.hip: the separate kernels' block
 
 
-def gemm_splits(M, N, K):
-    """gemm.hip gemm_f32: the number of split-K slabs of C[M][N] = A[M][K] B[K][N]."""
+def gemm_split_plan(M, N, K):
+    """gemm.hip gemm_f32: column tile width, tiles, the split estimate with its two caps, K values per split and the number
+    of split-K slabs of C[M][N] = A[M][K] B[K][N] (tests/gemm_plan.py labels its cases with all of them)."""
     TNs = 128 if (N >= 2048 and K >= 512) else 64
     tiles = cdiv(M, 64) * cdiv(N, TNs)
     slots = 1280 if TNs == 128 else 2048
-    splitK = max(1, min(K // 256, 16, slots // tiles))
-    kPerSplit = cdiv(cdiv(K, splitK), GBK) * GBK
-    return cdiv(K, kPerSplit)
+    by_k, by_slots = min(K // 256, 16), slots // tiles
+    estimate = max(1, min(by_k, by_slots))
+    kPerSplit = cdiv(cdiv(K, estimate), GBK) * GBK
+    return dict(TNs=TNs, tiles=tiles, slots=slots, by_k=by_k, by_slots=by_slots, estimate=estimate, kPerSplit=kPerSplit,
+                splitK=cdiv(K, kPerSplit))
+
+
+def gemm_splits(M, N, K):
+    """gemm.hip gemm_f32: the number of split-K slabs of C[M][N] = A[M][K] B[K][N]."""
+    return gemm_split_plan(M, N, K)["splitK"]
 
 
 def fold_state(M, N, K, defer):

@@ -116,9 +116,13 @@ def test_linear_forward_backward(F, O, R, I, Oo):
 @pytest.mark.parametrize("R", [138, 280, 560])
 def test_linear_fc1_split_bf16_form(F, O, R):
     """nn.Linear(13824, 1024) (models/model_utilities.lua:82; cnet layer 1 of vgg_small / duplo) in its three roles --
-    forward, input gradient, weight gradient -- at the row counts of a training step.  These products take the split-bf16
-    operand form of gemm.hip (six exact bf16 x bf16 partial products per fp32 product): against fp64 they must meet the
-    1e-4 bar AND be no worse than the fp32 matrix-core kernel on the same inputs (root-mean-square error <= 2x)."""
+    forward, input gradient, weight gradient -- at the row counts of a training step.  These products take the split operand
+    form of gemmx.hip.  Which one, by option x3_f16: with 1 (the default, and what runs here) every role takes the two-plane
+    fp16 form -- three exact fp16 x fp16 partial products per fp32 product, the operands scaled by their magnitude records;
+    forward and input gradient with the records of their activation operand and of the weights, the weight gradient with
+    those of gY and of X, as the model runs it.  With 0 every role takes the three-plane bf16 form (six exact bf16 x bf16
+    partial products); tests/test_gpu_gemm_plans.py runs both.  Against fp64 they must meet the 1e-4 bar AND be no worse than
+    the fp32 matrix-core kernel of gemm.hip on the same inputs (root-mean-square error <= 2x)."""
     I, Oo = 13824, 1024
     rng = np.random.RandomState(R)
     x = rng.randn(R, I).astype(np.float32)
@@ -149,8 +153,10 @@ def test_linear_fc1_split_bf16_form(F, O, R):
 
 @pytest.mark.parametrize("R,tm", [(33, None), (193, None), (561, 64), (561, 128), (561, 192), (561, 256), (1398, None)])
 def test_linear_fc1_split_form_tile_heights_and_ragged_rows(F, O, R, tm, monkeypatch):
-    """The split-form Linear kernels (gemmx.hip) with row counts that are no multiple of any tile (33: less than one tile;
-    193 / 561: one row into a new tile; 1398: the candidate count of an inference frame) and with every tile height forced
+    """The split-form Linear kernels (gemmx.hip) with row counts that are no multiple of any tile (33: less than one tile --
+    at this width below the split form's size floor R I O >= 1e9, so gemm.hip's kernel runs; tests/test_gpu_gemm_plans.py has
+    the split kernels with fewer rows than a tile; 193 / 561: one row into a new tile; 1398: the candidate count of an
+    inference frame, whose weight gradient folds two slabs) and with every tile height forced
     in turn (FRCNN_GX_TM; 256 rows exist for the planes x planes weight gradient only -- the other roles then keep their
     own choice): forward, input gradient and weight gradient against fp64 at the 1e-4 bar."""
     I, Oo = 13824, 1024
