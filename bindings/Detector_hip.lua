@@ -21,6 +21,11 @@
 -- winner's r2 becomes the weighted mean of the r2 of its class's survivors that overlap it; nothing else about a winner changes.
 -- And cfg.scoring = { classes = 'top' | 'all', min_confidence = 0.2, max_detections = M } (Detector.scoring_settings): the class
 -- test as ONE frcnn_detect_classes_batch launch per chunk; 'all' scores a candidate under every foreground class over the threshold.
+-- And cfg.tta = { hflip = false, scales = { 1.0 } } (Detector.tta_settings): test-time augmentation.  A frame is detected on V
+-- views of itself -- per scale the rescaled frame and, under hflip, its mirror --, which are the SEGMENTS of the chunk; behind the
+-- class test ONE frcnn_detect_merge_views launch makes one segment per frame of them, in the frame's coordinates, and the per-class
+-- pass, voting and the gather run on those.  A winner gains `view` (0-based); its r2 is in the frame's coordinates, its p, r and a
+-- describe the anchor in the view's, its candidate row counts through the views' candidates in view order.
 --
 --   main.lua:  require 'Detector'  ->  require 'Detector_hip'
 local ffi = require 'ffi'
@@ -48,6 +53,103 @@ function Detector:__init(model)                                         -- Detec
   self.nms_method, self.nms_overlap, self.nms_sigma, self.nms_min_score = Detector.nms_settings(self.model.cfg.nms)
   self.vote_overlap, self.vote_weight = Detector.box_voting_settings(self.model.cfg.box_voting)
   self:set_scoring(self.model.cfg.scoring)
+  self:set_tta(self.model.cfg.tta)
+end
+
+-- cfg.tta -> nil (the key is absent: one forward pass over the frame) or hflip, scales (validated on the host, before any device
+-- call).  The frame is detected on V = #scales * (hflip and 2 or 1) views of itself and the per-class pass -- hard or soft NMS,
+-- voting -- runs over the union of what they found.
+--   hflip   false (default) or true: behind every scale's view comes its left-right mirror
+--   scales  a non-empty list of distinct positive numbers, default { 1.0 }: per scale s, in the order given, an H x W frame is
+--           rescaled to max(1, floor(H * s)) x max(1, floor(W * s)) (BatchIterator.lua:52); s = 1 is the frame itself
+-- A table whose only view is the frame itself ({}, { scales = { 1 } }) is off: the launches and results of the key absent.
+function Detector.tta_settings(t)
+  if t == nil then return nil end
+  if type(t) ~= 'table' then error('cfg.tta must be a table of {hflip, scales}') end
+  for k, _ in pairs(t) do
+    if k ~= 'hflip' and k ~= 'scales' then error('cfg.tta: unknown key ' .. tostring(k)) end
+  end
+  local hflip = t.hflip
+  if hflip == nil then hflip = false end
+  if type(hflip) ~= 'boolean' then error('cfg.tta.hflip must be true or false') end
+  local scales = t.scales
+  if scales == nil then scales = { 1.0 } end
+  if type(scales) ~= 'table' or #scales == 0 then error('cfg.tta.scales must be a non-empty list of numbers') end
+  local n = 0
+  for _, _ in pairs(scales) do n = n + 1 end
+  if n ~= #scales then error('cfg.tta.scales must be a non-empty list of numbers') end
+  local out = {}
+  for i, v in ipairs(scales) do
+    if type(v) ~= 'number' then error('cfg.tta.scales: not a number') end
+    if not (v > 0 and v < math.huge) then error('cfg.tta.scales must be finite and > 0') end
+    for j = 1, i - 1 do
+      if out[j] == v then error('cfg.tta.scales: ' .. v .. ' is given twice') end
+    end
+    out[i] = v
+  end
+  return hflip, out
+end
+
+-- Makes a table as tta_settings takes it this Detector's setting from the next frame on (nil: no augmentation)
+function Detector:set_tta(t)
+  self.tta_hflip, self.tta_scales = Detector.tta_settings(t)
+end
+
+-- The views of the frames of `sizes` ({ 3, H, W } each) -> nil when the setting is off -- absent, or the frame alone --, else per
+-- frame a list of { scale, flip, dH, dW }, scale-major, the unmirrored view first.  Refused on the host, before anything is queued:
+-- more views a frame than Detector.BATCH segments, and a view too small for the proposal net (a head map without positions)
+function Detector:view_lists(sizes)
+  local scales = self.tta_scales
+  if scales == nil or (not self.tta_hflip and #scales == 1 and scales[1] == 1) then return nil end
+  local V = #scales * (self.tta_hflip and 2 or 1)
+  if V > Detector.BATCH then
+    error(string.format('cfg.tta: %d views a frame, more than the %d segments of a chunk (Detector.BATCH)', V, Detector.BATCH))
+  end
+  local lists = {}
+  for f, size in ipairs(sizes) do
+    local H, W = size[2], size[3]
+    local list = {}
+    for _, sc in ipairs(scales) do
+      local dH, dW = H, W
+      if sc ~= 1 then dH, dW = math.max(1, math.floor(H * sc)), math.max(1, math.floor(W * sc)) end
+      for i = 1, 4 do
+        local hw = self:layout(dH, dW).hw[i]
+        if hw[1] < 1 or hw[2] < 1 then
+          error(string.format("cfg.tta: scale %g makes a %dx%d view, too small for the proposal net's head maps", sc, dW, dH))
+        end
+      end
+      list[#list + 1] = { sc, false, dH, dW }
+      if self.tta_hflip then list[#list + 1] = { sc, true, dH, dW } end
+    end
+    lists[f] = list
+  end
+  return lists, V
+end
+
+-- The views of frame f (0-based) of a chunk, in scratch buffers of this Detector: per scale the rescaled frame (frcnn_image_scale;
+-- scale 1 is the frame itself: no launch, no copy), then -- hflip -- its mirror (frcnn_image_crop_flip over the whole view)
+function Detector:make_views(frame, list, f, prefix, out)
+  local scratch = self.scratch
+  local x = hip.to_device(frame)
+  local size = x:size()
+  local H, W = size[2], size[3]
+  local base
+  for i, v in ipairs(list) do
+    local sc, flip, dH, dW = v[1], v[2], v[3], v[4]
+    if not flip then
+      base = x
+      if sc ~= 1 then
+        base = hip.view(scratch(prefix .. 'tta_view_' .. f .. '_' .. i, 12 * dH * dW).ptr, { 3, dH, dW })
+        local tmp = scratch(prefix .. 'tta_tmp', 12 * H * dW)
+        check(C.frcnn_image_scale(x.ptr, 3, H, W, base.ptr, dH, dW, ffi.cast('float*', tmp.ptr), 0, nil))
+      end
+      out[#out + 1] = base
+    else                                               -- (the unmirrored view of this scale came just before)
+      local m = hip.view(scratch(prefix .. 'tta_view_' .. f .. '_' .. i, 12 * dH * dW).ptr, { 3, dH, dW })
+      check(C.frcnn_image_crop_flip(base.ptr, 3, dH, dW, 0, 0, dW, dH, 1, 0, m.ptr, nil))
+      out[#out + 1] = m
+    end
+  end
 end
 
 -- cfg.scoring -> nil (the key is absent: the reference's class test, launch for launch) or classes, min_confidence,
@@ -432,12 +534,14 @@ function Detector:proposals(input)
 end
 
 function Detector:detect(input)                                         -- Detector.lua:17-141
+  self:view_lists({ input:size() })                                     -- (cfg.tta: refused before anything is queued)
   return self:detect_chunk({ input }, false, '')[1]
 end
 
 -- Detector:detect_batch(inputs, opts) -- detect() for a list of frames -- of ONE size, or (opts.mixed_sizes) of any sizes: a list
 -- with one entry per frame, in order, each what detect(frame) returns.  opts: a table { shared_cnet = bool, mixed_sizes = bool,
--- scoring = a table as Detector.scoring_settings takes it }, or (as before) the boolean shared_cnet itself.
+-- scoring = a table as Detector.scoring_settings takes it, tta = a table as Detector.tta_settings takes it }, or (as before) the
+-- boolean shared_cnet itself.  Under cfg.tta a chunk holds max(1, floor(Detector.BATCH / V)) frames: its segments are their views.
 -- Chunks of Detector.BATCH frames: the proposal net runs frame by frame (its
 -- head maps and last feature map are copied to the frame's slot), then ONE scan, ONE segmented NMS, per frame with
 -- candidates the pooling / classification net / class test, ONE segmented per-class NMS and ONE gather; the host waits
@@ -457,6 +561,7 @@ function Detector:detect_batch(inputs, opts)
   if type(opts) == 'table' then
     shared_cnet, mixed_sizes = opts.shared_cnet, opts.mixed_sizes
     if opts.scoring ~= nil then self:set_scoring(opts.scoring) end     -- (validated before anything is queued; it stays set)
+    if opts.tta ~= nil then self:set_tta(opts.tta) end                 -- (likewise)
   end
   local nframes = #inputs
   local function same_size(i, j)
@@ -470,19 +575,27 @@ function Detector:detect_batch(inputs, opts)
       error('Detector:detect_batch: frames of different sizes in one call')
     end
   end
+  local sizes = {}
+  for i = 1, nframes do sizes[i] = inputs[i]:size() end
+  local step = Detector.BATCH
+  local lists, V = self:view_lists(sizes)                               -- (cfg.tta: refused before anything is queued)
+  if lists ~= nil then step = math.max(1, math.floor(step / V)) end     -- a chunk's segments are its frames' views
   local results = {}
   local lo = 1
   while lo <= nframes do
     local chunk = {}
-    for i = lo, math.min(lo + Detector.BATCH - 1, nframes) do chunk[#chunk + 1] = inputs[i] end
+    for i = lo, math.min(lo + step - 1, nframes) do chunk[#chunk + 1] = inputs[i] end
     for _, winners in ipairs(self:detect_chunk(chunk, shared_cnet, 'b_')) do results[#results + 1] = winners end
-    lo = lo + Detector.BATCH
+    lo = lo + step
   end
   return results
 end
 
 -- detect() of a chunk of frames -> one list of winners per frame: first_stage, then -- unless no frame has a match -- per
--- frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather, read-back 2 of 2
+-- frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather, read-back 2 of 2.
+-- Under cfg.tta the SEGMENTS of the chunk are the frames' views (frame f's V views at segments f * V ... f * V + V - 1):
+-- first_stage and step 4 run on them as on frames, ONE frcnn_detect_merge_views launch then makes one segment per frame of them,
+-- and step 5 runs on those -- B / V frames, V times the rows
 function Detector:detect_chunk(frames, shared, prefix)
   local model = self.model
   local cfg = model.cfg
@@ -495,6 +608,14 @@ function Detector:detect_chunk(frames, shared, prefix)
   local D = kh * kw * model.layers[#model.layers].filters
   local scratch = self.scratch
 
+  local sizes = {}
+  for f, x in ipairs(frames) do sizes[f] = x:size() end
+  local lists, V = self:view_lists(sizes)
+  if lists ~= nil then
+    local views = {}
+    for f, x in ipairs(frames) do self:make_views(x, lists[f], f - 1, prefix, views) end
+    frames = views
+  end
   local st = self:first_stage(frames, prefix)                           -- :17-85
   local B, cnt, cap, mp, mi, mr, dpick, count = st.B, st.cnt, st.cap, st.mp, st.mi, st.mr, st.dpick, st.count
   local fm, fslot, key_mode, key_col = st.fm, st.fslot, st.key_mode, st.key_col
@@ -503,7 +624,7 @@ function Detector:detect_chunk(frames, shared, prefix)
     if count[b] > 0 then Rmax = math.max(Rmax, count[B + b]) end
   end
   local results = {}
-  for b = 1, B do results[b] = {} end
+  for b = 1, (lists ~= nil) and B / V or B do results[b] = {} end
   if Rmax == 0 then return results end                                  -- :71, every frame
   -- ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into its segment
   --         (the net owns its outputs and reuses them, so a frame's class test follows its pass at once; the Python mirror, whose
@@ -598,6 +719,38 @@ function Detector:detect_chunk(frames, shared, prefix)
     check(C.frcnn_detect_classes_batch(all_cls, all_bbox, R_arg, row0_arg, B, mr, dpick, cap, ncls, bgclass, self.min_confidence, mode,
                                        dbb, dkc, dkeep, dr2, rows, cnt + 2 * B, nil, nil))
   end
+  --         Under cfg.tta: ONE frcnn_detect_merge_views launch -- every frame's V segments of survivors become one segment of
+  --         V * rows rows in the frame's coordinates (a view's geometry and its candidate count are host values since read-back 1:
+  --         kernel arguments), the views' picks one pick list over the frame's V * cap match rows.  From here on the chunk has
+  --         B / V segments; the match arrays are read where they lie
+  local roff = nil
+  if lists ~= nil then
+    local S = B
+    B = S / V
+    local flip, wv, ax, ay = ffi.new('int[?]', S), ffi.new('double[?]', S), ffi.new('double[?]', S), ffi.new('double[?]', S)
+    local R_seg = ffi.new('int[?]', S)
+    roff = {}
+    for f = 0, B - 1 do
+      roff[f] = { 0 }
+      for v = 0, V - 1 do
+        local i, view = f * V + v, lists[f + 1][v + 1]
+        flip[i], wv[i] = view[2] and 1 or 0, view[4]
+        ax[i], ay[i] = sizes[f + 1][3] / view[4], sizes[f + 1][2] / view[3]
+        if count[i] > 0 then R_seg[i] = count[S + i] end
+        roff[f][v + 2] = roff[f][v + 1] + R_seg[i]
+      end
+    end
+    local mbb = ffi.cast('float*', scratch(prefix .. 'tta_bb', 20 * S * rows).ptr)
+    local mkc = ffi.cast('int*', scratch(prefix .. 'tta_kc', 4 * S * rows).ptr)
+    local mkeep = ffi.cast('int*', scratch(prefix .. 'tta_keep_row', 4 * S * rows).ptr)
+    local mr2 = ffi.cast('double*', scratch(prefix .. 'tta_r2', 32 * S * rows).ptr)
+    local mpick = ffi.cast('long long*', scratch(prefix .. 'tta_pick', 8 * S * cap).ptr)
+    local mcnt = ffi.cast('int*', scratch(prefix .. 'tta_counts', 16 * B).ptr)
+    check(C.frcnn_detect_merge_views(dbb, dkc, dkeep, dr2, rows, cnt, dpick, cap, B, V, flip, wv, ax, ay, R_seg,
+                                     mbb, mkc, mkeep, mr2, mpick, mcnt, nil))
+    dbb, dkc, dkeep, dr2, dpick, cnt = mbb, mkc, mkeep, mr2, mpick, mcnt
+    rows, cap = V * rows, V * cap
+  end
   -- ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame), every class in ONE device pass: rows only suppress
   --         rows of their own class; a stable partition of the picks by class is, per class, exactly nms(bb, 0.1, bb[{{}, 5}])
   --         -- the score tensor is ignored by nms.lua:42, the key is max-y (order = 'score': column 5, the confidence).  The
@@ -677,6 +830,10 @@ function Detector:detect_chunk(frames, shared, prefix)
       local l, a, y, x = tonumber(v[12]), tonumber(v[13]), tonumber(v[14]), tonumber(v[15])
       local det = { p = v[3], a = self.anchors:get(l, a, y, x), l = l, r = Rect.new(v[4], v[5], v[6], v[7]),
                     r2 = Rect.new(v[8], v[9], v[10], v[11]), class = tonumber(v[0]), confidence = v[2] }
+      if roff ~= nil then          -- the 0-based view the candidate came from: v[1] counts through the views' candidates
+        det.candidate, det.view = tonumber(v[1]), 0
+        while det.view + 1 < V and det.candidate > roff[b][det.view + 2] do det.view = det.view + 1 end
+      end
       if not byclass[det.class] then
         byclass[det.class] = {}
         classes[#classes + 1] = det.class

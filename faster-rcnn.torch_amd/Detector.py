@@ -39,7 +39,15 @@ Nor is scoring a candidate under more than its arg-max class, off by default (cf
 scoring_settings): with the key the class test of a chunk is ONE frcnn_detect_classes_batch launch in place of two per frame, its
 threshold is min_confidence, and under classes = "all" a candidate yields one row per foreground class over the threshold -- the
 rows the per-class NMS, voting and the gather then work on; several winners may share a candidate (field `candidate`), with
-bit-identical r2 unless voted.  max_detections caps a frame's winners on the host."""
+bit-identical r2 unless voted.  max_detections caps a frame's winners on the host.
+
+Nor is test-time augmentation, off by default (cfg["tta"] / Detector(..., tta=...), see tta_settings): a frame is detected on V
+views of itself -- per scale the rescaled frame (frcnn_image_scale) and, under hflip, its mirror (frcnn_image_crop_flip) -- which
+are the SEGMENTS of the chunk: steps 1-4 run on them as they run on frames.  Behind the class test ONE frcnn_detect_merge_views
+launch turns the survivors of a frame's views into one segment in the frame's coordinates, on which the per-class pass (hard,
+soft, voting) and the gather run unchanged: winners compete, and vote, across views.  A detection gains `view`; its r2 is in the
+frame's coordinates, its p, r and a describe the anchor in the VIEW's coordinates, its candidate indexes the concatenation of the
+views' classification-net outputs."""
 import collections
 import ctypes as C
 import math
@@ -205,6 +213,50 @@ def scoring_settings(cfg_or_table):
     return classes, min_confidence, _count("scoring", "max_detections", t.get("max_detections"))
 
 
+TTA_DEFAULTS = dict(hflip=False, scales=[1.0])
+
+
+def tta_settings(cfg_or_table):
+    """cfg["tta"] -- or the table itself, or None -- -> None (the key is absent: one forward pass over the frame) or
+    (hflip, scales), validated on the host.  Test-time augmentation: the frame is detected on V = len(scales) * (2 if hflip else
+    1) views of itself (tta_views) and the per-class pass -- hard or soft NMS, voting -- runs over the union of what they found.
+      hflip   False (default) or True: behind every scale's view comes its left-right mirror
+      scales  a non-empty list of distinct positive numbers, default {1.0}: per scale s, in the order given, an H x W frame is
+              rescaled to max(1, int(H * s)) x max(1, int(W * s)) (truncated, as BatchIterator.lua:52 does); s = 1 is the frame
+    A table whose only view is the frame itself ({}, {scales = {1}}) is off: the launches and results of the key absent.  Raises
+    ValueError (before any device call) for an unknown key, an hflip that is no bool, scales that are empty or no list, a scale
+    that is a bool, no number, not finite or <= 0, and a scale given twice."""
+    t = _settings_table(cfg_or_table, "tta", TTA_DEFAULTS, optional=True)
+    if t is None:
+        return None
+    hflip = t.get("hflip", TTA_DEFAULTS["hflip"])
+    if not isinstance(hflip, (bool, np.bool_)):
+        raise ValueError("cfg.tta.hflip = %r (true or false)" % (hflip,))
+    scales = t.get("scales", TTA_DEFAULTS["scales"])
+    if not isinstance(scales, (list, tuple)) or len(scales) == 0:
+        raise ValueError("cfg.tta.scales = %r (a non-empty list of numbers)" % (scales,))
+    out = []
+    for v in scales:
+        v = _number("tta", "scales", v)
+        if not math.isfinite(v) or v <= 0.0:
+            raise ValueError("cfg.tta.scales: %r (finite and > 0)" % (v,))
+        if v in out:
+            raise ValueError("cfg.tta.scales: %r is given twice" % (v,))
+        out.append(v)
+    return bool(hflip), tuple(out)
+
+
+def tta_views(settings, H, W):
+    """The views of an H x W frame under settings = (hflip, scales) -- or None: the frame alone --, in segment order: a list of
+    (scale, flip, dH, dW), scale-major, the unmirrored view first.  View (1.0, False, H, W) is the frame itself."""
+    hflip, scales = settings or (False, (1.0,))
+    out = []
+    for sc in scales:
+        dH, dW = (H, W) if sc == 1.0 else (max(1, int(H * sc)), max(1, int(W * sc)))
+        out += [(sc, flip, dH, dW) for flip in ((False, True) if hflip else (False,))]
+    return out
+
+
 def scoring_rows(classes, min_confidence, ncls):
     """m: the rows a candidate can emit under a scoring setting, what the per-row buffers of a chunk are sized by (Rmax * m rows a
     frame).  "top": 1.  "all": min(ncls - 1, floor(1 / min_confidence) + 1) -- at most floor(1 / c) classes exceed c when the
@@ -228,8 +280,8 @@ class _Detections(object):
     classes ascending (pairs() order is unspecified in Lua), pick order within a class.  Backed by the winner records the
     device wrote; a table is built when it is looked at."""
 
-    def __init__(self, rec, anchors):
-        self._rec, self._anchors = rec, anchors
+    def __init__(self, rec, anchors, roff=None):
+        self._rec, self._anchors, self._roff = rec, anchors, roff   # roff (cfg.tta): the prefix sums of the views' candidate counts
         self._items = [None] * len(rec)
 
     def __len__(self):
@@ -242,6 +294,8 @@ class _Detections(object):
             idx = [int(t) for t in v[12:16]]
             x = dict(p=float(np.float32(v[3])), r=Rect(*v[4:8]), l=idx[0], a=self._anchors.get(*idx), r2=Rect(*v[8:12]),
                      confidence=float(np.float32(v[2])), candidate=int(v[1]), **{"class": int(v[0])})
+            if self._roff is not None:     # the 0-based view the candidate came from
+                x["view"] = int(np.searchsorted(self._roff, x["candidate"] - 1, side="right")) - 1
             self._items[q] = x
         return x
 
@@ -379,22 +433,69 @@ class _BatchRecord(object):
         return v[k]
 
 
-class _DetectorType(type):
-    """Detector(model, ..., box_voting=table, scoring=table): the voting and scoring settings are keywords of the class call, not
-    of __init__, whose parameter list stays what it was.  A table is validated before anything is built -- before the model is
-    looked at, let alone the device -- and set on the finished object; without it __init__ has read model["cfg"]["box_voting"] /
-    model["cfg"]["scoring"]."""
+class _FrameRecord(_BatchRecord):
+    """A frame's entry of Detector.last_batch under cfg["tta"]: ONE record for the frame's V views.  Keys: views (the V
+    _BatchRecords of the views, in view order: each what a frame's record is without the key, its scan rows and picks in the
+    VIEW's coordinates; a view's kept is counted from the merged keep_row when the views are looked at), roff (V + 1 prefix sums of
+    the views' candidate counts), n (the views' matches, summed), pick (the frame's candidates: the views' picks concatenated,
+    1-based rows of the frame's V * match-stride match rows, as frcnn_detect_merge_views rebased them), cnet (the views' outputs
+    concatenated: what `candidate` indexes), kept (the merged survivor count K'), and always bb, kc, r2, keep_row -- the merged
+    survivors as the per-class pass read them, r2 in the FRAME's coordinates, keep_row indexing the concatenated candidates --,
+    votes under box voting."""
+    _KEYS = ("n", "pick", "cnet", "kept", "views", "roff")
 
-    def __call__(cls, *args, box_voting=None, scoring=None, **kw):
+    def __init__(self, views, roff, dev):
+        _BatchRecord.__init__(self, sum(r["n"] for r in views), int(roff[-1]), dev)
+        self._v.update(views=views, roff=np.asarray(roff, np.int64))
+        self._counted = False
+
+    def detach(self):
+        _BatchRecord.detach(self)
+        for r in self._v["views"]:
+            r.detach()
+
+    def scan(self):
+        """Detector.last_scan of the frame: n and the views' scans."""
+        return dict(n=self._v["n"], views=[r.scan() for r in self._v["views"]])
+
+    def keys(self):
+        return list(self._KEYS) + [k for k in self._EXTRA if k in self._dev]
+
+    def __getitem__(self, k):
+        v = self._v
+        if k == "pick" and k not in self._dev:      # (no view of the chunk had a match: nothing was merged)
+            return np.zeros(0, np.int64)
+        if k == "views" and not self._counted and "keep_row" in self._dev:
+            self._counted = True
+            per = np.bincount(np.searchsorted(v["roff"][:-1], self["keep_row"], side="right") - 1, minlength=len(v["views"]))
+            for r, c in zip(v["views"], per.tolist()):
+                r._v["kept"] = c
+        if k == "cnet" and k not in v:
+            parts = [r["cnet"] for r in v["views"] if r["cnet"] is not None]
+            v[k] = dict((t, np.concatenate([p[t] for p in parts])) for t in ("bbox", "cls")) if parts else None
+        return _BatchRecord.__getitem__(self, k)
+
+
+class _DetectorType(type):
+    """Detector(model, ..., box_voting=table, scoring=table, tta=table): the voting, scoring and augmentation settings are
+    keywords of the class call, not of __init__, whose parameter list stays what it was.  A table is validated before anything is
+    built -- before the model is looked at, let alone the device -- and set on the finished object; without it __init__ has read
+    model["cfg"]["box_voting"] / model["cfg"]["scoring"] / model["cfg"]["tta"]."""
+
+    def __call__(cls, *args, box_voting=None, scoring=None, tta=None, **kw):
         if box_voting is not None:
             box_voting_settings(box_voting)
         if scoring is not None:
             scoring_settings(scoring)
+        if tta is not None:
+            tta_settings(tta)
         d = super().__call__(*args, **kw)
         if box_voting is not None:
             d.set_box_voting(box_voting)
         if scoring is not None:
             d.set_scoring(scoring)
+        if tta is not None:
+            d.set_tta(tta)
         return d
 
 
@@ -403,6 +504,7 @@ class Detector(object, metaclass=_DetectorType):
     nms_settings = staticmethod(nms_settings)
     box_voting_settings = staticmethod(box_voting_settings)
     scoring_settings = staticmethod(scoring_settings)
+    tta_settings = staticmethod(tta_settings)
 
     def __init__(self, model, static_weights=False, proposals=None, nms=None):  # Detector.lua:8-15
         """static_weights=True: the caller promises not to write the weight vector between detect() calls; the library then packs
@@ -413,13 +515,16 @@ class Detector(object, metaclass=_DetectorType):
         model["cfg"]["nms"] (absent: the reference's hard cut at 0.1).
         Box voting is model["cfg"]["box_voting"] (absent: none) unless the call names one: Detector(model, box_voting=table), a
         table as box_voting_settings takes it (see _DetectorType).  Likewise the class test: model["cfg"]["scoring"] (absent: the
-        reference's) unless the call names one, Detector(model, scoring=table), a table as scoring_settings takes it."""
+        reference's) unless the call names one, Detector(model, scoring=table), a table as scoring_settings takes it.  Likewise
+        test-time augmentation: model["cfg"]["tta"] (absent: none) unless the call names one, Detector(model, tta=table), a
+        table as tta_settings takes it."""
         if nms is not None:
             nms_settings(nms)
         self.set_proposals(proposals if proposals is not None else model["cfg"])
         self.set_nms(model["cfg"])
         self.set_box_voting(model["cfg"])
         self.set_scoring(model["cfg"])
+        self.set_tta(model["cfg"])
         if nms is not None:
             self.set_nms(nms)
         self.model = model
@@ -460,6 +565,50 @@ class Detector(object, metaclass=_DetectorType):
         """Validates a table as scoring_settings takes it and makes it this Detector's class test from the next frame on (None,
         or a cfg without the key: the reference's, launch for launch)."""
         self.scoring = scoring_settings(cfg_or_table)
+
+    def set_tta(self, cfg_or_table):
+        """Validates a table as tta_settings takes it and makes it this Detector's setting from the next frame on (None, or a
+        cfg without the key: no augmentation).  A table whose only view is the frame itself is kept as given and runs as None."""
+        self.tta = tta_settings(cfg_or_table)
+
+    def _view_lists(self, shapes):
+        """cfg["tta"]: None when the setting is off -- absent, or the frame alone --, else one tta_views list per frame of
+        `shapes` ((3, H, W) each).  Refused (ValueError), on the host: more views a frame than BATCH segments, and a view too
+        small for the proposal net (a head map without positions)."""
+        if self.tta is None or self.tta == (False, (1.0,)):
+            return None
+        lists = [tta_views(self.tta, H, W) for _, H, W in shapes]
+        V = len(tta_views(self.tta, 1, 1))
+        if V > max(int(self.BATCH), 1):
+            raise ValueError("cfg.tta: %d views a frame, more than the %d segments of a chunk (Detector.BATCH)" % (V, self.BATCH))
+        for vl in lists:
+            for sc, _, dH, dW in vl:
+                if any(h < 1 or w < 1 for h, w in self._layout_of(dH, dW).hw):
+                    raise ValueError("cfg.tta: scale %r makes a %dx%d view, too small for the proposal net's head maps"
+                                     % (sc, dW, dH))
+        return lists
+
+    def _make_views(self, frame, views, f, pre):
+        """The views of frame f of a chunk, on the caller's stream, in buffers of this Detector: per scale the rescaled frame
+        (frcnn_image_scale; scale 1 is the frame itself: no launch, no copy), then -- hflip -- its mirror (frcnn_image_crop_flip
+        over the whole view)."""
+        x = to_device(frame)
+        _, H, W = _frame_shape(x)
+        s = stream_ptr()
+        out = []
+        for i, (sc, flip, dH, dW) in enumerate(views):
+            if not flip:
+                base = x
+                if sc != 1.0:
+                    base = self._buf("%stta_view_%d_%d" % (pre, f, i), (3, dH, dW))
+                    _lib.call("frcnn_image_scale", ptr(x), 3, H, W, ptr(base), dH, dW, ptr(self._buf(pre + "tta_tmp", (3 * H * dW,))),
+                              0, s)
+                out.append(base)
+            else:       # (the unmirrored view of this scale came just before)
+                m = self._buf("%stta_view_%d_%d" % (pre, f, i), (3, dH, dW))
+                _lib.call("frcnn_image_crop_flip", ptr(base), 3, dH, dW, 0, 0, dW, dH, 1, 0, ptr(m), s)
+                out.append(m)
+        return out
 
     def __del__(self):
         if getattr(self, "_host", None):
@@ -560,6 +709,7 @@ class Detector(object, metaclass=_DetectorType):
     def detect(self, input):  # Detector.lua:17-141
         """The pipeline of detect_batch on a chunk of this one frame (whatever to_device takes; buffers without the b_ prefix, so
         what a detect_batch call left behind stays as it is).  last_scan, last_pick, last_cnet and _last read the frame's record."""
+        self._view_lists([_frame_shape(input)])     # (cfg.tta: refused before anything is queued)
         (winners,), (rec,) = self._detect_chunk([input], False, "")
         self.last_scan, self._last = rec.scan(), rec
         return winners
@@ -607,13 +757,19 @@ class Detector(object, metaclass=_DetectorType):
         follows -- frcnn_rpn_scan_batch when the chunk has one size (then the strides are that size's own), else
         frcnn_rpn_scan_ragged with per-frame map shapes and image sizes.  Everything behind the scan reads per-frame device
         counts already, so nothing else changes, the two waits per chunk included, and every frame's result and record stay
-        bit-identical to detect(frame)."""
+        bit-identical to detect(frame).
+        Under cfg["tta"] a chunk holds max(1, BATCH // V) frames -- its segments are their V views each --, last_batch holds one
+        _FrameRecord per frame, and more views than BATCH or a view too small for the proposal net are refused (ValueError)
+        before anything is queued; mixed_sizes keeps its meaning for the frames of a call, a frame's own views never need it."""
         frames = list(inputs)
         shapes = [_frame_shape(f) for f in frames]
         if not mixed_sizes and any(shp != shapes[0] for shp in shapes):
             raise ValueError("detect_batch: frames of different sizes in one call: %s" % sorted(set(shapes)))
         results, records = [], []
         step = max(int(self.BATCH), 1)
+        views = self._view_lists(shapes)     # (cfg.tta: refused before anything is queued)
+        if views is not None:                # a chunk's segments are its frames' views
+            step = max(1, step // len(views[0])) if views else step
         for lo in range(0, len(frames), step):
             for r in records:     # (the records of the previous chunk view buffers this chunk writes)
                 r.detach()
@@ -761,7 +917,10 @@ class Detector(object, metaclass=_DetectorType):
     def _detect_chunk(self, frames, shared, pre):
         """detect() of a chunk of frames -> (one result per frame, their records): _first_stage, then -- unless no frame has a match
         -- per frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather and
-        read-back 2 of 2."""
+        read-back 2 of 2.
+        Under cfg["tta"] the SEGMENTS of the chunk are the frames' views (frame f's V views at segments f * V ... f * V + V - 1,
+        made by _make_views): _first_stage and step 4 run on them as on frames, ONE frcnn_detect_merge_views launch then makes one
+        segment per frame of them, and step 5 runs on those -- B frames, V times the rows."""
         model = self.model
         cfg = model["cfg"]
         cnet = model["cnet"]
@@ -773,12 +932,19 @@ class Detector(object, metaclass=_DetectorType):
         L = _lib.load()
         i32 = np.int32
 
+        shapes = [_frame_shape(f) for f in frames]
+        view_lists = self._view_lists(shapes)
+        V = len(view_lists[0]) if view_lists else 1
+        if view_lists:
+            frames = [v for f, (x, vl) in enumerate(zip(frames, view_lists)) for v in self._make_views(x, vl, f, pre)]
         st = self._first_stage(frames, pre)   # :17-85
         B, counts, cap, mp, mi, mr, pick = st["B"], st["counts"], st["cap"], st["p"], st["idx"], st["rect"], st["pick"]
         ns, Rs, (key_mode, key_col) = st["ns"], st["Rs"], st["key"]
         c_K, c_W = counts.segment(2), ptr(counts.segment(3))
         Rmax = max([Rs[b] for b in range(B) if ns[b] > 0] + [0])
         if Rmax == 0:   # no frame has a match (:71)
+            if view_lists:
+                return [[] for _ in range(B // V)], self._frame_records(self._records(st), V, {})
             return [[] for _ in range(B)], self._records(st)
         # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) into the frame's rows.  These launches come first:
         #         the device has been idle since read-back 1, and whatever else the host prepares it prepares while they run
@@ -840,6 +1006,28 @@ class Detector(object, metaclass=_DetectorType):
                 _lib.call("frcnn_detect_post", ptr(dcls), ptr(dconf), ptr(more[b]["bbox"]), ptr(mr.segment(b)),
                           ptr(pick.segment(b)), Rs[b], ncls, 0.2, ptr(bb.segment(b)), ptr(kc.segment(b)),
                           ptr(keep_row.segment(b)), ptr(r2.segment(b)), ptr(c_Kb), s)
+        #      Under cfg["tta"]: ONE frcnn_detect_merge_views launch -- every frame's V segments of survivors become one segment of
+        #      V * rows rows in the frame's coordinates (the geometry of a view and its candidate count are host values since
+        #      read-back 1: kernel arguments), the views' picks one pick list over the frame's V * cap match rows.  From here on the
+        #      chunk has B / V segments; the match arrays are read where they lie
+        if view_lists:
+            S, B = B, B // V
+            geo = [(fl, float(dW), float(shp[2]) / dW, float(shp[1]) / dH)
+                   for shp, vl in zip(shapes, view_lists) for _, fl, dH, dW in vl]
+            R_seg = [Rs[b] if b in row0 else 0 for b in range(S)]
+            roffs = [np.concatenate([[0], np.cumsum(R_seg[f * V:f * V + V])]) for f in range(B)]
+            vbb, vkc, vkeep, vr2 = bb, kc, keep_row, r2
+            bb = self._buf(pre + "tta_bb", (B, V * rows, 5)); kc = self._buf(pre + "tta_kc", (B, V * rows), i32)
+            keep_row = self._buf(pre + "tta_keep_row", (B, V * rows), i32)
+            r2 = self._buf(pre + "tta_r2", (B, V * rows, 4), np.float64)
+            vpick, pick = pick, self._buf(pre + "tta_pick", (B, V * cap), np.int64)
+            vcounts, counts = counts, self._buf(pre + "tta_counts", (4, B), i32)
+            _lib.call("frcnn_detect_merge_views", ptr(vbb), ptr(vkc), ptr(vkeep), ptr(vr2), rows, ptr(vcounts), ptr(vpick), cap, B, V,
+                      (C.c_int * S)(*[int(g[0]) for g in geo]), (C.c_double * S)(*[g[1] for g in geo]),
+                      (C.c_double * S)(*[g[2] for g in geo]), (C.c_double * S)(*[g[3] for g in geo]), (C.c_int * S)(*R_seg),
+                      ptr(bb), ptr(kc), ptr(keep_row), ptr(r2), ptr(pick), ptr(counts), s)
+            c_K, c_W = counts.segment(2), ptr(counts.segment(3))
+            rows, cap = V * rows, V * cap
         # ---- 5. ONE segmented per-class NMS (:125-136; one segment per frame, rows only suppress rows of their own class: a stable
         #         partition of the picks by class is, per class, exactly nms(bb_class, 0.1, scores) -- key = max-y, or the confidence
         #         column under order = "score"), the survivor counts read from device memory; ONE gather of every frame's winner
@@ -888,22 +1076,39 @@ class Detector(object, metaclass=_DetectorType):
         _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, rows, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2_win),
                   ptr(pick), cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
         records = self._records(st, more)
+        if view_lists:    # one record per frame over its views' records
+            records = self._frame_records(records, V, dict((f, dict(pick=pick.segment(f, int(roffs[f][-1])))) for f in range(B)),
+                                          roffs)
         raw = self._read(out.ptr, out.nbytes, np.float64).reshape(out.shape)   # ---- read-back 2 of 2
         results = []
         for b in range(B):
             hdr = raw[b, 0].view(i32)
             K = int(hdr[2])
-            # (soft, voting: the class test's survivors as the pass read them, views of the chunk's buffers until detach())
-            extra = dict(bb=bb.segment(b, K), kc=kc.segment(b, K)) if soft or voting else {}
+            # (soft, voting: the class test's survivors as the pass read them, views of the chunk's buffers until detach();
+            # cfg.tta: always, and all of them -- the merged survivors exist nowhere else)
+            extra = dict(bb=bb.segment(b, K), kc=kc.segment(b, K)) if soft or voting or view_lists else {}
+            if voting or view_lists:
+                extra.update(r2=r2.segment(b, K), keep_row=keep_row.segment(b, K))
             if voting:
-                extra.update(r2=r2.segment(b, K), keep_row=keep_row.segment(b, K), votes=votes.segment(b, K))
+                extra.update(votes=votes.segment(b, K))
             records[b].finish(K, **extra)
-            if ns[b] == 0:
+            if records[b]["n"] == 0:
                 results.append([])
                 continue
             w = raw[b, 1:1 + int(hdr[3])]
             if scoring and scoring[2] is not None and len(w) > scoring[2]:   # max_detections: the best M, still in pick order
                 w = w[keep_best(w[:, 2], scoring[2])]
             # classes in ascending order (pairs() order is unspecified in Lua), pick order within a class
-            results.append(_Detections(w[np.argsort(w[:, 0], kind="stable")].copy(), self.anchors))
+            results.append(_Detections(w[np.argsort(w[:, 0], kind="stable")].copy(), self.anchors,
+                                       roffs[b][:-1] if view_lists else None))
         return results, records
+
+    def _frame_records(self, records, V, dev, roffs=None):
+        """cfg["tta"]: one _FrameRecord per frame over the chunk's per-view records (V consecutive ones a frame); dev[f]: the
+        frame's own device arrays; roffs[f]: the prefix sums of its views' candidate counts (None: no view has a candidate)."""
+        out = []
+        for f in range(len(records) // V):
+            views = records[f * V:f * V + V]
+            roff = roffs[f] if roffs is not None else np.zeros(V + 1, np.int64)
+            out.append(_FrameRecord(views, roff, dev.get(f, {})))
+        return out

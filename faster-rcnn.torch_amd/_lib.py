@@ -74,6 +74,8 @@ _SIGS = {
     "frcnn_detect_post": ([vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_detect_classes_batch": ([vp, vp, vp, vp, C.c_int, vp, vp, C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp,
                                     C.c_int, vp, vp, vp], C.c_int),
+    "frcnn_detect_merge_views": ([vp, vp, vp, vp, C.c_longlong, vp, vp, C.c_longlong, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp, vp], C.c_int),
     "frcnn_nms_host": ([vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp], C.c_int),
     "frcnn_conv2d_forward": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
     "frcnn_conv2d_backward_input": ([vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp], C.c_int),

@@ -219,6 +219,14 @@ int frcnn_detect_classes_batch(const float* cls_out, const float* bbox, const in
   return detect_classes_batch(cls_out, bbox, R_host, row0_host, B, rect, pick, match_stride, ncls, bgclass, min_conf, mode, bb, kc,
                               keep_row, r2, row_stride, K_dev, total_dev, S(stream));
 }
+int frcnn_detect_merge_views(const float* bb, const int* kc, const int* keep_row, const double* r2, long long row_stride,
+                             const int* counts, const long long* pick, long long match_stride, int F, int V,
+                             const int* flip_host, const double* wv_host, const double* ax_host, const double* ay_host,
+                             const int* R_host, float* bb_out, int* kc_out, int* keep_row_out, double* r2_out,
+                             long long* pick_out, int* counts_out, void* stream) {
+  return detect_merge_views(bb, kc, keep_row, r2, row_stride, counts, pick, match_stride, F, V, flip_host, wv_host, ax_host,
+                            ay_host, R_host, bb_out, kc_out, keep_row_out, r2_out, pick_out, counts_out, S(stream));
+}
 int frcnn_nms_host(const float* boxes_host, int n, int ncols, float overlap, int key_mode, int key_col,
                    long long* pick_host, int* count_host) {
   if (n <= 0) { *count_host = 0; return FRCNN_OK; }

@@ -8,6 +8,8 @@
 //   detect_classes_batch  the class test of a chunk of B frames in ONE launch, straight from the net's log-probabilities
 //                 (the arg-max of frcnn_cnet_decode folded in): mode 0 the rule above, one row per candidate at most; mode 1
 //                 one row per (candidate, foreground class) whose probability clears the threshold
+//   detect_merge_views  test-time augmentation: the survivors of a frame's V views (V segments) as ONE segment in the frame's
+//                 coordinates, the views' picks rebased for the gather -- one launch per chunk, no atomics
 //   detect_gather_batch  one table per frame: its counts, then one record per winner (class, candidate row, confidence, p,
 //                 anchor rect, decoded rect, anchor index)
 // Gather / scan work on a few thousand rows: latency-bound, no MFMA.  Double arithmetic follows the host mirror
@@ -15,6 +17,8 @@
 // Lua numbers are).  exp() is the device library's double exp: it may differ from the host libm in the last bit (both
 // are within an ulp), far inside the 1e-3 bar the decoded rects are compared at.
 #pragma clang fp contract(off)
+#include <cmath>
+
 #include "kernels.h"
 
 namespace frcnn {
@@ -270,6 +274,106 @@ int detect_classes_batch(const float* cls_out, const float* bbox, const int* R, 
     FR_LAUNCH(KC_ELEMWISE, 0, rows * (ncls * 4.0 + 64.0), s, detect_classes_batch_kernel, dim3(nb), dim3(DC_THREADS), 0, g, b0,
               cls_out, bbox, rect, pick, match_stride, ncls, bgclass, min_conf, mode, bb, kc, keep_row, r2, row_stride, K_dev,
               total_dev);
+  }
+  FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// ---- Test-time augmentation (cfg.tta): the class-test survivors of a frame's V views -- V consecutive segments of the chunk --
+// become ONE segment of V * row_stride rows in the frame's own coordinates, in view order and in row order within a view.  A
+// view's geometry (mirrored or not, its width, the two factors back to the frame) and its candidate count are HOST values and
+// travel by value as a kernel argument, MV_VIEWS views a launch (the way detect_classes_batch carries its descriptors).  Grid
+// (row tiles, V, frames): thread j of view v stores survivor j at the prefix of the views' device counts in front of it (at most
+// 7 loads: no scan, no atomics), and candidate j's pick at the prefix of the candidate counts, rebased by v * match_stride so that
+// detect_gather_batch finds the view's match rows behind it unchanged.  Coordinates in fp64, one rounding per operation:
+// BatchIterator.lua:57-62 backwards (x1' = Wv - x2, x2' = Wv - x1), then x * ax, y * ay; a factor of exactly 1 is not applied.
+#define MV_THREADS 256
+constexpr int MV_MAX_V = 8;
+constexpr int MV_VIEWS = 64;
+struct MergeView { double Wv, ax, ay; int flip, R, Roff, pad; };
+struct MergeGroup { MergeView v[MV_VIEWS]; };
+static_assert(sizeof(MergeGroup) <= 3072, "the descriptors of a group travel as a kernel argument");
+
+__global__ __launch_bounds__(MV_THREADS) void detect_merge_views_kernel(
+    MergeGroup g, int f0, int F, int V, const float* __restrict__ bb, const int* __restrict__ kc, const int* __restrict__ keep_row,
+    const double* __restrict__ r2, long long row_stride, const int* __restrict__ counts, const long long* __restrict__ pick,
+    long long match_stride, float* __restrict__ bb_out, int* __restrict__ kc_out, int* __restrict__ keep_row_out,
+    double* __restrict__ r2_out, long long* __restrict__ pick_out, int* __restrict__ counts_out) {
+  const int v = blockIdx.y, f = f0 + blockIdx.z;
+  const long long j = (long long)blockIdx.x * MV_THREADS + threadIdx.x;
+  const int S = F * V;                                   // segments of the chunk: counts is int[4][S]
+  const MergeView* views = g.v + (size_t)blockIdx.z * V;
+  const MergeView d = views[v];
+  const int* n_dev = counts + (size_t)f * V;             // the views' match counts; their survivor counts at + 2 * S
+  auto survivors = [&](int u) { return (long long)min(max(n_dev[2 * S + u], 0), (int)row_stride); };   // (V * row_stride fits an int)
+  long long before = 0;
+  for (int u = 0; u < v; ++u) before += survivors(u);
+  if (v == 0 && j == 0) {
+    long long matches = 0, cand = 0, K = 0;
+    for (int u = 0; u < V; ++u) { matches += n_dev[u]; cand += views[u].R; K += survivors(u); }
+    counts_out[f] = (int)matches; counts_out[F + f] = (int)cand; counts_out[2 * F + f] = (int)K;
+  }
+  const size_t seg = (size_t)f * V + v;
+  if (j < d.R)
+    pick_out[(size_t)f * V * match_stride + d.Roff + j] = (long long)v * match_stride + pick[seg * match_stride + j];
+  if (j >= survivors(v)) return;
+  const size_t src = seg * row_stride + j, dst = (size_t)f * V * row_stride + before + j;
+  double x1 = r2[4 * src], y1 = r2[4 * src + 1], x2 = r2[4 * src + 2], y2 = r2[4 * src + 3];
+  if (d.flip) {
+    const double a = d.Wv - x2, b = d.Wv - x1;
+    x1 = a; x2 = b;
+  }
+  if (d.ax != 1.0) { x1 = x1 * d.ax; x2 = x2 * d.ax; }
+  if (d.ay != 1.0) { y1 = y1 * d.ay; y2 = y2 * d.ay; }
+  double* o = r2_out + 4 * dst;
+  o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+  float* x = bb_out + 5 * dst;
+  x[0] = (float)x1; x[1] = (float)y1; x[2] = (float)x2; x[3] = (float)y2; x[4] = bb[5 * src + 4];
+  kc_out[dst] = kc[src];
+  keep_row_out[dst] = d.Roff + keep_row[src];
+}
+
+int detect_merge_views(const float* bb, const int* kc, const int* keep_row, const double* r2, long long row_stride,
+                       const int* counts, const long long* pick, long long match_stride, int F, int V, const int* flip,
+                       const double* Wv, const double* ax, const double* ay, const int* R, float* bb_out, int* kc_out,
+                       int* keep_row_out, double* r2_out, long long* pick_out, int* counts_out, hipStream_t s) {
+  // everything is checked before the first launch: a refused call has written nothing
+  FR_CHECK(F >= 1 && F <= 65535, "detect_merge_views: %d frames (1 ... 65535)", F);
+  FR_CHECK(V >= 1 && V <= MV_MAX_V, "detect_merge_views: %d views a frame (1 ... %d)", V, MV_MAX_V);
+  FR_CHECK(row_stride >= 0 && match_stride >= 0, "detect_merge_views: negative stride (%lld / %lld)", row_stride, match_stride);
+  FR_CHECK(row_stride * V <= 0x7fffffffLL && match_stride * V <= 0x7fffffffLL, "detect_merge_views: %d views of %lld / %lld rows",
+           V, row_stride, match_stride);
+  FR_CHECK(flip && Wv && ax && ay && R && counts && counts_out, "detect_merge_views: NULL argument");
+  long long rmax = 0;
+  for (int i = 0; i < F * V; ++i) {
+    FR_CHECK(std::isfinite(Wv[i]) && Wv[i] > 0 && std::isfinite(ax[i]) && ax[i] > 0 && std::isfinite(ay[i]) && ay[i] > 0,
+             "detect_merge_views: view %d of frame %d has width %g, factors %g / %g (finite and positive)", i % V, i / V, Wv[i],
+             ax[i], ay[i]);
+    FR_CHECK(R[i] >= 0 && R[i] <= match_stride, "detect_merge_views: view %d of frame %d has %d candidates (0 ... %lld)", i % V,
+             i / V, R[i], match_stride);
+    rmax = std::max(rmax, (long long)R[i]);
+  }
+  FR_CHECK(rmax == 0 || (pick && pick_out), "detect_merge_views: NULL pick");
+  FR_CHECK(row_stride == 0 || (bb && kc && keep_row && r2 && bb_out && kc_out && keep_row_out && r2_out),
+           "detect_merge_views: NULL argument");
+  const int tiles = (int)std::max(cdivl((long)std::max(row_stride, rmax), MV_THREADS), 1L);
+  const int per = MV_VIEWS / V;                          // frames a launch
+  for (int f0 = 0; f0 < F; f0 += per) {
+    const int nf = std::min(F - f0, per);
+    MergeGroup g;
+    memset(&g, 0, sizeof(g));
+    for (int i = 0; i < nf; ++i) {
+      int off = 0;
+      for (int v = 0; v < V; ++v) {
+        const int k = (f0 + i) * V + v;
+        MergeView& d = g.v[i * V + v];
+        d.Wv = Wv[k]; d.ax = ax[k]; d.ay = ay[k]; d.flip = flip[k] != 0; d.R = R[k]; d.Roff = off;
+        off += R[k];
+      }
+    }
+    FR_LAUNCH(KC_ELEMWISE, 0, (double)nf * V * (row_stride * 112.0 + rmax * 16.0), s, detect_merge_views_kernel,
+              dim3(tiles, V, nf), dim3(MV_THREADS), 0, g, f0, F, V, bb, kc, keep_row, r2, row_stride, counts, pick, match_stride,
+              bb_out, kc_out, keep_row_out, r2_out, pick_out, counts_out);
   }
   FR_LAUNCH_CHECK();
   return FRCNN_OK;

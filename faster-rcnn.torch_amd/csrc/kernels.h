@@ -318,6 +318,10 @@ int detect_post(const int* cls, const float* conf, const float* bbox, const doub
 int detect_classes_batch(const float* cls_out, const float* bbox, const int* R, const long long* row0, int B, const double* rect,
                          const long long* pick, long long match_stride, int ncls, int bgclass, double min_conf, int mode, float* bb,
                          int* kc, int* keep_row, double* r2, int row_stride, int* K_dev, int* total_dev, hipStream_t s);
+int detect_merge_views(const float* bb, const int* kc, const int* keep_row, const double* r2, long long row_stride,
+                       const int* counts, const long long* pick, long long match_stride, int F, int V, const int* flip,
+                       const double* Wv, const double* ax, const double* ay, const int* R, float* bb_out, int* kc_out,
+                       int* keep_row_out, double* r2_out, long long* pick_out, int* counts_out, hipStream_t s);
 int detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                         const float* bb, const double* r2, const long long* pick, long match_stride, const float* mp,
                         const double* rect, const int* midx, double* rec, hipStream_t s);

@@ -264,6 +264,36 @@ int frcnn_detect_classes_batch(const float *cls_out, const float *bbox, const in
 int frcnn_detect_gather_batch(const long long *wpick, const int *counts, int B, int row_stride, const int *keep_row,
                               const int *kc, const float *bb, const double *r2, const long long *pick, long long match_stride,
                               const float *match_p, const double *match_rect, const int *match_idx, double *rec, void *stream);
+/* frcnn_detect_merge_views: test-time augmentation (Detector under cfg.tta; not in the reference).  A frame was detected on V
+ * views of itself (rescaled and / or mirrored copies), V consecutive segments of a chunk of F*V segments; this ONE launch turns the
+ * class-test survivors of every frame's views into one segment of V*row_stride rows in the frame's own coordinates, which the
+ * per-class pass, voting and frcnn_detect_gather_batch then read with B = F, row stride V*row_stride, match stride V*match_stride.
+ * Inputs: bb / kc / keep_row / r2 as frcnn_detect_post or frcnn_detect_classes_batch left them (row_stride rows a segment),
+ * counts = device int[4][F*V] (row 0: the segments' matches, row 2: their survivors K, clipped to row_stride), pick = the first
+ * NMS's picks (match_stride rows a segment).  Geometry of view i = f*V + v, HOST arrays of F*V entries that travel as kernel
+ * arguments (no upload, no wait): flip_host (the view is mirrored left-right), wv_host (its width), ax_host / ay_host (frame width
+ * / view width, frame height / view height), R_host (its candidates, 0 ... match_stride).
+ * Frame f's outputs start at row f*V*row_stride (bb_out, kc_out, keep_row_out, r2_out) and f*V*match_stride (pick_out):
+ *   ROWS    survivor j of view v lies at row sum_{u<v} K_u + j: view order, row order within a view; nothing is written behind
+ *           row K' = sum K_u.  No atomics: a frame's output is a function of its own segments.
+ *   COORDS  fp64, every operation rounded on its own, in this order: a mirrored view un-mirrors (x1' = wv - x2, x2' = wv - x1:
+ *           BatchIterator.lua:57-62, its own inverse), then x1, x2 are multiplied by ax (unless ax == 1) and y1, y2 by ay (unless
+ *           ay == 1) -- an unmirrored view with ax == ay == 1 keeps its bits.  r2_out holds these doubles, bb_out[0..3] their
+ *           (float); bb_out[4] (the log-confidence) and kc_out are copied.
+ *   PICKS   the candidates of a frame are the concatenation of its views' candidates: keep_row_out = Roff_v + keep_row with
+ *           Roff_v = sum_{u<v} R_host[u], and pick_out[Roff_v + r] = v*match_stride + pick[r] (still 1-based) for EVERY candidate
+ *           r < R_host of view v; nothing behind sum R_host.  The match arrays stay where they are: a frame's views are
+ *           consecutive segments, so row pick_out - 1 of frame f's V*match_stride match rows is the view's own row.
+ *   COUNTS  counts_out = device int[4][F]: rows 0 ... 2 of frame f = the sum of its views' matches, of R_host, and K'; row 3 is
+ *           left to the per-class pass.
+ * Errors, returned before the launch: F outside 1 ... 65535, V outside 1 ... 8, a negative stride, V * stride beyond int, a NULL
+ * required pointer, an R_host outside 0 ... match_stride, a width or factor that is not finite or not positive.  One launch for
+ * up to 64 views (more: one per 64 / V frames).  Counted under FRCNN_KC_ELEMWISE. */
+int frcnn_detect_merge_views(const float *bb, const int *kc, const int *keep_row, const double *r2, long long row_stride,
+                             const int *counts, const long long *pick, long long match_stride, int F, int V,
+                             const int *flip_host, const double *wv_host, const double *ax_host, const double *ay_host,
+                             const int *R_host, float *bb_out, int *kc_out, int *keep_row_out, double *r2_out,
+                             long long *pick_out, int *counts_out, void *stream);
 /* Host-pointer variant (the reference's nms runs on CPU FloatTensors): uploads, runs the same
  * kernels, downloads, synchronises. */
 int frcnn_nms_host(const float *boxes_host, int n, int ncols, float overlap, int key_mode,
