@@ -6,6 +6,8 @@
 #include <mutex>
 
 #include "kernels.h"
+#include "own.h"
+#include "linear.h"
 
 namespace frcnn {
 
@@ -500,73 +502,26 @@ int frcnn_loss_accumulate(const double* ex_loss, int E, double* acc, void* strea
   return loss_accumulate(ex_loss, E, acc, S(stream));
 }
 
+// The Linear products as the classification net runs them (linear.h), on scratch of the call: planes and records for the requested
+// roles only, freed on return -- so a call that took the split form synchronises first.
 int frcnn_linear_forward(const float* x, int R, int I, const float* weight, const float* bias, int O, float* y,
                          void* stream) {
   // Y[R][O] = X[R][I] * W[O][I]^T + b
-  if (linear_x_eligible(1, R, I, O)) {   // split-bf16 operand form (gemmx.hip); the model runtime keeps the planes resident
-    void* xp = nullptr;
-    FR_HIP(hipMalloc(&xp, (size_t)3 * R * I * 2));
-    float* am = nullptr;   // (two-plane fp16 form: records of x and of the weight matrix)
-    int rc = x3_f16_records(&am);
-    if (am && rc == FRCNN_OK) {
-      rc = tensor_absmax(x, (long)R * I, am, S(stream));
-      if (rc == FRCNN_OK) rc = tensor_absmax(weight, (long)O * I, am + AMAX_REC, S(stream));
-    }
-    if (rc == FRCNN_OK) rc = split_planes(x, R, I, xp, nullptr, S(stream), am);
-    if (rc == FRCNN_OK) rc = linear_x_forward(xp, R, I, weight, bias, O, y, S(stream), 0, nullptr, am, am ? am + AMAX_REC : nullptr);
-    (void)hipStreamSynchronize(S(stream));
-    (void)hipFree(xp); (void)hipFree(am);
-    return rc;
-  }
-  return gemm_f32(x, I, 1, weight, 1, I, y, O, R, O, I, OUT_STORE, bias, S(stream));
+  Linear L;
+  int rc = L.ensure(R, I, O, 1);
+  if (rc == FRCNN_OK) rc = L.forward(x, weight, bias, y, -1, S(stream), 0, nullptr);
+  if (L.x_form) (void)hipStreamSynchronize(S(stream));
+  return rc;
 }
 int frcnn_linear_backward(const float* x, const float* gy, int R, int I, const float* weight, int O, float* gx,
                           float* gweight, float* gbias, void* stream) {
-  const bool xd = gx && linear_x_eligible(2, R, I, O), xw = gweight && linear_x_eligible(4, R, I, O);
-  if (xd || xw) {
-    const size_t Rp = (size_t)linear_x_rows_padded(R);
-    void *gp = nullptr, *gpT = nullptr, *xpT = nullptr;
-    int rc = FRCNN_OK;
-    auto alloc = [&](void** p, size_t bytes) {   // (a failed allocation frees what the earlier ones got: no early return)
-      if (rc != FRCNN_OK) return;
-      hipError_t e = hipMalloc(p, bytes);
-      if (e != hipSuccess) { set_error("frcnn_linear_backward: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); rc = FRCNN_ERR_HIP; }
-    };
-    if (xd) alloc(&gp, (size_t)3 * R * O * 2);
-    if (xw) { alloc(&gpT, (size_t)3 * O * Rp * 2); alloc(&xpT, (size_t)3 * I * Rp * 2); }
-    float* am = nullptr;   // (two-plane fp16 form of the input-gradient product)
-    if (rc == FRCNN_OK && xd) rc = x3_f16_records(&am);
-    // ... and of the weight-gradient product, as the model runs it (net.cpp frcnn_cnet_backward): records of gy and of x,
-    // of their own -- `am` holds gy and the weights
-    float* amw = nullptr;
-    if (xw && get_x3_f16()) alloc((void**)&amw, (size_t)2 * AMAX_REC * 4);
-    float* const rg = amw, * const rx = amw ? amw + AMAX_REC : nullptr;
-    if (rc == FRCNN_OK && amw) {
-      rc = tensor_absmax(gy, (long)R * O, rg, S(stream));
-      if (rc == FRCNN_OK) rc = tensor_absmax(x, (long)R * I, rx, S(stream));
-    }
-    if (rc == FRCNN_OK && am) {
-      rc = tensor_absmax(gy, (long)R * O, am, S(stream));
-      if (rc == FRCNN_OK) rc = tensor_absmax(weight, (long)O * I, am + AMAX_REC, S(stream));
-      if (rc == FRCNN_OK) rc = split_planes(gy, R, O, gp, nullptr, S(stream), am);
-      if (rc == FRCNN_OK && gpT) rc = split_planes(gy, R, O, nullptr, gpT, S(stream), rg);
-    } else if (rc == FRCNN_OK && amw) rc = split_planes(gy, R, O, nullptr, gpT, S(stream), rg);   // (the weight gradient alone)
-    else if (rc == FRCNN_OK) rc = split_planes(gy, R, O, gp, gpT, S(stream));
-    if (rc == FRCNN_OK && xw) rc = split_planes(x, R, I, nullptr, xpT, S(stream), rx);
-    if (rc == FRCNN_OK && xd) rc = linear_x_dgrad(gp, R, O, weight, I, gx, OUT_STORE, S(stream), 0, nullptr, am, am ? am + AMAX_REC : nullptr);
-    if (rc == FRCNN_OK && xw) rc = linear_x_wgrad(gpT, xpT, R, O, I, gweight, S(stream), 0, rg, rx);
-    (void)hipStreamSynchronize(S(stream));
-    (void)hipFree(gp); (void)hipFree(gpT); (void)hipFree(xpT); (void)hipFree(am); (void)hipFree(amw);
-    FR_TRY(rc);
-    if (gx && !xd) FR_TRY(gemm_f32(gy, O, 1, weight, I, 1, gx, I, R, I, O, OUT_STORE, nullptr, S(stream)));
-    if (gweight && !xw) FR_TRY(gemm_f32(gy, 1, O, x, I, 1, gweight, I, O, I, R, OUT_ADD, nullptr, S(stream)));
-    if (gbias) FR_TRY(channel_sum_cols(gy, R, O, gbias, S(stream)));
-    return FRCNN_OK;
-  }
-  if (gx) FR_TRY(gemm_f32(gy, O, 1, weight, I, 1, gx, I, R, I, O, OUT_STORE, nullptr, S(stream)));
-  if (gweight) FR_TRY(gemm_f32(gy, 1, O, x, I, 1, gweight, I, O, I, R, OUT_ADD, nullptr, S(stream)));
-  if (gbias) FR_TRY(channel_sum_cols(gy, R, O, gbias, S(stream)));
-  return FRCNN_OK;
+  Linear L;
+  int rc = L.ensure(R, I, O, (gx ? 2 : 0) | (gweight ? 4 : 0));
+  if (rc == FRCNN_OK) rc = L.weight_record(weight, -1, S(stream));   // (in the forward pass's place: the input gradient's fp16 form needs it)
+  if (rc == FRCNN_OK) rc = L.dgrad(gy, weight, gx, S(stream), 0, nullptr);
+  if (rc == FRCNN_OK) rc = L.wgrad(gy, x, weight, gweight, gbias, S(stream), 0);
+  if (L.x_form) (void)hipStreamSynchronize(S(stream));
+  return rc;
 }
 
 // optim.rmsprop (main.lua:122,133)

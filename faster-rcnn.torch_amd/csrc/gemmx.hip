@@ -158,8 +158,8 @@ int split_planes(const float* src, int R, int C, void* P, void* PT, hipStream_t 
     FR_LAUNCH(KC_ELEMWISE, 0, (double)R * C * 8.0, s, split_planes_kernel<2>, grid, dim3(256), 0,
               src, R, C, Rp, (unsigned short*)P, (unsigned short*)PT, amax);
   else
-  FR_LAUNCH(KC_ELEMWISE, 0, (double)R * C * (4.0 + (P ? 6.0 : 0.0) + (PT ? 6.0 : 0.0)), s, split_planes_kernel<3>, grid, dim3(256), 0,
-            src, R, C, Rp, (unsigned short*)P, (unsigned short*)PT, amax);
+    FR_LAUNCH(KC_ELEMWISE, 0, (double)R * C * (4.0 + (P ? 6.0 : 0.0) + (PT ? 6.0 : 0.0)), s, split_planes_kernel<3>, grid, dim3(256), 0,
+              src, R, C, Rp, (unsigned short*)P, (unsigned short*)PT, amax);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }

@@ -224,7 +224,7 @@ int get_gemm_x_roles();
 bool linear_x_eligible(int role, int R, int I, int O);   // role: 1 forward, 2 input gradient, 4 weight gradient
 int linear_x_rows_padded(int R);                       // rows of the transposed planes (R rounded up to 16, zero filled)
 int split_planes(const float* src, int R, int C, void* P /* [3][C/8][R][8] bf16 or null */, void* PT /* [3][Rp/8][C][8] or null */,
-                 hipStream_t s, const float* amax = nullptr);   // amax (record of src, amax.h): two fp16 planes [2][C/8][R][8] instead (P only)
+                 hipStream_t s, const float* amax = nullptr);   // amax (record of src, amax.h): two fp16 planes instead, [2][C/8][R][8] in P, [2][Rp/8][C][8] in PT
 // amax_x / amax_g + amax_w (records of the activation operand and of the weight matrix): the two-plane fp16 form (planes made by
 // split_planes with the same record)
 int linear_x_forward(const void* Xp, int R, int I, const float* W, const float* bias, int O, float* y, hipStream_t s, int ws_slot = 0,

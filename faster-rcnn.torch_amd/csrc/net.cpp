@@ -19,6 +19,7 @@
 
 #include "kernels.h"
 #include "own.h"
+#include "linear.h"
 
 namespace frcnn {
 
@@ -82,13 +83,7 @@ struct ClsLayer {
   long w_off, b_off, bnw_off, bnb_off, a_off;
   DevBuf lin, pre, post, xhat, invstd, mask, g;
   DevBuf gin;                 // gradient wrt this layer's input (layers > 0; a buffer of its own: the weight gradient reads the input beside it)
-  DevBuf xp, xpT, gp, gpT;    // split-bf16 planes of the layer's input and of its output gradient (gemmx.hip), when it takes that form
-  int x_form = 0;             // set per call: which of this layer's products run in the split-bf16 operand form
-                              // (bit 1 forward, 2 input gradient, 4 weight gradient: linear_x_eligible)
-  DevBuf am;                  // two-plane fp16 form of the forward / input-gradient products: magnitude records (amax.h) of the
-                              // layer's input, of its output gradient and of its weight matrix, AMAX_REC floats each
-  const float* am_w_of = nullptr;   // the weight vector the third record was taken from ...
-  long am_w_gen = -1;               // ... in an evaluate-mode pass of this static_weights generation (-1: a training pass)
+  Linear fc;                  // the layer's three large products and the operand forms they run in (linear.h)
 };
 
 }  // namespace frcnn
@@ -1806,11 +1801,6 @@ int frcnn_pnet_backward(frcnn_model* m, const float* w, float* grad, void* strea
 // ------------------------------------------------------------------------------------ cnet
 // the row-wise layers fused with the folds of the products around them (cnet.hip: "fused forms"); FRCNN_CNET_FUSE=0: one launch each
 static bool cnet_fuse() { return env_flag("FRCNN_CNET_FUSE", true); }   // (read per call: the tests switch it)
-// the classification net's large products in the two-plane fp16 form: with option x3_f16 (FRCNN_GEMM_F16=0: these stay three-plane)
-static bool gemm_f16_on() {
-  static const bool env_on = env_flag("FRCNN_GEMM_F16", true);
-  return env_on && get_x3_f16();
-}
 static int ensure_cnet(frcnn_model* m, int R) {
   for (auto& L : m->cls) {
     size_t n = (size_t)R * L.n * 4;
@@ -1820,13 +1810,7 @@ static int ensure_cnet(frcnn_model* m, int R) {
     FR_TRY(L.g.ensure(n));
     FR_TRY(L.gin.ensure((size_t)R * L.in * 4));
     if (L.p_drop > 0.f) FR_TRY(L.mask.ensure(n));
-    L.x_form = 0;
-    for (int role : {1, 2, 4}) if (linear_x_eligible(role, R, L.in, L.n)) L.x_form |= role;
-    const size_t Rp = (size_t)linear_x_rows_padded(R);
-    if (L.x_form & 1) FR_TRY(L.xp.ensure((size_t)3 * R * L.in * 2));
-    if (L.x_form & 2) FR_TRY(L.gp.ensure((size_t)3 * R * L.n * 2));
-    if (L.x_form & 4) { FR_TRY(L.xpT.ensure((size_t)3 * L.in * Rp * 2)); FR_TRY(L.gpT.ensure((size_t)3 * L.n * Rp * 2)); }
-    if (L.x_form & 7) FR_TRY(L.am.ensure((size_t)5 * AMAX_REC * 4));   // records: input, output gradient, weights; the weight-gradient stream's own two
+    FR_TRY(L.fc.ensure(R, L.in, L.n, 7));
   }
   int nc = m->d.class_count + 1;
   int nf = m->cls.empty() ? m->D : m->cls.back().n;
@@ -1852,25 +1836,8 @@ int frcnn_cnet_forward(frcnn_model* m, const float* weights, const float* x, int
     ClsLayer& L = m->cls[l];
     GemmFold fold;   // (fused: the layer's row-wise kernel folds the product's split-K slabs itself)
     GemmFold* defer = cnet_fuse() ? &fold : nullptr;
-    if ((L.x_form & 3) && gemm_f16_on()) {   // two-plane fp16 form: the weight matrix's magnitude (forward and input gradient share it)
-      float* rw = L.am.f() + 2 * AMAX_REC;
-      const bool have = !training && g_static_weights && L.am_w_gen == g_static_gen && L.am_w_of == w;
-      if (!have) FR_TRY(tensor_absmax(w + L.w_off, (long)L.n * L.in, rw, s));
-      L.am_w_of = w; L.am_w_gen = training ? -1 : g_static_gen;
-    } else {
-      L.am_w_of = nullptr;   // no record from THIS forward pass: the input-gradient product must not scale by an older step's
-    }
-    if ((L.x_form & 1) && gemm_f16_on()) {   // two fp16 planes of the input, scaled by its largest magnitude
-      float* rx = L.am.f();
-      FR_TRY(tensor_absmax(cur, (long)R * L.in, rx, s));
-      FR_TRY(split_planes(cur, R, L.in, L.xp.p, nullptr, s, rx));
-      FR_TRY(linear_x_forward(L.xp.p, R, L.in, w + L.w_off, w + L.b_off, L.n, L.lin.f(), s, 0, defer, rx, rx + 2 * AMAX_REC));
-    } else if (L.x_form & 1) {   // split-bf16 operand form: the input's planes once
-      FR_TRY(split_planes(cur, R, L.in, L.xp.p, nullptr, s));
-      FR_TRY(linear_x_forward(L.xp.p, R, L.in, w + L.w_off, w + L.b_off, L.n, L.lin.f(), s, 0, defer));
-    } else {
-      FR_TRY(gemm_f32(cur, L.in, 1, w + L.w_off, 1, L.in, L.lin.f(), L.n, R, L.n, L.in, OUT_STORE, w + L.b_off, s, 0, defer));
-    }
+    // (evaluate mode under static_weights: the weight matrix's magnitude record is kept within one generation)
+    FR_TRY(L.fc.forward(cur, w + L.w_off, w + L.b_off, L.lin.f(), (!training && g_static_weights) ? g_static_gen : -1, s, 0, defer));
     if (L.bn) FR_CHECK(training || bnr, "cnet_forward: evaluate mode needs bn_running");
     const float* mask = nullptr;
     float inv_keep = 1.f;
@@ -1999,39 +1966,9 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
     FR_TRY(fork());   // L.g is final
     const float* in = l == 0 ? m->cnet_x : m->cls[l - 1].post.f();
     float* gin = l == 0 ? gx : L.gin.f();
-    const bool xw = (L.x_form & 4) != 0, xd = (L.x_form & 2) != 0 && gin;
-    // chain: the gradient's planes (row-major orientation) and the input-gradient product
-    if (xd && gemm_f16_on() && L.am_w_of == w) {   // (the weight record of this step's forward pass)
-      float* rg = L.am.f() + AMAX_REC;
-      FR_TRY(tensor_absmax(L.g.f(), (long)R * L.n, rg, s));
-      FR_TRY(split_planes(L.g.f(), R, L.n, L.gp.p, nullptr, s, rg));
-      FR_TRY(linear_x_dgrad(L.gp.p, R, L.n, w + L.w_off, L.in, gin, OUT_STORE, s, 0, gdefer, rg, L.am.f() + 2 * AMAX_REC));
-    } else if (xd) {
-      FR_TRY(split_planes(L.g.f(), R, L.n, L.gp.p, nullptr, s));
-      FR_TRY(linear_x_dgrad(L.gp.p, R, L.n, w + L.w_off, L.in, gin, OUT_STORE, s, 0, gdefer));
-    } else if (gin) {
-      FR_TRY(gemm_f32(L.g.f(), L.n, 1, w + L.w_off, L.in, 1, gin, L.in, R, L.in, L.n, OUT_STORE, nullptr, s, 0, gdefer));
-    }
-    // beside it: the weight gradient (planes in the transposed orientation) and the bias sums
-    static const bool wgrad_f16 = env_flag("FRCNN_GEMM_WGRAD_F16", true);
-    if (xw && wgrad_f16 && gemm_f16_on() && L.am.bytes >= (size_t)5 * AMAX_REC * 4) {
-      // two fp16 planes per operand here too (round 6; three products instead of six): both tensors' magnitudes are taken on this
-      // stream (records 3 and 4 of the layer: the weight-gradient stream forked before the chain took its own)
-      float *rgT = L.am.f() + 3 * AMAX_REC, *rxT = L.am.f() + 4 * AMAX_REC;
-      FR_TRY(tensor_absmax(L.g.f(), (long)R * L.n, rgT, ws));
-      if ((L.x_form & 1) && L.am_w_of == w) rxT = L.am.f();   // (this step's forward pass took the input's magnitude for its own planes)
-      else FR_TRY(tensor_absmax(in, (long)R * L.in, rxT, ws));
-      FR_TRY(split_planes(L.g.f(), R, L.n, nullptr, L.gpT.p, ws, rgT));
-      FR_TRY(split_planes(in, R, L.in, nullptr, L.xpT.p, ws, rxT));
-      FR_TRY(linear_x_wgrad(L.gpT.p, L.xpT.p, R, L.n, L.in, grad + L.w_off, ws, wslot, rgT, rxT));
-    } else if (xw) {
-      FR_TRY(split_planes(L.g.f(), R, L.n, nullptr, L.gpT.p, ws));
-      FR_TRY(split_planes(in, R, L.in, nullptr, L.xpT.p, ws));
-      FR_TRY(linear_x_wgrad(L.gpT.p, L.xpT.p, R, L.n, L.in, grad + L.w_off, ws, wslot));
-    } else {
-      FR_TRY(gemm_f32(L.g.f(), 1, L.n, in, L.in, 1, grad + L.w_off, L.in, L.n, L.in, R, OUT_ADD, nullptr, ws, wslot));
-    }
-    FR_TRY(channel_sum_cols(L.g.f(), R, L.n, grad + L.b_off, ws));
+    // chain: the input-gradient product; beside it: the weight gradient and the bias sums
+    FR_TRY(L.fc.dgrad(L.g.f(), w + L.w_off, gin, s, 0, gdefer));
+    FR_TRY(L.fc.wgrad(L.g.f(), in, w + L.w_off, grad + L.w_off, grad + L.b_off, ws, wslot));
     g = gin;
   }
   if (m->cls.empty() && gx) FR_HIP(hipMemcpyAsync(gx, g, (size_t)R * m->D * 4, hipMemcpyDeviceToDevice, s));

@@ -495,6 +495,9 @@ int frcnn_rpn_loss(const float *const *maps_host, float *const *deltas_host, con
 int frcnn_loss_accumulate(const double *ex_loss, int E, double *acc, void *stream);
 
 /* ---- nn.Linear (models/model_utilities.lua:82,99,103) -------------------------------- */
+/* The products of one layer exactly as the classification net runs them (both run csrc/linear.h): fp32, or at large shapes
+ * three bf16 planes or, with option x3_f16, two fp16 planes; FRCNN_GEMM_F16=0 / FRCNN_GEMM_WGRAD_F16=0 hold here as there.
+ * Scratch for the requested roles is allocated and freed by the call; a call that took a split form synchronises the stream. */
 int frcnn_linear_forward(const float *x, int R, int I, const float *weight, const float *bias,
                          int O, float *y, void *stream);
 /* gx (may be NULL) = gy W ; gweight += gy^T x ; gbias += colsum(gy) (either may be NULL) */

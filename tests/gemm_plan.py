@@ -1,7 +1,8 @@
 """The case tables of tests/test_gpu_gemm_plans.py and a plain restatement of the host-side shape rules of the two files
 that compute every nn.Linear of the classification net: csrc/gemm.hip (gemm_f32: the fp32 matrix-core product) and
 csrc/gemmx.hip (gx_plan / gx_run / gemm_planes_kernel: the split-operand product), for the three products of
-Linear(R rows, I inputs, O outputs) as api.cpp frcnn_linear_forward / frcnn_linear_backward issue them.
+Linear(R rows, I inputs, O outputs) as csrc/linear.h issues them -- for the entry points frcnn_linear_forward /
+frcnn_linear_backward, which the GPU cases call, and for the classification net alike: both run that one header.
 
 As in tests/conv_plan.py, tests/convx_plan.py, tests/width_plan.py and tests/cnet_plan.py the restatement only LABELS the
 GPU cases with the branches they reach, so that tests/test_gemm_plan.py can check that the tables still reach every one of
@@ -28,7 +29,7 @@ EDGE_SIZES = (1, 4, 63, 64, 65)
 
 
 def f32_product(role, R, I, O):
-    """the call api.cpp makes: M, N, K, the four strides, and what becomes of the result"""
+    """the call linear.h makes: M, N, K, the four strides, and what becomes of the result"""
     if role == "forward":
         return dict(M=R, N=O, K=I, sAm=I, sAk=1, sBk=1, sBn=I, bias=True, add=False, a="x", b="w")
     if role == "input_gradient":

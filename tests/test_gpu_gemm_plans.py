@@ -1,7 +1,9 @@
 """The two products behind every nn.Linear of the classification net across their launch plans, through
 frcnn_linear_forward / frcnn_linear_backward: csrc/gemm.hip (gemm_f32, option gemm_x_roles = 0) and csrc/gemmx.hip
 (gemm_planes_kernel with split_planes_kernel and the slab fold, gemm_x_roles = 7, in both operand forms of option x3_f16:
-three bf16 planes / two fp16 planes; the weight gradient in the form the model runs, with magnitude records of gY and X).
+three bf16 planes / two fp16 planes; the weight gradient with magnitude records of gY and X).  The entry points and the
+classification net both run csrc/linear.h: what is tested here is what a training step executes
+(tests/test_gpu_linear_shared.py compares the two bit for bit, tests/test_linear_host.py checks the launch sequences).
 tests/gemm_plan.py holds the case tables and says which plan each case takes; tests/test_gemm_plan.py checks the tables
 without a GPU.
 
