@@ -21,10 +21,10 @@ from . import t7, traindata
 from .t7 import load_obj, restore_weights, save_model, save_obj
 from .synthetic import Roi, SyntheticBatchIterator, assemble_examples, clean_examples, output_map_sizes, synthetic_image, synthetic_rois
 from .tensor import DeviceTensor, ptr, stream_ptr, to_device
-from .utilities import combine_and_flatten_parameters, nag, optimizer, rmsprop, sgd
+from .utilities import adam, combine_and_flatten_parameters, nag, optimizer, rmsprop, sgd
 from .vgg_large import vgg_large
 from .vgg_small import vgg_small
 
 __all__ = ["Comm", "comm", "evaluation", "evaluate_detections", "mean_average_precision", "mean_average_precision_range", "proposal_recall", "validation_losses", "decode_image", "traindata", "t7", "load_obj", "restore_weights", "save_model", "save_obj", "BatchIterator", "find_target_size", "gaussian1D", "allreduce_begin", "allreduce_begin_rest", "Anchors", "Detector", "DeviceTensor", "FrcnnError", "Localizer", "MT19937", "Rect", "combine_and_flatten_parameters",
-           "create_model", "create_objective", "duplo_cfg", "extract_roi_pooling_input", "imgnet_cfg", "manualSeed", "nag", "nms", "soft_nms", "box_vote",
+           "adam", "create_model", "create_objective", "duplo_cfg", "extract_roi_pooling_input", "imgnet_cfg", "manualSeed", "nag", "nms", "soft_nms", "box_vote",
            "optimizer", "rmsprop", "sgd", "roi_pooling_settings", "roi_window", "roi_windows", "vgg_large", "vgg_small"]

@@ -123,6 +123,9 @@ _SIGS = {
     "frcnn_sgd_slice_dev": ([vp, vp, vp, C.c_longlong, C.c_longlong, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                             vp], C.c_int),
     "frcnn_nag_slice_dev": ([vp, vp, vp, C.c_longlong, C.c_longlong, vp, C.c_float, C.c_float, C.c_float, C.c_int, vp], C.c_int),
+    "frcnn_adam": ([vp, vp, vp, vp, C.c_longlong, C.c_float, vp] + [C.c_float] * 8 + [vp], C.c_int),
+    "frcnn_adam_slice": ([vp, vp, vp, vp, C.c_longlong, C.c_longlong, C.c_float] + [C.c_float] * 8 + [vp], C.c_int),
+    "frcnn_adam_slice_dev": ([vp, vp, vp, vp, C.c_longlong, C.c_longlong, vp] + [C.c_float] * 8 + [vp], C.c_int),
     "frcnn_grad_clip_workspace_bytes": ([C.c_longlong], C.c_size_t),
     "frcnn_grad_clip": ([vp, C.c_longlong, vp, C.c_int, C.c_double, vp, C.c_double, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_nag_lookahead": ([vp, vp, C.c_longlong, C.c_float, vp], C.c_int),

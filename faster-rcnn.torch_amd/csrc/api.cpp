@@ -581,6 +581,25 @@ int frcnn_nag_slice_dev(float* x, float* g, float* v, long long lo, long long hi
   FR_CHECK(gcount_dev, "frcnn_nag_slice_dev: NULL divisor");
   return nag_update(x, g, v, lo, hi, true, 1.f, gcount_dev, clr, wd, mom, first != 0, S(stream));
 }
+// optim.adam (optim/adam.lua; decay: AdamW)
+int frcnn_adam(float* x, float* g, float* m, float* v, long long n, float gscale, const double* gcount_dev, float step, float beta1,
+               float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay, void* stream) {
+  FR_CHECK(n >= 0, "frcnn_adam: bad length %lld", n);
+  return adam_update(x, g, m, v, 0, n, false, gscale, gcount_dev, step, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, wd,
+                     decay, S(stream));
+}
+int frcnn_adam_slice(float* x, float* g, float* m, float* v, long long lo, long long hi, float gscale, float step, float beta1,
+                     float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay, void* stream) {
+  return adam_update(x, g, m, v, lo, hi, true, gscale, nullptr, step, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, wd,
+                     decay, S(stream));
+}
+int frcnn_adam_slice_dev(float* x, float* g, float* m, float* v, long long lo, long long hi, const double* gcount_dev, float step,
+                         float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay,
+                         void* stream) {
+  FR_CHECK(gcount_dev, "frcnn_adam_slice_dev: NULL divisor");
+  return adam_update(x, g, m, v, lo, hi, true, 1.f, gcount_dev, step, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, wd,
+                     decay, S(stream));
+}
 size_t frcnn_grad_clip_workspace_bytes(long long n) { return grad_clip_workspace_bytes(n); }
 int frcnn_grad_clip(float* g, long long n, const long long* ranges_host, int nranges, double divisor, const double* divisor_dev,
                     double clip_norm, double* record_dev, void* workspace, size_t workspace_bytes, void* stream) {

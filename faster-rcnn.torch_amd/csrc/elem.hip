@@ -584,12 +584,14 @@ int dropout_mask(float* mask, long n, float p, unsigned long long seed, hipStrea
   return FRCNN_OK;
 }
 
-// ---------------------------------------------------------------- optim.rmsprop / optim.sgd / optim.nag
-// The three optimisers of main.lua:122-124,133-135 on the flat vectors: HBM-bound passes of 3 to 6 fp32 streams.
-// x = weights, g = the gradient the objective returned, v = the optimiser's state (rmsprop's m, state.dfdx of sgd and nag).
+// ---------------------------------------------------------------- optim.rmsprop / optim.sgd / optim.nag / optim.adam
+// The three optimisers of main.lua:122-124,133-135 on the flat vectors, and optim.adam beside them: HBM-bound passes of 3 to 8
+// fp32 streams.  x = weights, g = the gradient the objective returned, v = the optimiser's state (rmsprop's m, state.dfdx of sgd
+// and nag, adam's state.m), v2 = a second state vector where the Op declares one (kStates == 2: adam's state.v).
 // The contract, stated once:
 //   - one element of each update is ONE inline function (an Op's operator()), every Lua statement one separately rounded
-//     fp32 operation (fp contract off), its variants template parameters and not per-element branches;
+//     fp32 operation (fp contract off), its variants template parameters and not per-element branches; an Op with
+//     kStates == 2 takes (x, g, v, v2) and always reads and writes v2, one with kStates == 1 takes (x, g, v);
 //   - ONE kernel, optim_kernel<Op>, applies it to any range [lo, hi) of 16-byte aligned vectors, and the whole vector is the
 //     range [0, n) of that kernel.  So an update applied slice by slice (beside the backward pass, as slices of the gradient
 //     become final) leaves the same bits as one pass over the whole vector, wherever a slice boundary falls.
@@ -601,6 +603,7 @@ int dropout_mask(float* mask, long n, float p, unsigned long long seed, hipStrea
 template <bool SCALE>
 struct RmspropOp {
   static constexpr bool kScale = SCALE, kReadV = true, kWriteV = true, kWriteG = SCALE;
+  static constexpr int kStates = 1;
   static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV;   // fp32 streams moved per element
   float gscale, lr, alpha, oma, eps;   // oma = 1 - alpha
   __device__ __forceinline__ void operator()(float& x, float& g, float& m) const {
@@ -616,6 +619,7 @@ struct RmspropOp {
 template <bool SCALE, bool WD, int MOM, bool NEST>
 struct SgdOp {
   static constexpr bool kScale = SCALE, kReadV = MOM == 2, kWriteV = MOM != 0, kWriteG = SCALE || WD || NEST;
+  static constexpr int kStates = 1;
   static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV;   // fp32 streams moved per element
   float gscale, clr, wd, mom, omd;   // omd = 1 - dampening
   __device__ __forceinline__ void operator()(float& x, float& g, float& v) const {
@@ -638,6 +642,7 @@ struct SgdOp {
 template <bool SCALE, bool WD, bool FIRST>
 struct NagOp {
   static constexpr bool kScale = SCALE, kReadV = !FIRST, kWriteV = true, kWriteG = SCALE || WD;
+  static constexpr int kStates = 1;
   static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV;
   float gscale, clr, wd, mom;
   __device__ __forceinline__ void operator()(float& x, float& g, float& v) const {
@@ -650,33 +655,72 @@ struct NagOp {
   }
 };
 
+// optim.adam (optim/adam.lua), with AdamW's decoupled decay beside Torch's coupled one:  g *= gscale ; g += wd*x (WD == 1) ;
+// m = m*beta1 + (1-beta1)*g ; v = v*beta2 + ((1-beta2)*g)*g ; denom = sqrt(v) + eps ; x += ndecay*x (WD == 2) ;
+// x += (nstep*m)/denom.  nstep = -stepSize (the bias corrections folded in on the host, as adam.lua does), ndecay =
+// -(clr*weightDecay).  m travels as v, v as v2; both are read and written on every step (the host creates them as zeros, as
+// Torch does), state.denom is not kept.  7 fp32 streams, 8 where g is written back.
+template <bool SCALE, int WD>
+struct AdamOp {
+  static constexpr bool kScale = SCALE, kReadV = true, kWriteV = true, kWriteG = SCALE || WD == 1;
+  static constexpr int kStates = 2;
+  static constexpr int kStreams = 2 + kReadV + 1 + kWriteG + kWriteV + 2;   // (+ 2: v2 read and written)
+  float gscale, nstep, beta1, omb1, beta2, omb2, eps, wd, ndecay;   // omb = 1 - beta
+  __device__ __forceinline__ void operator()(float& x, float& g, float& m, float& v) const {
+#pragma clang fp contract(off)
+    if (SCALE) g = g * gscale;                   // gradient:div(n) (objective.lua:200)
+    if (WD == 1) g = g + wd * x;                 // dfdx:add(wd, x)
+    m = m * beta1 + omb1 * g;                    // state.m:mul(beta1):add(1-beta1, dfdx)
+    v = v * beta2 + (omb2 * g) * g;              // state.v:mul(beta2):addcmul(1-beta2, dfdx, dfdx)
+    const float d = sqrtf(v) + eps;              // state.denom:copy(state.v):sqrt():add(epsilon)
+    if (WD == 2) x = x + ndecay * x;             // AdamW: the decay leaves the gradient and the moments alone
+    x = x + (nstep * m) / d;                     // x:addcdiv(-stepSize, state.m, state.denom)
+  }
+};
+
 template <class Op>
-__device__ __forceinline__ void optim_four(float4* x4, float4* g4, float4* v4, long i, const Op& op) {
+__device__ __forceinline__ void optim_four(float4* x4, float4* g4, float4* v4, float4* u4, long i, const Op& op) {
   float4 xv = x4[i], gv = g4[i], vv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (Op::kReadV) vv = v4[i];
-  op(xv.x, gv.x, vv.x);
-  op(xv.y, gv.y, vv.y);
-  op(xv.z, gv.z, vv.z);
-  op(xv.w, gv.w, vv.w);
+  if constexpr (Op::kStates == 2) {
+    float4 uv = u4[i];
+    op(xv.x, gv.x, vv.x, uv.x);
+    op(xv.y, gv.y, vv.y, uv.y);
+    op(xv.z, gv.z, vv.z, uv.z);
+    op(xv.w, gv.w, vv.w, uv.w);
+    u4[i] = uv;
+  } else {
+    op(xv.x, gv.x, vv.x);
+    op(xv.y, gv.y, vv.y);
+    op(xv.z, gv.z, vv.z);
+    op(xv.w, gv.w, vv.w);
+  }
   if (Op::kWriteG) g4[i] = gv;
   if (Op::kWriteV) v4[i] = vv;
   x4[i] = xv;
 }
 template <class Op>
-__device__ __forceinline__ void optim_scalar(float* x, float* g, float* v, long i, const Op& op) {
+__device__ __forceinline__ void optim_scalar(float* x, float* g, float* v, float* u, long i, const Op& op) {
   float xi = x[i], gi = g[i], vi = 0.f;
   if (Op::kReadV) vi = v[i];
-  op(xi, gi, vi);
+  if constexpr (Op::kStates == 2) {
+    float ui = u[i];
+    op(xi, gi, vi, ui);
+    u[i] = ui;
+  } else {
+    op(xi, gi, vi);
+  }
   if (Op::kWriteG) g[i] = gi;
   if (Op::kWriteV) v[i] = vi;
   x[i] = xi;
 }
 
 // elements [lo, hi) of 16-byte aligned vectors: 16-byte groups grid-stride where the range covers them whole, the up to three
-// elements in front of the first and behind the last such group one by one (thread t < 8 of block 0)
+// elements in front of the first and behind the last such group one by one (thread t < 8 of block 0).  v2 comes last: an Op
+// with one state vector never looks at it, and the arguments it does read sit at the offsets they have without it
 template <class Op>
 __global__ void optim_kernel(float* __restrict__ x, float* __restrict__ g, float* __restrict__ v, long lo, long hi, Op op,
-                             const double* __restrict__ gcount) {
+                             const double* __restrict__ gcount, float* __restrict__ v2) {
   // gcount: the divisor of gradient:div (objective.lua:200) read from the device -- the all-reduced example count of a
   // data-parallel step, which no host has seen yet (a count of 0 leaves the gradient as it is)
   if (Op::kScale && gcount) { const double c = *gcount; op.gscale = c > 0.0 ? (float)(1.0 / c) : 1.0f; }
@@ -685,18 +729,19 @@ __global__ void optim_kernel(float* __restrict__ x, float* __restrict__ g, float
   float4* x4 = reinterpret_cast<float4*>(x + a);
   float4* g4 = reinterpret_cast<float4*>(g + a);
   float4* v4 = reinterpret_cast<float4*>(Op::kReadV || Op::kWriteV ? v + a : v);
+  float4* u4 = reinterpret_cast<float4*>(Op::kStates == 2 ? v2 + a : v2);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
-    optim_four(x4, g4, v4, i, op);
+    optim_four(x4, g4, v4, u4, i, op);
   if (blockIdx.x == 0 && threadIdx.x < 8) {
     const int t = threadIdx.x;
     const long i = t < 4 ? lo + t : b + (t - 4);
-    if (t < 4 ? i < a : i < hi) optim_scalar(x, g, v, i, op);
+    if (t < 4 ? i < a : i < hi) optim_scalar(x, g, v, v2, i, op);
   }
 }
 
 namespace {
 struct OptimRange {
-  float* x; float* g; float* v;
+  float* x; float* g; float* v; float* v2;   // v2: the second state vector of an Op with kStates == 2, else NULL
   long lo, hi;
   bool slice;             // a slice beside the backward pass (its grid capped lower) or the whole vector [0, hi)
   const double* gcount;   // the divisor on the device (NULL: the host's gscale)
@@ -710,7 +755,7 @@ int optim_launch(const Op& op, const OptimRange& r) {
   const double bytes = 4.0 * Op::kStreams * n;
   // a slice takes half the wave slots at most: it runs BESIDE other launches (the backward pass) and must not keep them waiting for slots
   const int grid = (int)std::min<long>(std::max<long>(1, cdivl(n / 4, 256)), r.slice ? 1024 : 2048);
-  FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op, r.gcount);
+  FR_LAUNCH(KC_OPTIM, 0, bytes, r.s, optim_kernel<Op>, dim3(grid), dim3(256), 0, r.x, r.g, r.v, r.lo, r.hi, op, r.gcount, r.v2);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
@@ -732,9 +777,9 @@ int nag_go(const OptimRange& r, float gscale, float clr, float wd, float mom, bo
                : optim_launch(NagOp<SCALE, WD, false>{gscale, clr, wd, mom}, r);
 }
 
-int optim_check(const char* what, const OptimRange& r, bool uses_v) {
-  FR_CHECK(r.x && r.g && (r.v || !uses_v), "%s: NULL vector", what);
-  FR_CHECK((((uintptr_t)r.x | (uintptr_t)r.g | (uintptr_t)r.v) & 15) == 0, "%s: the vectors must be 16-byte aligned", what);
+int optim_check(const char* what, const OptimRange& r, bool uses_v, bool uses_v2 = false) {
+  FR_CHECK(r.x && r.g && (r.v || !uses_v) && (r.v2 || !uses_v2), "%s: NULL vector", what);
+  FR_CHECK((((uintptr_t)r.x | (uintptr_t)r.g | (uintptr_t)r.v | (uintptr_t)r.v2) & 15) == 0, "%s: the vectors must be 16-byte aligned", what);
   FR_CHECK(r.lo >= 0 && r.lo <= r.hi, "%s: bad range [%ld, %ld)", what, r.lo, r.hi);
   return FRCNN_OK;
 }
@@ -742,7 +787,7 @@ int optim_check(const char* what, const OptimRange& r, bool uses_v) {
 
 int rmsprop_update(float* x, float* g, float* m, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float lr,
                    float alpha, float eps, hipStream_t s) {
-  const OptimRange r{x, g, m, lo, hi, slice, gcount_dev, s};
+  const OptimRange r{x, g, m, nullptr, lo, hi, slice, gcount_dev, s};
   FR_TRY(optim_check("rmsprop", r, true));
   const float oma = 1.0f - alpha;
   if (r.gcount || gscale != 1.f) return optim_launch(RmspropOp<true>{gscale, lr, alpha, oma, eps}, r);
@@ -751,7 +796,7 @@ int rmsprop_update(float* x, float* g, float* m, long lo, long hi, bool slice, f
 
 int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, float one_minus_damp, bool nesterov, bool first, hipStream_t s) {
-  const OptimRange r{x, g, mom != 0.f ? v : nullptr, lo, hi, slice, gcount_dev, s};
+  const OptimRange r{x, g, mom != 0.f ? v : nullptr, nullptr, lo, hi, slice, gcount_dev, s};
   FR_TRY(optim_check("sgd", r, mom != 0.f));
   FR_CHECK(!nesterov || (mom > 0.f && one_minus_damp == 1.f), "sgd: Nesterov momentum requires a momentum and zero dampening");
   const bool scale = r.gcount || gscale != 1.f;
@@ -764,12 +809,27 @@ int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float
 
 int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, bool first, hipStream_t s) {
-  const OptimRange r{x, g, v, lo, hi, slice, gcount_dev, s};
+  const OptimRange r{x, g, v, nullptr, lo, hi, slice, gcount_dev, s};
   FR_TRY(optim_check("nag", r, true));
   FR_CHECK(mom > 0.f, "nag: momentum must be positive for Nesterov Accelerated Gradient");
   const bool scale = r.gcount || gscale != 1.f;
   if (scale) return wd != 0.f ? nag_go<true, true>(r, gscale, clr, wd, mom, first) : nag_go<true, false>(r, gscale, clr, wd, mom, first);
   return wd != 0.f ? nag_go<false, true>(r, 1.f, clr, wd, mom, first) : nag_go<false, false>(r, 1.f, clr, wd, mom, first);
+}
+
+int adam_update(float* x, float* g, float* m, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev,
+                float step, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay,
+                hipStream_t s) {
+  const OptimRange r{x, g, m, v, lo, hi, slice, gcount_dev, s};
+  FR_TRY(optim_check("adam", r, true, true));
+  FR_CHECK(wd == 0.f || decay == 0.f, "adam: weight decay is either coupled (wd) or decoupled (decay), not both");
+  const bool scale = r.gcount || gscale != 1.f;
+  const float gs = scale ? gscale : 1.f;
+  const float nstep = -step, ndecay = -decay;   // both arrive positive, as Torch's stepSize and clr*weightDecay
+#define FR_ADAM(SCALE, WD) optim_launch(AdamOp<SCALE, WD>{gs, nstep, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, wd, ndecay}, r)
+  if (scale) return wd != 0.f ? FR_ADAM(true, 1) : decay != 0.f ? FR_ADAM(true, 2) : FR_ADAM(true, 0);
+  return wd != 0.f ? FR_ADAM(false, 1) : decay != 0.f ? FR_ADAM(false, 2) : FR_ADAM(false, 0);
+#undef FR_ADAM
 }
 
 // optim.nag's look-ahead before opfunc: x:add(mom, state.dfdx).  3 streams.

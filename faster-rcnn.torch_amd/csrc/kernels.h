@@ -162,6 +162,11 @@ int sgd_update(float* x, float* g, float* v, long lo, long hi, bool slice, float
 int nag_update(float* x, float* g, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev, float clr,
                float wd, float mom, bool first, hipStream_t s);
 int nag_lookahead(float* x, const float* v, long n, float mom, hipStream_t s);
+// optim.adam on the same kernel, with its two state vectors m and v.  step = Torch's stepSize, decay = clr * weightDecay of the
+// decoupled form (AdamW), both positive; wd = the coupled coefficient; wd and decay exclude each other.
+int adam_update(float* x, float* g, float* m, float* v, long lo, long hi, bool slice, float gscale, const double* gcount_dev,
+                float step, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay,
+                hipStream_t s);
 // the gradient guard (include/frcnn_hip.h "gradient-norm clipping"): the sum of squares of g over `ranges`, the clipped divisor
 // and the skip flag into record[4], g zero-filled over `ranges` when the sum is not finite.  Three launches on s.
 constexpr int GRAD_CLIP_MAX_RANGES = 16;

@@ -298,11 +298,73 @@ def nag(opfunc, x, config, state=None):
     return r
 
 
+def adam(opfunc, x, config, state=None):
+    """optim.adam(opfunc, x, config[, state]) [ext] (Torch's optim/adam.lua): config.learningRate (1e-3), learningRateDecay (0),
+    beta1 (0.9), beta2 (0.999), epsilon (1e-8), weightDecay (0), and decoupled (False; not in Torch: weightDecay becomes
+    AdamW's decay x -= clr*weightDecay*x, which the gradient and the moments never see, instead of Torch's g += wd*x).
+    m = m*beta1 + (1-beta1)*g ; v = v*beta2 + (1-beta2)*g*g ; x -= stepSize * m / (sqrt(v) + eps) with
+    clr = lr / (1 + t*lrd), t += 1, stepSize = clr * sqrt(1 - beta2^t) / (1 - beta1^t); state["t"], state["m"], state["v"]
+    (zeros before the first step).  One pass of frcnn_adam.  Bad values raise ValueError before x or opfunc is touched; a
+    step that raises leaves the state as it was.  Returns x, [f(x)] like the Lua function."""
+    import math
+    import torch
+    state = config if state is None else state
+    lr = _get(config, "learningRate", 1e-3); lrd = _get(config, "learningRateDecay", 0)
+    beta1 = _get(config, "beta1", 0.9); beta2 = _get(config, "beta2", 0.999)
+    eps = _get(config, "epsilon", 1e-8); wd = _get(config, "weightDecay", 0)
+    decoupled = _get(config, "decoupled", False)
+    for key, beta in (("beta1", beta1), ("beta2", beta2)):
+        if not 0 <= beta < 1:
+            raise ValueError("optim.adam: %s must lie in [0, 1), not %r" % (key, beta))
+    if not eps > 0:
+        raise ValueError("optim.adam: epsilon must be positive, not %r" % (eps,))
+    if not lr >= 0:
+        raise ValueError("optim.adam: learningRate must not be negative, not %r" % (lr,))
+    if not wd >= 0:
+        raise ValueError("optim.adam: weightDecay must not be negative, not %r" % (wd,))
+    if not isinstance(decoupled, (bool, np.bool_)):
+        raise ValueError("optim.adam: decoupled must be a boolean, not %r" % (decoupled,))
+    _no_per_parameter(config, "adam")
+    guard = _guard_config(config, state, "adam")
+    t = state.get("t") or 0
+    clr = lr / (1 + t * lrd)                # host scalars in double, as Lua computes them (the t from before the increment)
+    t += 1
+    bc1 = 1 - beta1 ** t
+    bc2 = 1 - beta2 ** t
+    step = clr * math.sqrt(bc2) / bc1
+    coupled, decay = (0.0, clr * wd) if decoupled else (wd, 0.0)
+    created = [key for key in ("m", "v") if key not in state]
+    for key in created:
+        state[key] = torch.zeros_like(x)    # (zeros always: every step reads both, and a frozen slice keeps them)
+    m, v = state["m"], state["v"]
+    args = (step, beta1, 1 - beta1, beta2, 1 - beta2, eps, coupled, decay)
+
+    def whole(dfdx, gscale):
+        gs, gcount = _fold_args(gscale)
+        _lib.call("frcnn_adam", ptr(x), ptr(dfdx), ptr(m), ptr(v), x.numel(), gs, gcount, *args, stream_ptr())
+
+    def update(w, g, lo, hi, gscale, on):
+        if hasattr(gscale, "ptr"):
+            _lib.call("frcnn_adam_slice_dev", ptr(w), ptr(g), ptr(m), ptr(v), lo, hi, ptr(gscale.ptr), *args, on)
+        else:
+            _lib.call("frcnn_adam_slice", ptr(w), ptr(g), ptr(m), ptr(v), lo, hi, gscale, *args, on)
+    try:
+        r = _step(opfunc, x, state, whole, update, guard)
+    except BaseException:
+        for key in created:
+            del state[key]
+        raise
+    state["t"] = t
+    return r
+
+
 _OPTIMIZERS = dict(rmsprop=rmsprop, sgd=sgd, nag=nag)
 
 
 def optimizer(name):
-    """The optimiser function for a value of main.lua's -opti (main.lua:35): 'rmsprop' (its default), 'sgd' or 'nag'."""
+    """The optimiser function for a value of main.lua's -opti (main.lua:35): 'rmsprop' (its default), 'sgd' or 'nag'.
+    This stays the table of main.lua's values: optim.adam is not one of them, so optimizer("adam") raises ValueError --
+    call F.adam directly."""
     try:
         return _OPTIMIZERS[name]
     except KeyError:

@@ -556,6 +556,34 @@ int frcnn_sgd_slice_dev(float *x, float *g, float *v, long long lo, long long hi
 int frcnn_nag_slice_dev(float *x, float *g, float *v, long long lo, long long hi, const double *gcount_dev, float clr,
                         float wd, float mom, int first, void *stream);
 
+/* ---- optim.adam (Torch's optim/adam.lua; not among main.lua's -opti values), with AdamW's decoupled weight decay beside it ----
+ * One step on the flat vectors through the kernel of the three optimisers above, every Lua statement one separately rounded
+ * fp32 operation.  x = weights, g = the gradient the objective returned, m = state.m, v = state.v (n floats each; the host
+ * creates both as zeros, as Torch does, and every step reads and writes both: there is no first-step form).  The host keeps
+ * state.t and computes in double, as Lua does: clr = learningRate / (1 + t * learningRateDecay) with the t from before the
+ * increment, then with t + 1: step = clr * sqrt(1 - beta2^t) / (1 - beta1^t), Torch's stepSize.  The divisor of gradient:div
+ * rides on the pass as in frcnn_sgd (gscale, or 1 / *gcount_dev when gcount_dev is not NULL; gscale = 1 or a count of 0: g
+ * unscaled).  Per element, in this order:
+ *   g += wd*x                                   (wd != 0: Torch's coupled L2 decay)
+ *   m = m*beta1 + one_minus_beta1*g ;  v = v*beta2 + (one_minus_beta2*g)*g ;  denom = sqrt(v) + eps (not kept)
+ *   x += -decay*x                               (decay != 0: AdamW, decay = clr * weightDecay; g, m and v never see it)
+ *   x += (-step*m)/denom
+ * step and decay arrive positive.  wd and decay exclude each other (both non-zero: an error).  g is left holding what Torch
+ * leaves in it: written back only where it was scaled or wd != 0.  x, g, m, v: 16-byte aligned, none NULL.  Argument errors are
+ * reported before anything is queued; an empty range succeeds and writes nothing. */
+int frcnn_adam(float *x, float *g, float *m, float *v, long long n, float gscale, const double *gcount_dev, float step,
+               float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay,
+               void *stream);
+/* frcnn_adam on elements [lo, hi) of the vectors only (x, g, m, v = the STARTS of the flat vectors; any bounds): what the
+ * whole-vector call does to that slice, bit for bit -- staged training and the update beside the backward pass (below). */
+int frcnn_adam_slice(float *x, float *g, float *m, float *v, long long lo, long long hi, float gscale, float step,
+                     float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float wd, float decay,
+                     void *stream);
+/* The slice form with the divisor read from the device (not NULL): what frcnn_adam with that gcount_dev does to [lo, hi). */
+int frcnn_adam_slice_dev(float *x, float *g, float *m, float *v, long long lo, long long hi, const double *gcount_dev,
+                         float step, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                         float wd, float decay, void *stream);
+
 /* ---- gradient-norm clipping and the non-finite-step guard (not in the reference: main.lua:133-135 applies whatever the pass
  * produced).  Queued between the pass (and the all-reduce, when data parallel) and the optimiser's update; off unless a host
  * asks for it.  g = the flat gradient, T = the trainable slices of the pass (ranges_host: nranges sorted, disjoint pairs
@@ -568,10 +596,11 @@ int frcnn_nag_slice_dev(float *x, float *g, float *v, long long lo, long long hi
  *   norm  = sqrt(S) / D: the L2 norm of the gradient the optimiser is about to see.
  *   D'    = D * max(1, norm / clip_norm) in fp64, each operation correctly rounded; clip_norm <= 0: D' = D (norm recorded,
  *           nothing clipped).  A CLIPPED STEP IS the optimiser's existing update with the device divisor D':
- *           frcnn_scale_rmsprop_dev / frcnn_sgd / frcnn_nag (or their _slice_dev forms) handed record_dev + 2.
+ *           frcnn_scale_rmsprop_dev / frcnn_sgd / frcnn_nag / frcnn_adam (or their _slice_dev forms) handed record_dev + 2.
  *   S not finite (inf or NaN; fp32 values as large as 3e38 have finite squares in fp64): the step treats the gradient as zero --
  *           g is overwritten with zeros on T (untouched elsewhere), D' = D, skipped = 1.  optim.rmsprop then leaves x as it
- *           is and decays m; optim.sgd / optim.nag continue on their momentum (and weight decay) alone.
+ *           is and decays m; optim.sgd / optim.nag continue on their momentum (and weight decay) alone, and so does
+ *           optim.adam on its moments m and v (and its weight decay, coupled or decoupled, if any).
  *   record_dev: double[4] = {S, norm, D', skipped} on the device; a host reads it when it reads its loss sums.
  * workspace: frcnn_grad_clip_workspace_bytes(n) bytes of device memory (the per-block partials).  Three launches on `stream`;
  * argument errors are reported before anything is queued. */

@@ -1,6 +1,6 @@
 """The optimiser passes alone on vgg_small's flat vector (26 784 106 parameters): HIP-event time of each whole-vector form of
-optim.rmsprop / optim.sgd / optim.nag (main.lua:122-124,133-135) and the effective bytes/s of the fp32 streams it moves
-(read x, g[, v]; write x[, g][, v]); the gradient guard (frcnn_grad_clip: one more read of g, two small launches behind it)
+optim.rmsprop / optim.sgd / optim.nag (main.lua:122-124,133-135) and optim.adam, and the effective bytes/s of the fp32 streams it
+moves (read x, g[, v]; write x[, g][, v]; adam reads and writes two state vectors); the gradient guard (frcnn_grad_clip: one more read of g, two small launches behind it)
 alone and in front of each optimiser's pass, which then takes its divisor from the guard's record.
 python tools/bench_optim.py [--n N] [--reps R] [--json FILE]"""
 import argparse
@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 import frcnn_amd as F
 
 
-def forms(x, g, v, gc, n, s):
+def forms(x, g, v, v2, gc, n, s):
     """(name, fp32 streams per element, launch) -- the streams as the kernels move them"""
     import torch
     P = F.ptr
@@ -28,6 +28,9 @@ def forms(x, g, v, gc, n, s):
     sgd = lambda gs, gcount, wd, mom, omd, nest, first: (
         lambda: F._lib.call("frcnn_sgd", P(x), P(g), P(v) if mom else None, n, gs, gcount, 1e-9, wd, mom, omd, nest, first, s))
     nag = lambda gs, wd, first: (lambda: F._lib.call("frcnn_nag", P(x), P(g), P(v), n, gs, None, 1e-9, wd, 0.9, first, s))
+    # optim.adam: m travels in v, v in v2 (non-negative, and it stays so)
+    adam = lambda gs, wd, decay: (lambda: F._lib.call("frcnn_adam", P(x), P(g), P(v), P(v2), n, gs, None, 1e-9, 0.9, 0.1, 0.999, 1e-3, 1e-8,
+                                                      wd, decay, s))
     return [
         ("rmsprop, scaled (the default)", 6, lambda: F._lib.call("frcnn_scale_rmsprop", P(x), P(g), sc, P(v), n, 1e-9, 0.99, 1e-8, s)),
         ("sgd plain", 3, sgd(1.0, None, 0.0, 0.0, 1.0, 0, 0)),
@@ -44,6 +47,12 @@ def forms(x, g, v, gc, n, s):
         ("grad_clip + rmsprop", 7, guarded(lambda: F._lib.call("frcnn_scale_rmsprop_dev", P(x), P(g), dp, P(v), n, 1e-9, 0.99, 1e-8, s))),
         ("grad_clip + sgd sgd_state", 7, guarded(sgd(1.0, dp, 5e-4, 0.9, 0.1, 0, 0))),
         ("grad_clip + nag nag_state", 7, guarded(lambda: F._lib.call("frcnn_nag", P(x), P(g), P(v), n, 1.0, dp, 1e-9, 0.0, 0.9, 0, s))),
+        ("adam, unscaled", 7, adam(1.0, 0.0, 0.0)),
+        ("adam, scaled", 8, adam(sc, 0.0, 0.0)),
+        ("adam, scaled, coupled decay", 8, adam(sc, 5e-4, 0.0)),
+        ("adam, scaled, decoupled decay", 8, adam(sc, 0.0, 1e-9)),
+        ("adam slice, scaled", 8, lambda: F._lib.call("frcnn_adam_slice", P(x), P(g), P(v), P(v2), 5, n - 2, sc, 1e-9, 0.9, 0.1, 0.999, 1e-3,
+                                                      1e-8, 0.0, 0.0, s)),
     ]
 
 
@@ -59,10 +68,11 @@ def main():
     n = a.n
     # tiny steps and a scale factor of 1 + 2^-23 (1 itself selects the unscaled form) keep the vectors finite and normal
     x = torch.randn(n, device="cuda"); g = torch.randn(n, device="cuda") * 1e-3; v = torch.rand(n, device="cuda")
+    v2 = torch.rand(n, device="cuda")
     gc = torch.tensor([1.0], dtype=torch.float64, device="cuda")
     s = F.stream_ptr()
     rows = []
-    for name, streams, fn in forms(x, g, v, gc, n, s):
+    for name, streams, fn in forms(x, g, v, v2, gc, n, s):
         for _ in range(5):
             fn()
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
