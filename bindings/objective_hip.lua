@@ -43,6 +43,10 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
   local acc = hip.buffer(8 * 8)        -- {cls_loss, reg_loss, -, -, creg_loss, ccls_loss, -, -} as device doubles
   local acc_host = ffi.new('double[8]')
   local scratch = hip.scratch()
+  -- cfg.roi_sampling (INTEGRATION.md): under source = 'proposals' the classification net's rows are a sample of the first NMS's
+  -- candidates on the pass's own head maps (hip.sample_proposals: scan, selection, NMS, frcnn_proposal_targets_batch)
+  local rs_state = { images = 0 }
+  local keep_gt
   local keep                            -- host staging of the last example tables (must outlive the queued copy)
 
   local function cleanAnchors(examples, outputs)                        -- :32-43
@@ -73,6 +77,8 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     -- before anything is queued: a bad cfg.train raises here.  The library skips the frozen parts' work, this pass skips a
     -- disabled stage, the optimiser updates `ranges` only
     local frozen_blocks, proposal, classification, ranges = stage()
+    local rs = hip.roi_sampling_settings(cfg)         -- (validated, like cfg.train, before anything is queued)
+    if rs and (rs.source ~= 'proposals' or not classification) then rs = nil end
     check(C.frcnn_model_set_trainable(native, frozen_blocks, proposal and 1 or 0, classification and 1 or 0))
     published.pass = ranges
     if w ~= weights then weights:copy(w) end                            -- :46-48
@@ -87,7 +93,8 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     for _, x in ipairs(batch) do
       local img = hip.to_device(x.img)                                  -- :66
       local p, n = x.positive, x.negative
-      local outputs = pnet:forward(img, true)                           -- :71 (anchor nets stay in flight)
+      -- :71 (anchor nets stay in flight; sampled proposals: the scan reads their dense maps on this stream, so the pass waits)
+      local outputs = pnet:forward(img, rs == nil)
       cleanAnchors(p, outputs)                                          -- :74-75
       cleanAnchors(n, outputs)
       local delta_outputs = pnet:delta_outputs()                        -- :78-84
@@ -95,6 +102,19 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
       local E = npos + nneg
       local fm = outputs[nheads + 1]
       local fs = fm:size()
+
+      local F_rows = npos
+      local d_gt, d_gc, G
+      if rs then                                      -- the ground truth of the proposal-target layer, uploaded on this stream
+        local gt, gcls
+        gt, gcls, G = hip.ground_truth_table(x, cfg.class_count)
+        keep_gt = { gt, gcls }
+        local g1 = math.max(G, 1)
+        local dg = scratch('rs_gt', 36 * g1).ptr
+        check(C.frcnn_memcpy_h2d(dg, gt, 32 * g1, nil))
+        check(C.frcnn_memcpy_h2d(dg + 32 * g1, gcls, 4 * g1, nil))
+        d_gt, d_gc = ffi.cast('const double*', dg), ffi.cast('const int*', dg + 32 * g1)
+      end
 
       if E > 0 then
         -- ---- host: the example tables, one upload ----------------------------------------------
@@ -170,7 +190,9 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
                                              ffi.cast('const double*', dblob + o_anchor), ffi.cast('const double*', dblob + o_roi),
                                              ffi.cast('const int*', dblob + o_class), npos, nneg, bgclass, ex_loss, crtarget,
                                              cctarget, ffi.cast('double*', acc.ptr), nil))
-        if not classification then
+        if rs then
+          -- (the sampled-proposals stage below takes the place of the example rows)
+        elseif not classification then
           -- staged training without the detector stage: no ROI pooling, no cnet (dcls / dreg are NaN below); its dropout
           -- stream advances as its forward would advance it
           cnet.seed = (cnet.seed or 0) + 1
@@ -208,10 +230,61 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         for l = 1, nheads do check(C.frcnn_pnet_set_sparse_deltas(native, l, nil, 0)) end
       end
 
+      if rs then
+        -- ---- the classification net on sampled proposals: S = F + Bq rows, the first F regress; their rects are constants
+        if rs_state.aw == nil then
+          local anchors = Anchors.new(pnet, cfg.scales)
+          rs_state.aw, rs_state.ah = hip.to_device(anchors.w), hip.to_device(anchors.h)
+        end
+        local isz = img:size()
+        local rec = hip.sample_proposals(rs_state, rs, scratch, outputs, nheads, isz[3], isz[2], d_gt, d_gc, G, bgclass)
+        stats.rois = stats.rois or {}
+        table.insert(stats.rois, rec.counts)
+        F_rows = rec.counts[3]
+        local S = rec.counts[3] + rec.counts[4]
+        if S == 0 then
+          cnet.seed = (cnet.seed or 0) + 1
+          check(C.frcnn_pnet_anchor_loss_wait(native, nil))
+        else
+          local cinput = hip.view(scratch('cinput', 4 * S * D).ptr, { S, D })
+          local pidx
+          if align then
+            check(C.frcnn_roi_align_forward(fm.ptr, fs[1], fs[2], fs[3], rec.roi, nil, S, inv_sx, inv_sy, kh, kw, sampling,
+                                            cinput.ptr, nil))
+          else
+            local nl = #localizer.layers
+            local layers = ffi.new('int[?]', 6 * nl)
+            for i, l in ipairs(localizer.layers) do
+              local o = 6 * (i - 1)
+              layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
+            end
+            local dwins = ffi.cast('int*', scratch('rs_wins', 16 * S).ptr)
+            pidx = ffi.cast('int*', scratch('pidx', 4 * S * D).ptr)
+            check(C.frcnn_roi_windows(rec.roi, nil, S, layers, nl, fs[2], fs[3], dwins, nil))
+            check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], dwins, S, kh, kw, cinput.ptr, pidx, nil))
+          end
+          local coutputs = cnet:forward(cinput)
+          local crout, ccout = coutputs[1], coutputs[2]
+          local crdelta = hip.view(scratch('crdelta', 16 * S).ptr, { S, 4 })
+          local ccdelta = hip.view(scratch('ccdelta', 4 * S * ncls).ptr, { S, ncls })
+          check(C.frcnn_pnet_anchor_loss_wait(native, nil))
+          check(C.frcnn_cnet_losses(crout.ptr, rec.crtarget, ccout.ptr, rec.cctarget, S, F_rows, ncls, crdelta.ptr, ccdelta.ptr,
+                                    ffi.cast('double*', acc.ptr) + 4, nil))
+          local post_roi_delta = cnet:backward(cinput, { crdelta, ccdelta })
+          if frozen_blocks < nblocks and align then
+            check(C.frcnn_roi_align_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr, rec.roi, nil, S,
+                                             inv_sx, inv_sy, kh, kw, sampling, nil))
+          elseif frozen_blocks < nblocks then
+            check(C.frcnn_roi_pool_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr, pidx, S, kh, kw,
+                                            nil))
+          end
+        end
+      end
+
       pnet:backward(img, delta_outputs)                                 -- :189
       reg_count = reg_count + npos                                      -- :194-198
       cls_count = cls_count + npos + nneg
-      creg_count = creg_count + npos
+      creg_count = creg_count + F_rows                                  -- (sampled proposals: the foreground rows regress)
       ccls_count = ccls_count + 1
     end
 

@@ -509,7 +509,7 @@ class BatchIterator(object):
                 self.log("Warning: Skipping image '%s'. Invalid size after process: (%dx%d)" % (fn, w, h))
                 return 0
             positive, negative = assemble_examples(self.anchors, cfg, rois, w, h, self.rng)   # :198-225
-            batch.append(dict(img=img, positive=positive, negative=negative))
+            batch.append(dict(img=img, positive=positive, negative=negative, rois=rois))   # (rois: cfg.roi_sampling matches proposals to them)
             self.log("'%s' (%dx%d); p: %d; n: %d" % (fn, w, h, len(positive), len(negative)))
             return len(positive) + len(negative)
 
@@ -521,7 +521,7 @@ class BatchIterator(object):
                 _, h, w = img.shape
                 if h >= 128 and w >= 128:
                     negative = self.anchors.sampleNegative(Rect(0, 0, w, h), [], 0, int(math.floor(count * 0.05)), self.rng)
-                    batch.append(dict(img=img, positive=[], negative=negative))
+                    batch.append(dict(img=img, positive=[], negative=negative, rois=[]))
                     count -= len(negative)
         guard = 0
         while count > 0:

@@ -69,6 +69,8 @@ _SIGS = {
     "frcnn_topk_select": ([vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, C.c_longlong, vp, vp, C.c_size_t, vp], C.c_int),
     "frcnn_rpn_gather_rows": ([vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, vp, C.c_longlong, vp, C.c_int, vp, vp, vp, vp, vp, vp,
                               C.c_longlong, vp], C.c_int),
+    "frcnn_proposal_targets_batch": ([vp, vp, C.c_longlong, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_double, C.c_double,
+                                      C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp], C.c_int),
     "frcnn_detect_gather_batch": ([vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_roi_windows": ([vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp], C.c_int),
     "frcnn_detect_post": ([vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp], C.c_int),

@@ -198,6 +198,15 @@ int frcnn_rpn_gather_rows(const float* match_p, const int* match_idx, const doub
   return rpn_gather_rows(match_p, match_idx, match_rect, match_box, B, (long)src_stride, src_rows, sel_row, (long)sel_stride,
                          k_dev, k_cap, dst_p, dst_idx, dst_rect, dst_box, box5, row, (long)dst_stride, S(stream));
 }
+int frcnn_proposal_targets_batch(const double* rect, const long long* pick, long long match_stride, const int* r_dev, int r_cap,
+                                 const double* gt_rect, const int* gt_class, int gt_stride, const int* G_host, int B,
+                                 int include_gt, double fg_iou, double bg_lo, double bg_hi, int fg_quota, int batch, int bgclass,
+                                 unsigned int seed, double* roi, float* crtarget, float* cctarget, int* src, int* gt_idx,
+                                 double* iou, int out_stride, int* counts, void* stream) {
+  return proposal_targets_batch(rect, pick, match_stride, r_dev, r_cap, gt_rect, gt_class, gt_stride, G_host, B, include_gt, fg_iou,
+                                bg_lo, bg_hi, fg_quota, batch, bgclass, seed, roi, crtarget, cctarget, src, gt_idx, iou, out_stride,
+                                counts, S(stream));
+}
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,
                               const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {

@@ -315,6 +315,13 @@ int topk_select(const float* score, int B, long stride, int n_cap, const int* n_
 int rpn_gather_rows(const float* p, const int* idx, const double* rect, const float* box, int B, long src_stride, int src_rows,
                     const int* sel_row, long sel_stride, const int* k_dev, int k_cap, float* dst_p, int* dst_idx,
                     double* dst_rect, float* dst_box, float* box5, int* row, long dst_stride, hipStream_t s);
+// ---- the proposal-target layer of training on sampled proposals (proposal_targets.hip): B segments, one workgroup each;
+// semantics in include/frcnn_hip.h
+int proposal_targets_batch(const double* rect, const long long* pick, long long match_stride, const int* r_dev, int r_cap,
+                           const double* gt_rect, const int* gt_class, int gt_stride, const int* G_host, int B, int include_gt,
+                           double fg_iou, double bg_lo, double bg_hi, int fg_quota, int batch, int bgclass, unsigned seed,
+                           double* roi, float* crtarget, float* cctarget, int* src, int* gt_idx, double* iou, int out_stride,
+                           int* counts, hipStream_t s);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

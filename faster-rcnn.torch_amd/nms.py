@@ -5,7 +5,10 @@ which is what both call sites of the reference pass (Detector.lua:82,133) -- sor
 Returns the 1-based row ids of the survivors in pick order (a LongTensor in the reference).
 
 soft_nms(boxes, overlap, score_col, ...) -- not in the reference: Soft-NMS (Bodla et al. 2017) over frcnn_soft_nms_batch, the
-greedy loop that lowers the neighbours' scores instead of deleting them (semantics: include/frcnn_hip.h)."""
+greedy loop that lowers the neighbours' scores instead of deleting them (semantics: include/frcnn_hip.h).
+
+box_vote(boxes, picks, ...) and proposal_targets(rect, pick, R, gt_rect, gt_class, ...) -- not in the reference either: bounding-box
+voting (frcnn_box_vote_batch) and the proposal-target layer of training on sampled proposals (frcnn_proposal_targets_batch)."""
 import ctypes as C
 import math
 import numbers
@@ -164,3 +167,48 @@ def box_vote(boxes, picks, overlap=0.5, score_col=5, weights="score", classes=No
               C.c_float(overlap), ptr(cls) if cls is not None else None, ptr(rect) if rect is not None else None, ptr(dpick),
               C.c_void_p(ctl.ptr + 4), ptr(out), ptr(votes), stream_ptr())
     return out.numpy()[hp - 1].copy(), votes.numpy()[hp - 1].copy()
+
+
+def proposal_targets(rect, pick, R, gt_rect, gt_class, bgclass, include_gt=True, fg_iou=0.5, bg_iou=(0.0, 0.5), fg_quota=32,
+                     batch=128, seed=0, r_cap=None):
+    """The proposal-target layer of training on sampled proposals (cfg["roi_sampling"]; not in the reference) over
+    frcnn_proposal_targets_batch, one segment on host arrays: the candidates -- the ground-truth boxes first (include_gt), then
+    the first min(R, r_cap) of the 1-based rows `pick` of rect (n x 4 float64) -- are matched to gt_rect (G x 4 float64, classes
+    gt_class, 1-based) by Rect.IoU, labelled foreground (best IoU >= fg_iou), background (bg_iou[0] <= best IoU < bg_iou[1]) or
+    ignored, and thinned to at most fg_quota foreground and batch rows in all (a class over its quota keeps the rows with the
+    smallest keys of the seeded hash) -> dict(roi S x 4 float64, crtarget S x 4 float32, cctarget S float32, src, gt_idx S int32,
+    iou S float64, counts (nfg, nbg, F, Bq)) with S = F + Bq rows: the F foreground rows in candidate order, then the Bq background
+    rows.  r_cap: the post-NMS cap (default: every pick).  Runs on the device: there is no host twin (semantics:
+    include/frcnn_hip.h); a refused setting raises FrcnnError before anything is launched."""
+    rect = np.ascontiguousarray(rect, dtype=np.float64).reshape(-1, 4)
+    pick = np.ascontiguousarray(pick, dtype=np.int64).reshape(-1)
+    gt_rect = np.ascontiguousarray(gt_rect, dtype=np.float64).reshape(-1, 4)
+    gt_class = np.ascontiguousarray(gt_class, dtype=np.int32).reshape(-1)
+    if gt_class.shape[0] != gt_rect.shape[0]:
+        raise ValueError("proposal_targets: %d ground-truth boxes, %d classes" % (gt_rect.shape[0], gt_class.shape[0]))
+    if pick.size and (pick.min() < 1 or pick.max() > rect.shape[0]):
+        raise ValueError("proposal_targets: picks are 1-based rows of rect (picks in [%d, %d], %d rows)"
+                         % (pick.min(), pick.max(), rect.shape[0]))
+    r_cap = int(pick.size if r_cap is None else r_cap)
+    if r_cap > pick.size:
+        raise ValueError("proposal_targets: r_cap %d beyond the %d picks" % (r_cap, pick.size))
+    G, batch = int(gt_rect.shape[0]), int(batch)
+    rows = max(batch, 1)
+    d_rect = DeviceTensor.from_numpy(rect if rect.size else np.zeros((1, 4)))
+    d_pick = DeviceTensor.from_numpy(pick if pick.size else np.zeros(1, np.int64))
+    d_gt = DeviceTensor.from_numpy(gt_rect if G else np.zeros((1, 4)))
+    d_gc = DeviceTensor.from_numpy(gt_class if G else np.zeros(1, np.int32))
+    ctl = DeviceTensor.from_numpy(np.array([0, 0, 0, 0, int(R), 0, 0, 0], np.int32))     # counts, then the candidate count
+    out = dict(roi=DeviceTensor.empty((rows, 4), np.float64), crtarget=DeviceTensor.empty((rows, 4), np.float32),
+               cctarget=DeviceTensor.empty((rows,), np.float32), src=DeviceTensor.empty((rows,), np.int32),
+               gt_idx=DeviceTensor.empty((rows,), np.int32), iou=DeviceTensor.empty((rows,), np.float64))
+    _lib.call("frcnn_proposal_targets_batch", ptr(d_rect), ptr(d_pick), max(int(rect.shape[0]), r_cap), C.c_void_p(ctl.ptr + 16), r_cap,
+              ptr(d_gt), ptr(d_gc), G, (C.c_int * 1)(G), 1, 1 if include_gt else 0, float(fg_iou), float(bg_iou[0]),
+              float(bg_iou[1]), int(fg_quota), batch, int(bgclass), C.c_uint(int(seed) & 0xFFFFFFFF), ptr(out["roi"]),
+              ptr(out["crtarget"]), ptr(out["cctarget"]), ptr(out["src"]), ptr(out["gt_idx"]), ptr(out["iou"]), rows, ptr(ctl),
+              stream_ptr())
+    counts = tuple(int(c) for c in ctl.numpy()[:4])
+    S = counts[2] + counts[3]
+    res = dict((k, t.numpy()[:S].copy()) for k, t in out.items())
+    res["counts"] = counts
+    return res

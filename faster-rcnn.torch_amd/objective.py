@@ -10,8 +10,13 @@ vector until the single read-back at the end of the call.
 Data parallelism (not in the reference): when torch.distributed is initialised, every
 rank processes its own images and the flat gradient + the 8 accumulators are all-reduced (sum) just
 before `gradient:div(cls_count)` (objective.lua:200), so the result equals the single-process result
-on the concatenated batch."""
+on the concatenated batch (not under cfg.roi_sampling.source = "proposals" where a quota cuts: every rank's objective counts its
+own images, so the ranks draw with seed + 0, seed + 1, ... each, where the single process draws with seed + k for its k-th image).
+
+Not in the reference: cfg["roi_sampling"] (roi_sampling_settings) trains the classification net on a sample of the first NMS's
+candidates instead of the example rows -- scan, selection, NMS and frcnn_proposal_targets_batch on the pass's own head maps."""
 import ctypes as C
+import math
 import os
 import sys
 
@@ -90,6 +95,104 @@ def align_geometry(localizer):
                          "Localizer.centred() is false")
     sx, sy = localizer.stride()
     return 1.0 / sx, 1.0 / sy
+
+
+ROI_SAMPLING_DEFAULTS = dict(source="examples", batch=128, fg_fraction=0.25, fg_iou=0.5, bg_iou=(0.0, 0.5), include_gt=True,
+                             threshold=0.5, nms_overlap=0.7, pre_nms_top_n=6000, post_nms_top_n=2000, seed=0)
+ROI_SAMPLING_MAX_GT = 64          # ground-truth boxes an image may carry (frcnn_proposal_targets_batch)
+ROI_SAMPLING_MAX_CANDIDATES = 4096   # ground truth + picks a segment of frcnn_proposal_targets_batch holds
+
+
+def roi_sampling_settings(cfg):
+    """cfg["roi_sampling"] (which rows the classification net is trained on; not in the reference) -> a dict of the validated
+    settings plus fg_quota = floor(batch * fg_fraction + 0.5), or None when the key is absent.
+      source          "examples" (default: objective.lua:91-140 -- the ground-truth rects of the positive anchors and the rects of
+                      the sampled negative anchors) or "proposals": a sample of the candidates the first NMS leaves on this very
+                      forward pass, matched to the image's ground truth by frcnn_proposal_targets_batch
+      batch           rows a image contributes at most (1 ... 4096); fg_fraction: the share of them that may be foreground (0 ... 1)
+      fg_iou          a candidate whose best IoU reaches it is foreground (0 ... 1)
+      bg_iou          {lo, hi}: background is lo <= best IoU < hi, with lo <= hi <= fg_iou; anything else is ignored
+      include_gt      the ground-truth boxes themselves are candidates too
+      threshold       the anchor scan's probability threshold (0 ... 1; Detector.lua:44 uses 0.95); nms_overlap: the first NMS's,
+                      in (0, 1], keyed by the score
+      pre_nms_top_n   the best-scoring matches the NMS sees (1 ... Detector.NMS_FIRST_CAP); post_nms_top_n: the picks that become
+                      candidates (1 ... 4096 - 64)
+      seed            of the sampling hash (0 ... 2^32 - 1); image k of an objective draws with seed + k
+    Raises FrcnnError -- before the model or the device is touched -- for an unknown key, a wrong type or a value out of range."""
+    t = cfg.get("roi_sampling")
+    if t is None:
+        return None
+    E = _lib.FrcnnError
+    if not isinstance(t, dict):
+        raise E("cfg.roi_sampling must be a table of {%s}" % ", ".join(ROI_SAMPLING_DEFAULTS))
+    unknown = sorted(set(t) - set(ROI_SAMPLING_DEFAULTS), key=str)
+    if unknown:
+        raise E("cfg.roi_sampling: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    out = dict(ROI_SAMPLING_DEFAULTS)
+    out.update(t)
+
+    def number(key, lo, hi, lo_open=False):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise E("cfg.roi_sampling.%s = %r is not a number" % (key, v))
+        if not (lo < v if lo_open else lo <= v) or not v <= hi:
+            raise E("cfg.roi_sampling.%s = %r outside %s%g, %g]" % (key, v, "(" if lo_open else "[", lo, hi))
+        return float(v)
+
+    def integer(key, lo, hi):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise E("cfg.roi_sampling.%s = %r is not an integer" % (key, v))
+        if not lo <= v <= hi:
+            raise E("cfg.roi_sampling.%s = %d outside %d ... %d" % (key, v, lo, hi))
+        return int(v)
+
+    if not isinstance(out["source"], str) or out["source"] not in ("examples", "proposals"):
+        raise E("cfg.roi_sampling.source = %r (\"examples\" or \"proposals\")" % (out["source"],))
+    if not isinstance(out["include_gt"], bool):
+        raise E("cfg.roi_sampling.include_gt = %r (true or false)" % (out["include_gt"],))
+    from .Detector import Detector
+    out["batch"] = integer("batch", 1, ROI_SAMPLING_MAX_CANDIDATES)
+    out["fg_fraction"] = number("fg_fraction", 0.0, 1.0)
+    out["fg_iou"] = number("fg_iou", 0.0, 1.0)
+    bg = out["bg_iou"]
+    if isinstance(bg, dict):        # (a Lua table {lo, hi} as the t7 reader hands it over)
+        bg = [bg[k] for k in sorted(bg)] if sorted(bg) == [1, 2] else None
+    if not isinstance(bg, (list, tuple)) or len(bg) != 2:
+        raise E("cfg.roi_sampling.bg_iou = %r (a pair {lo, hi})" % (out["bg_iou"],))
+    for v in bg:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise E("cfg.roi_sampling.bg_iou: %r is not a number" % (v,))
+    if not 0.0 <= bg[0] <= bg[1] <= out["fg_iou"]:
+        raise E("cfg.roi_sampling.bg_iou = {%g, %g} (need 0 <= lo <= hi <= fg_iou = %g)" % (bg[0], bg[1], out["fg_iou"]))
+    out["bg_iou"] = (float(bg[0]), float(bg[1]))
+    out["threshold"] = number("threshold", 0.0, 1.0)
+    out["nms_overlap"] = number("nms_overlap", 0.0, 1.0, lo_open=True)
+    out["pre_nms_top_n"] = integer("pre_nms_top_n", 1, Detector.NMS_FIRST_CAP)
+    out["post_nms_top_n"] = integer("post_nms_top_n", 1, ROI_SAMPLING_MAX_CANDIDATES - ROI_SAMPLING_MAX_GT)
+    out["seed"] = integer("seed", 0, 0xFFFFFFFF)
+    out["fg_quota"] = int(math.floor(out["batch"] * out["fg_fraction"] + 0.5))
+    return out
+
+
+def ground_truth_table(x, class_count=None):
+    """The ground truth of a batch entry for frcnn_proposal_targets_batch: x["rois"] (objects with .rect and .class_index) ->
+    (gt_rect G x 4 float64, gt_class G int32).  Raises FrcnnError for an entry without the key, more than 64 boxes, a box whose
+    width or height is not positive, or (class_count given) a class outside 1 ... class_count."""
+    if "rois" not in x or x["rois"] is None:
+        raise _lib.FrcnnError("cfg.roi_sampling.source = \"proposals\" needs the ground truth of every batch entry: "
+                              "the entry has no key \"rois\"")
+    rois = list(x["rois"])
+    if len(rois) > ROI_SAMPLING_MAX_GT:
+        raise _lib.FrcnnError("roi_sampling: an image with %d ground-truth boxes (at most %d)" % (len(rois), ROI_SAMPLING_MAX_GT))
+    gt = np.array([(r.rect.minX, r.rect.minY, r.rect.maxX, r.rect.maxY) for r in rois], dtype=np.float64).reshape(-1, 4)
+    cls = np.array([r.class_index for r in rois], dtype=np.int32).reshape(-1)
+    if len(rois) and not (np.all(np.isfinite(gt)) and np.all(gt[:, 2] - gt[:, 0] > 0) and np.all(gt[:, 3] - gt[:, 1] > 0)):
+        raise _lib.FrcnnError("roi_sampling: a ground-truth box without a positive, finite width and height")
+    if class_count is not None and len(rois) and (cls.min() < 1 or cls.max() > class_count):
+        raise _lib.FrcnnError("roi.class_index %d outside 1..%d (class_count)"
+                              % (int(cls.min() if cls.min() < 1 else cls.max()), class_count))
+    return gt, cls
 
 
 class _Scratch(object):
@@ -347,6 +450,71 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         return [e for e in examples
                 if not (e[0].index[1] > outputs[e[0].layer - 1].shape[1] or e[0].index[2] > outputs[e[0].layer - 1].shape[2])]
 
+    # ---- cfg["roi_sampling"] (roi_sampling_settings): under source = "proposals" the classification net's rows are a sample of
+    # the first NMS's candidates on the pass's own head maps (sample_proposals below); absent or "examples": nothing here runs
+    rs_state = dict(images=0, aw=None, ah=None, loc=None)
+
+    def sampling_on():
+        """the validated settings when this pass trains the classification net on sampled proposals, else None"""
+        rs = roi_sampling_settings(cfg)
+        if rs is None or rs["source"] != "proposals" or not train_settings(cfg, nblk_all)[2]:
+            return None
+        return rs
+
+    def sample_proposals(rs, outputs, H, W, d_gt, d_gc, G):
+        """Detector.lua:39-85 on the training pass's own head maps, then the proposal-target layer, all on the caller's stream
+        with the counts on the device: frcnn_rpn_scan_batch (B = 1) at rs.threshold, frcnn_topk_select + frcnn_rpn_gather_rows
+        (rects and the score rows {box, p}), frcnn_nms_device_batch keyed by the score, frcnn_proposal_targets_batch; then ONE
+        read-back of the four counts -> (record, F, Bq): record holds the device buffers (debug["roi_sampling"])."""
+        if rs_state["aw"] is None:
+            a = Anchors(pnet, cfg["scales"])
+            rs_state["aw"], rs_state["ah"] = DeviceTensor.from_numpy(a.w), DeviceTensor.from_numpy(a.h)
+            rs_state["loc"] = np.array([[l["kW"], l["kH"], l["dW"], l["dH"], l["padW"], l["padH"]] for l in localizer.layers],
+                                       dtype=np.int32).reshape(-1, 6)
+        s = stream_ptr()
+        i32 = np.int32
+        hw = [tuple(o.shape[1:]) for o in outputs[:4]]
+        Hs = (C.c_int * 4)(*[h for h, _ in hw]); Ws = (C.c_int * 4)(*[w for _, w in hw])
+        cap = sum(int(o.shape[0]) // 6 * h * w for o, (h, w) in zip(outputs[:4], hw))   # every anchor of the four maps
+        maps = (C.c_void_p * 4)(*[o.ptr for o in outputs[:4]])
+        ctl = scratch.get("rs_ctl", (8,), i32)     # {nfg, nbg, F, Bq}, matches, selected rows, candidates
+        c_n, c_k, c_R = (C.c_void_p(ctl.ptr + 4 * k) for k in (4, 5, 6))
+        wsb = L.frcnn_rpn_scan_batch_workspace_bytes(Hs, Ws, 1)
+        mp = scratch.get("rs_match_p", (cap,)); mi = scratch.get("rs_match_idx", (cap, 4), i32)
+        mr = scratch.get("rs_match_rect", (cap, 4), np.float64); mb = scratch.get("rs_match_box", (cap, 4))
+        _lib.call("frcnn_rpn_scan_batch", maps, Hs, Ws, 1, 0, ptr(rs_state["aw"]), ptr(rs_state["ah"]), float(W), float(H),
+                  rs["threshold"], cap, ptr(mp), ptr(mi), ptr(mr), ptr(mb), c_n, ptr(scratch.get("rs_scan_ws", (wsb,), np.uint8)),
+                  wsb, s)
+        kcap = min(cap, rs["pre_nms_top_n"])
+        sel = scratch.get("rs_sel", (kcap,), i32)
+        wsb = L.frcnn_topk_select_workspace_bytes(1, cap)
+        _lib.call("frcnn_topk_select", ptr(mp), 1, cap, cap, c_n, rs["pre_nms_top_n"], ptr(sel), kcap, c_k,
+                  ptr(scratch.get("rs_sel_ws", (wsb,), np.uint8)), wsb, s)
+        rect = scratch.get("rs_rect", (kcap, 4), np.float64); box5 = scratch.get("rs_box5", (kcap, 5))
+        _lib.call("frcnn_rpn_gather_rows", ptr(mp), ptr(mi), ptr(mr), ptr(mb), 1, cap, cap, ptr(sel), kcap, c_k, kcap, None, None,
+                  ptr(rect), None, ptr(box5), None, kcap, s)
+        pick = scratch.get("rs_pick", (kcap,), np.int64)
+        wsb = L.frcnn_nms_batch_workspace_bytes(1, kcap)
+        _lib.call("frcnn_nms_device_batch", ptr(box5), 1, kcap, kcap, c_k, 5, C.c_float(rs["nms_overlap"]), 2, 5, None, ptr(pick),
+                  c_R, ptr(scratch.get("rs_nms_ws", (wsb,), np.uint8)), wsb, s)
+        rows = rs["batch"]
+        seed = (rs["seed"] + rs_state["images"]) & 0xFFFFFFFF
+        rs_state["images"] += 1
+        rec = dict(rect=rect, pick=pick, R=DeviceTensor(ctl.ptr + 24, (1,), i32, owner=ctl), stride=kcap,
+                   r_cap=min(kcap, rs["post_nms_top_n"]), seed=seed, settings=rs, bgclass=bgclass,
+                   roi=scratch.get("rs_roi", (rows, 4), np.float64), crtarget=scratch.get("rs_crtarget", (rows, 4)),
+                   cctarget=scratch.get("rs_cctarget", (rows,)), src=scratch.get("rs_src", (rows,), i32),
+                   gt_idx=scratch.get("rs_gt_idx", (rows,), i32), iou=scratch.get("rs_iou", (rows,), np.float64))
+        _lib.call("frcnn_proposal_targets_batch", ptr(rect), ptr(pick), kcap, c_R, rec["r_cap"], C.c_void_p(d_gt), C.c_void_p(d_gc),
+                  max(G, 1), (C.c_int * 1)(G), 1, 1 if rs["include_gt"] else 0, rs["fg_iou"], rs["bg_iou"][0], rs["bg_iou"][1],
+                  rs["fg_quota"], rows, bgclass, C.c_uint(seed), ptr(rec["roi"]), ptr(rec["crtarget"]), ptr(rec["cctarget"]),
+                  ptr(rec["src"]), ptr(rec["gt_idx"]), ptr(rec["iou"]), rows, ptr(ctl), s)
+        host = np.zeros(4, i32)
+        _lib.call("frcnn_memcpy_d2h", host.ctypes.data_as(C.c_void_p), ptr(ctl), 16, s)     # the ONE read-back of the stage
+        _lib.call("frcnn_stream_sync", s)
+        rec["counts"] = tuple(int(v) for v in host)
+        return rec, rec["counts"][2], rec["counts"][3]
+
     prepared = {}   # id(batch entry) -> (the entry itself, tables packed ahead of the pass: finish(), while the host waits for
                     # the device); the entry is held so that its id cannot be re-used by another object while the tables wait
 
@@ -372,7 +540,17 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         n = clean_examples(x["negative"], sizes)
         npos, E = len(p), len(p) + len(n)
         prep = dict(p=p, n=n, sizes=sizes, fm=(fmH, fmW))
+        if sampling_on() is not None:   # the ground-truth table of the proposal-target layer rides at the end of the blob
+            gt, gcls = ground_truth_table(x, cfg["class_count"])
+            G = len(gcls)
+            # (G x 4 doubles, then G ints; an image without boxes carries one unread row)
+            prep.update(gt_rect=gt, gt_class=gcls,
+                        gt_blob=np.concatenate([gt.view(np.uint8).ravel() if G else np.zeros(32, np.uint8),
+                                                gcls.view(np.uint8).ravel() if G else np.zeros(4, np.uint8)]))
         if E == 0:
+            if "gt_blob" in prep:
+                prep["blob"] = prep["gt_blob"]
+                prep["gt_off"] = 0
             return prep
         anch = [e[0] for e in p] + [e[0] for e in n]
         ex_idx = np.array([(a.layer, a.aspect, a.index[1], a.index[2]) for a in anch], dtype=np.int32)
@@ -403,6 +581,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         if align:   # (the rects are doubles: their offset in the blob is rounded up to 8 bytes)
             head.append(np.zeros(-sum(a.size for a in head) % 8, np.uint8))
         blob = np.concatenate(head + [wins.view(np.uint8).ravel(), sp_all.view(np.uint8).ravel()])
+        if "gt_blob" in prep:   # (doubles: at a multiple of 16 bytes)
+            prep["gt_off"] = blob.size + (-blob.size % 16)
+            blob = np.concatenate([blob, np.zeros(-blob.size % 16, np.uint8), prep["gt_blob"]])
         prep.update(ex_anchor=ex_anchor, ex_roi=ex_roi, ex_idx=ex_idx, ex_class=ex_class, wins=wins, sp=sp, blob=blob)
         return prep
 
@@ -425,6 +606,17 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         guard["deferred"] = False
         guard["divisor"] = None
         frozen_blocks, proposal, classification, ranges = stage_ranges()
+        rs = sampling_on()   # (cfg.roi_sampling: validated, like cfg.train, before anything is queued)
+        if rs is not None:   # ... and so is the ground truth of the batch this pass will process
+            if next_batch[0] is None:
+                next_batch[0] = batch_iterator.nextTraining()
+            try:
+                for xb in next_batch[0]:
+                    ground_truth_table(xb, cfg["class_count"])
+            except _lib.FrcnnError:
+                next_batch[0] = None   # (a refused batch is dropped: the next call draws a new one)
+                prepared.clear()
+                raise
         _lib.call("frcnn_model_set_trainable", native.h, frozen_blocks, int(proposal), int(classification))
         stage[0] = ranges
         trunk_frozen = frozen_blocks == nblk_all
@@ -481,7 +673,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             eager["groups"] = set()
             eager["slice"] = eager_slice
         dev_tail = (dev_tail_ok and defer == "fold" and _dist() is not None and getattr(gradient, "is_cuda", False)
-                    and ranges is None)   # (a staged pass: the optimisers' slice forms take a host divisor)
+                    and ranges is None    # (a staged pass: the optimisers' slice forms take a host divisor)
+                    and rs is None)       # (sampled proposals: creg_count is known after the stage's read-back only)
         c4 = None
         if dev_tail:
             from .synthetic import clean_examples, output_map_sizes
@@ -504,8 +697,12 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             # pass is queued, not between it and the stage that consumes them, where the device would run dry
             held = prepared.pop(id(x), None)
             prep = held[1] if held is not None and held[0] is x else prepare_examples(x)
+            if rs is not None and "gt_blob" not in prep:   # (packed ahead, before the setting was switched on)
+                prep = prepare_examples(x)
             img = to_device(x["img"])  # :66
-            outputs = pnet.forward(img, async_heads=True)  # :71 (the anchor nets stay in flight beside the cnet stage)
+            # :71 (the anchor nets stay in flight beside the cnet stage; sampled proposals: the scan reads their dense maps on this
+            # stream -- the sampled-position path computes none -- so the pass waits for them)
+            outputs = pnet.forward(img, async_heads=rs is None)
             if prep["sizes"] != [tuple(o.shape[1:]) for o in outputs[:len(prep["sizes"])]] or prep["fm"] != tuple(outputs[-1].shape[1:]):
                 raise _lib.FrcnnError("lossAndGradient: the example tables were packed for other map sizes than this image's")
             p, n = prep["p"], prep["n"]  # :74-75
@@ -514,6 +711,12 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             E = npos + nneg
             fm = outputs[-1]
             fmC, fmH, fmW = fm.shape
+            if E == 0 and rs is not None:   # (no example: the blob is the ground-truth table alone)
+                blob = prep["blob"]
+                dblob = scratch.get("blob", (blob.size,), np.uint8)
+                hblob, staged = pinned.stage(blob)
+                _lib.call("frcnn_memcpy_h2d", ptr(dblob), C.c_void_p(hblob), blob.nbytes, s)
+                staged()
             if E > 0:
                 ex_anchor, ex_roi, ex_idx, ex_class, wins, sp, blob = (prep[k] for k in ("ex_anchor", "ex_roi", "ex_idx", "ex_class", "wins", "sp", "blob"))
                 dblob = scratch.get("blob", (blob.size,), np.uint8)
@@ -540,7 +743,47 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 cctarget = scratch.get("cctarget", (E,))
                 pnet.anchor_loss_begin(d_idx, d_anchor, d_roi, d_class, npos, nneg, bgclass, ex_loss, crtarget,
                                        cctarget, acc_dev)
-            if E > 0 and not classification:
+            F_rows = npos
+            if rs is not None:
+                # ---- the classification net on sampled proposals (cfg.roi_sampling): the candidates of the first NMS on this
+                # pass's head maps (only head_forward writes them: the side stream's loss and backward launches read them beside
+                # the scan), matched, labelled and sampled on the device; their rects are constants of the pass
+                G = len(prep["gt_class"])
+                d_gt = dblob.ptr + prep["gt_off"]
+                rec, F_rows, Bq = sample_proposals(rs, outputs, int(img.shape[1]), int(img.shape[2]), d_gt, d_gt + 32 * max(G, 1), G)
+                S = F_rows + Bq
+                rec.update(gt_rect=prep["gt_rect"], gt_class=prep["gt_class"], cinput=None)
+                debug["roi_sampling"] = rec
+                stats.setdefault("rois", []).append(rec["counts"])
+                if S == 0:
+                    native.seed += 1              # (the cnet's dropout draw is skipped: the seed advances as its forward would)
+                    pnet.anchor_loss_wait()       # (the accumulators are read on this stream)
+                else:
+                    cinput = rec["cinput"] = scratch.get("cinput", (S, D))
+                    if align:
+                        _lib.call("frcnn_roi_align_forward", ptr(fm), fmC, fmH, fmW, ptr(rec["roi"]), None, S, inv_sx, inv_sy,
+                                  kh, kw, sampling, ptr(cinput), s)
+                    else:
+                        loc = rs_state["loc"]
+                        dwins = scratch.get("rs_wins", (S, 4), np.int32)
+                        pidx = scratch.get("pidx", (S, D), np.int32)
+                        _lib.call("frcnn_roi_windows", ptr(rec["roi"]), None, S, loc.ctypes.data_as(C.c_void_p), len(loc), fmH, fmW,
+                                  ptr(dwins), s)
+                        _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(dwins), S, kh, kw, ptr(cinput), ptr(pidx), s)
+                    crout, ccout = cnet.forward(cinput)
+                    crdelta = scratch.get("crdelta", (S, 4))
+                    ccdelta = scratch.get("ccdelta", (S, ncls))
+                    pnet.anchor_loss_wait()       # (the accumulators: the anchor losses land in the same vector)
+                    _lib.call("frcnn_cnet_losses", ptr(crout), ptr(rec["crtarget"]), ptr(ccout), ptr(rec["cctarget"]), S, F_rows, ncls,
+                              ptr(crdelta), ptr(ccdelta), C.c_void_p(acc_dev.ptr + 4 * 8), s)
+                    post_roi_delta = cnet.backward(cinput, [crdelta, ccdelta])
+                    if not trunk_frozen and align:
+                        _lib.call("frcnn_roi_align_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),
+                                  ptr(rec["roi"]), None, S, inv_sx, inv_sy, kh, kw, sampling, s)
+                    elif not trunk_frozen:
+                        _lib.call("frcnn_roi_pool_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta), ptr(pidx),
+                                  S, kh, kw, s)
+            elif E > 0 and not classification:
                 # staged training without the detector stage: no ROI pooling, no cnet; dcls / dreg are reported as NaN (finish).
                 # The cnet's dropout draw is skipped too: the seed advances as its forward would advance it, so that every
                 # later pass draws what it would draw unstaged
@@ -655,7 +898,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 _probe_mark("rest of the backbone", lo_rest, hi_rest, "end of frcnn_pnet_backward on the caller's stream")
             reg_count += npos  # :194-198
             cls_count += npos + nneg
-            creg_count += npos
+            creg_count += F_rows   # (sampled proposals: the foreground rows regress)
             ccls_count += 1
 
         # ---- statistics: one read-back per call ------------------------------------------
@@ -816,6 +1059,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     lossAndGradient.trainable_ranges = lambda: stage_ranges()[3]
     lossAndGradient.pass_ranges = lambda: stage[0]
     lossAndGradient.debug = debug   # (tests: the scratch buffers, the example count and -- RoIAlign -- the rects of the image being processed)
+    # cfg.roi_sampling.source = "proposals": debug["roi_sampling"] holds the last image's sampler record -- the candidates (rect, pick, R,
+    # stride, r_cap), the kernel's outputs (roi, crtarget, cctarget, src, gt_idx, iou, counts), the seed, the ground truth and cinput
     return lossAndGradient
 
 

@@ -222,6 +222,47 @@ int frcnn_soft_nms_batch(const float *boxes, int B, long long row_stride, int n_
 int frcnn_box_vote_batch(const float *boxes, int B, long long row_stride, int n_cap, const int *n_dev, int ncols, int score_col,
                          int weight_mode, float overlap, const int *cls, const double *rect, const long long *pick,
                          const int *count, double *rect_out, int *votes_out, void *stream);
+/* ---- The proposal-target layer (Ren et al. 2015, training the detector on the RPN's proposals; not in the reference;
+ * csrc/proposal_targets.hip) ---------------------------------------------------------------------------------------------------
+ * objective.lua:91-140 trains the classification net on the ground-truth rects of the positive anchors and the rects of the sampled
+ * negative anchors; under cfg.roi_sampling = { source = "proposals", ... } its rows are a sample of what the first NMS leaves.  This
+ * ONE launch sits between frcnn_nms_device_batch and frcnn_roi_windows / RoIAlign: it matches a segment's candidates to its
+ * ground truth, labels them, draws a batch and writes the rect table and the targets frcnn_cnet_losses reads.
+ * Segment b (one frame): rect + b*match_stride*4 (device double[match_stride][4]) and pick + b*match_stride (device int64, 1-based
+ * rows of the segment's rect) as the first NMS leaves them; r_dev[b] (device int) the candidate count, of which the kernel uses the
+ * first R = min(max(r_dev[b], 0), r_cap) picks -- the post-NMS cap, applied on the device; gt_rect + b*gt_stride*4 (device
+ * double[gt_stride][4]), gt_class + b*gt_stride (device int, 1-based); G_host[b] its ground-truth count, a HOST array that travels
+ * as a kernel argument (no upload, no wait).
+ *   CANDIDATES  index i in [0, G) is ground-truth box i when include_gt != 0; behind them i = G' + j is pick j (G' = G or 0);
+ *               N = G' + R <= 4096.  A pick outside 1 ... match_stride is read nowhere and counts as an ignored candidate.
+ *   RULE        fp64, every operation rounded on its own, the formula of Rect.lua:126-141 (no + 1, unlike nms): with max(a, b) = b
+ *               when b > a else a, min(a, b) = b when b < a else a, minx = max(c.minX, g.minX) ..., the intersection is
+ *               (maxx - minx) * (maxy - miny) when maxx >= minx && maxy >= miny, else 0; iou = inter / ((area_c + area_g) - inter),
+ *               a quotient that is not a number counts as 0.  best = the FIRST maximum over g (the lowest g wins a tie); G = 0:
+ *               best_iou = 0, gt_idx = -1.  A candidate with a coordinate that is not finite, or a width or height <= 0, is
+ *               ignored.  fg: gt_idx >= 0 && best_iou >= fg_iou -- foreground needs a box it matched, so a segment with G = 0 has none
+ *               whatever fg_iou is (fg_iou = 0 included).  bg: not fg && bg_lo <= best_iou < bg_hi.  Everything else is ignored.
+ *   QUOTAS      F = min(nfg, fg_quota), Bq = min(nbg, batch - F).  A class over its quota keeps the rows with the smallest keys;
+ *               key of row i, all operations uint32: x = seed + 0x9E3779B9*(i+1) + 0x85EBCA6B*b; x ^= x>>16; x *= 0x85EBCA6B;
+ *               x ^= x>>13; x *= 0xC2B2AE35; x ^= x>>16.  The mix is a bijection and a segment's pre-images differ: keys never tie.
+ *   OUTPUTS     rows at b*out_stride: the F fg rows in candidate order, then the Bq bg rows in candidate order; nothing is stored
+ *               behind row F + Bq.  roi[4] (double) = the candidate's rect bit for bit; crtarget[4] (float) =
+ *               (float) Anchors.inputToAnchor(candidate, gt[best]) (Anchors.lua:237-243: (gx - cx) / cw, (gy - cy) / ch,
+ *               log(gw / cw), log(gh / ch) in fp64) for fg, zeros for bg; cctarget (float) = gt_class[best] for fg, bgclass for bg;
+ *               src (int) = i; gt_idx (int) = best; iou (double) = best_iou.  counts[b][4] = {nfg, nbg, F, Bq}.  A segment with
+ *               N = 0 writes its counts (all 0) and nothing else.
+ * One workgroup per segment, no atomics, no workspace: a segment's output is a function of its own data, b and seed -- not of B, of
+ * its neighbours or of the run.  One launch for up to 128 segments.  Everything but log() is exact; log is the device library's
+ * (within an ulp).  roi, crtarget and counts are stored 16 bytes at a time and must be 16-byte aligned.
+ * Errors, returned before any launch (B = 0 returns at once): B outside 0 ... 65535, G_host[b] outside 0 ... 64 or above gt_stride,
+ * r_cap negative or r_cap + 64 > 4096, match_stride < r_cap, bg_hi > fg_iou or bg_lo > bg_hi (or a NaN), batch < 1, fg_quota
+ * outside 0 ... batch, out_stride < batch, bgclass < 1, a NULL required pointer (rect / pick only with r_cap > 0, gt_rect / gt_class
+ * only with a G_host > 0), a misaligned roi / crtarget / counts.  Counted under FRCNN_KC_RPN. */
+int frcnn_proposal_targets_batch(const double *rect, const long long *pick, long long match_stride, const int *r_dev, int r_cap,
+                                 const double *gt_rect, const int *gt_class, int gt_stride, const int *G_host, int B,
+                                 int include_gt, double fg_iou, double bg_lo, double bg_hi, int fg_quota, int batch, int bgclass,
+                                 unsigned int seed, double *roi, float *crtarget, float *cctarget, int *src, int *gt_idx,
+                                 double *iou, int out_stride, int *counts, void *stream);
 /* ---- Detector:detect glue kept on the device (Detector.lua:88-136; csrc/detect.hip) ------------------------------
  * frcnn_roi_windows: extract_roi_pooling_input (objective.lua:5-13) for k ROIs at once -- Localizer:inputToFeatureRect
  * (Localizer.lua:41-67, the reference's double arithmetic incl. its dH/dW mix-ups) over layers_host[nlayers][6] =
