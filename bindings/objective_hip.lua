@@ -44,7 +44,9 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
   local acc_host = ffi.new('double[8]')
   local scratch = hip.scratch()
   -- cfg.roi_sampling (INTEGRATION.md): under source = 'proposals' the classification net's rows are a sample of the first NMS's
-  -- candidates on the pass's own head maps (hip.sample_proposals: scan, selection, NMS, frcnn_proposal_targets_batch)
+  -- candidates on the pass's own head maps (hip.sample_proposals: scan, selection, NMS, frcnn_proposal_targets_batch); under
+  -- source = 'hard' every labelled candidate is pooled and scored in evaluate mode first, and the rows of largest loss train
+  -- (hip.mine_hard: frcnn_roi_hard_keys_batch, the NMS keyed by the loss, frcnn_roi_hard_gather_batch)
   local rs_state = { images = 0 }
   local keep_gt
   local keep                            -- host staging of the last example tables (must outlive the queued copy)
@@ -78,7 +80,7 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     -- disabled stage, the optimiser updates `ranges` only
     local frozen_blocks, proposal, classification, ranges = stage()
     local rs = hip.roi_sampling_settings(cfg)         -- (validated, like cfg.train, before anything is queued)
-    if rs and (rs.source ~= 'proposals' or not classification) then rs = nil end
+    if rs and ((rs.source ~= 'proposals' and rs.source ~= 'hard') or not classification) then rs = nil end
     check(C.frcnn_model_set_trainable(native, frozen_blocks, proposal and 1 or 0, classification and 1 or 0))
     published.pass = ranges
     if w ~= weights then weights:copy(w) end                            -- :46-48
@@ -238,6 +240,37 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         end
         local isz = img:size()
         local rec = hip.sample_proposals(rs_state, rs, scratch, outputs, nheads, isz[3], isz[2], d_gt, d_gc, G, bgclass)
+        local layers, nl
+        if not align then
+          nl = #localizer.layers
+          layers = ffi.new('int[?]', 6 * nl)
+          for i, l in ipairs(localizer.layers) do
+            local o = 6 * (i - 1)
+            layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
+          end
+        end
+        if rs.source == 'hard' then
+          -- online hard example mining: the N labelled candidates are pooled (no arg-max record) and scored in evaluate mode --
+          -- nothing is drawn, no state of the net changes -- and the rows of largest loss become the training tables
+          local N = rec.counts[3] + rec.counts[4]
+          local score
+          if N > 0 then
+            local hin = hip.view(scratch('rh_cinput', 4 * N * D).ptr, { N, D })
+            if align then
+              check(C.frcnn_roi_align_forward(fm.ptr, fs[1], fs[2], fs[3], rec.roi, nil, N, inv_sx, inv_sy, kh, kw, sampling,
+                                              hin.ptr, nil))
+            else
+              local hwins = ffi.cast('int*', scratch('rh_wins', 16 * N).ptr)
+              check(C.frcnn_roi_windows(rec.roi, nil, N, layers, nl, fs[2], fs[3], hwins, nil))
+              check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], hwins, N, kh, kw, hin.ptr, nil, nil))
+            end
+            score = cnet:score(hin, hip.view(scratch('rh_crout', 16 * N).ptr, { N, 4 }),
+                               hip.view(scratch('rh_ccout', 4 * N * ncls).ptr, { N, ncls }))
+          end
+          rec = hip.mine_hard(rs, rec, scratch, N, score and score[1].ptr, score and score[2].ptr, ncls)
+          stats.hard = stats.hard or {}
+          table.insert(stats.hard, rec.hard)
+        end
         stats.rois = stats.rois or {}
         table.insert(stats.rois, rec.counts)
         F_rows = rec.counts[3]
@@ -252,12 +285,6 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
             check(C.frcnn_roi_align_forward(fm.ptr, fs[1], fs[2], fs[3], rec.roi, nil, S, inv_sx, inv_sy, kh, kw, sampling,
                                             cinput.ptr, nil))
           else
-            local nl = #localizer.layers
-            local layers = ffi.new('int[?]', 6 * nl)
-            for i, l in ipairs(localizer.layers) do
-              local o = 6 * (i - 1)
-              layers[o], layers[o + 1], layers[o + 2], layers[o + 3], layers[o + 4], layers[o + 5] = l.kW, l.kH, l.dW, l.dH, l.padW, l.padH
-            end
             local dwins = ffi.cast('int*', scratch('rs_wins', 16 * S).ptr)
             pidx = ffi.cast('int*', scratch('pidx', 4 * S * D).ptr)
             check(C.frcnn_roi_windows(rec.roi, nil, S, layers, nl, fs[2], fs[3], dwins, nil))

@@ -191,10 +191,18 @@ _SIGS = {
     "frcnn_image_contrastive_norm": ([vp, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp], C.c_int),
 }
 
+# the entry points of include/frcnn_hip_hard.h (online hard example mining), which frcnn_hip.h includes
+HARD_SIGS = {
+    "frcnn_roi_hard_keys_batch": ([vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, vp, vp, C.c_int, vp, vp, vp], C.c_int),
+    "frcnn_roi_hard_gather_batch": ([vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_longlong, C.c_int, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp, C.c_int, vp, vp], C.c_int),
+}
+
 _lib = None
 
 
 def exported_symbols():
+    """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -217,7 +225,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in _SIGS.items():
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

@@ -207,6 +207,21 @@ int frcnn_proposal_targets_batch(const double* rect, const long long* pick, long
                                 bg_lo, bg_hi, fg_quota, batch, bgclass, seed, roi, crtarget, cctarget, src, gt_idx, iou, out_stride,
                                 counts, S(stream));
 }
+int frcnn_roi_hard_keys_batch(const double* roi, const float* crout, const float* crtarget, const float* ccout,
+                              const float* cctarget, int B, long long row_stride, int n_cap, const int* n_dev, const int* nfg_dev,
+                              int ncls, float* box5, float* loss, void* stream) {
+  return roi_hard_keys_batch(roi, crout, crtarget, ccout, cctarget, B, row_stride, n_cap, n_dev, nfg_dev, ncls, box5, loss,
+                             S(stream));
+}
+int frcnn_roi_hard_gather_batch(const long long* pick, const int* count_dev, int batch, const double* roi, const float* crtarget,
+                                const float* cctarget, const int* src, const int* gt_idx, const double* iou, const float* loss,
+                                int B, long long row_stride, int n_cap, const int* n_dev, const int* nfg_dev, double* roi_out,
+                                float* crtarget_out, float* cctarget_out, int* src_out, int* gt_idx_out, double* iou_out,
+                                float* loss_out, int out_stride, int* counts, void* stream) {
+  return roi_hard_gather_batch(pick, count_dev, batch, roi, crtarget, cctarget, src, gt_idx, iou, loss, B, row_stride, n_cap, n_dev,
+                               nfg_dev, roi_out, crtarget_out, cctarget_out, src_out, gt_idx_out, iou_out, loss_out, out_stride,
+                               counts, S(stream));
+}
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,
                               const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {

@@ -322,6 +322,16 @@ int proposal_targets_batch(const double* rect, const long long* pick, long long 
                            double fg_iou, double bg_lo, double bg_hi, int fg_quota, int batch, int bgclass, unsigned seed,
                            double* roi, float* crtarget, float* cctarget, int* src, int* gt_idx, double* iou, int out_stride,
                            int* counts, hipStream_t s);
+// ---- online hard example mining for the classification net (roi_hard.hip): the loss keys in front of the library's NMS and the
+// selection behind it; B segments; semantics in include/frcnn_hip_hard.h
+int roi_hard_keys_batch(const double* roi, const float* crout, const float* crtarget, const float* ccout, const float* cctarget,
+                        int B, long long row_stride, int n_cap, const int* n_dev, const int* nfg_dev, int ncls, float* box5,
+                        float* loss, hipStream_t s);
+int roi_hard_gather_batch(const long long* pick, const int* count_dev, int batch, const double* roi, const float* crtarget,
+                          const float* cctarget, const int* src, const int* gt_idx, const double* iou, const float* loss, int B,
+                          long long row_stride, int n_cap, const int* n_dev, const int* nfg_dev, double* roi_out,
+                          float* crtarget_out, float* cctarget_out, int* src_out, int* gt_idx_out, double* iou_out,
+                          float* loss_out, int out_stride, int* counts, hipStream_t s);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

@@ -271,6 +271,18 @@ class ClassificationNet(object):
         self.output = [bbox, cls]
         return self.output
 
+    def score(self, cinput, out):
+        """The evaluate-mode forward pass as a side computation (hard example mining, cfg.roi_sampling.source = "hard"): writes
+        out = (bbox R x 4, cls R x (classes + 1)), device tensors of the caller, on the current stream.  Nothing is drawn and the
+        module's state stays as it is: native.seed does not advance, the input and output the next backward() belongs to are not
+        replaced, and evaluate mode leaves bn_running untouched (it normalises with the running statistics)."""
+        nat = self.native
+        cinput = to_device(cinput)
+        bbox, cls = out
+        _lib.call("frcnn_cnet_forward", nat.h, ptr(nat.weights), ptr(cinput), cinput.shape[0], 0, None, nat.seed,
+                  ptr(nat.bn_running), ptr(bbox), ptr(cls), stream_ptr())
+        return [bbox, cls]
+
     def backward(self, cinput, grad_outputs):
         nat = self.native
         R, D = self._input.shape

@@ -8,7 +8,10 @@ soft_nms(boxes, overlap, score_col, ...) -- not in the reference: Soft-NMS (Bodl
 greedy loop that lowers the neighbours' scores instead of deleting them (semantics: include/frcnn_hip.h).
 
 box_vote(boxes, picks, ...) and proposal_targets(rect, pick, R, gt_rect, gt_class, ...) -- not in the reference either: bounding-box
-voting (frcnn_box_vote_batch) and the proposal-target layer of training on sampled proposals (frcnn_proposal_targets_batch)."""
+voting (frcnn_box_vote_batch) and the proposal-target layer of training on sampled proposals (frcnn_proposal_targets_batch).
+
+roi_hard_select(roi, crout, crtarget, ccout, cctarget, nfg, ...) -- online hard example mining of the classification net's rows:
+frcnn_roi_hard_keys_batch, the NMS keyed by the loss, frcnn_roi_hard_gather_batch."""
 import ctypes as C
 import math
 import numbers
@@ -211,4 +214,65 @@ def proposal_targets(rect, pick, R, gt_rect, gt_class, bgclass, include_gt=True,
     S = counts[2] + counts[3]
     res = dict((k, t.numpy()[:S].copy()) for k, t in out.items())
     res["counts"] = counts
+    return res
+
+
+def roi_hard_select(roi, crout, crtarget, ccout, cctarget, nfg, batch=128, overlap=0.7, src=None, gt_idx=None, iou=None):
+    """Online hard example mining (cfg["roi_sampling"].source = "hard"; not in the reference) on host arrays, one segment:
+    frcnn_roi_hard_keys_batch, frcnn_nms_device_batch keyed by the loss, frcnn_roi_hard_gather_batch.  roi (n x 4 float64), crout and
+    crtarget (n x 4 float32), ccout (n x ncls float32 log-probabilities), cctarget (n float32, 1-based classes): the n <= 4096 labelled
+    candidates, the first nfg of them foreground; src, gt_idx (int32) and iou (float64) travel with their rows (default: src = the
+    row, gt_idx = -1, iou = 0).  A row's loss is -ccout[target] + 10 * SmoothL1(crout - crtarget) (foreground only) in fp32; the NMS
+    at `overlap` picks in descending loss order (equal losses: the higher row first), and the first `batch` picks leave in ascending
+    row order -> dict(roi, crtarget, cctarget, src, gt_idx, iou, loss: the S = F + Bq selected rows, foreground first; counts
+    (F, Bq, survivors, n); box5 n x 5 float32, loss_all n float32, pick: the survivors, 1-based, in pick order).  Runs on the
+    device: there is no host twin (semantics: include/frcnn_hip_hard.h); a refused setting raises FrcnnError before anything is launched."""
+    roi = np.ascontiguousarray(roi, dtype=np.float64).reshape(-1, 4)
+    n = int(roi.shape[0])
+    crout = np.ascontiguousarray(crout, dtype=np.float32).reshape(-1, 4)
+    crtarget = np.ascontiguousarray(crtarget, dtype=np.float32).reshape(-1, 4)
+    cctarget = np.ascontiguousarray(cctarget, dtype=np.float32).reshape(-1)
+    ccout = np.ascontiguousarray(ccout, dtype=np.float32)
+    if ccout.ndim != 2 or ccout.shape[0] != n or ccout.shape[1] < 1:
+        raise ValueError("roi_hard_select: ccout must be %d x ncls" % n)
+    ncls = int(ccout.shape[1])
+    src = np.arange(n, dtype=np.int32) if src is None else np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+    gt_idx = np.full(n, -1, np.int32) if gt_idx is None else np.ascontiguousarray(gt_idx, dtype=np.int32).reshape(-1)
+    iou = np.zeros(n, np.float64) if iou is None else np.ascontiguousarray(iou, dtype=np.float64).reshape(-1)
+    for name, a in (("crout", crout), ("crtarget", crtarget), ("cctarget", cctarget), ("src", src), ("gt_idx", gt_idx), ("iou", iou)):
+        if a.shape[0] != n:
+            raise ValueError("roi_hard_select: %s has %d rows, roi %d" % (name, a.shape[0], n))
+    if not 0 <= int(nfg) <= n:
+        raise ValueError("roi_hard_select: nfg %d outside 0 ... %d" % (nfg, n))
+    batch = int(batch)
+    rows = max(min(batch, n), 1)
+
+    def dev(a):
+        return DeviceTensor.from_numpy(a if a.size else np.zeros((1,) + a.shape[1:], a.dtype))
+    d = dict(roi=dev(roi), crout=dev(crout), crtarget=dev(crtarget), ccout=dev(ccout), cctarget=dev(cctarget), src=dev(src),
+             gt_idx=dev(gt_idx), iou=dev(iou))
+    ctl = DeviceTensor.from_numpy(np.array([n, int(nfg), 0, 0, 0, 0, 0, 0], np.int32))   # n, nfg, survivors, -, then the counts
+    c_n, c_f, c_surv, c_out = (C.c_void_p(ctl.ptr + 4 * k) for k in (0, 1, 2, 4))
+    box5 = DeviceTensor.empty((max(n, 1), 5), np.float32)
+    loss = DeviceTensor.empty((max(n, 1),), np.float32)
+    pick = DeviceTensor.empty((max(n, 1),), np.int64)
+    out = dict(roi=DeviceTensor.empty((rows, 4), np.float64), crtarget=DeviceTensor.empty((rows, 4), np.float32),
+               cctarget=DeviceTensor.empty((rows,), np.float32), src=DeviceTensor.empty((rows,), np.int32),
+               gt_idx=DeviceTensor.empty((rows,), np.int32), iou=DeviceTensor.empty((rows,), np.float64),
+               loss=DeviceTensor.empty((rows,), np.float32))
+    s = stream_ptr()
+    _lib.call("frcnn_roi_hard_keys_batch", ptr(d["roi"]), ptr(d["crout"]), ptr(d["crtarget"]), ptr(d["ccout"]), ptr(d["cctarget"]), 1, n, n,
+              c_n, c_f, ncls, ptr(box5), ptr(loss), s)
+    if n:
+        wsb = _lib.load().frcnn_nms_batch_workspace_bytes(1, n)
+        ws = DeviceTensor.empty((wsb,), np.uint8)
+        _lib.call("frcnn_nms_device_batch", ptr(box5), 1, n, n, c_n, 5, C.c_float(overlap), 2, 5, None, ptr(pick), c_surv, ptr(ws),
+                  wsb, s)
+    _lib.call("frcnn_roi_hard_gather_batch", ptr(pick), c_surv, batch, ptr(d["roi"]), ptr(d["crtarget"]), ptr(d["cctarget"]),
+              ptr(d["src"]), ptr(d["gt_idx"]), ptr(d["iou"]), ptr(loss), 1, n, n, c_n, c_f, ptr(out["roi"]), ptr(out["crtarget"]),
+              ptr(out["cctarget"]), ptr(out["src"]), ptr(out["gt_idx"]), ptr(out["iou"]), ptr(out["loss"]), rows, c_out, s)
+    counts = tuple(int(c) for c in ctl.numpy()[4:8])
+    S = counts[0] + counts[1]
+    res = dict((k, t.numpy()[:S].copy()) for k, t in out.items())
+    res.update(counts=counts, box5=box5.numpy()[:n].copy(), loss_all=loss.numpy()[:n].copy(), pick=pick.numpy()[:counts[2]].copy())
     return res

@@ -11,10 +11,16 @@ Data parallelism (not in the reference): when torch.distributed is in
 rank processes its own images and the flat gradient + the 8 accumulators are all-reduced (sum) just
 before `gradient:div(cls_count)` (objective.lua:200), so the result equals the single-process result
 on the concatenated batch (not under cfg.roi_sampling.source = "proposals" where a quota cuts: every rank's objective counts its
-own images, so the ranks draw with seed + 0, seed + 1, ... each, where the single process draws with seed + k for its k-th image).
+own images, so the ranks draw with seed + 0, seed + 1, ... each, where the single process draws with seed + k for its k-th image;
+under source = "hard" nothing is drawn -- the loss decides -- so there the data-parallel result on the concatenated batch IS the
+single-process one).
 
 Not in the reference: cfg["roi_sampling"] (roi_sampling_settings) trains the classification net on a sample of the first NMS's
-candidates instead of the example rows -- scan, selection, NMS and frcnn_proposal_targets_batch on the pass's own head maps."""
+candidates instead of the example rows -- scan, selection, NMS and frcnn_proposal_targets_batch on the pass's own head maps.
+Under source = "hard" (online hard example mining) every labelled candidate is scored first and the rows of largest loss train
+(mine_hard).  The scoring pass runs the classification net in evaluate mode: it normalises with the BatchNormalization layers'
+RUNNING statistics and applies no dropout, while the training pass behind it uses the batch's statistics and draws its masks --
+the loss that ranks a row is the deployed net's, not the one the row's gradient is taken of."""
 import ctypes as C
 import math
 import os
@@ -98,7 +104,8 @@ def align_geometry(localizer):
 
 
 ROI_SAMPLING_DEFAULTS = dict(source="examples", batch=128, fg_fraction=0.25, fg_iou=0.5, bg_iou=(0.0, 0.5), include_gt=True,
-                             threshold=0.5, nms_overlap=0.7, pre_nms_top_n=6000, post_nms_top_n=2000, seed=0)
+                             threshold=0.5, nms_overlap=0.7, pre_nms_top_n=6000, post_nms_top_n=2000, seed=0,
+                             hard_nms_overlap=0.7)
 ROI_SAMPLING_MAX_GT = 64          # ground-truth boxes an image may carry (frcnn_proposal_targets_batch)
 ROI_SAMPLING_MAX_CANDIDATES = 4096   # ground truth + picks a segment of frcnn_proposal_targets_batch holds
 
@@ -108,7 +115,10 @@ def roi_sampling_settings(cfg):
     settings plus fg_quota = floor(batch * fg_fraction + 0.5), or None when the key is absent.
       source          "examples" (default: objective.lua:91-140 -- the ground-truth rects of the positive anchors and the rects of
                       the sampled negative anchors) or "proposals": a sample of the candidates the first NMS leaves on this very
-                      forward pass, matched to the image's ground truth by frcnn_proposal_targets_batch
+                      forward pass, matched to the image's ground truth by frcnn_proposal_targets_batch; or "hard": online hard
+                      example mining (Shrivastava et al. 2016) -- EVERY labelled candidate is scored by the net in evaluate mode,
+                      an NMS keyed by the loss removes near-duplicates, and the `batch` survivors of largest loss are the rows
+                      the net is trained on
       batch           rows a image contributes at most (1 ... 4096); fg_fraction: the share of them that may be foreground (0 ... 1)
       fg_iou          a candidate whose best IoU reaches it is foreground (0 ... 1)
       bg_iou          {lo, hi}: background is lo <= best IoU < hi, with lo <= hi <= fg_iou; anything else is ignored
@@ -118,6 +128,11 @@ def roi_sampling_settings(cfg):
       pre_nms_top_n   the best-scoring matches the NMS sees (1 ... Detector.NMS_FIRST_CAP); post_nms_top_n: the picks that become
                       candidates (1 ... 4096 - 64)
       seed            of the sampling hash (0 ... 2^32 - 1); image k of an objective draws with seed + k
+      hard_nms_overlap  the overlap of the NMS among the scored candidates under "hard", in (0, 1] (1: no row suppresses another --
+                      an IoU never exceeds 1); accepted and unused under the other sources, as every key but source is under "examples"
+                      (the validated table of another source carries the key only when cfg sets it)
+    Under "hard" batch, fg_iou, bg_iou, include_gt, threshold, nms_overlap, pre_nms_top_n and post_nms_top_n keep their meaning;
+    fg_fraction and seed are NOT applied: no quota is drawn, the loss decides which rows train and how many are foreground.
     Raises FrcnnError -- before the model or the device is touched -- for an unknown key, a wrong type or a value out of range."""
     t = cfg.get("roi_sampling")
     if t is None:
@@ -147,8 +162,8 @@ def roi_sampling_settings(cfg):
             raise E("cfg.roi_sampling.%s = %d outside %d ... %d" % (key, v, lo, hi))
         return int(v)
 
-    if not isinstance(out["source"], str) or out["source"] not in ("examples", "proposals"):
-        raise E("cfg.roi_sampling.source = %r (\"examples\" or \"proposals\")" % (out["source"],))
+    if not isinstance(out["source"], str) or out["source"] not in ("examples", "proposals", "hard"):
+        raise E("cfg.roi_sampling.source = %r (\"examples\", \"proposals\" or \"hard\")" % (out["source"],))
     if not isinstance(out["include_gt"], bool):
         raise E("cfg.roi_sampling.include_gt = %r (true or false)" % (out["include_gt"],))
     from .Detector import Detector
@@ -171,6 +186,9 @@ def roi_sampling_settings(cfg):
     out["pre_nms_top_n"] = integer("pre_nms_top_n", 1, Detector.NMS_FIRST_CAP)
     out["post_nms_top_n"] = integer("post_nms_top_n", 1, ROI_SAMPLING_MAX_CANDIDATES - ROI_SAMPLING_MAX_GT)
     out["seed"] = integer("seed", 0, 0xFFFFFFFF)
+    out["hard_nms_overlap"] = number("hard_nms_overlap", 0.0, 1.0, lo_open=True)
+    if out["source"] != "hard" and "hard_nms_overlap" not in t:   # (the validated table of the other sources stays the one it was)
+        del out["hard_nms_overlap"]
     out["fg_quota"] = int(math.floor(out["batch"] * out["fg_fraction"] + 0.5))
     return out
 
@@ -457,7 +475,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     def sampling_on():
         """the validated settings when this pass trains the classification net on sampled proposals, else None"""
         rs = roi_sampling_settings(cfg)
-        if rs is None or rs["source"] != "proposals" or not train_settings(cfg, nblk_all)[2]:
+        if rs is None or rs["source"] not in ("proposals", "hard") or not train_settings(cfg, nblk_all)[2]:
             return None
         return rs
 
@@ -497,23 +515,90 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         wsb = L.frcnn_nms_batch_workspace_bytes(1, kcap)
         _lib.call("frcnn_nms_device_batch", ptr(box5), 1, kcap, kcap, c_k, 5, C.c_float(rs["nms_overlap"]), 2, 5, None, ptr(pick),
                   c_R, ptr(scratch.get("rs_nms_ws", (wsb,), np.uint8)), wsb, s)
-        rows = rs["batch"]
         seed = (rs["seed"] + rs_state["images"]) & 0xFFFFFFFF
         rs_state["images"] += 1
+        r_cap = min(kcap, rs["post_nms_top_n"])
+        # "hard": no quota cuts and the seed decides nothing -- every labelled candidate leaves, foreground rows first (the "all"
+        # table of mine_hard, at most r_cap + 64 rows)
+        hard = rs["source"] == "hard"
+        rows = r_cap + (ROI_SAMPLING_MAX_GT if rs["include_gt"] else 0) if hard else rs["batch"]
+        quota = rows if hard else rs["fg_quota"]
+        pre = "rh_all_" if hard else "rs_"
         rec = dict(rect=rect, pick=pick, R=DeviceTensor(ctl.ptr + 24, (1,), i32, owner=ctl), stride=kcap,
-                   r_cap=min(kcap, rs["post_nms_top_n"]), seed=seed, settings=rs, bgclass=bgclass,
-                   roi=scratch.get("rs_roi", (rows, 4), np.float64), crtarget=scratch.get("rs_crtarget", (rows, 4)),
-                   cctarget=scratch.get("rs_cctarget", (rows,)), src=scratch.get("rs_src", (rows,), i32),
-                   gt_idx=scratch.get("rs_gt_idx", (rows,), i32), iou=scratch.get("rs_iou", (rows,), np.float64))
+                   r_cap=r_cap, seed=seed, settings=rs, bgclass=bgclass,
+                   roi=scratch.get(pre + "roi", (rows, 4), np.float64), crtarget=scratch.get(pre + "crtarget", (rows, 4)),
+                   cctarget=scratch.get(pre + "cctarget", (rows,)), src=scratch.get(pre + "src", (rows,), i32),
+                   gt_idx=scratch.get(pre + "gt_idx", (rows,), i32), iou=scratch.get(pre + "iou", (rows,), np.float64))
         _lib.call("frcnn_proposal_targets_batch", ptr(rect), ptr(pick), kcap, c_R, rec["r_cap"], C.c_void_p(d_gt), C.c_void_p(d_gc),
                   max(G, 1), (C.c_int * 1)(G), 1, 1 if rs["include_gt"] else 0, rs["fg_iou"], rs["bg_iou"][0], rs["bg_iou"][1],
-                  rs["fg_quota"], rows, bgclass, C.c_uint(seed), ptr(rec["roi"]), ptr(rec["crtarget"]), ptr(rec["cctarget"]),
+                  quota, rows, bgclass, C.c_uint(seed), ptr(rec["roi"]), ptr(rec["crtarget"]), ptr(rec["cctarget"]),
                   ptr(rec["src"]), ptr(rec["gt_idx"]), ptr(rec["iou"]), rows, ptr(ctl), s)
         host = np.zeros(4, i32)
         _lib.call("frcnn_memcpy_d2h", host.ctypes.data_as(C.c_void_p), ptr(ctl), 16, s)     # the ONE read-back of the stage
         _lib.call("frcnn_stream_sync", s)
         rec["counts"] = tuple(int(v) for v in host)
         return rec, rec["counts"][2], rec["counts"][3]
+
+    def mine_hard(rs, rec, fm):
+        """Online hard example mining behind sample_proposals (source = "hard"): rec holds the "all" table -- every labelled
+        candidate, the F_all foreground rows first -- and its counts.  The N = F_all + B_all rows are pooled (no arg-max record)
+        and scored by the classification net in evaluate mode (cnet.score: nothing is drawn, no state of the module changes);
+        frcnn_roi_hard_keys_batch writes {rect, loss} rows, frcnn_nms_device_batch keyed by the loss at rs.hard_nms_overlap picks
+        in descending loss order, frcnn_roi_hard_gather_batch writes the first rs.batch picks' rows, in ascending row order, as
+        the training tables; then the stage's SECOND read-back, of the gather's four counts -> (F, Bq).  rec keeps its fields
+        for the training tables and gains all, score, box5, loss, loss_sel, hard_pick and hard_counts = (F, Bq, survivors, N)."""
+        s = stream_ptr()
+        i32 = np.int32
+        names = ("roi", "crtarget", "cctarget", "src", "gt_idx", "iou")
+        nfg, nbg, Fa, Ba = rec["counts"]
+        N, Ncap = Fa + Ba, int(rec["roi"].shape[0])
+        rec["all"] = dict([(k, rec[k]) for k in names], counts=rec["counts"])
+        rows = min(rs["batch"], Ncap)
+        rec.update(roi=scratch.get("rs_roi", (rows, 4), np.float64), crtarget=scratch.get("rs_crtarget", (rows, 4)),
+                   cctarget=scratch.get("rs_cctarget", (rows,)), src=scratch.get("rs_src", (rows,), i32),
+                   gt_idx=scratch.get("rs_gt_idx", (rows,), i32), iou=scratch.get("rs_iou", (rows,), np.float64),
+                   loss_sel=scratch.get("rh_loss_sel", (rows,)), score=None, box5=None, loss=None, hard_pick=None,
+                   hard_counts=(0, 0, 0, 0), counts=(nfg, nbg, 0, 0))
+        if N == 0:
+            stats.setdefault("hard", []).append((0, 0))
+            return 0, 0
+        fmC, fmH, fmW = fm.shape
+        cin = scratch.get("rh_cinput", (N, D))
+        a = rec["all"]
+        if align:
+            _lib.call("frcnn_roi_align_forward", ptr(fm), fmC, fmH, fmW, ptr(a["roi"]), None, N, inv_sx, inv_sy, kh, kw, sampling,
+                      ptr(cin), s)
+        else:
+            loc = rs_state["loc"]
+            wins = scratch.get("rh_wins", (N, 4), i32)
+            _lib.call("frcnn_roi_windows", ptr(a["roi"]), None, N, loc.ctypes.data_as(C.c_void_p), len(loc), fmH, fmW, ptr(wins), s)
+            _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(wins), N, kh, kw, ptr(cin), None, s)
+        score = cnet.score(cin, (scratch.get("rh_crout", (N, 4)), scratch.get("rh_ccout", (N, ncls))))
+        # {N, F_all, survivors, -}, then the gather's {F, Bq, survivors, N}: the row counts are host numbers since the first
+        # read-back and travel back as 16 bytes from page-locked memory (the NMS reads its count on the device)
+        hctl = scratch.get("rh_ctl", (8,), i32)
+        hn, staged = pinned.stage(np.array([N, Fa, 0, 0], i32).view(np.uint8))
+        _lib.call("frcnn_memcpy_h2d", ptr(hctl), C.c_void_p(hn), 16, s)
+        staged()
+        c_n, c_f, c_surv, c_out = (C.c_void_p(hctl.ptr + 4 * k) for k in (0, 1, 2, 4))
+        box5 = scratch.get("rh_box5", (Ncap, 5)); loss = scratch.get("rh_loss", (Ncap,))
+        _lib.call("frcnn_roi_hard_keys_batch", ptr(a["roi"]), ptr(score[0]), ptr(a["crtarget"]), ptr(score[1]), ptr(a["cctarget"]), 1,
+                  Ncap, Ncap, c_n, c_f, ncls, ptr(box5), ptr(loss), s)
+        pick = scratch.get("rh_pick", (Ncap,), np.int64)
+        wsb = L.frcnn_nms_batch_workspace_bytes(1, Ncap)
+        _lib.call("frcnn_nms_device_batch", ptr(box5), 1, Ncap, Ncap, c_n, 5, C.c_float(rs["hard_nms_overlap"]), 2, 5, None, ptr(pick),
+                  c_surv, ptr(scratch.get("rh_nms_ws", (wsb,), np.uint8)), wsb, s)
+        _lib.call("frcnn_roi_hard_gather_batch", ptr(pick), c_surv, rs["batch"], ptr(a["roi"]), ptr(a["crtarget"]), ptr(a["cctarget"]),
+                  ptr(a["src"]), ptr(a["gt_idx"]), ptr(a["iou"]), ptr(loss), 1, Ncap, Ncap, c_n, c_f, ptr(rec["roi"]),
+                  ptr(rec["crtarget"]), ptr(rec["cctarget"]), ptr(rec["src"]), ptr(rec["gt_idx"]), ptr(rec["iou"]),
+                  ptr(rec["loss_sel"]), rows, c_out, s)
+        host = np.zeros(4, i32)
+        _lib.call("frcnn_memcpy_d2h", host.ctypes.data_as(C.c_void_p), c_out, 16, s)     # the second read-back of the stage
+        _lib.call("frcnn_stream_sync", s)
+        F, Bq, surv, n = (int(v) for v in host)
+        rec.update(score=score, box5=box5, loss=loss, hard_pick=pick, hard_counts=(F, Bq, surv, n), counts=(nfg, nbg, F, Bq))
+        stats.setdefault("hard", []).append((n, surv))
+        return F, Bq
 
     prepared = {}   # id(batch entry) -> (the entry itself, tables packed ahead of the pass: finish(), while the host waits for
                     # the device); the entry is held so that its id cannot be re-used by another object while the tables wait
@@ -751,6 +836,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 G = len(prep["gt_class"])
                 d_gt = dblob.ptr + prep["gt_off"]
                 rec, F_rows, Bq = sample_proposals(rs, outputs, int(img.shape[1]), int(img.shape[2]), d_gt, d_gt + 32 * max(G, 1), G)
+                if rs["source"] == "hard":   # the rows of largest loss among them, chosen by the net as it stands
+                    F_rows, Bq = mine_hard(rs, rec, fm)
                 S = F_rows + Bq
                 rec.update(gt_rect=prep["gt_rect"], gt_class=prep["gt_class"], cinput=None)
                 debug["roi_sampling"] = rec
@@ -1059,8 +1146,10 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     lossAndGradient.trainable_ranges = lambda: stage_ranges()[3]
     lossAndGradient.pass_ranges = lambda: stage[0]
     lossAndGradient.debug = debug   # (tests: the scratch buffers, the example count and -- RoIAlign -- the rects of the image being processed)
-    # cfg.roi_sampling.source = "proposals": debug["roi_sampling"] holds the last image's sampler record -- the candidates (rect, pick, R,
-    # stride, r_cap), the kernel's outputs (roi, crtarget, cctarget, src, gt_idx, iou, counts), the seed, the ground truth and cinput
+    # cfg.roi_sampling.source = "proposals" / "hard": debug["roi_sampling"] holds the last image's sampler record -- the candidates (rect, pick, R,
+    # stride, r_cap), the kernel's outputs (roi, crtarget, cctarget, src, gt_idx, iou, counts), the seed, the ground truth and cinput;
+    # under "hard" those are the tables the net trained on, and the record gains all (every labelled candidate: the six tensors and
+    # their counts), score (crout, ccout of the scoring pass), box5, loss, loss_sel, hard_pick and hard_counts (mine_hard)
     return lossAndGradient
 
 

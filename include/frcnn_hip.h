@@ -952,4 +952,8 @@ int frcnn_broadcast_f32(frcnn_comm *, float *buf, long long n, int root, void *s
 #ifdef __cplusplus
 }
 #endif
+
+/* Online hard example mining for the classification net (cfg.roi_sampling.source = "hard"): its two entry points are declared,
+ * with their semantics, in a header of their own; a host that includes this file gets them too. */
+#include "frcnn_hip_hard.h"
 #endif /* FRCNN_HIP_H */
