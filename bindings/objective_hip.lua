@@ -80,6 +80,10 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
     -- disabled stage, the optimiser updates `ranges` only
     local frozen_blocks, proposal, classification, ranges = stage()
     local rs = hip.roi_sampling_settings(cfg)         -- (validated, like cfg.train, before anything is queued)
+    -- cfg.cnet_loss (INTEGRATION.md): nil -- the reference's losses (frcnn_cnet_losses) -- or the description of
+    -- frcnn_cnet_loss_rows, whose rows frcnn_loss_accumulate sums into the same two accumulators
+    local cl = hip.cnet_loss_settings(cfg)
+    local cl_desc = cl and hip.cnet_loss_desc(cl, bgclass) or nil
     if rs and ((rs.source ~= 'proposals' and rs.source ~= 'hard') or not classification) then rs = nil end
     check(C.frcnn_model_set_trainable(native, frozen_blocks, proposal and 1 or 0, classification and 1 or 0))
     published.pass = ranges
@@ -217,8 +221,13 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
         local crdelta = hip.view(scratch('crdelta', 16 * E).ptr, { E, 4 })
         local ccdelta = hip.view(scratch('ccdelta', 4 * E * ncls).ptr, { E, ncls })
         check(C.frcnn_pnet_anchor_loss_wait(native, nil))               -- crtarget is relative to the proposals (:156)
-        check(C.frcnn_cnet_losses(crout.ptr, crtarget, ccout.ptr, cctarget, E, npos, ncls, crdelta.ptr, ccdelta.ptr,
-                                  ffi.cast('double*', acc.ptr) + 4, nil))               -- :170-177
+        if cl_desc == nil then
+          check(C.frcnn_cnet_losses(crout.ptr, crtarget, ccout.ptr, cctarget, E, npos, ncls, crdelta.ptr, ccdelta.ptr,
+                                    ffi.cast('double*', acc.ptr) + 4, nil))               -- :170-177
+        else
+          hip.cnet_losses(cl_desc, scratch, crout.ptr, crtarget, ccout.ptr, cctarget, E, npos, ncls, crdelta.ptr, ccdelta.ptr,
+                          ffi.cast('double*', acc.ptr) + 4)
+        end
         local post_roi_delta = cnet:backward(cinput, { crdelta, ccdelta })              -- :179
         if frozen_blocks < nblocks and align then       -- (a frozen backbone: the library left the input gradient unwritten)
           check(C.frcnn_roi_align_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr,
@@ -267,7 +276,7 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
             score = cnet:score(hin, hip.view(scratch('rh_crout', 16 * N).ptr, { N, 4 }),
                                hip.view(scratch('rh_ccout', 4 * N * ncls).ptr, { N, ncls }))
           end
-          rec = hip.mine_hard(rs, rec, scratch, N, score and score[1].ptr, score and score[2].ptr, ncls)
+          rec = hip.mine_hard(rs, rec, scratch, N, score and score[1].ptr, score and score[2].ptr, ncls, cl_desc)
           stats.hard = stats.hard or {}
           table.insert(stats.hard, rec.hard)
         end
@@ -295,8 +304,13 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
           local crdelta = hip.view(scratch('crdelta', 16 * S).ptr, { S, 4 })
           local ccdelta = hip.view(scratch('ccdelta', 4 * S * ncls).ptr, { S, ncls })
           check(C.frcnn_pnet_anchor_loss_wait(native, nil))
-          check(C.frcnn_cnet_losses(crout.ptr, rec.crtarget, ccout.ptr, rec.cctarget, S, F_rows, ncls, crdelta.ptr, ccdelta.ptr,
-                                    ffi.cast('double*', acc.ptr) + 4, nil))
+          if cl_desc == nil then
+            check(C.frcnn_cnet_losses(crout.ptr, rec.crtarget, ccout.ptr, rec.cctarget, S, F_rows, ncls, crdelta.ptr, ccdelta.ptr,
+                                      ffi.cast('double*', acc.ptr) + 4, nil))
+          else
+            hip.cnet_losses(cl_desc, scratch, crout.ptr, rec.crtarget, ccout.ptr, rec.cctarget, S, F_rows, ncls, crdelta.ptr,
+                            ccdelta.ptr, ffi.cast('double*', acc.ptr) + 4)
+          end
           local post_roi_delta = cnet:backward(cinput, { crdelta, ccdelta })
           if frozen_blocks < nblocks and align then
             check(C.frcnn_roi_align_backward(delta_outputs[nheads + 1].ptr, fs[1], fs[2], fs[3], post_roi_delta.ptr, rec.roi, nil, S,

@@ -198,11 +198,23 @@ HARD_SIGS = {
                                      vp, vp, vp, C.c_int, vp, vp], C.c_int),
 }
 
+# the entry point of include/frcnn_hip_loss.h (cfg.cnet_loss: the classification net's losses row by row) and its description
+LOSS_SIGS = {
+    "frcnn_cnet_loss_rows": ([vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+}
+
+
+class CnetLossDesc(C.Structure):
+    """frcnn_cnet_loss_desc of include/frcnn_hip_loss.h"""
+    _fields_ = [("cls", C.c_int), ("box", C.c_int), ("bgclass", C.c_int), ("gamma", C.c_double), ("alpha", C.c_double),
+                ("smoothing", C.c_double), ("beta", C.c_double), ("box_weight", C.c_double)]
+
+
 _lib = None
 
 
 def exported_symbols():
-    """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS)"""
+    """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -225,7 +237,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

@@ -222,6 +222,12 @@ int frcnn_roi_hard_gather_batch(const long long* pick, const int* count_dev, int
                                nfg_dev, roi_out, crtarget_out, cctarget_out, src_out, gt_idx_out, iou_out, loss_out, out_stride,
                                counts, S(stream));
 }
+int frcnn_cnet_loss_rows(float* crout, const float* crtarget, const float* ccout, const float* cctarget, const double* roi, int R,
+                         int npos, int ncls, const frcnn_cnet_loss_desc* desc_host, float* crdelta, float* ccdelta,
+                         double* row_loss, float* key, float* box5, void* stream) {
+  return cnet_loss_rows(crout, crtarget, ccout, cctarget, roi, R, npos, ncls, desc_host, crdelta, ccdelta, row_loss, key, box5,
+                        S(stream));
+}
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,
                               const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {

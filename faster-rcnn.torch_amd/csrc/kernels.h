@@ -332,6 +332,10 @@ int roi_hard_gather_batch(const long long* pick, const int* count_dev, int batch
                           long long row_stride, int n_cap, const int* n_dev, const int* nfg_dev, double* roi_out,
                           float* crtarget_out, float* cctarget_out, int* src_out, int* gt_idx_out, double* iou_out,
                           float* loss_out, int out_stride, int* counts, hipStream_t s);
+// ---- the classification net's losses row by row (cnet_loss.hip; cfg.cnet_loss): semantics in include/frcnn_hip_loss.h
+int cnet_loss_rows(float* crout, const float* crtarget, const float* ccout, const float* cctarget, const double* roi, int R,
+                   int npos, int ncls, const frcnn_cnet_loss_desc* desc, float* crdelta, float* ccdelta, double* row_loss,
+                   float* key, float* box5, hipStream_t s);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

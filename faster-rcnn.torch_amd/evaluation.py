@@ -28,19 +28,23 @@ from .Anchors import MT19937
 from .BatchIterator import assemble_examples
 from .Localizer import Localizer
 from .Rect import Rect
-from .objective import align_geometry, roi_pooling_settings, roi_windows
+from .objective import align_geometry, cnet_loss_desc, cnet_loss_settings, roi_pooling_settings, roi_windows
 from .synthetic import clean_examples, output_map_sizes
 from .tensor import DeviceTensor, ptr, stream_ptr, to_device
 
 
-def validation_losses(model, batch_iterator, count, seed=1234, negatives=16):
+def validation_losses(model, batch_iterator, count, seed=1234, negatives=16, debug=None):
     """-> dict(pcls, preg, dcls, dreg, images, examples, positives).  `batch_iterator` needs nextValidation(n) -> [{img, rois}]
-    and .anchors (BatchIterator / any object with the same two members)."""
+    and .anchors (BatchIterator / any object with the same two members).  dcls / dreg are the losses of cfg["cnet_loss"] when the
+    model's cfg carries that key (cnet_loss_settings), else the reference's.  debug: a list that receives, per image with
+    examples, the host copies of the classification net's rows (crout, ccout, crtarget, cctarget, R, npos)."""
     import torch
     cfg = model["cfg"]
     pnet, cnet, native = model["pnet"], model["cnet"], model["native"]
     bgclass = cfg["class_count"] + 1
     ncls = cfg["class_count"] + 1
+    cl = cnet_loss_settings(cfg)     # cfg.cnet_loss (validated before the device is touched); None: the reference's losses
+    cl_desc = None if cl is None else cnet_loss_desc(cl, bgclass)
     kh, kw, method, sampling = roi_pooling_settings(cfg)
     planes = model["layers"][-1]["filters"]
     D = kh * kw * planes
@@ -106,9 +110,20 @@ def validation_losses(model, batch_iterator, count, seed=1234, negatives=16):
                     _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(d_wins), E, kh, kw, ptr(cinput), ptr(pidx), s)
                 crout, ccout = cnet.forward(cinput)
                 crdelta = DeviceTensor.empty((E, 4)); ccdelta = DeviceTensor.empty((E, ncls))
-                _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), E, npos, ncls,
-                          ptr(crdelta), ptr(ccdelta), C.c_void_p(acc.data_ptr() + 4 * 8), s)
-                keep.append((d_idx, d_anchor, d_roi, d_class, d_wins, scratch, ex_loss, crtarget, cctarget, cinput, pidx, crdelta, ccdelta))
+                row_loss = None
+                if cl_desc is None:
+                    _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), E, npos, ncls,
+                              ptr(crdelta), ptr(ccdelta), C.c_void_p(acc.data_ptr() + 4 * 8), s)
+                else:   # cfg.cnet_loss: the loss the objective trains on, row by row, summed in frcnn_loss_accumulate's order
+                    row_loss = DeviceTensor.empty((E, 2), np.float64)
+                    _lib.call("frcnn_cnet_loss_rows", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), None, E, npos, ncls,
+                              C.byref(cl_desc), ptr(crdelta), ptr(ccdelta), ptr(row_loss), None, None, s)
+                    _lib.call("frcnn_loss_accumulate", ptr(row_loss), E, C.c_void_p(acc.data_ptr() + 4 * 8), s)
+                if debug is not None:
+                    debug.append(dict(crout=crout.numpy(), ccout=ccout.numpy(), crtarget=crtarget.numpy(), cctarget=cctarget.numpy(),
+                                      R=E, npos=npos))
+                keep.append((d_idx, d_anchor, d_roi, d_class, d_wins, scratch, ex_loss, crtarget, cctarget, cinput, pidx, crdelta, ccdelta,
+                             row_loss))
                 reg_count += npos; cls_count += E; creg_count += npos      # :194-197
         a = acc.cpu().numpy()
     finally:

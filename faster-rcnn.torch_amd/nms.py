@@ -11,7 +11,9 @@ box_vote(boxes, picks, ...) and proposal_targets(rect, pick, R, gt_rect, gt_clas
 voting (frcnn_box_vote_batch) and the proposal-target layer of training on sampled proposals (frcnn_proposal_targets_batch).
 
 roi_hard_select(roi, crout, crtarget, ccout, cctarget, nfg, ...) -- online hard example mining of the classification net's rows:
-frcnn_roi_hard_keys_batch, the NMS keyed by the loss, frcnn_roi_hard_gather_batch."""
+frcnn_roi_hard_keys_batch, the NMS keyed by the loss, frcnn_roi_hard_gather_batch.
+
+cnet_loss(crout, crtarget, ccout, cctarget, npos, settings, ...) -- the losses of cfg["cnet_loss"] row by row: frcnn_cnet_loss_rows."""
 import ctypes as C
 import math
 import numbers
@@ -275,4 +277,56 @@ def roi_hard_select(roi, crout, crtarget, ccout, cctarget, nfg, batch=128, overl
     S = counts[0] + counts[1]
     res = dict((k, t.numpy()[:S].copy()) for k, t in out.items())
     res.update(counts=counts, box5=box5.numpy()[:n].copy(), loss_all=loss.numpy()[:n].copy(), pick=pick.numpy()[:counts[2]].copy())
+    return res
+
+
+def cnet_loss(crout, crtarget, ccout, cctarget, npos, settings=None, roi=None, train=True):
+    """The losses of the classification net under cfg["cnet_loss"] (not in the reference beyond its defaults) on host arrays:
+    frcnn_cnet_loss_rows.  crout and crtarget (R x 4 float32), ccout (R x ncls float32 log-probabilities), cctarget (R float32,
+    1-based classes), the first npos rows foreground; settings: a table as cfg["cnet_loss"] takes it (None or {}: the defaults --
+    NLL and SmoothL1 * 10), validated by cnet_loss_settings, with the background class ncls; roi (R x 4 float64): the rects of
+    box5.  train=True: the training mode -- crdelta and ccdelta are written and the rows >= npos of crout zeroed; False: the
+    scoring mode -- crout is only read.  -> dict(row_loss R x 2 float64 {box_weight * box, cls / R}, key R float32, loss
+    (creg, ccls): frcnn_loss_accumulate's sums of row_loss, box5 R x 5 float32 with roi, and under train crout, crdelta, ccdelta).
+    Runs on the device: there is no host twin (semantics: include/frcnn_hip_loss.h); a refused setting raises FrcnnError before
+    anything is launched."""
+    from .objective import cnet_loss_desc, cnet_loss_settings
+    st = cnet_loss_settings(dict(cnet_loss={} if settings is None else settings))
+    crout = np.ascontiguousarray(crout, dtype=np.float32).reshape(-1, 4)
+    R = int(crout.shape[0])
+    crtarget = np.ascontiguousarray(crtarget, dtype=np.float32).reshape(-1, 4)
+    cctarget = np.ascontiguousarray(cctarget, dtype=np.float32).reshape(-1)
+    ccout = np.ascontiguousarray(ccout, dtype=np.float32)
+    if ccout.ndim != 2 or ccout.shape[0] != R or ccout.shape[1] < 1:
+        raise ValueError("cnet_loss: ccout must be %d x ncls" % R)
+    ncls = int(ccout.shape[1])
+    if crtarget.shape[0] != R or cctarget.shape[0] != R:
+        raise ValueError("cnet_loss: crtarget and cctarget need %d rows" % R)
+    if roi is not None:
+        roi = np.ascontiguousarray(roi, dtype=np.float64).reshape(-1, 4)
+        if roi.shape[0] != R:
+            raise ValueError("cnet_loss: roi has %d rows, crout %d" % (roi.shape[0], R))
+    desc = cnet_loss_desc(st, ncls)
+
+    def dev(a):
+        return DeviceTensor.from_numpy(a if a.size else np.zeros((1,) + a.shape[1:], a.dtype))
+    n = max(R, 1)
+    d_crout, d_crt, d_cco, d_cct = dev(crout), dev(crtarget), dev(ccout), dev(cctarget)
+    d_roi = dev(roi) if roi is not None else None
+    crdelta = DeviceTensor.zeros((n, 4)) if train else None
+    ccdelta = DeviceTensor.zeros((n, ncls)) if train else None
+    row_loss = DeviceTensor.zeros((n, 2), np.float64)
+    key = DeviceTensor.zeros((n,))
+    box5 = DeviceTensor.zeros((n, 5)) if roi is not None else None
+    acc = DeviceTensor.zeros((2,), np.float64)
+    s = stream_ptr()
+    _lib.call("frcnn_cnet_loss_rows", ptr(d_crout), ptr(d_crt), ptr(d_cco), ptr(d_cct), ptr(d_roi) if d_roi is not None else None, R,
+              int(npos), ncls, C.byref(desc), ptr(crdelta) if train else None, ptr(ccdelta) if train else None, ptr(row_loss),
+              ptr(key), ptr(box5) if box5 is not None else None, s)
+    _lib.call("frcnn_loss_accumulate", ptr(row_loss), R, ptr(acc), s)
+    res = dict(row_loss=row_loss.numpy()[:R].copy(), key=key.numpy()[:R].copy(), loss=tuple(float(v) for v in acc.numpy()))
+    if box5 is not None:
+        res["box5"] = box5.numpy()[:R].copy()
+    if train:
+        res.update(crout=d_crout.numpy()[:R].copy(), crdelta=crdelta.numpy()[:R].copy(), ccdelta=ccdelta.numpy()[:R].copy())
     return res

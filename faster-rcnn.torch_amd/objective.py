@@ -20,7 +20,11 @@ candidates instead of the example rows -- scan, selection, NMS and frcnn_proposa
 Under source = "hard" (online hard example mining) every labelled candidate is scored first and the rows of largest loss train
 (mine_hard).  The scoring pass runs the classification net in evaluate mode: it normalises with the BatchNormalization layers'
 RUNNING statistics and applies no dropout, while the training pass behind it uses the batch's statistics and draws its masks --
-the loss that ranks a row is the deployed net's, not the one the row's gradient is taken of."""
+the loss that ranks a row is the deployed net's, not the one the row's gradient is taken of.
+
+Not in the reference either: cfg["cnet_loss"] (cnet_loss_settings) replaces the fixed losses of objective.lua:170-177 -- SmoothL1 * 10
+and ClassNLL -- by frcnn_cnet_loss_rows: focal loss, label smoothing, a GIoU box loss, computed row by row and summed by
+frcnn_loss_accumulate; under source = "hard" the same kernel writes the keys the candidates are ranked by."""
 import ctypes as C
 import math
 import os
@@ -191,6 +195,64 @@ def roi_sampling_settings(cfg):
         del out["hard_nms_overlap"]
     out["fg_quota"] = int(math.floor(out["batch"] * out["fg_fraction"] + 0.5))
     return out
+
+
+CNET_LOSS_DEFAULTS = dict(cls="nll", gamma=2.0, alpha=None, label_smoothing=0.0, box="smooth_l1", beta=1.0, box_weight=10.0)
+
+
+def cnet_loss_settings(cfg):
+    """cfg["cnet_loss"] (not in the reference): which losses the classification net is trained on and reported with -> the
+    validated settings, or None when the key is absent (then the pass is the reference's: frcnn_cnet_losses, objective.lua:170-177).
+    With the key present -- {} included -- the losses run row by row in frcnn_cnet_loss_rows and are summed by
+    frcnn_loss_accumulate (semantics and arithmetic: include/frcnn_hip_loss.h).
+      cls              "nll" (default: ClassNLL averaged over the rows) or "focal" (Lin et al. 2017: -w (1 - p_t)^gamma log p_t)
+      gamma            the focal exponent, 0 ... 5 (default 2; 0 is nll); unused under "nll"
+      alpha            absent (default: every row weighs 1), or in (0, 1): a foreground row weighs alpha, a background row 1 - alpha
+      label_smoothing  in [0, 1) (default 0): the target distribution is (1 - e) at the class plus e / classes everywhere; refused
+                       with "focal" unless 0
+      box              "smooth_l1" (default) or "giou" (Rezatofighi et al. 2019, taken in the space of the box deltas)
+      beta             the SmoothL1 threshold, finite and > 0 (default 1: the reference's criterion); unused under "giou"
+      box_weight       the factor of the box loss and of its gradient, finite and >= 0 (default 10: objective.lua:172-173)
+    Raises FrcnnError -- before the model or the device is touched -- for an unknown key, a wrong type or a value out of range."""
+    t = cfg.get("cnet_loss")
+    if t is None:
+        return None
+    E = _lib.FrcnnError
+    if not isinstance(t, dict):
+        raise E("cfg.cnet_loss must be a table of {%s}" % ", ".join(CNET_LOSS_DEFAULTS))
+    unknown = sorted(set(t) - set(CNET_LOSS_DEFAULTS), key=str)
+    if unknown:
+        raise E("cfg.cnet_loss: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    out = dict(CNET_LOSS_DEFAULTS)
+    out.update(t)
+
+    def number(key, ok, what):
+        v = out[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise E("cfg.cnet_loss.%s = %r is not a finite number" % (key, v))
+        if not ok(v):
+            raise E("cfg.cnet_loss.%s = %r (%s)" % (key, v, what))
+        return float(v)
+
+    for key, names in (("cls", ("nll", "focal")), ("box", ("smooth_l1", "giou"))):
+        if not isinstance(out[key], str) or out[key] not in names:
+            raise E("cfg.cnet_loss.%s = %r (\"%s\" or \"%s\")" % ((key, out[key]) + names))
+    out["gamma"] = number("gamma", lambda v: 0.0 <= v <= 5.0, "0 ... 5")
+    if out["alpha"] is not None:
+        out["alpha"] = number("alpha", lambda v: 0.0 < v < 1.0, "absent, or in (0, 1)")
+    out["label_smoothing"] = number("label_smoothing", lambda v: 0.0 <= v < 1.0, "in [0, 1)")
+    if out["cls"] == "focal" and out["label_smoothing"] != 0.0:
+        raise E("cfg.cnet_loss.label_smoothing = %r is not defined under cls = \"focal\"" % (out["label_smoothing"],))
+    out["beta"] = number("beta", lambda v: v > 0.0, "finite, > 0")
+    out["box_weight"] = number("box_weight", lambda v: v >= 0.0, "finite, >= 0")
+    return out
+
+
+def cnet_loss_desc(settings, bgclass):
+    """the validated settings of cnet_loss_settings -> the frcnn_cnet_loss_desc frcnn_cnet_loss_rows reads on the host"""
+    return _lib.CnetLossDesc(cls=("nll", "focal").index(settings["cls"]), box=("smooth_l1", "giou").index(settings["box"]),
+                             bgclass=int(bgclass), gamma=settings["gamma"], alpha=-1.0 if settings["alpha"] is None else settings["alpha"],
+                             smoothing=settings["label_smoothing"], beta=settings["beta"], box_weight=settings["box_weight"])
 
 
 def ground_truth_table(x, class_count=None):
@@ -472,6 +534,21 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     # the first NMS's candidates on the pass's own head maps (sample_proposals below); absent or "examples": nothing here runs
     rs_state = dict(images=0, aw=None, ah=None, loc=None)
 
+    loss_state = dict(settings=None, desc=None)   # cfg.cnet_loss of the pass being queued (lossAndGradient sets it)
+
+    def cnet_losses(crout, crtarget, ccout, cctarget, R, npos_rows, crdelta, ccdelta):
+        """objective.lua:170-177 on R rows, the first npos_rows of them foreground: frcnn_cnet_losses, or -- under cfg.cnet_loss --
+        frcnn_cnet_loss_rows and the fixed-order sum of its rows into the same two accumulators"""
+        s = stream_ptr()
+        if loss_state["desc"] is None:
+            _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), R, npos_rows, ncls,
+                      ptr(crdelta), ptr(ccdelta), C.c_void_p(acc_dev.ptr + 4 * 8), s)
+            return
+        row_loss = scratch.get("cl_row_loss", (R, 2), np.float64)
+        _lib.call("frcnn_cnet_loss_rows", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), None, R, npos_rows, ncls,
+                  C.byref(loss_state["desc"]), ptr(crdelta), ptr(ccdelta), ptr(row_loss), None, None, s)
+        _lib.call("frcnn_loss_accumulate", ptr(row_loss), R, C.c_void_p(acc_dev.ptr + 4 * 8), s)
+
     def sampling_on():
         """the validated settings when this pass trains the classification net on sampled proposals, else None"""
         rs = roi_sampling_settings(cfg)
@@ -582,8 +659,12 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         staged()
         c_n, c_f, c_surv, c_out = (C.c_void_p(hctl.ptr + 4 * k) for k in (0, 1, 2, 4))
         box5 = scratch.get("rh_box5", (Ncap, 5)); loss = scratch.get("rh_loss", (Ncap,))
-        _lib.call("frcnn_roi_hard_keys_batch", ptr(a["roi"]), ptr(score[0]), ptr(a["crtarget"]), ptr(score[1]), ptr(a["cctarget"]), 1,
-                  Ncap, Ncap, c_n, c_f, ncls, ptr(box5), ptr(loss), s)
+        if loss_state["desc"] is None:
+            _lib.call("frcnn_roi_hard_keys_batch", ptr(a["roi"]), ptr(score[0]), ptr(a["crtarget"]), ptr(score[1]), ptr(a["cctarget"]), 1,
+                      Ncap, Ncap, c_n, c_f, ncls, ptr(box5), ptr(loss), s)
+        else:   # cfg.cnet_loss: the keys are the loss the rows will be trained on (scoring mode: the scores are only read)
+            _lib.call("frcnn_cnet_loss_rows", ptr(score[0]), ptr(a["crtarget"]), ptr(score[1]), ptr(a["cctarget"]), ptr(a["roi"]), N, Fa,
+                      ncls, C.byref(loss_state["desc"]), None, None, None, ptr(loss), ptr(box5), s)
         pick = scratch.get("rh_pick", (Ncap,), np.int64)
         wsb = L.frcnn_nms_batch_workspace_bytes(1, Ncap)
         _lib.call("frcnn_nms_device_batch", ptr(box5), 1, Ncap, Ncap, c_n, 5, C.c_float(rs["hard_nms_overlap"]), 2, 5, None, ptr(pick),
@@ -692,6 +773,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
         guard["divisor"] = None
         frozen_blocks, proposal, classification, ranges = stage_ranges()
         rs = sampling_on()   # (cfg.roi_sampling: validated, like cfg.train, before anything is queued)
+        cl = cnet_loss_settings(cfg)   # (cfg.cnet_loss likewise; None: the reference's losses, frcnn_cnet_losses)
+        loss_state.update(settings=cl, desc=None if cl is None else cnet_loss_desc(cl, bgclass))
         if rs is not None:   # ... and so is the ground truth of the batch this pass will process
             if next_batch[0] is None:
                 next_batch[0] = batch_iterator.nextTraining()
@@ -861,8 +944,8 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                     crdelta = scratch.get("crdelta", (S, 4))
                     ccdelta = scratch.get("ccdelta", (S, ncls))
                     pnet.anchor_loss_wait()       # (the accumulators: the anchor losses land in the same vector)
-                    _lib.call("frcnn_cnet_losses", ptr(crout), ptr(rec["crtarget"]), ptr(ccout), ptr(rec["cctarget"]), S, F_rows, ncls,
-                              ptr(crdelta), ptr(ccdelta), C.c_void_p(acc_dev.ptr + 4 * 8), s)
+                    cnet_losses(crout, rec["crtarget"], ccout, rec["cctarget"], S, F_rows, crdelta, ccdelta)
+                    rec.update(crout=crout, ccout=ccout, crdelta=crdelta, ccdelta=ccdelta)
                     post_roi_delta = cnet.backward(cinput, [crdelta, ccdelta])
                     if not trunk_frozen and align:
                         _lib.call("frcnn_roi_align_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),
@@ -893,8 +976,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                 crdelta = scratch.get("crdelta", (E, 4))
                 ccdelta = scratch.get("ccdelta", (E, ncls))
                 pnet.anchor_loss_wait()   # crtarget is relative to the anchor nets' proposals (:156)
-                _lib.call("frcnn_cnet_losses", ptr(crout), ptr(crtarget), ptr(ccout), ptr(cctarget), E, npos, ncls,
-                          ptr(crdelta), ptr(ccdelta), C.c_void_p(acc_dev.ptr + 4 * 8), s)  # :170-177
+                cnet_losses(crout, crtarget, ccout, cctarget, E, npos, crdelta, ccdelta)  # :170-177
+                debug["cnet_loss"] = dict(crout=crout, ccout=ccout, crtarget=crtarget, cctarget=cctarget, crdelta=crdelta,
+                                          ccdelta=ccdelta, R=E, npos=npos)
                 post_roi_delta = cnet.backward(cinput, [crdelta, ccdelta])  # :179
                 if not trunk_frozen and align:   # (a frozen backbone: the library left the input gradient unwritten)
                     _lib.call("frcnn_roi_align_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),

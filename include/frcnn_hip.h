@@ -956,4 +956,6 @@ int frcnn_broadcast_f32(frcnn_comm *, float *buf, long long n, int root, void *s
 /* Online hard example mining for the classification net (cfg.roi_sampling.source = "hard"): its two entry points are declared,
  * with their semantics, in a header of their own; a host that includes this file gets them too. */
 #include "frcnn_hip_hard.h"
+/* The configurable losses of the classification net (cfg.cnet_loss): one entry point and its description, likewise. */
+#include "frcnn_hip_loss.h"
 #endif /* FRCNN_HIP_H */
