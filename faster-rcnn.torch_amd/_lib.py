@@ -86,6 +86,8 @@ _SIGS = {
     "frcnn_maxpool_act_backward": ([vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),
     "frcnn_act_forward": ([vp, C.c_int, C.c_longlong, vp, vp, vp, vp], C.c_int),
     "frcnn_act_backward": ([vp, vp, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_conv2d_forward_pool": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_conv2d_backward_weight_pooled": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp], C.c_int),
     "frcnn_amax_record_floats": ([], C.c_int),
     "frcnn_tensor_absmax": ([vp, C.c_longlong, vp, vp], C.c_int),
     "frcnn_maxpool_act_forward_rec": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),

@@ -446,6 +446,39 @@ int frcnn_act_backward(const float* gy, const float* x, int C, long long hw, con
                        const float* scale, float* gx, float* gbias, float* gslope, void* stream) {
   return act_backward(gy, x, C, hw, slope, scale, gx, gbias, gslope, S(stream));
 }
+// ---- test entry points: the two fused launches of the backbone's training step (net.cpp) that nothing else reaches
+int frcnn_conv2d_forward_pool(const float* in, int C, int H, int W, const float* in_slope, const float* in_scale, const float* weight,
+                              const float* bias, int O, int pad, const float* pool_slope, const float* pool_scale, float* out,
+                              float* pooled, unsigned char* pidx, float* rec, int* fused_out, void* stream) {
+  FR_CHECK(in && weight && out && pooled && pidx, "frcnn_conv2d_forward_pool: NULL argument");
+  if (fused_out) *fused_out = 0;
+  float* wf = nullptr;
+  FR_HIP(hipMalloc((void**)&wf, conv_pack_floats(C, O, 3) * 4));
+  // the model's call for a block's last convolution without the split form, and its fallback when the launch left the pool out
+  IgemmPool pl = {pooled, pidx, pool_slope, pool_scale, rec};
+  bool fused = false;
+  int rc = conv_pack_weights(weight, O, C, 3, wf, nullptr, S(stream));
+  if (rc == FRCNN_OK) rc = conv_igemm(in, C, H, W, in_slope, in_scale, wf, bias, O, 3, pad, out, OUT_STORE, 0, S(stream), 0, &pl, &fused);
+  if (rc == FRCNN_OK && !fused)
+    rc = maxpool_act_forward(out, O, H + 2 * pad - 2, W + 2 * pad - 2, pool_slope, pool_scale, pooled, pidx, S(stream), rec);
+  (void)hipStreamSynchronize(S(stream));
+  (void)hipFree(wf);
+  if (fused_out) *fused_out = fused ? 1 : 0;
+  return rc;
+}
+int frcnn_conv2d_backward_weight_pooled(const float* in, int C, int H, int W, const float* gpool, const unsigned char* pidx,
+                                        const float* x, const float* slope, int O, int pad, float* gweight, float* gbias,
+                                        float* gslope, void* stream) {
+  FR_CHECK(in && gpool && pidx && x && gweight && gbias && gslope, "frcnn_conv2d_backward_weight_pooled: NULL argument");
+  FR_CHECK(C >= 1 && O >= 1 && H + 2 * pad - 2 >= 1 && W + 2 * pad - 2 >= 1, "frcnn_conv2d_backward_weight_pooled: empty shape");
+  const size_t wsb = conv_wgrad_workspace_bytes(C, H, W, O, 3, pad);   // what the model allocates for its first convolution
+  void* ws = nullptr;
+  FR_HIP(hipMalloc(&ws, wsb));
+  int rc = conv_wgrad_first_pooled(in, C, H, W, gpool, pidx, x, slope, O, pad, gweight, gbias, gslope, ws, wsb, S(stream));
+  (void)hipStreamSynchronize(S(stream));
+  (void)hipFree(ws);
+  return rc;
+}
 
 int frcnn_roi_pool_forward(const float* fmap, int C, int H, int W, const int* wins, int R, int kh, int kw,
                            float* out, int* idx, void* stream) {

@@ -369,6 +369,25 @@ int frcnn_act_forward(const float *x, int C, long long hw, const float *slope, c
                       float *y, void *stream);
 int frcnn_act_backward(const float *gy, const float *x, int C, long long hw, const float *slope,
                        const float *scale, float *gx, float *gbias, float *gslope, void *stream);
+/* Test entry points of two fused launches that the model's training step makes and no other entry point reaches.
+ *
+ * frcnn_conv2d_forward_pool: the last 3x3 convolution of a backbone block on the fp32 kernel (whatever the split-form
+ * options say), with the block's nn.PReLU + nn.SpatialDropout + 2x2 ceil-mode max pool offered to the launch's epilogue:
+ * out[O][Ho][Wo] as frcnn_conv2d_forward (k = 3); pooled[O][Hp][Wp], pidx[O][Hp][Wp] as frcnn_maxpool_act_forward(out, O,
+ * Ho, Wo, pool_slope, pool_scale), Hp = (Ho - 1) / 2 + 1; rec (NULL: none) the record of `pooled`.  The launch takes the
+ * pool only for some shapes; for the others the pooling kernel runs behind it, as in the model.  *fused_out (host int,
+ * NULL: not wanted) = 1 when the launch took it.  Synchronises. */
+int frcnn_conv2d_forward_pool(const float *in, int C, int H, int W, const float *in_slope,
+                              const float *in_scale, const float *weight, const float *bias, int O, int pad,
+                              const float *pool_slope, const float *pool_scale, float *out, float *pooled,
+                              unsigned char *pidx, float *rec, int *fused_out, void *stream);
+/* frcnn_conv2d_backward_weight_pooled: :accGradParameters of a first-layer 3x3 convolution (C <= 3, O <= 64, Wo >= 2)
+ * straight from the gradient of its pooled map: with g = unpool(gpool, pidx) * prelu'(x, *slope), x[O][Ho][Wo] the
+ * convolution's output, gweight += g (x) in, gbias += sum g, *gslope += sum_{x<=0} x * unpool(gpool, pidx).  An error,
+ * and nothing is written, for any other shape or a NULL slope.  Synchronises. */
+int frcnn_conv2d_backward_weight_pooled(const float *in, int C, int H, int W, const float *gpool,
+                                        const unsigned char *pidx, const float *x, const float *slope, int O,
+                                        int pad, float *gweight, float *gbias, float *gslope, void *stream);
 
 /* ---- magnitude records of the two-plane fp16 form (option "x3_f16") ----------------------------
  * The split convolutions scale each operand by a power of two taken from the tensor's largest magnitude.  That number

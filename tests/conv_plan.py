@@ -9,11 +9,20 @@ a branch computes the right thing.  The GPU tests against the fp64 references ar
 Shapes are written as the operator sees them: (C, H, W, O, k, pad) = input channels, input map, filters, kernel, padding.
 The input gradient of such a convolution is conv_igemm run on the gradient map with the roles of C and O exchanged
 (K channels = O, M = C, pad' = k - 1 - pad); mirror() turns a forward shape into the input-gradient shape that takes
-exactly the same launch plan, so ONE table serves both roles."""
+exactly the same launch plan, so ONE table serves both roles.
+
+The tables of tests/test_gpu_conv_pool.py live here as well: pool_plan restates when conv_igemm takes a block's max pool into
+its epilogue (POOL_CASES, shapes (C, H, W, M) at pad 1), first_pooled_plan the first layer's weight gradient from the pooled
+map's gradient (FIRST_POOLED_CASES, shapes (C, H, W, O, pad)), with the float32 / fp64 restatements those tests compare with."""
 import numpy as np
 
 import width_plan as WP
 from width_plan import cdiv
+
+
+def case(name, shape, *want):
+    """an entry of a case table: the labels in `want` are what the case is listed for"""
+    return dict(name=name, shape=tuple(shape), want=set(want))
 
 # ---- conv.hip: forward / input gradient -------------------------------------------------------------------------------
 IG_NTW = 2          # 32-pixel tiles per wave along N: an output tile has at most 64 * IG_NTW = 128 pixels
@@ -136,6 +145,143 @@ def igemm_labels(p):
     return L
 
 
+# ---- conv.hip: the 2x2 max pool in conv_igemm's epilogue (frcnn_conv2d_forward_pool) -------------------------------------
+AMAX_MAX_BLOCKS = 16384   # kernels.h: a launch that keeps a magnitude record may have at most this many blocks
+
+
+def pool_plan(C, H, W, M, pad):
+    """conv.hip conv_igemm's "fused max pool" rule for a 3x3 launch that is offered an IgemmPool and stores plainly: the
+    launch takes the pool when the fixed 4 x 32 tile (64-row M tiles) leaves ONE K split (the first-layer instantiation,
+    Cin <= 4, never splits) and costs no more rounds of 256 blocks than the tile of choose_tile would."""
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    assert Ho > 0 and Wo > 0
+    free = igemm_plan(C, H, W, M, 3, pad)
+    mTiles = conv_mpad(M) // 64
+    nChunks = cdiv(C, conv_cc(3))
+    slots, minChunks = 256 * IG_BPC, max(1, cdiv(200, conv_cc(3) * 9))
+
+    def splits_for(blocks):
+        return min(min(max(1, slots // blocks), IG_MAX_SPLITS), max(1, nChunks // minChunks))
+
+    blocks = cdiv(Wo, 32) * cdiv(Ho, 4) * mTiles
+    first = C <= 4
+    one_split = first or splits_for(blocks) == 1
+    tile_refused = cdiv(blocks, 256) > cdiv(free["blocks"], 256)
+    fused = one_split and not tile_refused
+    return dict(C=C, M=M, Ho=Ho, Wo=Wo, Hp=(Ho - 1) // 2 + 1, Wp=(Wo - 1) // 2 + 1, first=first, mTiles=mTiles, blocks=blocks,
+                free_blocks=free["blocks"], one_split=one_split, tile_refused=tile_refused, fused=fused,
+                splits_wanted=1 if first else splits_for(blocks), could_split=(not first) and nChunks // minChunks > 1,
+                tilesX=cdiv(Wo, 32), tilesY=cdiv(Ho, 4), lastChunkChannels=C - (cdiv(C, 4 if first else 8) - 1) * (4 if first else 8),
+                cc=4 if first else 8,
+                # the launch that runs: the fixed tile in one split, or conv_igemm's free plan with the pooling kernel behind it
+                K=C * 9, splitK=1 if fused else free["splitK"], grid=blocks if fused else free["blocks"] * free["splitK"],
+                late_record=fused and blocks > AMAX_MAX_BLOCKS)
+
+
+def pool_labels(p):
+    L = {"first_kernel" if p["first"] else "generic_kernel"}
+    if p["fused"]:
+        L.add("fused")
+        L.add("fused_first" if p["first"] else "fused_generic")
+        if p["mTiles"] > 1:
+            L.add("m_tiles")
+        if p["M"] % 64:
+            L.add("rows_beyond_m")
+        if p["M"] == 1:
+            L.add("m1")
+        if p["Wo"] < 32:
+            L.add("wo_below_32")
+        if p["Ho"] == 1 and p["Wo"] == 1:
+            L.add("one_pixel")
+        else:
+            if p["Wo"] == 1:
+                L.add("wo1")
+            if p["Ho"] == 1:
+                L.add("ho1")
+        if p["Ho"] % 2 and p["Ho"] > 1:
+            L.add("odd_ho")
+        if p["Wo"] % 2 and p["Wo"] > 1:
+            L.add("odd_wo")
+        if p["tilesX"] > 1 and p["Wo"] % 32:
+            L.add("ragged_x")
+        if p["tilesY"] > 1 and p["Ho"] % 4:
+            L.add("ragged_y")
+        if p["lastChunkChannels"] < p["cc"]:
+            L.add("last_chunk_partial")
+        if p["could_split"]:
+            L.add("one_split_by_full_grid")
+        L.add("late_record" if p["late_record"] else "record_in_launch")
+    else:
+        L.add("not_fused")
+        if not p["one_split"]:
+            L.add("refused_by_splits")
+        if p["tile_refused"]:
+            L.add("refused_by_tile_first" if p["first"] else "refused_by_tile_generic")
+    return L
+
+
+POOL_CASES = [
+    case("p_first_odd", (3, 5, 7, 64), "fused_first", "odd_ho", "odd_wo", "wo_below_32", "record_in_launch"),
+    case("p_first_m20", (3, 5, 7, 20), "fused_first", "rows_beyond_m"),
+    case("p_first_m1_wide", (3, 9, 67, 1), "fused_first", "m1", "ragged_x", "odd_wo", "ragged_y"),
+    case("p_one_pixel", (1, 1, 1, 64), "fused_first", "one_pixel"),
+    case("p_wo1", (3, 4, 1, 8), "fused_first", "wo1"),
+    case("p_ho1", (3, 1, 40, 8), "fused_first", "ho1", "ragged_x"),
+    case("p_generic_c9", (9, 13, 18, 20), "fused_generic", "last_chunk_partial", "rows_beyond_m", "odd_ho"),
+    case("p_generic_m70", (40, 13, 18, 70), "fused_generic", "m_tiles", "rows_beyond_m"),
+    case("p_generic_m130", (8, 6, 34, 130), "fused_generic", "m_tiles", "ragged_x"),
+    case("p_generic_model", (16, 29, 50, 40), "fused_generic", "odd_ho", "ragged_x", "ragged_y"),
+    case("p_full_grid", (48, 120, 700, 48), "fused_generic", "one_split_by_full_grid"),
+    case("p_two_splits", (48, 13, 18, 48), "not_fused", "refused_by_splits", "generic_kernel"),
+    case("p_four_splits", (96, 67, 91, 96), "not_fused", "refused_by_splits"),
+    case("p_tile_first", (3, 65, 97, 130), "not_fused", "refused_by_tile_first"),
+    case("p_tile_generic", (8, 65, 97, 130), "not_fused", "refused_by_tile_generic"),
+    case("p_late_record", (1, 1026, 2046, 1), "fused_first", "late_record"),
+]
+POOL_PAD = 1
+# what the issue's table says of those shapes: name -> (fused, blocks of the fixed tile, K splits of the launch that runs)
+POOL_WANT = {
+    "p_first_odd": (True, 2, 1), "p_first_m20": (True, 2, 1), "p_first_m1_wide": (True, 9, 1), "p_one_pixel": (True, 1, 1),
+    "p_wo1": (True, 1, 1), "p_ho1": (True, 2, 1), "p_generic_c9": (True, 4, 1), "p_generic_m70": (True, 8, 1),
+    "p_generic_m130": (True, 16, 1), "p_generic_model": (True, 16, 1), "p_full_grid": (True, 660, 1),
+    "p_two_splits": (False, 4, 2), "p_four_splits": (False, 102, 4), "p_tile_first": (False, 272, 1),
+    "p_tile_generic": (False, 272, 1), "p_late_record": (True, 16448, 1),
+}
+# variants of one fused case per kernel.  A variant names what differs from the base call (pool slope 0.25, no pool scale,
+# a bias, a record, no input activation); "scale": entries of {0, 1} and one other (0.6; 0.75 in the exact-data run) -- a
+# zero entry makes every window of its channel a four-way tie
+POOL_VARIANT_BASES = ("p_first_m20", "p_generic_m70")
+POOL_VARIANTS = ("scale", "slope_0", "slope_-0.5", "slope_1.5", "no_slope", "scale_no_slope", "in_act", "no_bias", "no_rec")
+POOL_REQUIRED = {
+    "first_kernel", "generic_kernel", "fused_first", "fused_generic", "not_fused", "refused_by_splits", "refused_by_tile_first",
+    "refused_by_tile_generic", "m_tiles", "rows_beyond_m", "m1", "wo_below_32", "one_pixel", "wo1", "ho1", "odd_ho", "odd_wo",
+    "ragged_x", "ragged_y", "last_chunk_partial", "one_split_by_full_grid", "late_record", "record_in_launch",
+}
+
+
+def pool_variant(name):
+    """-> dict(slope, scale, in_act, bias, rec) of a POOL_VARIANTS name (None: the base call)"""
+    v = dict(slope=0.25, scale=False, in_act=False, bias=True, rec=True)
+    if name is None:
+        return v
+    assert name in POOL_VARIANTS, name
+    if name.startswith("slope_"):
+        v["slope"] = float(name[6:])
+    elif name == "no_slope":
+        v["slope"] = None
+    elif name == "scale":
+        v["scale"] = True
+    elif name == "scale_no_slope":
+        v["scale"], v["slope"] = True, None
+    elif name == "in_act":
+        v["in_act"] = True
+    elif name == "no_bias":
+        v["bias"] = False
+    elif name == "no_rec":
+        v["rec"] = False
+    return v
+
+
 # ---- conv.hip: weight gradient ----------------------------------------------------------------------------------------
 WG_NT = 64          # gradient pixels per tile
 WG_PM = 3           # patch slots per lane
@@ -248,10 +394,6 @@ GPU_CONV_CASES = [
 
 
 # ---- case tables ------------------------------------------------------------------------------------------------------
-def case(name, shape, *want):
-    return dict(name=name, shape=tuple(shape), want=set(want))
-
-
 def _m_sweep():
     out = []
     maps = {1: (33, 9, 11, 0), 3: (9, 9, 11, 1), 5: (5, 12, 14, 0), 7: (3, 13, 16, 0)}   # k -> (C, H, W, pad)
@@ -382,6 +524,105 @@ WGRAD_REQUIRED = {
     "block_walks_tiles", "ragged_o", "ragged_c", "o_tiles", "c_tiles",
 }
 
+# ---- conv.hip: the first layer's weight gradient from the pooled map's gradient (frcnn_conv2d_backward_weight_pooled) ------
+def first_pooled_eligible(C, O, Wo):
+    """conv_wgrad_first_pooled_eligible (k = 3): one MFMA column must stay free for the column of ones, hence < 32"""
+    return C * 9 < 32 and O <= 64 and Wo >= 2
+
+
+def first_pooled_plan(C, H, W, O, pad):
+    """conv.hip conv_wgrad_first_pooled: conv_wgrad_first_kernel<3, true> on 4 x 64 tiles, one slab slice per block, O + 1
+    floats (bias sums, slope sum) behind every slice.  wgrad_reduce_first takes the tall fold whenever there are extras, so
+    the 127 / 128 slab boundary of the un-fused kernel is no boundary of the fold here: the cases on either side of it stay
+    (they mirror the first_* cases of WGRAD_CASES), and the label says which side they are on."""
+    Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
+    assert Ho > 0 and Wo > 0 and first_pooled_eligible(C, O, Wo)
+    tilesX, tilesY = cdiv(Wo, W1_TW), cdiv(Ho, W1_TH)
+    tiles = tilesX * tilesY
+    nSplit = min(W1_MAX_SLABS, tiles)
+    return dict(Cin=C, O=O, Ho=Ho, Wo=Wo, Hp=(Ho - 1) // 2 + 1, Wp=(Wo - 1) // 2 + 1, tilesX=tilesX, tilesY=tilesY, tiles=tiles,
+                nSplit=nSplit, tilesPerBlock=cdiv(tiles, nSplit), fold="tall", ones_lane=9 * C, K=Ho * Wo,
+                slab_floats=nSplit * (9 * O * C + O + 1))
+
+
+# The slope gradient's summation order, from conv_wgrad_first_kernel<3, true>: a thread owns one 2x2 window of a tile and the
+# 16 channels of its wave, and chains its 4 * 16 = 64 terms x * g of that tile -- and of every further tile its block walks --
+# with one fmaf each (one rounding per term; the product is not rounded); then 6 xor-shuffle levels inside the wave and 2
+# levels over the four waves, (r0 + r1) + (r2 + r3).  A term therefore passes at most 64 * tilesPerBlock + 6 + 2 roundings
+# before it leaves the block.  The fold of the nSplit block sums and the accumulating store are rounding_bound's S and + 2.
+W1_SLOPE_CHAIN = 64     # terms per lane chain and tile
+W1_SLOPE_LEVELS = 6 + 2  # shuffle levels of a 64-lane wave, levels over four waves
+
+
+def first_pooled_slope_terms(p):
+    return W1_SLOPE_CHAIN * p["tilesPerBlock"] + W1_SLOPE_LEVELS
+
+
+def first_pooled_labels(p):
+    L = {"ones_lane_%d" % p["ones_lane"]}
+    L.add("one_tile" if p["tiles"] == 1 else "slabs_below_128" if p["nSplit"] < W1_TALL else "slabs_from_128")
+    if p["tiles"] > W1_MAX_SLABS:
+        L.add("block_walks_tiles")
+    if p["tiles"] % p["nSplit"] or p["tilesPerBlock"] == 1:
+        L.add("prefetch_past_the_end")   # a block whose next tile does not exist issues that tile's loads all the same
+    if p["O"] % 16:
+        L.add("o_not_multiple_of_16")
+    if p["O"] < 16:
+        L.add("idle_waves")
+    if p["Wo"] % 2:
+        L.add("shifted_column")
+        if p["Wo"] % W1_TW == 1:
+            L.add("shifted_opens_tile")
+    if p["Wo"] == 2:
+        L.add("wo2")
+    if p["Wo"] % W1_TW and p["tilesX"] > 1:
+        L.add("ragged_x")
+    if p["Ho"] == 1:
+        L.add("ho1")
+    elif p["Ho"] % 2:
+        L.add("odd_ho")
+    if p["Ho"] % W1_TH:
+        L.add("ragged_y")
+    return L
+
+
+# (C, H, W, O, pad); the first eight mirror the first_* cases of WGRAD_CASES
+FIRST_POOLED_CASES = [
+    case("fp_c1_o1_tile", (1, 4, 30, 1, 1), "one_tile", "ones_lane_9", "idle_waves"),
+    case("fp_c2_o17", (2, 9, 70, 17, 1), "ones_lane_18", "o_not_multiple_of_16", "slabs_below_128", "ragged_x", "odd_ho"),
+    case("fp_c3_o64", (3, 37, 53, 64, 1), "ones_lane_27", "shifted_column", "odd_ho"),
+    case("fp_c3_o64_valid", (3, 14, 131, 64, 0), "shifted_opens_tile", "ragged_x"),
+    case("fp_wo2", (3, 3, 2, 5, 1), "wo2", "one_tile", "o_not_multiple_of_16", "idle_waves"),
+    case("fp_ho1", (3, 1, 4, 8, 1), "ho1", "one_tile"),
+    case("fp_127", (3, 508, 20, 4, 1), "slabs_below_128"),
+    case("fp_128", (3, 512, 20, 4, 1), "slabs_from_128"),
+    case("fp_tall_o17", (2, 64, 513, 17, 1), "slabs_from_128", "shifted_opens_tile", "o_not_multiple_of_16"),
+    case("fp_cap", (3, 690, 190, 4, 1), "block_walks_tiles", "prefetch_past_the_end"),
+]
+FIRST_POOLED_MIRROR = {   # name -> the un-fused case of WGRAD_CASES with the same shape
+    "fp_c1_o1_tile": "first_c1_o1_tile", "fp_c2_o17": "first_c2_o17", "fp_c3_o64": "first_c3_o64",
+    "fp_c3_o64_valid": "first_c3_o64_valid", "fp_127": "first_127", "fp_128": "first_128", "fp_tall_o17": "first_tall_o17",
+    "fp_cap": "first_cap",
+}
+# shapes the entry point must refuse: name -> ((C, H, W, O, pad), slope given)
+FIRST_POOLED_ERRORS = {
+    "c4": ((4, 8, 8, 8, 1), True), "o65": ((3, 8, 8, 65, 1), True), "wo1": ((3, 8, 1, 8, 1), True),
+    "no_slope": ((3, 8, 8, 8, 1), False),
+}
+FIRST_POOLED_REQUIRED = {
+    "ones_lane_9", "ones_lane_18", "ones_lane_27", "one_tile", "slabs_below_128", "slabs_from_128", "block_walks_tiles",
+    "prefetch_past_the_end", "o_not_multiple_of_16", "idle_waves", "shifted_column", "shifted_opens_tile", "wo2", "ragged_x",
+    "ho1", "odd_ho", "ragged_y",
+}
+
+
+def find_pool(name):
+    for c in POOL_CASES + FIRST_POOLED_CASES:
+        if c["name"] == name:
+            return c
+    raise KeyError(name)
+
+
 # call-order independence: (role, case A, activation of A, role, case B, activation of B)
 ORDER_PAIRS = [
     ("forward", "split24_k3", None, "forward", "split_tail1_k3", None),
@@ -459,3 +700,57 @@ def rounding_bound(K, S, mag):
     S slabs folded (S - 1), a bias or an accumulating destination added (2 more), to first order in u; mag = the same sum
     over magnitudes"""
     return (K + S + 2) * U * np.asarray(mag, np.float64)
+
+
+# ---- the pooling of the epilogue and its backward, restated -------------------------------------------------------------
+POOL_WINDOW = ((0, 0), (0, 1), (1, 0), (1, 1))   # code dy * 2 + dx
+
+
+def pool_act_fp32(x, slope, scale):
+    """elem.hip maxpool_act_forward_kernel in numpy float32: act = PReLU, then the channel's scale (activate(): one rounding
+    each, no fused multiply-add), then the 2x2 stride-2 ceil-mode window in the order (0,0), (0,1), (1,0), (1,1) with a strict
+    `>`: the first maximum wins.  -> (pooled float32 [C][Hp][Wp], code uint8)"""
+    a = activate(x, slope, scale)
+    C, H, W = a.shape
+    Hp, Wp = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    best = np.ascontiguousarray(a[:, 0::2, 0::2])
+    assert best.shape == (C, Hp, Wp) and best.dtype == np.float32
+    code = np.zeros((C, Hp, Wp), np.uint8)
+    for e, (dy, dx) in enumerate(POOL_WINDOW[1:], 1):
+        v = a[:, dy::2, dx::2]
+        cand = np.full((C, Hp, Wp), -np.inf, np.float32)   # a position outside the map never wins
+        cand[:, :v.shape[1], :v.shape[2]] = v
+        take = cand > best
+        best = np.where(take, cand, best)
+        code[take] = e
+    return best, code
+
+
+def pool_route(gpool, code, Ho, Wo):
+    """the pool's backward: every pooled gradient goes to the position its code names (which must lie inside the map)"""
+    gpool = np.asarray(gpool, np.float64)
+    C, Hp, Wp = gpool.shape
+    out = np.zeros((C, 2 * Hp, 2 * Wp))
+    for e, (dy, dx) in enumerate(POOL_WINDOW):
+        out[:, dy::2, dx::2] = np.where(code == e, gpool, 0.0)
+    assert not out[:, Ho:, :].any() and not out[:, :, Wo:].any(), "a code names a position outside the map"
+    return np.ascontiguousarray(out[:, :Ho, :Wo])
+
+
+def ref_pooled_weight_gradient(inp, gpool, code, x, slope, pad):
+    """fp64 by the definition -> (gw, gb, gslope) and the same sums over magnitudes (mw, mb, mslope)"""
+    x = np.asarray(x, np.float64)
+    _, Ho, Wo = x.shape
+    r = pool_route(gpool, code, Ho, Wo)
+    g = r * np.where(x > 0, 1.0, float(slope))
+    gw, gb = ref_weight_gradient(inp, g, 3, pad)
+    mw, mb = ref_weight_gradient(np.abs(np.asarray(inp, np.float64)), np.abs(g), 3, pad)
+    neg = x <= 0
+    return (gw, gb, float((x * r)[neg].sum())), (mw, mb, float(np.abs(x * r)[neg].sum()))
+
+
+def assert_exact_in_fp32(mag, quantum, what=""):
+    """Every partial sum of a sum whose terms are multiples of `quantum` and whose magnitudes add up to `mag` is a multiple
+    of `quantum` below `mag`: exactly representable in fp32, in whatever order the terms are added, when mag / quantum < 2^24"""
+    top = float(np.max(mag)) / quantum
+    assert top < 2.0 ** 24, "%s: sum of magnitudes %g quanta: the exact-data run would round" % (what, top)

@@ -226,3 +226,98 @@ def test_fp64_references_agree_with_the_oracle(O):
     assert np.array_equal(CP.activate(x, 0.25, [1.0, 2.0]), np.array([[[1.5, -0.5]], [[-2.0, 16.0]]], np.float32))
     assert np.array_equal(CP.activate(x, None, [0.0, 1.0])[0], np.zeros((1, 2), np.float32))
     assert CP.activate(x, 0.5, None).dtype == np.float32
+
+
+# ---- the fused pooling epilogue and the pooled first-layer weight gradient (tests/test_gpu_conv_pool.py) -------------------
+def test_pool_restatement_at_known_values():
+    # block 0 of vgg_small at the benchmark frame (3 -> 64 on 450x800): the first-layer kernel, fused, 25 x 113 tiles
+    p = CP.pool_plan(3, 450, 800, 64, 1)
+    assert (p["first"], p["fused"], p["blocks"], p["mTiles"]) == (True, True, 25 * 113, 1)
+    # the layer named in conv_igemm's comment (200x113): 812 blocks of the fixed tile, a fourth round of 256 where the free tile needs three: refused
+    p = CP.pool_plan(128, 113, 200, 256, 1)   # (four M tiles)
+    assert (p["blocks"], CP.cdiv(p["blocks"], 256), CP.cdiv(p["free_blocks"], 256), p["tile_refused"], p["fused"]) == (812, 4, 3, True, False)
+    # the non-reference backbones of tests/width_plan.py on a 133 x 181 map: the split rule asks for 2 and 3 splits, no fusion
+    assert [CP.pool_plan(c, 133, 181, c, 1)["fused"] for c in (48, 96)] == [False, False]
+    assert [CP.pool_plan(c, 133, 181, c, 1)["splits_wanted"] for c in (48, 96)] == [2, 3]
+
+
+def test_pool_cases_reach_what_they_are_listed_for():
+    reached = set()
+    names = [c["name"] for c in CP.POOL_CASES]
+    assert len(names) == len(set(names)) == 16 and set(names) == set(CP.POOL_WANT)
+    for c in CP.POOL_CASES:
+        C, H, W, M = c["shape"]
+        p = CP.pool_plan(C, H, W, M, CP.POOL_PAD)
+        labels = CP.pool_labels(p)
+        assert c["want"] <= labels, (c["name"], sorted(c["want"] - labels))
+        assert (p["fused"], p["blocks"], p["splitK"]) == CP.POOL_WANT[c["name"]], (c["name"], p["fused"], p["blocks"], p["splitK"])
+        assert p["fused"] == (p["one_split"] and not p["tile_refused"])
+        reached |= labels
+    assert CP.POOL_REQUIRED <= reached, sorted(CP.POOL_REQUIRED - reached)
+    # the two refusals by the tile rule: 272 blocks of the fixed tile against 208
+    for n in ("p_tile_first", "p_tile_generic"):
+        p = CP.pool_plan(*CP.find_pool(n)["shape"], CP.POOL_PAD)
+        assert (p["blocks"], p["free_blocks"], p["one_split"]) == (272, 208, True)
+    # Cin = 48 on a full grid: the split rule would allow 2 splits, 1280 // 660 = 1 leaves one
+    p = CP.pool_plan(*CP.find_pool("p_full_grid")["shape"], CP.POOL_PAD)
+    assert p["could_split"] and p["splits_wanted"] == 1 and not p["first"]
+    p = CP.pool_plan(*CP.find_pool("p_late_record")["shape"], CP.POOL_PAD)
+    assert p["grid"] == 16448 > CP.AMAX_MAX_BLOCKS and p["late_record"]
+    for n in CP.POOL_VARIANT_BASES:
+        assert CP.pool_plan(*CP.find_pool(n)["shape"], CP.POOL_PAD)["fused"]
+    assert [CP.pool_plan(*CP.find_pool(n)["shape"], CP.POOL_PAD)["first"] for n in CP.POOL_VARIANT_BASES] == [True, False]
+    got = [CP.pool_variant(v) for v in CP.POOL_VARIANTS]
+    assert {v["slope"] for v in got} == {0.25, 0.0, -0.5, 1.5, None}
+    assert any(v["scale"] for v in got) and any(v["in_act"] for v in got) and any(not v["bias"] for v in got)
+    assert any(not v["rec"] for v in got) and CP.pool_variant(None)["rec"]
+
+
+def test_first_pooled_cases_reach_what_they_are_listed_for():
+    reached = set()
+    names = [c["name"] for c in CP.FIRST_POOLED_CASES]
+    assert len(names) == len(set(names)) == 10
+    for c in CP.FIRST_POOLED_CASES:
+        p = CP.first_pooled_plan(*c["shape"])
+        labels = CP.first_pooled_labels(p)
+        assert c["want"] <= labels, (c["name"], sorted(c["want"] - labels))
+        reached |= labels
+        # what the entry point allocates (conv_wgrad_workspace_bytes) holds the slabs with their extras
+        C, H, W, O, pad = c["shape"]
+        assert CP.wgrad_plan(C, H, W, O, 3, pad)["kernel"] == "first"
+    assert CP.FIRST_POOLED_REQUIRED <= reached, sorted(CP.FIRST_POOLED_REQUIRED - reached)
+    for name, mirror in CP.FIRST_POOLED_MIRROR.items():   # the two tables stay comparable
+        C, H, W, O, pad = CP.find_pool(name)["shape"]
+        assert CP.find(mirror)["shape"] == (C, H, W, O, 3, pad)
+        assert CP.first_pooled_plan(C, H, W, O, pad)["nSplit"] == CP.wgrad_plan(C, H, W, O, 3, pad)["nSplit"]
+    slabs = {n: CP.first_pooled_plan(*CP.find_pool(n)["shape"]) for n in names}
+    assert slabs["fp_127"]["nSplit"] == 127 and slabs["fp_128"]["nSplit"] == 128
+    assert (slabs["fp_cap"]["tiles"], slabs["fp_cap"]["nSplit"], slabs["fp_cap"]["tilesPerBlock"]) == (519, 512, 2)
+    assert slabs["fp_c3_o64_valid"]["Wo"] == 129 and slabs["fp_wo2"]["Wo"] == 2 and slabs["fp_ho1"]["Ho"] == 1
+    assert CP.first_pooled_slope_terms(slabs["fp_cap"]) == 136 and CP.first_pooled_slope_terms(slabs["fp_127"]) == 72
+    # the refused shapes: one term of the predicate fails each
+    for name, ((C, H, W, O, pad), slope) in CP.FIRST_POOLED_ERRORS.items():
+        assert (not CP.first_pooled_eligible(C, O, W + 2 * pad - 2)) == (name != "no_slope"), name
+        assert slope == (name != "no_slope")
+
+
+def test_pool_restatement_in_numpy():
+    """pool_act_fp32 / pool_route / ref_pooled_weight_gradient at values that can be checked by hand"""
+    x = np.array([[[1.0, 1.0, -2.0], [1.0, 3.0, -8.0], [-4.0, -4.0, 5.0]]], np.float32)
+    best, code = CP.pool_act_fp32(x, 0.25, None)
+    assert np.array_equal(best, [[[3.0, -0.5], [-1.0, 5.0]]]) and np.array_equal(code, [[[3, 0], [0, 0]]])
+    best, code = CP.pool_act_fp32(np.ones((1, 2, 2), np.float32), None, None)   # a four-way tie: the first wins
+    assert np.array_equal(code, [[[0]]])
+    best, code = CP.pool_act_fp32(x, -0.5, np.array([0.0], np.float32))         # scale 0: ties of +-0 everywhere
+    assert not best.any() and not code.any()
+    r = CP.pool_route(np.array([[[2.0, 3.0], [5.0, 7.0]]]), np.array([[[3, 0], [0, 0]]], np.uint8), 3, 3)
+    assert np.array_equal(r, [[[0, 0, 3.0], [0, 2.0, 0], [5.0, 0, 7.0]]])
+    with pytest.raises(AssertionError):
+        CP.pool_route(np.ones((1, 2, 2)), np.array([[[0, 1], [0, 0]]], np.uint8), 3, 3)
+    inp = np.ones((1, 3, 3), np.float32)
+    (gw, gb, gs), (mw, mb, ms) = CP.ref_pooled_weight_gradient(inp, np.array([[[2.0, 3.0], [5.0, 7.0]]]),
+                                                                np.array([[[3, 0], [0, 0]]], np.uint8), x, 0.25, 1)
+    # g = [[0, 0, .75], [0, 2, 0], [1.25, 0, 7]]
+    assert gb[0] == 11.0 and gw[0, 0, 1, 1] == 11.0 and gw[0, 0, 0, 0] == 9.0 and gs == -2.0 * 3.0 + -4.0 * 5.0 and ms == 26.0
+    CP.assert_exact_in_fp32(mw, 0.25)
+    with pytest.raises(AssertionError):
+        CP.assert_exact_in_fp32(2.0 ** 23, 0.25)

@@ -202,7 +202,7 @@ def test_entry_point_is_declared_everywhere(F):
     assert "frcnn_proposal_targets_batch" in F._lib.exported_symbols()
     assert len(F._lib._SIGS["frcnn_proposal_targets_batch"][0]) == 27
     assert hasattr(F._lib.load(), "frcnn_proposal_targets_batch")
-    assert len(set(re.findall(r"\b(frcnn_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))) == 141
+    assert len(set(re.findall(r"\b(frcnn_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))) == 143
     for fn in ("objective_hip.lua", "frcnn_shims.lua.in"):
         assert "frcnn_proposal_targets_batch" in open(os.path.join(ROOT, "bindings", fn)).read(), fn
     assert callable(F.proposal_targets) and callable(F.roi_sampling_settings)
