@@ -187,7 +187,12 @@ end
 
 -- Makes a table as scoring_settings takes it this Detector's class test from the next frame on (nil: the reference's)
 function Detector:set_scoring(t)
-  self.scoring_classes, self.min_confidence, self.max_detections = Detector.scoring_settings(t)
+  local classes, min_confidence, max_detections = Detector.scoring_settings(t)
+  -- a per-class box head (cfg.box_head) has one box per (candidate, class); classes = 'all' decodes ONE box per candidate
+  if classes == 'all' and self.model.box_per_class then
+    error('cfg.scoring.classes = "all" cannot be combined with cfg.box_head.per_class = true')
+  end
+  self.scoring_classes, self.min_confidence, self.max_detections = classes, min_confidence, max_detections
 end
 
 -- m: the rows a candidate can emit, what the per-row buffers of a chunk are sized by (Rmax * m rows a frame).  'top': 1.  'all':

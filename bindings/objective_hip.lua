@@ -216,7 +216,8 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
                                          cinput.ptr, pidx, nil))
         end
         -- ---- fine-tuning stage (:146-186) --------------------------------------------------------------------
-        local coutputs = cnet:forward(cinput)                           -- :164
+        -- (a per-class box head, cfg.box_head, reads the classes of the example table: final on this stream since the upload)
+        local coutputs = cnet:forward(cinput, model.box_per_class and { 'int', ffi.cast('const int*', dblob + o_class), npos } or nil)  -- :164
         local crout, ccout = coutputs[1], coutputs[2]
         local crdelta = hip.view(scratch('crdelta', 16 * E).ptr, { E, 4 })
         local ccdelta = hip.view(scratch('ccdelta', 4 * E * ncls).ptr, { E, ncls })
@@ -274,7 +275,8 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
               check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], hwins, N, kh, kw, hin.ptr, nil, nil))
             end
             score = cnet:score(hin, hip.view(scratch('rh_crout', 16 * N).ptr, { N, 4 }),
-                               hip.view(scratch('rh_ccout', 4 * N * ncls).ptr, { N, ncls }))
+                               hip.view(scratch('rh_ccout', 4 * N * ncls).ptr, { N, ncls }),
+                               model.box_per_class and { 'float', rec.cctarget } or nil)   -- (the loss a row would be trained on)
           end
           rec = hip.mine_hard(rs, rec, scratch, N, score and score[1].ptr, score and score[2].ptr, ncls, cl_desc)
           stats.hard = stats.hard or {}
@@ -299,7 +301,7 @@ function create_objective(model, weights, gradient, batch_iterator, stats)
             check(C.frcnn_roi_windows(rec.roi, nil, S, layers, nl, fs[2], fs[3], dwins, nil))
             check(C.frcnn_roi_pool_forward(fm.ptr, fs[1], fs[2], fs[3], dwins, S, kh, kw, cinput.ptr, pidx, nil))
           end
-          local coutputs = cnet:forward(cinput)
+          local coutputs = cnet:forward(cinput, model.box_per_class and { 'float', rec.cctarget } or nil)
           local crout, ccout = coutputs[1], coutputs[2]
           local crdelta = hip.view(scratch('crdelta', 16 * S).ptr, { S, 4 })
           local ccdelta = hip.view(scratch('ccdelta', 4 * S * ncls).ptr, { S, ncls })

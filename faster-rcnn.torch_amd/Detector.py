@@ -520,6 +520,7 @@ class Detector(object, metaclass=_DetectorType):
         table as tta_settings takes it."""
         if nms is not None:
             nms_settings(nms)
+        self.model = model           # (set_scoring looks at the model's box head)
         self.set_proposals(proposals if proposals is not None else model["cfg"])
         self.set_nms(model["cfg"])
         self.set_box_voting(model["cfg"])
@@ -527,7 +528,6 @@ class Detector(object, metaclass=_DetectorType):
         self.set_tta(model["cfg"])
         if nms is not None:
             self.set_nms(nms)
-        self.model = model
         if static_weights or os.environ.get("FRCNN_STATIC_WEIGHTS"):
             _lib.call("frcnn_set_option", b"static_weights", 1)
         cfg = model["cfg"]
@@ -564,7 +564,14 @@ class Detector(object, metaclass=_DetectorType):
     def set_scoring(self, cfg_or_table):
         """Validates a table as scoring_settings takes it and makes it this Detector's class test from the next frame on (None,
         or a cfg without the key: the reference's, launch for launch)."""
-        self.scoring = scoring_settings(cfg_or_table)
+        scoring = scoring_settings(cfg_or_table)
+        # a per-class box head (cfg.box_head) has one box per (candidate, class); classes = "all" decodes ONE box per candidate
+        # for all its class rows: refused until frcnn_detect_classes_batch takes a box per row
+        model = getattr(self, "model", None)
+        if scoring is not None and scoring[0] == "all" and model is not None and int(model["native"].desc.box_per_class):
+            raise _lib.FrcnnError("cfg.scoring.classes = \"all\" cannot be combined with cfg.box_head.per_class = true: that pass decodes "
+                             "one box per candidate for all its class rows")
+        self.scoring = scoring
 
     def set_tta(self, cfg_or_table):
         """Validates a table as tta_settings takes it and makes it this Detector's setting from the next frame on (None, or a

@@ -28,6 +28,7 @@ class ModelDesc(C.Structure):
         ("cls_dropout", C.c_float * 8),
         ("class_count", C.c_int),
         ("kh", C.c_int), ("kw", C.c_int),
+        ("box_per_class", C.c_int),
     ]
 
 
@@ -212,11 +213,19 @@ class CnetLossDesc(C.Structure):
                 ("smoothing", C.c_double), ("beta", C.c_double), ("box_weight", C.c_double)]
 
 
+# the entry points of include/frcnn_hip_box.h (cfg.box_head: per-class box regression in the classification net)
+BOX_SIGS = {
+    "frcnn_box_head_forward": ([vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp], C.c_int),
+    "frcnn_box_head_backward": ([vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp], C.c_int),
+    "frcnn_cnet_box_classes": ([vp, vp, C.c_int, C.c_int], C.c_int),
+}
+
 _lib = None
 
 
 def exported_symbols():
-    """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS)"""
+    """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS; of
+    frcnn_hip_box.h: BOX_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -239,7 +248,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

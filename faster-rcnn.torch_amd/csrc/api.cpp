@@ -228,6 +228,14 @@ int frcnn_cnet_loss_rows(float* crout, const float* crtarget, const float* ccout
   return cnet_loss_rows(crout, crtarget, ccout, cctarget, roi, R, npos, ncls, desc_host, crdelta, ccdelta, row_loss, key, box5,
                         S(stream));
 }
+int frcnn_box_head_forward(const float* x, int R, int nf, const float* W, const float* b, int C, const void* classes, int kind, int n,
+                           const float* lsm, int ncls, float* out, int* sel, void* stream) {
+  return box_head_forward(x, R, nf, W, b, C, classes, kind, n, lsm, ncls, out, sel, S(stream));
+}
+int frcnn_box_head_backward(const float* g, const float* x, const int* sel, int R, int nf, const float* W, int C, float* gfeat,
+                            float* gW, float* gb, void* stream) {
+  return box_head_backward(g, x, sel, R, nf, W, C, gfeat, gW, gb, S(stream), S(stream));
+}
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,
                               const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {

@@ -336,6 +336,13 @@ int roi_hard_gather_batch(const long long* pick, const int* count_dev, int batch
 int cnet_loss_rows(float* crout, const float* crtarget, const float* ccout, const float* cctarget, const double* roi, int R,
                    int npos, int ncls, const frcnn_cnet_loss_desc* desc, float* crdelta, float* ccdelta, double* row_loss,
                    float* key, float* box5, hipStream_t s);
+// ---- the per-class box head (box_head.hip; semantics: include/frcnn_hip_box.h).  classes / kind / n_fg: the class source (0 none:
+// the first maximum of lsm's row, 1 int32 for the first n_fg rows, 2 fp32 per row); sel[r] = the class used, 0 for none.
+int box_head_forward(const float* x, int R, int nf, const float* W, const float* b, int C, const void* classes, int kind, int n_fg,
+                     const float* lsm, int ncls, float* out, int* sel, hipStream_t s);
+// gfeat (stored; on s_chain) and / or gW, gb (added to; on s_wgrad); either part may be left out with a null output
+int box_head_backward(const float* g, const float* x, const int* sel, int R, int nf, const float* W, int C, float* gfeat, float* gW,
+                      float* gb, hipStream_t s_chain, hipStream_t s_wgrad);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

@@ -217,6 +217,11 @@ struct frcnn_model {
   int R = 0, D = 0;
   const float* cnet_x = nullptr;
   DevBuf feat_g, logits, lsm, glog, gtmp;
+  // the per-class box head (desc.box_per_class; box_head.hip): the class each row of the last forward pass used, and the class
+  // source frcnn_cnet_box_classes set for the NEXT forward pass (0: none -- the first maximum of the pass's own log-probabilities)
+  DevBuf box_sel;
+  const void* box_classes = nullptr;
+  int box_kind = 0, box_n = 0;
   std::vector<std::array<long long, 4>> table;
 };
 
@@ -292,10 +297,11 @@ static void build_layout(frcnn_model* m) {
     in = L.n;
     m->cls.push_back(std::move(L));
   }
-  m->bbox_w_off = off; m->bbox_b_off = off + (long)in * 4;
-  m->table.push_back({m->bbox_w_off, (long long)in * 4, 3, in});
-  m->table.push_back({m->bbox_b_off, 4, 4, in});
-  off += (long)in * 4 + 4;
+  const int brows = d.box_per_class ? 4 * d.class_count : 4;   // per class: row 4 (c - 1) + j = coordinate j of foreground class c
+  m->bbox_w_off = off; m->bbox_b_off = off + (long)in * brows;
+  m->table.push_back({m->bbox_w_off, (long long)in * brows, 3, in});
+  m->table.push_back({m->bbox_b_off, brows, 4, in});
+  off += (long)in * brows + brows;
   int nc = d.class_count + 1;
   m->clsw_off = off; m->clsb_off = off + (long)in * nc;
   m->table.push_back({m->clsw_off, (long long)in * nc, 3, in});
@@ -589,6 +595,7 @@ int frcnn_model_create(const frcnn_model_desc* desc, frcnn_model** out) {
     FR_CHECK(desc->head_k[h] == 1 || desc->head_k[h] == 3 || desc->head_k[h] == 5 || desc->head_k[h] == 7,
              "anchor net %d: kernel size %d unsupported", h + 1, desc->head_k[h]);
   }
+  FR_CHECK(!desc->box_per_class || desc->class_count >= 1, "frcnn_model_create: box_per_class with %d classes", desc->class_count);
   frcnn_model* m = new frcnn_model();
   m->d = *desc;
   build_layout(m);
@@ -1818,6 +1825,17 @@ static int ensure_cnet(frcnn_model* m, int R) {
   FR_TRY(m->logits.ensure((size_t)R * nc * 4));
   FR_TRY(m->lsm.ensure((size_t)R * nc * 4));
   FR_TRY(m->glog.ensure((size_t)R * nc * 4));
+  if (m->d.box_per_class) FR_TRY(m->box_sel.ensure((size_t)R * 4));
+  return FRCNN_OK;
+}
+
+int frcnn_cnet_box_classes(frcnn_model* m, const void* classes, int kind, int n) {
+  FR_CHECK(m != nullptr, "cnet_box_classes: null model");
+  FR_CHECK(m->d.box_per_class, "cnet_box_classes: the model's box head is shared (frcnn_model_desc.box_per_class is 0)");
+  FR_CHECK(kind >= 0 && kind <= 2, "cnet_box_classes: class source %d (0 none, 1 int32, 2 fp32)", kind);
+  FR_CHECK(kind == 0 || classes, "cnet_box_classes: class source %d without classes", kind);
+  FR_CHECK(kind != 1 || n >= 0, "cnet_box_classes: %d foreground rows", n);
+  m->box_classes = kind ? classes : nullptr; m->box_kind = kind; m->box_n = kind == 1 ? n : 0;
   return FRCNN_OK;
 }
 
@@ -1825,7 +1843,12 @@ int frcnn_cnet_forward(frcnn_model* m, const float* weights, const float* x, int
                        const float* const* drop_masks, unsigned long long seed, float* bn_running,
                        float* bbox_out, float* cls_out, void* stream) {
   hipStream_t s = S(stream);
+  // the class source of the per-class box head serves this call only, whatever becomes of it
+  const void* box_classes = m->box_classes;
+  const int box_kind = m->box_kind, box_n = m->box_n;
+  m->box_classes = nullptr; m->box_kind = 0; m->box_n = 0;
   FR_CHECK(R > 0, "cnet_forward: empty batch");
+  FR_CHECK(box_kind != 1 || box_n <= R, "cnet_forward: %d foreground classes for %d rows (frcnn_cnet_box_classes)", box_n, R);
   FR_TRY(cw_join(m, s));   // (weight gradients of a previous backward pass still read the buffers written below)
   FR_TRY(ensure_cnet(m, R));
   m->R = R; m->cnet_x = x; m->training = training;
@@ -1874,6 +1897,20 @@ int frcnn_cnet_forward(frcnn_model* m, const float* weights, const float* x, int
   }
   const int nf = m->cls.empty() ? m->D : m->cls.back().n;
   const int nc = m->d.class_count + 1;
+  if (m->d.box_per_class) {
+    // the class head first: without a class source a row's box is the one of the class its own log-probabilities predict
+    if (cnet_fuse()) {
+      GemmFold fold;
+      FR_TRY(gemm_f32(cur, nf, 1, w + m->clsw_off, 1, nf, m->logits.f(), nc, R, nc, nf, OUT_STORE, w + m->clsb_off, s, 0, &fold));
+      FR_TRY(log_softmax_rows_fold(m->logits.f(), fold, R, nc, m->lsm.f(), cls_out, s));
+    } else {
+      FR_TRY(gemm_f32(cur, nf, 1, w + m->clsw_off, 1, nf, m->logits.f(), nc, R, nc, nf, OUT_STORE, w + m->clsb_off, s));
+      FR_TRY(log_softmax_rows(m->logits.f(), R, nc, m->lsm.f(), s));
+      FR_HIP(hipMemcpyAsync(cls_out, m->lsm.p, (size_t)R * nc * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return box_head_forward(cur, R, nf, w + m->bbox_w_off, w + m->bbox_b_off, m->d.class_count, box_classes, box_kind, box_n,
+                            m->lsm.f(), nc, bbox_out, (int*)m->box_sel.p, s);
+  }
   if (cnet_fuse() && cnet_heads_fused_eligible(nf, nc)) {   // both heads, nn.LogSoftMax and the copy to the caller's tensor: one launch
     return cnet_heads_forward(cur, R, nf, w + m->bbox_w_off, w + m->bbox_b_off, w + m->clsw_off, w + m->clsb_off, nc, bbox_out,
                               m->logits.f(), m->lsm.f(), cls_out, s);
@@ -1916,7 +1953,8 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
   };
   // heads: LogSoftMax backward first, then the two input gradients on the chain, the two weight gradients beside it
   bool top_act_done = false;   // the last hidden layer's Dropout + PReLU backward was applied by the heads' launch (L.g is final)
-  if (cnet_fuse() && cnet_heads_fused_eligible(nf, nc)) {   // LogSoftMax backward + both input gradients: one launch
+  const bool per_class = m->d.box_per_class != 0;   // (the fused two-heads launches know the shared box head only)
+  if (!per_class && cnet_fuse() && cnet_heads_fused_eligible(nf, nc)) {   // LogSoftMax backward + both input gradients: one launch
     HeadsPostAct post;
     float* dst = m->feat_g.f();
     if (!m->cls.empty() && !m->cls.back().bn && !deterministic()) {
@@ -1933,11 +1971,20 @@ int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbo
   } else {
     FR_TRY(log_softmax_backward(g_cls, m->lsm.f(), R, nc, m->glog.f(), s));
     FR_TRY(fork());
-    FR_TRY(gemm_f32(g_bbox, 4, 1, w + m->bbox_w_off, nf, 1, m->feat_g.f(), nf, R, nf, 4, OUT_STORE, nullptr, s));
+    if (per_class)   // the rows of each example's class, stored; the class head's input gradient is added on top
+      FR_TRY(box_head_backward(g_bbox, nullptr, (const int*)m->box_sel.p, R, nf, w + m->bbox_w_off, m->d.class_count, m->feat_g.f(),
+                               nullptr, nullptr, s, s));
+    else
+      FR_TRY(gemm_f32(g_bbox, 4, 1, w + m->bbox_w_off, nf, 1, m->feat_g.f(), nf, R, nf, 4, OUT_STORE, nullptr, s));
     FR_TRY(gemm_f32(m->glog.f(), nc, 1, w + m->clsw_off, nf, 1, m->feat_g.f(), nf, R, nf, nc, OUT_ADD, nullptr, s));
   }
-  FR_TRY(gemm_f32(g_bbox, 1, 4, feat, nf, 1, grad + m->bbox_w_off, nf, 4, nf, R, OUT_ADD, nullptr, ws, wslot));
-  FR_TRY(channel_sum_cols(g_bbox, R, 4, grad + m->bbox_b_off, ws));
+  if (per_class) {   // the box head's weight and bias gradient, segmented by class (classes without a row are not touched)
+    FR_TRY(box_head_backward(g_bbox, feat, (const int*)m->box_sel.p, R, nf, nullptr, m->d.class_count, nullptr, grad + m->bbox_w_off,
+                             grad + m->bbox_b_off, ws, ws));
+  } else {
+    FR_TRY(gemm_f32(g_bbox, 1, 4, feat, nf, 1, grad + m->bbox_w_off, nf, 4, nf, R, OUT_ADD, nullptr, ws, wslot));
+    FR_TRY(channel_sum_cols(g_bbox, R, 4, grad + m->bbox_b_off, ws));
+  }
   FR_TRY(gemm_f32(m->glog.f(), 1, nc, feat, nf, 1, grad + m->clsw_off, nf, nc, nf, R, OUT_ADD, nullptr, ws, wslot));
   FR_TRY(channel_sum_cols(m->glog.f(), R, nc, grad + m->clsb_off, ws));
   const float* g = m->feat_g.f();

@@ -108,7 +108,11 @@ def validation_losses(model, batch_iterator, count, seed=1234, negatives=16, deb
                 else:
                     pidx = DeviceTensor.empty((E, D), np.int32)
                     _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(d_wins), E, kh, kw, ptr(cinput), ptr(pidx), s)
-                crout, ccout = cnet.forward(cinput)
+                # (a per-class box head, cfg.box_head: the rows of each example's class, as the objective trains them)
+                if model["native"].desc.box_per_class:
+                    crout, ccout = cnet.forward(cinput, box_classes=("int", d_class, npos))
+                else:
+                    crout, ccout = cnet.forward(cinput)
                 crdelta = DeviceTensor.empty((E, 4)); ccdelta = DeviceTensor.empty((E, ncls))
                 row_loss = None
                 if cl_desc is None:

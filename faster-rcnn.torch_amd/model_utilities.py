@@ -44,6 +44,8 @@ class NativeModel(object):
         d.class_count = cfg["class_count"]
         from .objective import roi_pooling_settings
         d.kh, d.kw = roi_pooling_settings(cfg)[:2]
+        from .objective import box_head_settings
+        d.box_per_class = 1 if box_head_settings(cfg)["per_class"] else 0   # (validated before the library is called)
         self.desc = d
         h = C.c_void_p()
         _lib.call("frcnn_model_create", C.byref(d), C.byref(h))
@@ -254,9 +256,28 @@ class ClassificationNet(object):
     def evaluate(self):
         self.train = False
 
-    def forward(self, cinput, out=None):
+    def _box_classes(self, box_classes, R):
+        """The class source of a per-class box head (cfg.box_head) for the forward pass queued next: ("int", dev, n) -- int32
+        classes of the first n rows, the rest background -- or ("float", dev) -- an fp32 1-based class per row; None: the box of
+        the class each row's own log-probabilities predict.  A model with the shared head takes none."""
+        nat = self.native
+        if box_classes is None:
+            return
+        if not nat.desc.box_per_class:
+            raise _lib.FrcnnError("cnet: box_classes given, but the model's box head is shared (cfg.box_head.per_class is off)")
+        if box_classes[0] == "int" and len(box_classes) == 3:
+            n = int(box_classes[2])
+            if not 0 <= n <= R:
+                raise _lib.FrcnnError("cnet: box_classes names %d foreground rows of %d" % (n, R))
+            _lib.call("frcnn_cnet_box_classes", nat.h, ptr(box_classes[1]), 1, n)
+        elif box_classes[0] == "float" and len(box_classes) == 2:
+            _lib.call("frcnn_cnet_box_classes", nat.h, ptr(box_classes[1]), 2, 0)
+        else:
+            raise _lib.FrcnnError("cnet: box_classes is (\"int\", dev, n) or (\"float\", dev), not %r" % (box_classes[:1],))
+
+    def forward(self, cinput, out=None, box_classes=None):
         """out (optional): (bbox R x 4, cls R x (classes + 1)) device tensors of the caller to write the outputs to, instead of
-        the module-owned buffers the next call reuses."""
+        the module-owned buffers the next call reuses.  box_classes (optional, per-class box head only): see _box_classes."""
         nat = self.native
         cinput = to_device(cinput)
         R, D = cinput.shape
@@ -265,20 +286,23 @@ class ClassificationNet(object):
         arr, keep = _mask_ptrs(self.drop_masks, nat.desc.ncls)
         nat.seed += 1
         self._input = cinput
+        self._box_classes(box_classes, R)
         _lib.call("frcnn_cnet_forward", nat.h, ptr(nat.weights), ptr(cinput), R, 1 if self.train else 0,
                   C.cast(arr, C.c_void_p) if arr is not None else None, nat.seed, ptr(nat.bn_running), ptr(bbox),
                   ptr(cls), stream_ptr())
         self.output = [bbox, cls]
         return self.output
 
-    def score(self, cinput, out):
+    def score(self, cinput, out, box_classes=None):
         """The evaluate-mode forward pass as a side computation (hard example mining, cfg.roi_sampling.source = "hard"): writes
         out = (bbox R x 4, cls R x (classes + 1)), device tensors of the caller, on the current stream.  Nothing is drawn and the
         module's state stays as it is: native.seed does not advance, the input and output the next backward() belongs to are not
-        replaced, and evaluate mode leaves bn_running untouched (it normalises with the running statistics)."""
+        replaced, and evaluate mode leaves bn_running untouched (it normalises with the running statistics).  box_classes: as
+        forward takes it (the classes the rows would be trained on: the keys then rank rows by that loss)."""
         nat = self.native
         cinput = to_device(cinput)
         bbox, cls = out
+        self._box_classes(box_classes, cinput.shape[0])
         _lib.call("frcnn_cnet_forward", nat.h, ptr(nat.weights), ptr(cinput), cinput.shape[0], 0, None, nat.seed,
                   ptr(nat.bn_running), ptr(bbox), ptr(cls), stream_ptr())
         return [bbox, cls]

@@ -330,3 +330,62 @@ def cnet_loss(crout, crtarget, ccout, cctarget, npos, settings=None, roi=None, t
     if train:
         res.update(crout=d_crout.numpy()[:R].copy(), crdelta=crdelta.numpy()[:R].copy(), ccdelta=ccdelta.numpy()[:R].copy())
     return res
+
+
+def box_head(x, W, b, classes=None, lsm=None, n_fg=None, g=None, gW=None, gb=None):
+    """The per-class box head of cfg["box_head"] (not in the reference) on host arrays: frcnn_box_head_forward and, with g given,
+    frcnn_box_head_backward.  x (R x nf float32), W (4C x nf), b (4C).  The class source: classes as an int32 array with n_fg given
+    (the first n_fg rows are foreground with those classes, the rest background), classes as a float32 array (a 1-based class
+    per row, the cctarget format), or classes=None and lsm (R x ncls log-probabilities: the first maximum of each row).
+    -> dict(out R x 4, sel R int32); with g (R x 4) also gfeat (R x nf) and gW, gb: the given arrays (default zeros) plus the
+    gradient, classes without a row untouched.  Runs on the device: there is no host twin (semantics: include/frcnn_hip_box.h)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("box_head: x must be R x nf")
+    R, nf = int(x.shape[0]), int(x.shape[1])
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+    if W.ndim != 2 or W.shape[1] != nf or W.shape[0] % 4 or W.shape[0] < 4 or b.shape[0] != W.shape[0]:
+        raise ValueError("box_head: W must be 4C x %d and b 4C" % nf)
+    Cn = int(W.shape[0]) // 4
+    kind, n, d_cls, d_lsm, ncls = 0, 0, None, None, 0
+
+    def dev(a):
+        return DeviceTensor.from_numpy(a if a.size else np.zeros((1,) + a.shape[1:], a.dtype))
+    if classes is None:
+        if lsm is None:
+            raise ValueError("box_head: classes or lsm")
+        lsm = np.ascontiguousarray(lsm, dtype=np.float32)
+        if lsm.ndim != 2 or lsm.shape[0] != R or lsm.shape[1] < 1:
+            raise ValueError("box_head: lsm must be %d x ncls" % R)
+        d_lsm, ncls = dev(lsm), int(lsm.shape[1])
+    elif n_fg is not None:
+        classes = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+        kind, n = 1, int(n_fg)
+        if classes.shape[0] < n:
+            raise ValueError("box_head: %d classes for n_fg = %d" % (classes.shape[0], n))
+        d_cls = dev(classes)
+    else:
+        classes = np.ascontiguousarray(classes, dtype=np.float32).reshape(-1)
+        if classes.shape[0] != R:
+            raise ValueError("box_head: a float class per row (%d rows)" % R)
+        kind, d_cls = 2, dev(classes)
+    rows = max(R, 1)
+    d_x, d_W, d_b = dev(x), dev(W), dev(b)
+    out = DeviceTensor.zeros((rows, 4))
+    sel = DeviceTensor.zeros((rows,), np.int32)
+    s = stream_ptr()
+    _lib.call("frcnn_box_head_forward", ptr(d_x), R, nf, ptr(d_W), ptr(d_b), Cn, ptr(d_cls) if d_cls is not None else None, kind, n,
+              ptr(d_lsm) if d_lsm is not None else None, ncls, ptr(out), ptr(sel), s)
+    res = dict(out=out.numpy()[:R].copy(), sel=sel.numpy()[:R].copy())
+    if g is not None:
+        g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1, 4)
+        if g.shape[0] != R:
+            raise ValueError("box_head: g must be %d x 4" % R)
+        gW0 = np.zeros_like(W) if gW is None else np.ascontiguousarray(gW, dtype=np.float32).reshape(W.shape)
+        gb0 = np.zeros_like(b) if gb is None else np.ascontiguousarray(gb, dtype=np.float32).reshape(b.shape)
+        d_g, d_gW, d_gb = dev(g), dev(gW0), dev(gb0)
+        gfeat = DeviceTensor.zeros((rows, nf))
+        _lib.call("frcnn_box_head_backward", ptr(d_g), ptr(d_x), ptr(sel), R, nf, ptr(d_W), Cn, ptr(gfeat), ptr(d_gW), ptr(d_gb), s)
+        res.update(gfeat=gfeat.numpy()[:R].copy(), gW=d_gW.numpy().copy(), gb=d_gb.numpy().copy())
+    return res

@@ -248,6 +248,36 @@ def cnet_loss_settings(cfg):
     return out
 
 
+def box_head_settings(cfg):
+    """cfg["box_head"] (not in the reference): the shape of the classification net's box head -> dict(per_class=bool).
+      per_class   false (default; also the key absent and {}): the reference's Linear(nf, 4), one regressor for every class
+                  (model_utilities.lua:117-124) -- the model, its parameter count, launches and results are unchanged;
+                  true: a Linear(nf, 4 * class_count).  Row 4 (c - 1) + j of its weight and bias is coordinate j of foreground
+                  class c; training moves the rows of each example's class, detection decodes the rows of the predicted class
+                  (layout, class sources and arithmetic: include/frcnn_hip_box.h).
+    Not combined with cfg.scoring.classes = "all", which decodes ONE box per candidate for all its class rows: that raises here.
+    Raises FrcnnError -- before the model or the device is touched -- for an unknown key or a value that is not a boolean."""
+    t = cfg.get("box_head")
+    E = _lib.FrcnnError
+    out = dict(per_class=False)
+    if t is None:
+        return out
+    if not isinstance(t, dict):
+        raise E("cfg.box_head must be a table of {per_class}")
+    unknown = sorted(set(t) - set(out), key=str)
+    if unknown:
+        raise E("cfg.box_head: unknown key(s) %s" % ", ".join(map(str, unknown)))
+    v = t.get("per_class", False)
+    if not isinstance(v, (bool, np.bool_)):
+        raise E("cfg.box_head.per_class = %r is not a boolean" % (v,))
+    out["per_class"] = bool(v)
+    sc = cfg.get("scoring")
+    if out["per_class"] and isinstance(sc, dict) and sc.get("classes") == "all":
+        raise E("cfg.box_head.per_class = true cannot be combined with cfg.scoring.classes = \"all\": that pass decodes one box per "
+                "candidate for all its class rows, a per-class head has one box per (candidate, class)")
+    return out
+
+
 def cnet_loss_desc(settings, bgclass):
     """the validated settings of cnet_loss_settings -> the frcnn_cnet_loss_desc frcnn_cnet_loss_rows reads on the host"""
     return _lib.CnetLossDesc(cls=("nll", "focal").index(settings["cls"]), box=("smooth_l1", "giou").index(settings["box"]),
@@ -496,6 +526,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
     cnet_input_planes = model["layers"][-1]["filters"]
     D = kh * kw * cnet_input_planes
     ncls = cfg["class_count"] + 1
+    per_class = bool(native.desc.box_per_class)   # cfg.box_head as the model was built with it (box_head_settings)
     scratch = _Scratch()
     pinned = _PinnedRing()
     import torch
@@ -650,7 +681,9 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
             wins = scratch.get("rh_wins", (N, 4), i32)
             _lib.call("frcnn_roi_windows", ptr(a["roi"]), None, N, loc.ctypes.data_as(C.c_void_p), len(loc), fmH, fmW, ptr(wins), s)
             _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(wins), N, kh, kw, ptr(cin), None, s)
-        score = cnet.score(cin, (scratch.get("rh_crout", (N, 4)), scratch.get("rh_ccout", (N, ncls))))
+        outs = (scratch.get("rh_crout", (N, 4)), scratch.get("rh_ccout", (N, ncls)))
+        # (a per-class box head scores the box of the class a row would be trained on; the shared head is called as ever)
+        score = cnet.score(cin, outs, box_classes=("float", a["cctarget"])) if per_class else cnet.score(cin, outs)
         # {N, F_all, survivors, -}, then the gather's {F, Bq, survivors, N}: the row counts are host numbers since the first
         # read-back and travel back as 16 bytes from page-locked memory (the NMS reads its count on the device)
         hctl = scratch.get("rh_ctl", (8,), i32)
@@ -940,7 +973,7 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                         _lib.call("frcnn_roi_windows", ptr(rec["roi"]), None, S, loc.ctypes.data_as(C.c_void_p), len(loc), fmH, fmW,
                                   ptr(dwins), s)
                         _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, ptr(dwins), S, kh, kw, ptr(cinput), ptr(pidx), s)
-                    crout, ccout = cnet.forward(cinput)
+                    crout, ccout = cnet.forward(cinput, box_classes=("float", rec["cctarget"])) if per_class else cnet.forward(cinput)
                     crdelta = scratch.get("crdelta", (S, 4))
                     ccdelta = scratch.get("ccdelta", (S, ncls))
                     pnet.anchor_loss_wait()       # (the accumulators: the anchor losses land in the same vector)
@@ -971,14 +1004,16 @@ def create_objective(model, weights, gradient, batch_iterator, stats):  # object
                     _lib.call("frcnn_roi_pool_forward", ptr(fm), fmC, fmH, fmW, C.c_void_p(d_wins), E, kh, kw,
                               ptr(cinput), ptr(pidx), s)
                 # ---- fine-tuning stage (:146-186) --------------------------------------------
-                coutputs = cnet.forward(cinput)  # :164
+                # (a per-class box head reads the classes from the example table: final on this stream since the upload above, so
+                # the pass still overlaps frcnn_pnet_anchor_loss_begin, which writes cctarget on the side stream)
+                coutputs = cnet.forward(cinput, box_classes=("int", d_class, npos)) if per_class else cnet.forward(cinput)  # :164
                 crout, ccout = coutputs
                 crdelta = scratch.get("crdelta", (E, 4))
                 ccdelta = scratch.get("ccdelta", (E, ncls))
                 pnet.anchor_loss_wait()   # crtarget is relative to the anchor nets' proposals (:156)
                 cnet_losses(crout, crtarget, ccout, cctarget, E, npos, crdelta, ccdelta)  # :170-177
                 debug["cnet_loss"] = dict(crout=crout, ccout=ccout, crtarget=crtarget, cctarget=cctarget, crdelta=crdelta,
-                                          ccdelta=ccdelta, R=E, npos=npos)
+                                          ccdelta=ccdelta, R=E, npos=npos, cinput=cinput)
                 post_roi_delta = cnet.backward(cinput, [crdelta, ccdelta])  # :179
                 if not trunk_frozen and align:   # (a frozen backbone: the library left the input gradient unwritten)
                     _lib.call("frcnn_roi_align_backward", ptr(delta_outputs[4]), fmC, fmH, fmW, ptr(post_roi_delta),

@@ -688,6 +688,8 @@ typedef struct {
   float cls_dropout[8];
   int class_count;                  /* cfg.class_count (excluding background) */
   int kh, kw;                       /* cfg.roi_pooling */
+  int box_per_class;                /* cfg.box_head.per_class: the box head is a Linear(nf, 4 * class_count), one box per
+                                       foreground class (frcnn_hip_box.h); 0: the reference's shared Linear(nf, 4) */
 } frcnn_model_desc;
 
 typedef struct frcnn_model frcnn_model;
@@ -977,4 +979,6 @@ int frcnn_broadcast_f32(frcnn_comm *, float *buf, long long n, int root, void *s
 #include "frcnn_hip_hard.h"
 /* The configurable losses of the classification net (cfg.cnet_loss): one entry point and its description, likewise. */
 #include "frcnn_hip_loss.h"
+/* Per-class box regression of the classification net (cfg.box_head): three entry points, likewise. */
+#include "frcnn_hip_box.h"
 #endif /* FRCNN_HIP_H */
