@@ -19,7 +19,8 @@
 -- the per-class pass.  Under 'linear' or 'gaussian' a winner's confidence is its DECAYED log-score, the one it was ranked by.
 -- And cfg.box_voting = { overlap = 0.5, weight = 'score' | 'uniform' } (Detector.box_voting_settings): behind the per-class pass a
 -- winner's r2 becomes the weighted mean of the r2 of its class's survivors that overlap it; nothing else about a winner changes.
--- And cfg.scoring = { classes = 'top' | 'all', min_confidence = 0.2, max_detections = M } (Detector.scoring_settings): the class
+-- And cfg.scoring = { classes = 'top' | 'all', min_confidence = 0.2, max_detections = M, boxes = 'candidate' | 'class' }
+-- (Detector.scoring_settings, Detector.scoring_boxes; boxes = 'class': the box of its own class for every class row): the class
 -- test as ONE frcnn_detect_classes_batch launch per chunk; 'all' scores a candidate under every foreground class over the threshold.
 -- And cfg.tta = { hflip = false, scales = { 1.0 } } (Detector.tta_settings): test-time augmentation.  A frame is detected on V
 -- views of itself -- per scale the rescaled frame and, under hflip, its mirror --, which are the SEGMENTS of the chunk; behind the
@@ -166,7 +167,7 @@ function Detector.scoring_settings(t)
   if t == nil then return nil end
   if type(t) ~= 'table' then error('cfg.scoring must be a table of {classes, min_confidence, max_detections}') end
   for k, _ in pairs(t) do
-    if k ~= 'classes' and k ~= 'min_confidence' and k ~= 'max_detections' then
+    if k ~= 'classes' and k ~= 'min_confidence' and k ~= 'max_detections' and k ~= 'boxes' then   -- (boxes: scoring_boxes)
       error('cfg.scoring: unknown key ' .. tostring(k))
     end
   end
@@ -185,14 +186,34 @@ function Detector.scoring_settings(t)
   return classes, min_confidence, M
 end
 
+-- cfg.scoring.boxes -> 'candidate' (default, also without the table: a candidate has ONE box, the net's, and under classes =
+-- 'all' all its class rows carry it) or 'class': every emitted row (candidate r, class c) carries the box class c's four
+-- regressor rows predict for r -- ONE frcnn_detect_class_boxes_batch launch per chunk behind the class test.  Needs a per-class
+-- box head (cfg.box_head.per_class); under classes = 'top' the row's class is the arg-max, whose box the net wrote already: the
+-- launches of 'candidate'.  1:1 with scoring_boxes of the Python mirror.
+function Detector.scoring_boxes(t)
+  if t == nil then return 'candidate' end
+  if type(t) ~= 'table' then error('cfg.scoring must be a table of {classes, min_confidence, max_detections, boxes}') end
+  local boxes = t.boxes
+  if boxes == nil then return 'candidate' end
+  if boxes ~= 'candidate' and boxes ~= 'class' then error('cfg.scoring.boxes must be "candidate" or "class"') end
+  return boxes
+end
+
 -- Makes a table as scoring_settings takes it this Detector's class test from the next frame on (nil: the reference's)
 function Detector:set_scoring(t)
   local classes, min_confidence, max_detections = Detector.scoring_settings(t)
+  local boxes = Detector.scoring_boxes(t)
+  if boxes == 'class' and not self.model.box_per_class then
+    error('cfg.scoring.boxes = "class" needs cfg.box_head.per_class = true: a shared box head has one box per candidate')
+  end
   -- a per-class box head (cfg.box_head) has one box per (candidate, class); classes = 'all' decodes ONE box per candidate
-  if classes == 'all' and self.model.box_per_class then
-    error('cfg.scoring.classes = "all" cannot be combined with cfg.box_head.per_class = true')
+  if classes == 'all' and self.model.box_per_class and boxes ~= 'class' then
+    error('cfg.scoring.classes = "all" cannot be combined with cfg.box_head.per_class = true; cfg.scoring.boxes = "class" gives ' ..
+          'every class row the box of its own class')
   end
   self.scoring_classes, self.min_confidence, self.max_detections = classes, min_confidence, max_detections
+  self.scoring_box = boxes
 end
 
 -- m: the rows a candidate can emit, what the per-row buffers of a chunk are sized by (Rmax * m rows a frame).  'top': 1.  'all':
@@ -679,6 +700,13 @@ function Detector:detect_chunk(frames, shared, prefix)
     end
     return cinput
   end
+  -- cfg.scoring.boxes = 'class' under 'all': the box head's input of every pass is kept, in the rows of all_bbox / all_cls, for
+  -- the class-row launch behind the class test
+  local class_boxes = scoring and self.scoring_classes == 'all' and self.scoring_box == 'class'
+  local nf, all_feat = cnet.feature_count, nil
+  if class_boxes then
+    all_feat = ffi.cast('float*', scratch(prefix .. 'feat', 4 * nf * (shared and total or B * Rmax)).ptr)
+  end
   local all_bbox, all_cls
   if shared then
     for b = 0, B - 1 do
@@ -686,6 +714,7 @@ function Detector:detect_chunk(frames, shared, prefix)
     end
     local coutputs = cnet:forward(hip.view(cbuf, { total, D }))         -- :101, all frames
     all_bbox, all_cls = ffi.cast('float*', coutputs[1].ptr), ffi.cast('float*', coutputs[2].ptr)
+    if class_boxes then cnet:features(all_feat) end
   elseif scoring then      -- the net reuses its outputs: every frame's are copied to its rows (b * Rmax) for the one launch
     all_bbox = ffi.cast('float*', scratch(prefix .. 'bbox', 16 * B * Rmax).ptr)
     all_cls = ffi.cast('float*', scratch(prefix .. 'cls_out', 4 * ncls * B * Rmax).ptr)
@@ -706,6 +735,7 @@ function Detector:detect_chunk(frames, shared, prefix)
           check(C.frcnn_memcpy_d2d(all_bbox + 4 * b * Rmax, bbox_ptr, 16 * R, nil))
           check(C.frcnn_memcpy_d2d(all_cls + ncls * b * Rmax, cls_ptr, 4 * ncls * R, nil))
           R_arg[b], row0_arg[b] = R, b * Rmax
+          if class_boxes then cnet:features(all_feat + nf * b * Rmax) end
         end
       end
       if not scoring then
@@ -723,6 +753,13 @@ function Detector:detect_chunk(frames, shared, prefix)
     if self.scoring_classes == 'all' then mode = 1 end
     check(C.frcnn_detect_classes_batch(all_cls, all_bbox, R_arg, row0_arg, B, mr, dpick, cap, ncls, bgclass, self.min_confidence, mode,
                                        dbb, dkc, dkeep, dr2, rows, cnt + 2 * B, nil, nil))
+    if class_boxes then
+      -- ONE launch: row (r, c) gets the box class c's regressor rows predict for candidate r (the one written above was a
+      -- placeholder); the row counts stay on the device.  In front of the merge of cfg.tta, which transforms these boxes too
+      local W_box, b_box = hip.box_head_parameters(self.model)
+      check(hip.CX.frcnn_detect_class_boxes_batch(all_feat, nf, row0_arg, B, W_box, b_box, ncls - 1, mr, dpick, cap, dkc, dkeep,
+                                                  cnt + 2 * B, rows, dbb, dr2, nil))
+    end
   end
   --         Under cfg.tta: ONE frcnn_detect_merge_views launch -- every frame's V segments of survivors become one segment of
   --         V * rows rows in the frame's coordinates (a view's geometry and its candidate count are host values since read-back 1:

@@ -39,7 +39,9 @@ Nor is scoring a candidate under more than its arg-max class, off by default (cf
 scoring_settings): with the key the class test of a chunk is ONE frcnn_detect_classes_batch launch in place of two per frame, its
 threshold is min_confidence, and under classes = "all" a candidate yields one row per foreground class over the threshold -- the
 rows the per-class NMS, voting and the gather then work on; several winners may share a candidate (field `candidate`), with
-bit-identical r2 unless voted.  max_detections caps a frame's winners on the host.
+bit-identical r2 unless voted.  max_detections caps a frame's winners on the host.  On a per-class box head (cfg["box_head"])
+boxes = "class" (scoring_boxes) gives every such row the box of ITS class: one frcnn_detect_class_boxes_batch launch behind the
+class test, on the box head's input kept from every pass (cnet.features).
 
 Nor is test-time augmentation, off by default (cfg["tta"] / Detector(..., tta=...), see tta_settings): a frame is detected on V
 views of itself -- per scale the rescaled frame (frcnn_image_scale) and, under hflip, its mirror (frcnn_image_crop_flip) -- which
@@ -183,8 +185,9 @@ def box_voting_settings(cfg_or_table):
     return overlap, weight
 
 
-SCORING_DEFAULTS = dict(classes="top", min_confidence=0.2, max_detections=None)
+SCORING_DEFAULTS = dict(classes="top", min_confidence=0.2, max_detections=None, boxes="candidate")
 SCORING_MODES = dict(top=0, all=1)   # mode of frcnn_detect_classes_batch
+SCORING_BOXES = ("candidate", "class")
 
 
 def scoring_settings(cfg_or_table):
@@ -200,7 +203,7 @@ def scoring_settings(cfg_or_table):
                       earlier pick), applied on the host behind read-back 2
     An empty table is "top" at 0.2: the results of the key absent, from one launch.  Raises ValueError (before any device call)
     for an unknown key, an unknown classes, a bool or a non-number, a min_confidence outside [0, 1) and a max_detections that is
-    not an integer >= 1."""
+    not an integer >= 1.  The table's fourth key, boxes, is not part of the tuple: scoring_boxes validates and returns it."""
     t = _settings_table(cfg_or_table, "scoring", SCORING_DEFAULTS, optional=True)
     if t is None:
         return None
@@ -211,6 +214,26 @@ def scoring_settings(cfg_or_table):
     if not (0.0 <= min_confidence < 1.0):
         raise ValueError("cfg.scoring.min_confidence = %r (in [0, 1))" % (min_confidence,))
     return classes, min_confidence, _count("scoring", "max_detections", t.get("max_detections"))
+
+
+def scoring_boxes(cfg_or_table):
+    """cfg["scoring"]["boxes"] -- of a cfg, of the table itself, or of None -- -> "candidate" or "class", validated on the host.
+      boxes  "candidate" (default, also without the table): a candidate has ONE box, the one the classification net wrote for it,
+             and under classes = "all" every class row of the candidate carries it;
+             "class": every emitted row (candidate r, class c) carries the box that class c's four regressor rows predict for
+             candidate r -- ONE frcnn_detect_class_boxes_batch launch per chunk behind the class test (step 4 of _detect_chunk).
+             Needs a per-class box head (cfg["box_head"]["per_class"]: Detector.set_scoring and box_head_settings refuse it on a
+             shared one).  Under classes = "top" a row's class is the arg-max, whose box the net wrote already: accepted, and
+             the launches are those of "candidate".
+    Raises ValueError (before any device call) for any other value, a bool or a non-string, and whatever is wrong with the table's
+    shape (scoring_settings validates the other keys)."""
+    t = _settings_table(cfg_or_table, "scoring", SCORING_DEFAULTS, optional=True)
+    if t is None:
+        return SCORING_DEFAULTS["boxes"]
+    boxes = t.get("boxes", SCORING_DEFAULTS["boxes"])
+    if not isinstance(boxes, str) or boxes not in SCORING_BOXES:
+        raise ValueError("cfg.scoring.boxes = %r (\"candidate\" or \"class\")" % (boxes,))
+    return boxes
 
 
 TTA_DEFAULTS = dict(hflip=False, scales=[1.0])
@@ -487,6 +510,7 @@ class _DetectorType(type):
             box_voting_settings(box_voting)
         if scoring is not None:
             scoring_settings(scoring)
+            scoring_boxes(scoring)
         if tta is not None:
             tta_settings(tta)
         d = super().__call__(*args, **kw)
@@ -504,6 +528,7 @@ class Detector(object, metaclass=_DetectorType):
     nms_settings = staticmethod(nms_settings)
     box_voting_settings = staticmethod(box_voting_settings)
     scoring_settings = staticmethod(scoring_settings)
+    scoring_boxes = staticmethod(scoring_boxes)
     tta_settings = staticmethod(tta_settings)
 
     def __init__(self, model, static_weights=False, proposals=None, nms=None):  # Detector.lua:8-15
@@ -563,15 +588,21 @@ class Detector(object, metaclass=_DetectorType):
 
     def set_scoring(self, cfg_or_table):
         """Validates a table as scoring_settings takes it and makes it this Detector's class test from the next frame on (None,
-        or a cfg without the key: the reference's, launch for launch)."""
-        scoring = scoring_settings(cfg_or_table)
+        or a cfg without the key: the reference's, launch for launch); self.boxes is the table's boxes (scoring_boxes)."""
+        scoring, boxes = scoring_settings(cfg_or_table), scoring_boxes(cfg_or_table)
         # a per-class box head (cfg.box_head) has one box per (candidate, class); classes = "all" decodes ONE box per candidate
-        # for all its class rows: refused until frcnn_detect_classes_batch takes a box per row
+        # for all its class rows: refused unless boxes = "class" asks for the row's own (frcnn_detect_class_boxes_batch)
         model = getattr(self, "model", None)
-        if scoring is not None and scoring[0] == "all" and model is not None and int(model["native"].desc.box_per_class):
+        wanted = boxes == "class" or (scoring is not None and scoring[0] == "all")     # (else the model is not looked at)
+        per_class = wanted and model is not None and int(model["native"].desc.box_per_class)
+        if boxes == "class" and model is not None and not per_class:
+            raise _lib.FrcnnError("cfg.scoring.boxes = \"class\" needs cfg.box_head.per_class = true: a shared box head has one box "
+                                  "per candidate")
+        if scoring is not None and scoring[0] == "all" and per_class and boxes != "class":
             raise _lib.FrcnnError("cfg.scoring.classes = \"all\" cannot be combined with cfg.box_head.per_class = true: that pass decodes "
-                             "one box per candidate for all its class rows")
-        self.scoring = scoring
+                             "one box per candidate for all its class rows; cfg.scoring.boxes = \"class\" gives every class row the "
+                             "box of its own class")
+        self.scoring, self.boxes = scoring, boxes
 
     def set_tta(self, cfg_or_table):
         """Validates a table as tta_settings takes it and makes it this Detector's setting from the next frame on (None, or a
@@ -967,6 +998,12 @@ class Detector(object, metaclass=_DetectorType):
                 total += Rs[b]
         cinput_buf = self._buf(pre + "cinput", (total if shared else Rmax, D))
         bbox_all = self._buf(pre + "bbox", (B, Rmax, 4)); cls_all = self._buf(pre + "cls_out", (B, Rmax, ncls))
+        # cfg["scoring"]["boxes"] = "class" under "all": the box head's input of every pass is kept, in the rows of bbox_all and
+        # cls_all, for the class-row launch behind the class test ("top": the net's own box IS the row's class's)
+        class_boxes = bool(self.scoring) and self.scoring[0] == "all" and self.boxes == "class"
+        if class_boxes:
+            nf = cnet.feature_count
+            feat_all = self._buf(pre + "feat", (B, Rmax, nf))
 
         def pooled(b):    # the region features of frame b's candidates (_pool) -> its input rows
             R = Rs[b]
@@ -985,9 +1022,13 @@ class Detector(object, metaclass=_DetectorType):
                 more[b].update(pooled=pooled(b))
             else:
                 cnet.forward(pooled(b), out=(more[b]["bbox"], more[b]["cls"]))  # :101
+                if class_boxes:
+                    cnet.features(feat_all.offset_view(nf * row0[b], (Rs[b], nf)))
         if shared:
             cnet.forward(cinput_buf, out=(bbox_all.offset_view(0, (total, 4)),
                                           cls_all.offset_view(0, (total, ncls))))  # :101, all frames
+            if class_boxes:
+                cnet.features(feat_all.offset_view(0, (total, nf)))
         # ---- then, per frame, the class test (:106-122) into the frame's segment: r2 = Anchors.anchorToInput(r, bbox) in double,
         #      survivors compacted in order
         #      Under cfg["scoring"]: ONE frcnn_detect_classes_batch launch for the chunk, which reads the net's log-probabilities
@@ -1002,6 +1043,13 @@ class Detector(object, metaclass=_DetectorType):
             row0_arg = (C.c_longlong * B)(*[row0.get(b, 0) for b in range(B)])
             _lib.call("frcnn_detect_classes_batch", ptr(cls_all), ptr(bbox_all), R_arg, row0_arg, B, ptr(mr), ptr(pick), cap, ncls,
                       ncls, scoring[1], SCORING_MODES[scoring[0]], ptr(bb), ptr(kc), ptr(keep_row), ptr(r2), rows, ptr(c_K), None, s)
+            if class_boxes:
+                # ONE launch: row (r, c) gets the box class c's regressor rows predict for candidate r (the one written above
+                # was a placeholder), read from the kept features; the row counts stay on the device.  In front of the merge of
+                # cfg["tta"], which then transforms the per-class boxes like any others
+                W_box, b_box = model["native"].box_head_parameters()
+                _lib.call("frcnn_detect_class_boxes_batch", ptr(feat_all), nf, row0_arg, B, ptr(W_box), ptr(b_box), ncls - 1, ptr(mr),
+                          ptr(pick), cap, ptr(kc), ptr(keep_row), ptr(c_K), rows, ptr(bb), ptr(r2), s)
         else:
             dcls = self._buf(pre + "cls", (Rmax,), i32); dconf = self._buf(pre + "conf", (Rmax,))
             for b in range(B):

@@ -220,12 +220,19 @@ BOX_SIGS = {
     "frcnn_cnet_box_classes": ([vp, vp, C.c_int, C.c_int], C.c_int),
 }
 
+# the entry points of include/frcnn_hip_classbox.h (cfg.scoring.boxes = "class": the box of its own class for every class row)
+CLASSBOX_SIGS = {
+    "frcnn_cnet_features": ([vp, vp, vp], C.c_int),
+    "frcnn_detect_class_boxes_batch": ([vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_longlong, vp, vp, vp, C.c_int, vp, vp, vp],
+                                       C.c_int),
+}
+
 _lib = None
 
 
 def exported_symbols():
     """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS; of
-    frcnn_hip_box.h: BOX_SIGS)"""
+    frcnn_hip_box.h: BOX_SIGS; of frcnn_hip_classbox.h: CLASSBOX_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -248,7 +255,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

@@ -236,6 +236,12 @@ int frcnn_box_head_backward(const float* g, const float* x, const int* sel, int 
                             float* gW, float* gb, void* stream) {
   return box_head_backward(g, x, sel, R, nf, W, C, gfeat, gW, gb, S(stream), S(stream));
 }
+int frcnn_detect_class_boxes_batch(const float* feat, int nf, const long long* row0_host, int B, const float* W, const float* b, int C,
+                                   const double* rect, const long long* pick, long long match_stride, const int* kc,
+                                   const int* keep_row, const int* K_dev, int row_stride, float* bb, double* r2, void* stream) {
+  return detect_class_boxes_batch(feat, nf, row0_host, B, W, b, C, rect, pick, match_stride, kc, keep_row, K_dev, row_stride, bb, r2,
+                                  S(stream));
+}
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,
                               const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {

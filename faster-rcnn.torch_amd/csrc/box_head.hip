@@ -4,17 +4,9 @@
 // beyond the int sel[R] the forward kernel writes and the two backward kernels read; each is a pure function of its inputs, so
 // every result is bit-reproducible run to run, in and out of deterministic mode.
 #include "kernels.h"
+#include "box_row.h"   // BH_WAVE, bh_wave_sum and the row product, shared with class_boxes.hip
 
 namespace frcnn {
-
-static constexpr int BH_WAVE = 64;
-
-// fixed-order sum of one value per lane over the wave (butterfly: every lane ends with the same bits)
-__device__ __forceinline__ float bh_wave_sum(float v) {
-#pragma unroll
-  for (int o = BH_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, BH_WAVE);
-  return v;
-}
 
 // The class of row r (1-based, 0 = none), uniform over the wave that owns the row.
 //   kind 1: int32 classes of the first n rows, every row behind them background;
@@ -52,7 +44,7 @@ __device__ __forceinline__ int bh_row_class(int r, int lane, const void* __restr
 
 // ---- 1. forward: out[r][j] = b[4(c-1)+j] + sum_k x[r][k] W[4(c-1)+j][k], c = the row's class; sel[r] = c ------------------------
 // One wave a row, four rows a workgroup.  VEC: 16-byte pieces of the row and of the four weight rows (nf % 4 == 0, x and W 16-byte
-// aligned), else one float at a time.  Four accumulators a lane, then the butterfly.
+// aligned), else one float at a time.  Four accumulators a lane, then the butterfly (bh_row_product, box_row.h).
 template <bool VEC>
 __global__ __launch_bounds__(256) void box_head_forward_kernel(const float* __restrict__ x, int R, int nf, const float* __restrict__ W,
                                                                const float* __restrict__ b, int C, const void* __restrict__ classes,
@@ -70,32 +62,8 @@ __global__ __launch_bounds__(256) void box_head_forward_kernel(const float* __re
   }
   const float* xr = x + (size_t)r * nf;
   const float* w0 = W + (size_t)(4 * (c - 1)) * nf;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (VEC) {
-    const int nq = nf >> 2;
-    const float4* xq = reinterpret_cast<const float4*>(xr);
-    const float4* q0 = reinterpret_cast<const float4*>(w0);
-    const float4* q1 = reinterpret_cast<const float4*>(w0 + nf);
-    const float4* q2 = reinterpret_cast<const float4*>(w0 + 2 * (size_t)nf);
-    const float4* q3 = reinterpret_cast<const float4*>(w0 + 3 * (size_t)nf);
-    for (int q = lane; q < nq; q += BH_WAVE) {
-      const float4 v = xq[q];
-      const float4 u0 = q0[q], u1 = q1[q], u2 = q2[q], u3 = q3[q];
-      a0 += v.x * u0.x + v.y * u0.y + v.z * u0.z + v.w * u0.w;
-      a1 += v.x * u1.x + v.y * u1.y + v.z * u1.z + v.w * u1.w;
-      a2 += v.x * u2.x + v.y * u2.y + v.z * u2.z + v.w * u2.w;
-      a3 += v.x * u3.x + v.y * u3.y + v.z * u3.z + v.w * u3.w;
-    }
-  } else {
-    for (int k = lane; k < nf; k += BH_WAVE) {
-      const float v = xr[k];
-      a0 += v * w0[k];
-      a1 += v * w0[(size_t)nf + k];
-      a2 += v * w0[2 * (size_t)nf + k];
-      a3 += v * w0[3 * (size_t)nf + k];
-    }
-  }
-  a0 = bh_wave_sum(a0); a1 = bh_wave_sum(a1); a2 = bh_wave_sum(a2); a3 = bh_wave_sum(a3);
+  float a0, a1, a2, a3;
+  bh_row_product<VEC>(xr, w0, nf, lane, a0, a1, a2, a3);
   if (lane < 4) {
     const float a = lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3;
     o[lane] = a + b[4 * (c - 1) + lane];

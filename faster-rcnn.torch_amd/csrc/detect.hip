@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "kernels.h"
+#include "anchor_decode.h"
 
 namespace frcnn {
 
@@ -66,15 +67,7 @@ int roi_windows(const double* rect, const long long* pick, int k, const int* lay
   return FRCNN_OK;
 }
 
-// Anchors.anchorToInput (Anchors.lua:245-252) + Rect.fromXYWidthHeight: a = the anchor's input rect, t = the net's 4 deltas;
-// products and sums separately rounded, as Lua numbers are
-__device__ __forceinline__ void anchor_to_input(const double* __restrict__ a, const float* __restrict__ t, double* __restrict__ o) {
-  const double aw = a[2] - a[0], ah = a[3] - a[1];
-  double x0 = (double)t[0] * aw; x0 = x0 + a[0];
-  double y0 = (double)t[1] * ah; y0 = y0 + a[1];
-  const double ew = exp((double)t[2]) * aw, eh = exp((double)t[3]) * ah;
-  o[0] = x0; o[1] = y0; o[2] = x0 + ew; o[3] = y0 + eh;
-}
+// (anchor_to_input -- Anchors.anchorToInput, Anchors.lua:245-252 -- lives in anchor_decode.h: class_boxes.hip decodes with it too)
 
 // One block, ordered compaction.  For candidate r (row pick[r] of the match arrays): keep iff cls != bgclass and
 // exp(conf) > min_conf.  Survivor j (in candidate order): bb[j] = {float(r2), conf}, kc[j] = class, keep_row[j] = r,

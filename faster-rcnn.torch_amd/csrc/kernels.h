@@ -343,6 +343,10 @@ int box_head_forward(const float* x, int R, int nf, const float* W, const float*
 // gfeat (stored; on s_chain) and / or gW, gb (added to; on s_wgrad); either part may be left out with a null output
 int box_head_backward(const float* g, const float* x, const int* sel, int R, int nf, const float* W, int C, float* gfeat, float* gW,
                       float* gb, hipStream_t s_chain, hipStream_t s_wgrad);
+// ---- the per-class boxes of the class test's rows (class_boxes.hip; semantics: include/frcnn_hip_classbox.h).  row0: host values.
+int detect_class_boxes_batch(const float* feat, int nf, const long long* row0, int B, const float* W, const float* b, int C,
+                             const double* rect, const long long* pick, long long match_stride, const int* kc, const int* keep_row,
+                             const int* K_dev, int row_stride, float* bb, double* r2, hipStream_t s);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

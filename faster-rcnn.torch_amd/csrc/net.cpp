@@ -1928,6 +1928,18 @@ int frcnn_cnet_forward(frcnn_model* m, const float* weights, const float* x, int
   return FRCNN_OK;
 }
 
+// the box head's input of the last forward pass (R x nf: the last class layer's output, or the caller's input without class
+// layers) -> dst, on `stream`
+int frcnn_cnet_features(frcnn_model* m, float* dst, void* stream) {
+  FR_CHECK(m != nullptr, "cnet_features: null model");
+  FR_CHECK(m->R > 0, "cnet_features: call frcnn_cnet_forward first");
+  FR_CHECK(dst != nullptr, "cnet_features: NULL dst");
+  const int nf = m->cls.empty() ? m->D : m->cls.back().n;
+  const float* feat = m->cls.empty() ? m->cnet_x : m->cls.back().post.f();
+  FR_HIP(hipMemcpyAsync(dst, feat, (size_t)m->R * nf * 4, hipMemcpyDeviceToDevice, S(stream)));
+  return FRCNN_OK;
+}
+
 int frcnn_cnet_backward(frcnn_model* m, const float* weights, const float* g_bbox, const float* g_cls, float* gx,
                         float* grad, void* stream) {
   hipStream_t s = S(stream);

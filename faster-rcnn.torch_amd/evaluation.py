@@ -212,7 +212,8 @@ def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_
     The precision/recall curves are only as long as the detector's list: mAP is meant to be computed under a detector with
     cfg["scoring"] = {classes = "all", min_confidence = a low value such as 0.05} (Detector.scoring_settings), which scores a
     region under every class over the threshold; the reference's class test (arg-max only, p > 0.2) cuts the low-confidence
-    tail off every curve."""
+    tail off every curve.  A model with a per-class box head (cfg["box_head"]) is evaluated that way with boxes = "class" in the
+    same table (Detector.scoring_boxes): every (region, class) row is then scored with the box of its own class."""
     detections, ground_truth = [], []
     images = 0
     pending = []     # (image id, frame) -- of one size unless mixed_sizes -- waiting for detect_batch

@@ -92,6 +92,15 @@ class NativeModel(object):
                 w[off:off + cnt] = rng.uniform(0.0, 1.0, cnt).astype(np.float32)
         return w
 
+    def box_head_parameters(self):
+        """(W, b): the box head's weight (4 x nf, or 4 C x nf under cfg.box_head.per_class) and bias as views of the flat weight
+        vector -- the two tensors in front of the class head's in the parameter table (kinds 3 and 4)."""
+        if self.weights is None:
+            raise _lib.FrcnnError("box_head_parameters() before combine_and_flatten_parameters()")
+        (wo, wn, wk, _), (bo, bn, bk, _) = (tuple(int(v) for v in row) for row in self.param_table[-4:-2])
+        assert (wk, bk) == (3, 4) and bo == wo + wn
+        return self.weights[wo:wo + wn], self.weights[bo:bo + bn]
+
     def bn_running_size(self):
         return int(sum(2 * self.desc.cls_n[i] for i in range(self.desc.ncls) if self.desc.cls_bn[i]))
 
@@ -306,6 +315,18 @@ class ClassificationNet(object):
         _lib.call("frcnn_cnet_forward", nat.h, ptr(nat.weights), ptr(cinput), cinput.shape[0], 0, None, nat.seed,
                   ptr(nat.bn_running), ptr(bbox), ptr(cls), stream_ptr())
         return [bbox, cls]
+
+    @property
+    def feature_count(self):
+        """nf: the row length of the box head's (and the class head's) input -- the last class layer's n, or the pooled row
+        length D without class layers (the fan-in the parameter table records for the box head's weight)."""
+        return int(self.native.param_table[-4][3])
+
+    def features(self, out):
+        """Copies the box head's input of the last forward() / score() -- R x nf (feature_count), R that pass's row count -- to
+        the device tensor `out` on the current stream (frcnn_cnet_features: one device-to-device copy)."""
+        _lib.call("frcnn_cnet_features", self.native.h, ptr(out), stream_ptr())
+        return out
 
     def backward(self, cinput, grad_outputs):
         nat = self.native

@@ -389,3 +389,49 @@ def box_head(x, W, b, classes=None, lsm=None, n_fg=None, g=None, gW=None, gb=Non
         _lib.call("frcnn_box_head_backward", ptr(d_g), ptr(d_x), ptr(sel), R, nf, ptr(d_W), Cn, ptr(gfeat), ptr(d_gW), ptr(d_gb), s)
         res.update(gfeat=gfeat.numpy()[:R].copy(), gW=d_gW.numpy().copy(), gb=d_gb.numpy().copy())
     return res
+
+
+def class_boxes(feat, row0, W, b, rect, pick, kc, keep_row, K, bb, r2, overrides=None):
+    """frcnn_detect_class_boxes_batch (cfg["scoring"]["boxes"] = "class"; not in the reference) on host arrays: the box of ITS
+    class for every row of an all-class class test.  feat (N x nf float32, every frame's feature rows), row0 (B first rows of
+    the frames in feat), W (4C x nf) and b (4C) of a per-class box head, rect (B x match_stride x 4 float64) and pick
+    (B x match_stride int64, 1-based rows of rect), kc and keep_row (B x row_stride int32: a row's 1-based class and 0-based
+    candidate), K (B int32: the frames' row counts, read on the device), bb (B x row_stride x 5 float32) and r2
+    (B x row_stride x 4 float64): the arrays the launch rewrites, as they are before it.
+    -> dict(code, bb, r2): the library's return code (0: done; an argument error has launched nothing) and the two arrays after
+    the call.  overrides: scalar arguments (nf, B, C, match_stride, row_stride) passed in place of the arrays' own, for the error
+    paths.  Runs on the device: there is no host twin (semantics: include/frcnn_hip_classbox.h)."""
+    feat = np.ascontiguousarray(feat, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+    rect = np.ascontiguousarray(rect, dtype=np.float64)
+    pick = np.ascontiguousarray(pick, dtype=np.int64)
+    kc = np.ascontiguousarray(kc, dtype=np.int32)
+    keep_row = np.ascontiguousarray(keep_row, dtype=np.int32)
+    K = np.ascontiguousarray(K, dtype=np.int32).reshape(-1)
+    bb = np.ascontiguousarray(bb, dtype=np.float32)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64)
+    row0 = [int(v) for v in row0]
+    if feat.ndim != 2 or W.ndim != 2 or W.shape[1] != feat.shape[1] or W.shape[0] % 4 or b.shape[0] != W.shape[0]:
+        raise ValueError("class_boxes: feat must be N x nf, W 4C x nf and b 4C")
+    B = len(row0)
+    if rect.ndim != 3 or rect.shape[0] != B or rect.shape[2] != 4 or pick.shape != rect.shape[:2]:
+        raise ValueError("class_boxes: rect must be B x match_stride x 4 and pick B x match_stride")
+    if kc.ndim != 2 or kc.shape[0] != B or keep_row.shape != kc.shape or K.shape[0] != B:
+        raise ValueError("class_boxes: kc and keep_row must be B x row_stride and K B")
+    if bb.shape != kc.shape + (5,) or r2.shape != kc.shape + (4,):
+        raise ValueError("class_boxes: bb must be B x row_stride x 5 and r2 B x row_stride x 4")
+    a = dict(nf=int(feat.shape[1]), B=B, C=int(W.shape[0]) // 4, match_stride=int(rect.shape[1]), row_stride=int(kc.shape[1]))
+    a.update(overrides or {})
+
+    def dev(x):
+        return DeviceTensor.from_numpy(x if x.size else np.zeros((1,) + x.shape[1:], x.dtype).reshape(-1))
+    d = [dev(x) for x in (feat, W, b, rect, pick, kc, keep_row, K, bb, r2)]
+    d_feat, d_W, d_b, d_rect, d_pick, d_kc, d_keep, d_K, d_bb, d_r2 = d
+    row0_arg = (C.c_longlong * max(len(row0), 1))(*row0)
+    code = _lib.load().frcnn_detect_class_boxes_batch(ptr(d_feat), a["nf"], row0_arg, a["B"], ptr(d_W), ptr(d_b), a["C"], ptr(d_rect),
+                                                      ptr(d_pick), a["match_stride"], ptr(d_kc), ptr(d_keep), ptr(d_K),
+                                                      a["row_stride"], ptr(d_bb), ptr(d_r2), stream_ptr())
+    out_bb = d_bb.numpy().reshape(-1)[:bb.size].reshape(bb.shape).copy()
+    out_r2 = d_r2.numpy().reshape(-1)[:r2.size].reshape(r2.shape).copy()
+    return dict(code=int(code), bb=out_bb, r2=out_r2)

@@ -255,26 +255,31 @@ def box_head_settings(cfg):
                   true: a Linear(nf, 4 * class_count).  Row 4 (c - 1) + j of its weight and bias is coordinate j of foreground
                   class c; training moves the rows of each example's class, detection decodes the rows of the predicted class
                   (layout, class sources and arithmetic: include/frcnn_hip_box.h).
-    Not combined with cfg.scoring.classes = "all", which decodes ONE box per candidate for all its class rows: that raises here.
+    Not combined with cfg.scoring.classes = "all", which decodes ONE box per candidate for all its class rows: that raises here --
+    unless cfg.scoring.boxes = "class" (Detector.scoring_boxes) asks for the box of its own class for every class row, which in
+    turn needs per_class = true and raises here with a shared head.
     Raises FrcnnError -- before the model or the device is touched -- for an unknown key or a value that is not a boolean."""
     t = cfg.get("box_head")
     E = _lib.FrcnnError
     out = dict(per_class=False)
-    if t is None:
-        return out
-    if not isinstance(t, dict):
-        raise E("cfg.box_head must be a table of {per_class}")
-    unknown = sorted(set(t) - set(out), key=str)
-    if unknown:
-        raise E("cfg.box_head: unknown key(s) %s" % ", ".join(map(str, unknown)))
-    v = t.get("per_class", False)
-    if not isinstance(v, (bool, np.bool_)):
-        raise E("cfg.box_head.per_class = %r is not a boolean" % (v,))
-    out["per_class"] = bool(v)
+    if t is not None:
+        if not isinstance(t, dict):
+            raise E("cfg.box_head must be a table of {per_class}")
+        unknown = sorted(set(t) - set(out), key=str)
+        if unknown:
+            raise E("cfg.box_head: unknown key(s) %s" % ", ".join(map(str, unknown)))
+        v = t.get("per_class", False)
+        if not isinstance(v, (bool, np.bool_)):
+            raise E("cfg.box_head.per_class = %r is not a boolean" % (v,))
+        out["per_class"] = bool(v)
     sc = cfg.get("scoring")
-    if out["per_class"] and isinstance(sc, dict) and sc.get("classes") == "all":
+    boxes = sc.get("boxes") if isinstance(sc, dict) else None      # (its value is validated by Detector.scoring_boxes)
+    if out["per_class"] and isinstance(sc, dict) and sc.get("classes") == "all" and boxes != "class":
         raise E("cfg.box_head.per_class = true cannot be combined with cfg.scoring.classes = \"all\": that pass decodes one box per "
-                "candidate for all its class rows, a per-class head has one box per (candidate, class)")
+                "candidate for all its class rows, a per-class head has one box per (candidate, class); cfg.scoring.boxes = \"class\" "
+                "gives every class row the box of its own class")
+    if boxes == "class" and not out["per_class"]:
+        raise E("cfg.scoring.boxes = \"class\" needs cfg.box_head.per_class = true: a shared box head has one box per candidate")
     return out
 
 

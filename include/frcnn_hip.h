@@ -981,4 +981,6 @@ int frcnn_broadcast_f32(frcnn_comm *, float *buf, long long n, int root, void *s
 #include "frcnn_hip_loss.h"
 /* Per-class box regression of the classification net (cfg.box_head): three entry points, likewise. */
 #include "frcnn_hip_box.h"
+/* The box of its own class for every row of the all-class class test (cfg.scoring.boxes = "class"): two entry points, likewise. */
+#include "frcnn_hip_classbox.h"
 #endif /* FRCNN_HIP_H */
