@@ -227,12 +227,39 @@ CLASSBOX_SIGS = {
                                        C.c_int),
 }
 
+
+class GemmJob(C.Structure):
+    """frcnn_gemm_job of include/frcnn_hip_heads.h"""
+    _fields_ = [("A", vp), ("sAm", C.c_longlong), ("sAk", C.c_longlong), ("B", vp), ("sBk", C.c_longlong), ("sBn", C.c_longlong),
+                ("C", vp), ("ldc", C.c_longlong), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("out_mode", C.c_int),
+                ("splits", C.c_int)]
+
+
+class HeadNet(C.Structure):
+    """frcnn_head_net of include/frcnn_hip_heads.h"""
+    _fields_ = ([(n, C.c_int) for n in ("Cin", "H", "W", "k", "n", "P", "force_splits")] +
+                [(n, vp) for n in ("pos", "in_", "gin", "w3", "bias3", "slope", "w1", "bias1", "gw3", "gbias3", "gslope", "gw1", "gbias1",
+                                   "out", "delta", "COL", "HX", "HY", "OUT", "D", "GH", "DX", "slab")] +
+                [("slab_floats", C.c_longlong)])
+
+
+# the test-facing entry points of include/frcnn_hip_heads.h (the anchor nets' sparse chain without a model)
+HEADS_SIGS = {
+    "frcnn_gemm_group": ([C.POINTER(GemmJob), C.c_int, vp], C.c_int),
+    "frcnn_heads_chain_forward": ([C.POINTER(HeadNet), C.c_int, C.POINTER(C.c_int), vp], C.c_int),
+    "frcnn_heads_chain_backward": ([C.POINTER(HeadNet), C.c_int, vp], C.c_int),
+    "frcnn_heads_plan_splits": ([C.c_int, C.c_int, C.c_int], C.c_int),
+    "frcnn_gather_positions": ([vp, C.c_int, C.c_longlong, vp, C.c_int, vp, vp, vp, vp], C.c_int),
+    "frcnn_im2col_positions": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp], C.c_int),
+    "frcnn_col2im_positions_add": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp], C.c_int),
+}
+
 _lib = None
 
 
 def exported_symbols():
     """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS; of
-    frcnn_hip_box.h: BOX_SIGS; of frcnn_hip_classbox.h: CLASSBOX_SIGS)"""
+    frcnn_hip_box.h: BOX_SIGS; of frcnn_hip_classbox.h: CLASSBOX_SIGS; of frcnn_hip_heads.h: HEADS_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -255,7 +282,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()) + list(HEADS_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

@@ -494,6 +494,81 @@ int frcnn_conv2d_backward_weight_pooled(const float* in, int C, int H, int W, co
   return rc;
 }
 
+// ---- test entry points (include/frcnn_hip_heads.h): the anchor nets' sparse chain, its grouped product and the per-net helpers
+int frcnn_gemm_group(const frcnn_gemm_job* jobs, int n, void* stream) {
+  FR_CHECK(jobs && n >= 1 && n <= GEMM_GROUP_MAX, "frcnn_gemm_group: %d jobs", n);
+  GemmJob q[GEMM_GROUP_MAX];
+  for (int i = 0; i < n; ++i) {
+    const frcnn_gemm_job& j = jobs[i];
+    FR_CHECK(j.K >= 1 && j.M >= 0 && j.N >= 0 && j.splits >= 1, "frcnn_gemm_group: job %d is %d x %d x %d in %d splits", i, j.M, j.N,
+             j.K, j.splits);
+    FR_CHECK(j.out_mode == OUT_STORE || j.out_mode == OUT_ADD, "frcnn_gemm_group: job %d: out_mode %d", i, j.out_mode);
+    const bool blocks = j.M > 0 && j.N > 0;
+    FR_CHECK(!blocks || (j.A && j.B && j.C), "frcnn_gemm_group: job %d: NULL operand", i);
+    FR_CHECK(!blocks || j.splits > 1 || j.ldc >= j.N, "frcnn_gemm_group: job %d: ldc %lld below N = %d", i, j.ldc, j.N);
+    // (a job without blocks takes no part in the launch: its split count is not held against its K)
+    q[i] = GemmJob{j.A, (long)j.sAm, (long)j.sAk, j.B, (long)j.sBk, (long)j.sBn, j.C, (long)j.ldc, j.M, j.N, j.K, j.out_mode,
+                   blocks ? j.splits : 1};
+  }
+  return gemm_f32_group(q, n, S(stream));
+}
+
+static int heads_table(const char* who, const frcnn_head_net* nets, int n, bool backward, HeadJobs& g, int* splits_host) {
+  FR_CHECK(nets && n >= 1 && n <= 4, "%s: %d nets", who, n);
+  g.n = 0;
+  for (int i = 0; i < n; ++i) {
+    const frcnn_head_net& t = nets[i];
+    if (splits_host) splits_host[i] = 0;
+    if (t.P <= 0) continue;
+    FR_CHECK(t.P <= 4096 && t.k >= 1 && t.H >= t.k && t.W >= t.k && t.Cin >= 1 && t.n >= 1, "%s: net %d: bad geometry", who, i);
+    FR_CHECK(t.pos && t.in && t.w3 && t.bias3 && t.slope && t.w1 && t.bias1 && t.out && t.COL && t.HX && t.HY && t.OUT && t.slab,
+             "%s: net %d: NULL argument", who, i);
+    FR_CHECK(!backward || (t.delta && t.D && t.GH && t.gw3 && t.gbias3 && t.gslope && t.gw1 && t.gbias1 && (!t.gin || t.DX)),
+             "%s: net %d: NULL argument of the backward pass", who, i);
+    HeadJob j;
+    j.Cin = t.Cin; j.H = t.H; j.W = t.W; j.k = t.k; j.Ho = t.H - t.k + 1; j.Wo = t.W - t.k + 1; j.n = t.n;
+    j.P = t.P; j.pos = t.pos;
+    j.in = t.in; j.gin = t.gin;
+    j.bias3 = t.bias3; j.slope = t.slope; j.bias1 = t.bias1;
+    j.gbias3 = t.gbias3; j.gslope = t.gslope; j.gbias1 = t.gbias1;
+    j.w3 = t.w3; j.w1 = t.w1; j.gw3 = t.gw3; j.gw1 = t.gw1;
+    j.out = t.out; j.delta = t.delta;
+    j.COL = t.COL; j.HX = t.HX; j.HY = t.HY; j.OUT = t.OUT; j.D = t.D; j.GH = t.GH; j.DX = t.DX;
+    j.hx_slab = t.slab; j.hx_splits = 0;
+    FR_TRY(heads_add_job(g, j, t.force_splits, t.slab_floats > 0 ? (size_t)t.slab_floats : 0));
+    if (splits_host) splits_host[i] = g.j[g.n - 1].hx_splits;
+  }
+  return FRCNN_OK;
+}
+int frcnn_heads_chain_forward(const frcnn_head_net* nets, int n, int* splits_host, void* stream) {
+  HeadJobs g;
+  FR_TRY(heads_table("frcnn_heads_chain_forward", nets, n, false, g, splits_host));
+  return heads_chain_forward(g, S(stream));
+}
+int frcnn_heads_chain_backward(const frcnn_head_net* nets, int n, void* stream) {
+  HeadJobs g;
+  FR_TRY(heads_table("frcnn_heads_chain_backward", nets, n, true, g, nullptr));
+  FR_TRY(heads_chain_backward_input(g, S(stream)));
+  return heads_chain_backward_params(g, S(stream));
+}
+int frcnn_heads_plan_splits(int n, int ckk, int P) { return heads_plan_splits(n, ckk, P); }
+int frcnn_gather_positions(const float* src, int C, long long hw, const int* pos, int P, float* dst, const float* slope,
+                           float* dst_act, void* stream) {
+  if (P <= 0) return FRCNN_OK;
+  FR_CHECK(src && pos && dst && C >= 1 && hw >= 1 && (!slope == !dst_act), "frcnn_gather_positions: bad arguments");
+  return gather_positions(src, C, hw, pos, P, dst, slope, dst_act, S(stream));
+}
+int frcnn_im2col_positions(const float* X, int C, int H, int W, int k, int Wo, const int* pos, int P, float* col, void* stream) {
+  if (P <= 0) return FRCNN_OK;
+  FR_CHECK(X && pos && col && C >= 1 && k >= 1 && H >= k && W >= k && Wo == W - k + 1, "frcnn_im2col_positions: bad arguments");
+  return im2col_positions(X, C, H, W, k, Wo, pos, P, col, S(stream));
+}
+int frcnn_col2im_positions_add(const float* col, int C, int H, int W, int k, int Wo, const int* pos, int P, float* gX, void* stream) {
+  if (P <= 0) return FRCNN_OK;
+  FR_CHECK(col && pos && gX && C >= 1 && k >= 1 && H >= k && W >= k && Wo == W - k + 1, "frcnn_col2im_positions_add: bad arguments");
+  return col2im_positions_add(col, C, H, W, k, Wo, pos, P, gX, S(stream));
+}
+
 int frcnn_roi_pool_forward(const float* fmap, int C, int H, int W, const int* wins, int R, int kh, int kw,
                            float* out, int* idx, void* stream) {
   return roi_pool_forward(fmap, C, H, W, wins, R, kh, kw, out, idx, S(stream));

@@ -14,7 +14,11 @@
 // anchor net on those streams: 58 launches on five streams, which the runtime multiplexes onto four hardware queues together
 // with the caller's stream -- the chains serialised in pairs and the caller's stream waited for them (tools/r6_hwq.sh).  Here
 // every step of the chain is ONE launch for all anchor nets (blockIdx.y = the anchor net; the products: gemm_f32_group), the whole
-// chain runs on one stream: 13 launches.
+// chain runs on one stream: 5 launches forward, 7 backward (plus the losses between them).
+// The chain itself lives here, as functions of a job table and a stream (heads_chain_forward, heads_chain_backward_input,
+// heads_chain_backward_params), with the table's builder and its K-split rule (heads_add_job, heads_plan_splits): the model
+// (net.cpp) fills the table and records its event between the two backward parts, and the entry points of
+// include/frcnn_hip_heads.h run the same functions on buffers of the caller (tests/test_gpu_heads_chain.py).
 #include "kernels.h"
 
 namespace frcnn {
@@ -145,36 +149,130 @@ static int hd_grid(const HeadJobs& g, int mode) {   // blocks along x: enough fo
   return (int)std::min<long>(cdivl(most, 256), 4096);
 }
 
-int heads_im2col(const HeadJobs& g, hipStream_t s) {
+static int heads_im2col(const HeadJobs& g, hipStream_t s) {
   FR_LAUNCH(KC_ELEMWISE, 0, 0, s, hd_im2col_kernel, dim3(hd_grid(g, 0), g.n), dim3(256), 0, g);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
-int heads_bias_act(const HeadJobs& g, hipStream_t s) {
+static int heads_bias_act(const HeadJobs& g, hipStream_t s) {
   FR_LAUNCH(KC_ELEMWISE, 0, 0, s, hd_bias_act_kernel, dim3(hd_grid(g, 1), g.n), dim3(256), 0, g);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
-int heads_scatter(const HeadJobs& g, hipStream_t s) {
+static int heads_scatter(const HeadJobs& g, hipStream_t s) {
   FR_LAUNCH(KC_ELEMWISE, 0, 0, s, hd_scatter_kernel, dim3(hd_grid(g, 2), g.n), dim3(256), 0, g);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
-int heads_gather_delta(const HeadJobs& g, hipStream_t s) {
+static int heads_gather_delta(const HeadJobs& g, hipStream_t s) {
   FR_LAUNCH(KC_ELEMWISE, 0, 0, s, hd_gather_delta_kernel, dim3(FRCNN_HEAD_OUT, g.n), dim3(256), 0, g);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
-int heads_act_backward(const HeadJobs& g, hipStream_t s) {
+static int heads_act_backward(const HeadJobs& g, hipStream_t s) {
   int nmax = 1;
   for (int i = 0; i < g.n; ++i) nmax = std::max(nmax, g.j[i].n);
   FR_LAUNCH(KC_ELEMWISE, 0, 0, s, hd_act_backward_kernel, dim3(nmax, g.n), dim3(256), 0, g);
   FR_LAUNCH_CHECK();
   return FRCNN_OK;
 }
-int heads_col2im(const HeadJobs& g, hipStream_t s) {
+static int heads_col2im(const HeadJobs& g, hipStream_t s) {
   FR_LAUNCH(KC_ELEMWISE, 0, 0, s, hd_col2im_kernel, dim3(hd_grid(g, 0), g.n), dim3(256), 0, g);
   FR_LAUNCH_CHECK();
+  return FRCNN_OK;
+}
+
+// K splits of HX = W COL^T: K = ckk is long, the tile grid (n / 64) x (P / 64) small -- about a thousand blocks in all.
+// The slab holds 4096 positions' partial sums: 256 / tiles keeps splits * P under that only for n >= 256 (four tile rows), so
+// narrower nets are capped at 4096 / P as well; rounding `per` up afterwards can only lower splits.
+int heads_plan_splits(int n, int ckk, int P) {
+  if (n < 1 || ckk < 1 || P < 1) return 0;
+  const long tiles = (long)cdiv(n, 64) * cdiv(P, 64);
+  const int splits = (int)std::max<long>(1, std::min<long>(std::min<long>(std::min<long>((long)ckk / 256, 64), 256 / tiles), 4096 / P));
+  const int per = cdiv(cdiv(ckk, splits), 32) * 32;
+  return cdiv(ckk, per);
+}
+
+int heads_add_job(HeadJobs& g, const HeadJob& job, int force_splits, size_t slab_floats) {
+  if (job.P <= 0) return FRCNN_OK;
+  FR_CHECK(g.n < 4, "heads_add_job: more than 4 anchor nets");
+  const int ckk = job.Cin * job.k * job.k;
+  int splits = heads_plan_splits(job.n, ckk, job.P);
+  if (force_splits > 0) {
+    const int per = cdiv(cdiv(ckk, force_splits), 32) * 32;
+    FR_CHECK(cdiv(ckk, per) == force_splits, "heads_add_job: %d forced splits of K = %d leave one empty", force_splits, ckk);
+    splits = force_splits;
+  }
+  FR_CHECK(splits >= 1 && (size_t)splits * job.n * job.P <= slab_floats, "heads_jobs: %d K splits of %d positions", splits, job.P);
+  HeadJob& j = g.j[g.n++];
+  j = job;
+  j.hx_splits = splits;
+  return FRCNN_OK;
+}
+
+// forward at the sampled positions: the output maps are written THERE only (objective.lua:91-140 reads nothing else)
+int heads_chain_forward(const HeadJobs& g, hipStream_t s) {
+  if (g.n == 0) return FRCNN_OK;
+  FR_TRY(heads_im2col(g, s));
+  GemmJob q[4];
+  for (int i = 0; i < g.n; ++i) {   // HX[n][P] = W[n][ckk] COL[P][ckk]^T, K-split partial sums
+    const HeadJob& j = g.j[i];
+    const int ckk = j.Cin * j.k * j.k;
+    // (a single split still goes through the slab: heads_bias_act folds `hx_splits` of them)
+    q[i] = GemmJob{j.w3, (long)ckk, 1, j.COL, 1, (long)ckk, const_cast<float*>(j.hx_slab), (long)j.P, j.n, j.P, ckk, OUT_STORE, j.hx_splits};
+  }
+  FR_TRY(gemm_f32_group(q, g.n, s));
+  FR_TRY(heads_bias_act(g, s));
+  for (int i = 0; i < g.n; ++i) {   // OUT[18][P] = W1[18][n] HY[n][P]
+    const HeadJob& j = g.j[i];
+    q[i] = GemmJob{j.w1, (long)j.n, 1, j.HY, (long)j.P, 1, j.OUT, (long)j.P, FRCNN_HEAD_OUT, j.P, j.n, OUT_STORE, 1};
+  }
+  FR_TRY(gemm_f32_group(q, g.n, s));
+  FR_TRY(heads_scatter(g, s));
+  return FRCNN_OK;
+}
+
+// backward at the sampled positions, the part the input maps' gradients wait for (HX, HY and COL are the forward pass's)
+int heads_chain_backward_input(const HeadJobs& g, hipStream_t s) {
+  if (g.n == 0) return FRCNN_OK;
+  FR_TRY(heads_gather_delta(g, s));                    // D, gb1
+  GemmJob q[4];
+  for (int i = 0; i < g.n; ++i) {                      // GH[n][P] = W1^T[n][18] D[18][P]
+    const HeadJob& j = g.j[i];
+    q[i] = GemmJob{j.w1, 1, (long)j.n, j.D, (long)j.P, 1, j.GH, (long)j.P, j.n, j.P, FRCNN_HEAD_OUT, OUT_STORE, 1};
+  }
+  FR_TRY(gemm_f32_group(q, g.n, s));
+  FR_TRY(heads_act_backward(g, s));                    // PReLU backward, gb3, gslope
+  HeadJobs gi;                                         // (staged training: the nets whose input block is trained)
+  gi.n = 0;
+  for (int i = 0; i < g.n; ++i)
+    if (g.j[i].gin) gi.j[gi.n++] = g.j[i];
+  if (gi.n == 0) return FRCNN_OK;
+  for (int i = 0; i < gi.n; ++i) {                     // DX[P][ckk] = GH^T[P][n] W[n][ckk]
+    const HeadJob& j = gi.j[i];
+    const int ckk = j.Cin * j.k * j.k;
+    q[i] = GemmJob{j.GH, 1, (long)j.P, j.w3, (long)ckk, 1, j.DX, (long)ckk, j.P, ckk, j.n, OUT_STORE, 1};
+  }
+  FR_TRY(gemm_f32_group(q, gi.n, s));
+  FR_TRY(heads_col2im(gi, s));                         // the input maps' gradients
+  return FRCNN_OK;
+}
+
+// ... and the parameter gradients that follow
+int heads_chain_backward_params(const HeadJobs& g, hipStream_t s) {
+  if (g.n == 0) return FRCNN_OK;
+  GemmJob q[4];
+  for (int i = 0; i < g.n; ++i) {                      // gW1[18][n] += D[18][P] HY[n][P]^T
+    const HeadJob& j = g.j[i];
+    q[i] = GemmJob{j.D, (long)j.P, 1, j.HY, 1, (long)j.P, j.gw1, (long)j.n, FRCNN_HEAD_OUT, j.n, j.P, OUT_ADD, 1};
+  }
+  FR_TRY(gemm_f32_group(q, g.n, s));
+  for (int i = 0; i < g.n; ++i) {                      // gW[n][ckk] += GH[n][P] COL[P][ckk]
+    const HeadJob& j = g.j[i];
+    const int ckk = j.Cin * j.k * j.k;
+    q[i] = GemmJob{j.GH, (long)j.P, 1, j.COL, (long)ckk, 1, j.gw3, (long)ckk, j.n, ckk, j.P, OUT_ADD, 1};
+  }
+  FR_TRY(gemm_f32_group(q, g.n, s));
   return FRCNN_OK;
 }
 

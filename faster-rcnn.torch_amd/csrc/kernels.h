@@ -183,17 +183,26 @@ struct HeadJob {
   const float* in; float* gin;         // the input map and its gradient
   const float *bias3, *slope, *bias1;  // parameters: k x k bias, PReLU slope, 1 x 1 bias
   float *gbias3, *gslope, *gbias1;     // ... their gradients
+  const float *w3, *w1;                // the two weight matrices: [n][ckk], [18][n]
+  float *gw3, *gw1;                    // ... their gradients
   float* out; const float* delta;      // the 1 x 1 convolution's output map [18][Ho Wo] and its gradient map
   float *COL, *HX, *HY, *OUT, *D, *GH, *DX;   // scratch: [P][ckk], [n][P], [n][P], [18][P], [18][P], [n][P], [P][ckk]
   const float* hx_slab; int hx_splits; // partial sums of HX over K splits, [split][n][P]
 };
 struct HeadJobs { HeadJob j[4]; int n; };
-int heads_im2col(const HeadJobs& g, hipStream_t s);
-int heads_bias_act(const HeadJobs& g, hipStream_t s);
-int heads_scatter(const HeadJobs& g, hipStream_t s);
-int heads_gather_delta(const HeadJobs& g, hipStream_t s);
-int heads_act_backward(const HeadJobs& g, hipStream_t s);
-int heads_col2im(const HeadJobs& g, hipStream_t s);
+// K splits of HX[n][P] = W[n][ckk] COL[P][ckk]^T (the rule: heads.hip)
+int heads_plan_splits(int n, int ckk, int P);
+// The job table's one builder.  `j`: everything but hx_splits; a net with P <= 0 is skipped (nothing of it is launched).
+// force_splits > 0: that split count instead of the planner's (refused when it leaves a split empty).  slab_floats: the
+// capacity of j.hx_slab, which splits * n * P may not exceed.  gin == nullptr: no input-map gradient for this net.
+int heads_add_job(HeadJobs& g, const HeadJob& j, int force_splits, size_t slab_floats);
+// The chain, every step ONE launch for all jobs, on one stream (nothing is launched for an empty table):
+//   forward          im2col | HX slabs | bias + PReLU | OUT | scatter                                            5 launches
+//   backward, input  gather_delta (+ gbias1) | GH | PReLU backward (+ gbias3, gslope) | jobs with a gin: DX | col2im   3 or 5
+//   backward, params gw1 += D HY^T | gw3 += GH COL                                                               2
+int heads_chain_forward(const HeadJobs& g, hipStream_t s);
+int heads_chain_backward_input(const HeadJobs& g, hipStream_t s);
+int heads_chain_backward_params(const HeadJobs& g, hipStream_t s);
 
 // ---------------------------------------------------------------- gemm (gemm.hip)
 // C[M][N] (=|+=) A[M][K] * B[K][N] with explicit element strides.  defer: see GemmFold below.

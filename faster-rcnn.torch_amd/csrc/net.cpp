@@ -1323,7 +1323,8 @@ static bool heads_all_sparse(const frcnn_model* m) {
   return !m->heads.empty() && m->heads.size() <= 4;
 }
 
-// The job table of the sparse path: the anchor nets that have sampled positions in this pass
+// The job table of the sparse path: the anchor nets that have sampled positions in this pass (heads_add_job skips the others
+// and plans the K splits).  Staged training: a net whose input block is frozen has no gin.
 static int heads_jobs(frcnn_model* m, const float* w, float* grad, HeadJobs& g) {
   g.n = 0;
   for (auto& h : m->heads) {
@@ -1335,97 +1336,30 @@ static int heads_jobs(frcnn_model* m, const float* w, float* grad, HeadJobs& g) 
     FR_TRY(h.spD.ensure((size_t)HEAD_OUT * cap * 4)); FR_TRY(h.spOut.ensure((size_t)HEAD_OUT * cap * 4));
     FR_TRY(h.spHX.ensure(n * cap * 4)); FR_TRY(h.spHY.ensure(n * cap * 4)); FR_TRY(h.spGH.ensure(n * cap * 4));
     FR_TRY(h.spCol.ensure(ckk * cap * 4)); FR_TRY(h.spDX.ensure(ckk * cap * 4));
-    HeadJob& j = g.j[g.n++];
+    FR_TRY(h.spSlab.ensure(n * 4096 * 4));   // (splits * P <= 4096 whatever P and n: allocated once)
+    HeadJob j;
     j.Cin = a.Cin; j.H = a.H; j.W = a.W; j.k = a.k; j.Ho = a.Ho; j.Wo = a.Wo; j.n = a.Cout;
     j.P = P; j.pos = h.sp_pos;
-    j.in = in.pooled.f(); j.gin = in.gpooled.f();
+    j.in = in.pooled.f(); j.gin = head_needs_gin(m, h) ? in.gpooled.f() : nullptr;
     j.bias3 = w + a.b_off; j.slope = w + a.a_off; j.bias1 = w + c.b_off;
     j.gbias3 = grad ? grad + a.b_off : nullptr; j.gslope = grad ? grad + a.a_off : nullptr; j.gbias1 = grad ? grad + c.b_off : nullptr;
+    j.w3 = w + a.w_off; j.w1 = w + c.w_off;
+    j.gw3 = grad ? grad + a.w_off : nullptr; j.gw1 = grad ? grad + c.w_off : nullptr;
     j.out = c.x.f(); j.delta = h.delta.f();
     j.COL = h.spCol.f(); j.HX = h.spHX.f(); j.HY = h.spHY.f(); j.OUT = h.spOut.f(); j.D = h.spD.f(); j.GH = h.spGH.f(); j.DX = h.spDX.f();
-    // K splits of HX = W COL^T: K = ckk is long, the tile grid (n / 64) x (P / 64) small -- about a thousand blocks in all.
-    // The slab holds 4096 positions' partial sums: 256 / tiles keeps splits * P under that only for n >= 256 (four tile rows), so
-    // narrower nets are capped at 4096 / P as well; rounding `per` up afterwards can only lower splits.
-    const long tiles = (long)cdiv((int)n, 64) * cdiv(P, 64);
-    int splits = (int)std::max<long>(1, std::min<long>(std::min<long>(std::min<long>((long)ckk / 256, 64), 256 / tiles), 4096 / P));
-    const int per = cdiv(cdiv((int)ckk, splits), 32) * 32;
-    splits = cdiv((int)ckk, per);
-    FR_TRY(h.spSlab.ensure(n * 4096 * 4));   // (splits * P <= 4096 whatever P and n: allocated once)
-    FR_CHECK((size_t)splits * P <= 4096, "heads_jobs: %d K splits of %d positions", splits, P);
-    j.hx_slab = h.spSlab.f(); j.hx_splits = splits;
+    j.hx_slab = h.spSlab.f(); j.hx_splits = 0;
+    FR_TRY(heads_add_job(g, j, 0, n * 4096));
   }
   return FRCNN_OK;
 }
 
-// forward at the sampled positions: the output maps are written THERE only (objective.lua:91-140 reads nothing else)
-static int heads_sparse_forward(frcnn_model* m, const float* w, const HeadJobs& g, hipStream_t s) {
+// backward at the sampled positions (heads.hip): the model's part is the event between the chain's two halves and the hints
+static int heads_sparse_backward(frcnn_model* m, const HeadJobs& g, hipStream_t s) {
   if (g.n == 0) return FRCNN_OK;
-  FR_TRY(heads_im2col(g, s));
-  GemmJob q[4];
-  for (int i = 0; i < g.n; ++i) {   // HX[n][P] = W[n][ckk] COL[P][ckk]^T, K-split partial sums
-    const HeadJob& j = g.j[i];
-    const Head* hd = nullptr;
-    for (auto& h : m->heads) if (h.spCol.f() == j.COL) hd = &h;
-    const int ckk = j.Cin * j.k * j.k;
-    q[i] = GemmJob{w + hd->c3.w_off, (long)ckk, 1, j.COL, 1, (long)ckk, const_cast<float*>(j.hx_slab), (long)j.P, j.n, j.P, ckk, OUT_STORE, j.hx_splits};
-    if (j.hx_splits == 1) q[i].splits = 1;
-  }
-  // (a single split still goes through the slab: heads_bias_act folds `hx_splits` of them)
-  for (int i = 0; i < g.n; ++i) if (q[i].splits == 1) { q[i].out_mode = OUT_STORE; }
-  FR_TRY(gemm_f32_group(q, g.n, s));
-  FR_TRY(heads_bias_act(g, s));
-  for (int i = 0; i < g.n; ++i) {   // OUT[18][P] = W1[18][n] HY[n][P]
-    const HeadJob& j = g.j[i];
-    const Head* hd = nullptr;
-    for (auto& h : m->heads) if (h.spCol.f() == j.COL) hd = &h;
-    q[i] = GemmJob{w + hd->c1.w_off, (long)j.n, 1, j.HY, (long)j.P, 1, j.OUT, (long)j.P, HEAD_OUT, j.P, j.n, OUT_STORE, 1};
-  }
-  FR_TRY(gemm_f32_group(q, g.n, s));
-  FR_TRY(heads_scatter(g, s));
-  return FRCNN_OK;
-}
-
-// backward at the sampled positions (the arithmetic of backward_head's sparse branch; HX, HY and COL are the forward pass's)
-static int heads_sparse_backward(frcnn_model* m, const float* w, float* grad, const HeadJobs& g, hipStream_t s) {
-  if (g.n == 0) return FRCNN_OK;
-  auto head_of = [&](const HeadJob& j) -> const Head* {
-    for (auto& h : m->heads) if (h.spCol.f() == j.COL) return &h;
-    return nullptr;
-  };
-  FR_TRY(heads_gather_delta(g, s));                    // D, gb1
-  GemmJob q[4];
-  for (int i = 0; i < g.n; ++i) {                      // GH[n][P] = W1^T[n][18] D[18][P]
-    const HeadJob& j = g.j[i]; const Head* hd = head_of(j);
-    q[i] = GemmJob{w + hd->c1.w_off, 1, (long)j.n, j.D, (long)j.P, 1, j.GH, (long)j.P, j.n, j.P, HEAD_OUT, OUT_STORE, 1};
-  }
-  FR_TRY(gemm_f32_group(q, g.n, s));
-  FR_TRY(heads_act_backward(g, s));                    // PReLU backward, gb3, gslope
-  HeadJobs gi;                                         // (staged training: the nets whose input block is trained)
-  gi.n = 0;
-  for (int i = 0; i < g.n; ++i)
-    if (head_needs_gin(m, *head_of(g.j[i]))) gi.j[gi.n++] = g.j[i];
-  for (int i = 0; i < gi.n; ++i) {                     // DX[P][ckk] = GH^T[P][n] W[n][ckk]
-    const HeadJob& j = gi.j[i]; const Head* hd = head_of(j);
-    const int ckk = j.Cin * j.k * j.k;
-    q[i] = GemmJob{j.GH, 1, (long)j.P, w + hd->c3.w_off, (long)ckk, 1, j.DX, (long)ckk, j.P, ckk, j.n, OUT_STORE, 1};
-  }
-  if (gi.n) {
-    FR_TRY(gemm_f32_group(q, gi.n, s));
-    FR_TRY(heads_col2im(gi, s));                       // the pooled maps' gradients
-  }
+  FR_TRY(heads_chain_backward_input(g, s));
   FR_TRY(m->heads_gin_ev.record(s));                   // what the backbone's backward pass waits for; the parameter gradients follow
   m->heads_gin = true;
-  for (int i = 0; i < g.n; ++i) {                      // gW1[18][n] += D[18][P] HY[n][P]^T
-    const HeadJob& j = g.j[i]; const Head* hd = head_of(j);
-    q[i] = GemmJob{j.D, (long)j.P, 1, j.HY, 1, (long)j.P, grad + hd->c1.w_off, (long)j.n, HEAD_OUT, j.n, j.P, OUT_ADD, 1};
-  }
-  FR_TRY(gemm_f32_group(q, g.n, s));
-  for (int i = 0; i < g.n; ++i) {                      // gW[n][ckk] += GH[n][P] COL[P][ckk]
-    const HeadJob& j = g.j[i]; const Head* hd = head_of(j);
-    const int ckk = j.Cin * j.k * j.k;
-    q[i] = GemmJob{j.GH, (long)j.P, 1, j.COL, (long)ckk, 1, grad + hd->c3.w_off, (long)ckk, j.n, ckk, j.P, OUT_ADD, 1};
-  }
-  FR_TRY(gemm_f32_group(q, g.n, s));
+  FR_TRY(heads_chain_backward_params(g, s));
   for (auto& h : m->heads) { h.sp_count = -1; h.sp_pos = nullptr; }   // one-shot hints
   return FRCNN_OK;
 }
@@ -1478,7 +1412,7 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
     HeadJobs g;
     FR_TRY(heads_jobs(m, w, grad, g));
     FR_TRY(fork_side(m, s, m->blocks.size() + 1));
-    FR_TRY(heads_sparse_forward(m, w, g, m->side));
+    FR_TRY(heads_chain_forward(g, m->side));
     m->heads_deferred = false; m->heads_sparse_fwd = true;
     FR_TRY(rpn_loss(L, deltas, ex_idx, ex_anchor, ex_roi, ex_class, npos, nneg, bgclass, ex_loss, crtarget, cctarget, m->side));
     FR_TRY(loss_accumulate(ex_loss, E, acc, m->side));
@@ -1486,7 +1420,7 @@ int frcnn_pnet_anchor_loss_begin(frcnn_model* m, const float* w, float* grad, co
     m->loss_pending = true;
     if (!m->train_heads) return heads_frozen_begun(m);   // staged training: the chain stops after the losses
     if (backbone_trained(m)) FR_TRY(fill_zero((char*)m->zero_arena.p + m->delta_bytes, m->gpool_bytes, m->side));
-    FR_TRY(heads_sparse_backward(m, w, grad, g, m->side));
+    FR_TRY(heads_sparse_backward(m, g, m->side));
     m->heads_begun = true;
     return FRCNN_OK;
   }

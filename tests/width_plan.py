@@ -100,7 +100,7 @@ def compact_plan(filters, b, nk):
 
 
 def head_splits(n, Cin, k, P, capped=True):
-    """net.cpp heads_jobs: the K splits of the sparse anchor net's product HX = W COL^T at P positions.  capped=False: the
+    """heads.hip heads_plan_splits (net.cpp heads_jobs through heads_add_job): the K splits of the sparse anchor net's product HX = W COL^T at P positions.  capped=False: the
     rule before the cap at 4096 / P (the K-split slab holds n x 4096 partial sums)."""
     ckk = Cin * k * k
     tiles = cdiv(n, 64) * cdiv(P, 64)
