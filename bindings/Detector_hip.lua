@@ -617,12 +617,252 @@ function Detector:detect_batch(inputs, opts)
   return results
 end
 
+-- Detector:match_batch(inputs, ground_truth, opts) -- detect_batch(inputs) matched to the frames' ground truth ON THE DEVICE, for
+-- mean average precision (not in the reference; include/frcnn_hip_eval.h).  ground_truth[f]: the frame's boxes, a list of
+-- { class_index = c, rect = Rect } (what nextValidation hands out) or of { c, Rect }, at most 1024.  opts: detect_batch's table,
+-- and iou_thresholds (default { 0.5 }, at most 16) and with_iou.  -> per frame { cls, confidence, tp, gt [, iou] }: arrays whose
+-- entry k describes detect_batch(inputs)[f][k]; bit t of tp[k] (bit.band(tp[k], bit.lshift(1, t)) ~= 0) is a true positive at
+-- threshold t + 1 of the list, gt[k] the 1-based box (0: none).  The pipeline is detect_batch's, unchanged, up to and including
+-- the gather; behind it max_detections is applied by frcnn_eval_conf_rows + frcnn_topk_select, ONE frcnn_eval_match_batch matches
+-- the chunk, and read-back 2 brings 16 bytes a row in place of the 128-byte records.  Under cfg.tta: one result per original
+-- frame.  1:1 with Detector.match_batch of the Python host mirror.
+Detector.MATCH_MAX_THRESHOLDS, Detector.MATCH_MAX_BOXES = 16, 1024
+function Detector:match_batch(inputs, ground_truth, opts)
+  opts = opts or {}
+  local thr = opts.iou_thresholds or { 0.5 }
+  if #thr < 1 or #thr > Detector.MATCH_MAX_THRESHOLDS then error('Detector:match_batch: 1 ... 16 IoU thresholds') end
+  for _, t in ipairs(thr) do if type(t) ~= 'number' or t ~= t then error('Detector:match_batch: a threshold is not a number') end end
+  if #ground_truth ~= #inputs then error('Detector:match_batch: ground truth for ' .. #ground_truth .. ' of ' .. #inputs .. ' frames') end
+  local gts = {}
+  for f, boxes in ipairs(ground_truth) do
+    if #boxes > Detector.MATCH_MAX_BOXES then error('Detector:match_batch: more than 1024 ground-truth boxes in a frame') end
+    local g = { cls = {}, rect = {} }
+    for i, x in ipairs(boxes) do
+      local r = x.rect or x[2]
+      g.cls[i], g.rect[i] = x.class_index or x[1], { r.minX, r.minY, r.maxX, r.maxY }
+    end
+    gts[f] = g
+  end
+  if opts.scoring ~= nil then self:set_scoring(opts.scoring) end
+  if opts.tta ~= nil then self:set_tta(opts.tta) end
+  local nframes, sizes = #inputs, {}
+  for i = 1, nframes do
+    sizes[i] = inputs[i]:size()
+    if inputs[i]:dim() ~= 3 or sizes[i][1] ~= 3 then error('Detector:match_batch: expected 3xHxW frames') end
+    if not opts.mixed_sizes and (sizes[i][2] ~= sizes[1][2] or sizes[i][3] ~= sizes[1][3]) then
+      error('Detector:match_batch: frames of different sizes in one call')
+    end
+  end
+  local step = Detector.BATCH
+  local lists, V = self:view_lists(sizes)
+  if lists ~= nil then step = math.max(1, math.floor(step / V)) end
+  local results = {}
+  local lo = 1
+  while lo <= nframes do
+    local chunk, gt = {}, {}
+    for i = lo, math.min(lo + step - 1, nframes) do chunk[#chunk + 1], gt[#gt + 1] = inputs[i], gts[i] end
+    local m = { gt = gt, thr = thr, with_iou = opts.with_iou and true or false }
+    for _, r in ipairs(self:detect_chunk(chunk, opts.shared_cnet, 'b_', m)) do results[#results + 1] = r end
+    lo = lo + step
+  end
+  return results
+end
+
+-- The chunk's winner tables `out` (just queued) against match.gt: the ground truth's upload, under max_detections
+-- frcnn_eval_conf_rows + frcnn_topk_select (the rank of the host's sort: fp32 values, ties to the earlier pick), ONE
+-- frcnn_eval_match_batch, then read-back 2 of 2 -- the match tables and, asked for, the overlaps, in ONE copy and wait
+function Detector:match_tables(match, out, B, rows, prefix)
+  local scratch, CE = self.scratch, hip.CE
+  local row0 = ffi.new('long long[?]', B + 1)
+  local G = 0
+  for b = 1, B do
+    row0[b - 1] = G
+    G = G + #match.gt[b].cls
+  end
+  row0[B] = G
+  local hrect, hcls = ffi.new('double[?]', 4 * math.max(G, 1)), ffi.new('int[?]', math.max(G, 1))
+  local g = 0
+  for b = 1, B do
+    for i, c in ipairs(match.gt[b].cls) do
+      hcls[g] = c
+      for t = 1, 4 do hrect[4 * g + t - 1] = match.gt[b].rect[i][t] end
+      g = g + 1
+    end
+  end
+  local drect = ffi.cast('double*', scratch(prefix .. 'gt_rect', 32 * math.max(G, 1)).ptr)
+  local dcls = ffi.cast('int*', scratch(prefix .. 'gt_class', 4 * math.max(G, 1)).ptr)
+  if G > 0 then
+    check(C.frcnn_memcpy_h2d(drect, hrect, 32 * G, nil))
+    check(C.frcnn_memcpy_h2d(dcls, hcls, 4 * G, nil))
+  end
+  local sel, kcap, kd = nil, 0, nil
+  if self.max_detections ~= nil and rows > 0 then
+    kcap = math.min(rows, self.max_detections)
+    local conf = ffi.cast('float*', scratch(prefix .. 'eval_conf', 4 * B * rows).ptr)
+    local wcnt = ffi.cast('int*', scratch(prefix .. 'eval_count', 4 * B).ptr)
+    sel = ffi.cast('int*', scratch(prefix .. 'eval_sel', 4 * B * kcap).ptr)
+    kd = ffi.cast('int*', scratch(prefix .. 'eval_k', 4 * B).ptr)
+    local wsb = tonumber(C.frcnn_topk_select_workspace_bytes(B, rows))
+    local ws = scratch(prefix .. 'eval_sel_ws', wsb)
+    check(CE.frcnn_eval_conf_rows(out, B, rows, conf, wcnt, nil))
+    check(C.frcnn_topk_select(conf, B, rows, rows, wcnt, self.max_detections, sel, kcap, kd, ws.ptr, wsb, nil))
+  end
+  local T = #match.thr
+  local thr = ffi.new('double[?]', T)
+  for t = 1, T do thr[t - 1] = match.thr[t] end
+  local tbytes = 16 * B * (rows + 2)
+  local nbytes = tbytes + (match.with_iou and 8 * B * rows or 0)
+  local dev = ffi.cast('char*', scratch(prefix .. 'eval_match', nbytes).ptr)
+  local diou = nil
+  if match.with_iou then diou = ffi.cast('double*', dev + tbytes) end
+  check(CE.frcnn_eval_match_batch(out, B, rows, sel, kcap, kd, drect, dcls, row0, thr, T, ffi.cast('int*', dev), diou, nil))
+  local h = ffi.new('char[?]', nbytes)
+  check(C.frcnn_memcpy_d2h(h, dev, nbytes, nil))                          -- ---- read-back 2 of 2: 16 bytes a row
+  check(C.frcnn_stream_sync(nil))
+  local tabs, ious = ffi.cast('int*', h), ffi.cast('double*', h + tbytes)
+  local results = {}
+  for b = 0, B - 1 do
+    local tab = tabs + 4 * b * (rows + 2)
+    local n = tab[4]
+    -- classes in ascending order, the table's order within a class: the order of detect_batch's list
+    local order = {}
+    for q = 1, n do order[q] = q end
+    table.sort(order, function(i, j)
+      local ci, cj = tab[4 * (i + 1)], tab[4 * (j + 1)]
+      if ci ~= cj then return ci < cj end
+      return i < j
+    end)
+    local r = { cls = {}, confidence = {}, tp = {}, gt = {}, iou = match.with_iou and {} or nil }
+    for k, q in ipairs(order) do
+      local v = tab + 4 * (q + 1)
+      r.cls[k], r.tp[k], r.gt[k] = v[0], v[2], v[3]
+      r.confidence[k] = tonumber(ffi.cast('float*', v + 1)[0])
+      if match.with_iou then r.iou[k] = ious[b * rows + q - 1] end
+    end
+    results[b + 1] = r
+  end
+  return results
+end
+
+-- Detector.average_precision_from_matches(matches, ground_truth, thresholds, use_07_metric) -- AP per class and mAP from what
+-- match_batch returns (the matching is done: per class the stable sort by decreasing confidence across the frames, the
+-- cumulative sums, the area under the monotone precision envelope or the 11-point average).  thresholds: the list match_batch
+-- was called with -> { mAP, by_iou = { [t] = { mAP, ap, npos, tp, fp } } }.  1:1 with evaluation.average_precision_from_matches.
+function Detector.average_precision_from_matches(matches, ground_truth, thresholds, use_07_metric)
+  local npos, classes = {}, {}
+  for _, boxes in ipairs(ground_truth) do
+    for _, x in ipairs(boxes) do
+      local c = x.class_index or x[1]
+      if npos[c] == nil then
+        npos[c] = 0
+        classes[#classes + 1] = c
+      end
+      npos[c] = npos[c] + 1
+    end
+  end
+  table.sort(classes)
+  local by_iou, sum = {}, 0
+  for ti, t in ipairs(thresholds) do
+    local res = { ap = {}, npos = npos, tp = 0, fp = 0 }
+    local total = 0
+    for _, c in ipairs(classes) do
+      local dets = {}
+      for f, m in ipairs(matches) do
+        for k = 1, #m.cls do
+          if m.cls[k] == c then dets[#dets + 1] = { m.confidence[k], #dets + 1, bit.band(m.tp[k], bit.lshift(1, ti - 1)) ~= 0 } end
+        end
+      end
+      table.sort(dets, function(a, b)
+        if a[1] ~= b[1] then return a[1] > b[1] end
+        return a[2] < b[2]
+      end)
+      local rec, prec, ctp = {}, {}, 0
+      for k, d in ipairs(dets) do
+        if d[3] then ctp = ctp + 1 end
+        rec[k], prec[k] = ctp / npos[c], ctp / k
+      end
+      res.tp, res.fp = res.tp + ctp, res.fp + #dets - ctp
+      local ap = 0
+      if use_07_metric then
+        for i = 0, 10 do
+          local p = 0
+          for k = 1, #dets do if rec[k] >= i / 10 and prec[k] > p then p = prec[k] end end
+          ap = ap + p / 11
+        end
+      else
+        for k = #dets - 1, 1, -1 do prec[k] = math.max(prec[k], prec[k + 1]) end
+        local last = 0
+        for k = 1, #dets do
+          ap = ap + (rec[k] - last) * prec[k]
+          last = rec[k]
+        end
+      end
+      res.ap[c] = ap
+      total = total + ap
+    end
+    res.mAP = #classes > 0 and total / #classes or 0 / 0
+    by_iou[t] = res
+    sum = sum + res.mAP
+  end
+  return { mAP = sum / #thresholds, by_iou = by_iou }
+end
+
+-- Detector:evaluate_detections(frames, ground_truth, opts) -- mean average precision of this Detector on frames with their
+-- ground truth (evaluation.evaluate_detections of the Python mirror on frames already loaded).  opts.match = 'host' (default): the
+-- lists of detect_batch are matched here, detection by detection (the greedy loop: by decreasing confidence, a box is used by the
+-- first that reaches it); 'device': match_batch.  The same table either way; anything else is refused before the device is touched.
+function Detector:evaluate_detections(frames, ground_truth, opts)
+  opts = opts or {}
+  local how = opts.match or 'host'
+  if how ~= 'host' and how ~= 'device' then error("Detector:evaluate_detections: match must be 'host' or 'device'") end
+  local thr = opts.iou_thresholds or { 0.5 }
+  local matches
+  if how == 'device' then
+    matches = self:match_batch(frames, ground_truth, opts)
+  else
+    matches = {}
+    for f, winners in ipairs(self:detect_batch(frames, opts)) do
+      local m = { cls = {}, confidence = {}, tp = {}, gt = {} }
+      local order = {}
+      for k, w in ipairs(winners) do
+        m.cls[k], m.confidence[k], m.tp[k], m.gt[k] = w.class, tonumber(ffi.cast('float', w.confidence)), 0, 0
+        order[k] = k
+        local best = -1
+        for j, x in ipairs(ground_truth[f]) do
+          if (x.class_index or x[1]) == w.class then
+            local v = Rect.IoU(w.r2, x.rect or x[2])
+            if v > best then best, m.gt[k] = v, j end
+          end
+        end
+        w.best = best
+      end
+      table.sort(order, function(i, j)
+        if m.confidence[i] ~= m.confidence[j] then return m.confidence[i] > m.confidence[j] end
+        return i < j
+      end)
+      for ti, t in ipairs(thr) do
+        local used = {}
+        for _, k in ipairs(order) do
+          if m.gt[k] > 0 and winners[k].best >= t and not used[m.gt[k]] then
+            used[m.gt[k]] = true
+            m.tp[k] = bit.bor(m.tp[k], bit.lshift(1, ti - 1))
+          end
+        end
+      end
+      matches[f] = m
+    end
+  end
+  return Detector.average_precision_from_matches(matches, ground_truth, thr, opts.use_07_metric)
+end
+
 -- detect() of a chunk of frames -> one list of winners per frame: first_stage, then -- unless no frame has a match -- per
 -- frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather, read-back 2 of 2.
 -- Under cfg.tta the SEGMENTS of the chunk are the frames' views (frame f's V views at segments f * V ... f * V + V - 1):
 -- first_stage and step 4 run on them as on frames, ONE frcnn_detect_merge_views launch then makes one segment per frame of them,
 -- and step 5 runs on those -- B / V frames, V times the rows
-function Detector:detect_chunk(frames, shared, prefix)
+-- match (Detector:match_batch; nil: nothing below is launched, allocated or read differently): { gt, thr, with_iou } -- behind
+-- the gather the winners are matched to the ground truth on the device (match_tables), and a frame's result is its match arrays
+function Detector:detect_chunk(frames, shared, prefix, match)
   local model = self.model
   local cfg = model.cfg
   local cnet = model.cnet
@@ -650,7 +890,10 @@ function Detector:detect_chunk(frames, shared, prefix)
     if count[b] > 0 then Rmax = math.max(Rmax, count[B + b]) end
   end
   local results = {}
-  for b = 1, (lists ~= nil) and B / V or B do results[b] = {} end
+  for b = 1, (lists ~= nil) and B / V or B do
+    results[b] = {}
+    if match ~= nil then results[b] = { cls = {}, confidence = {}, tp = {}, gt = {}, iou = match.with_iou and {} or nil } end
+  end
   if Rmax == 0 then return results end                                  -- :71, every frame
   -- ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) and the class test (:106-122) into its segment
   --         (the net owns its outputs and reuses them, so a frame's class test follows its pass at once; the Python mirror, whose
@@ -846,6 +1089,7 @@ function Detector:detect_chunk(frames, shared, prefix)
   end
   local out = ffi.cast('double*', scratch(prefix .. 'winners', 128 * B * (rows + 1)).ptr)
   check(C.frcnn_detect_gather_batch(cpick, cnt, B, rows, dkeep, dkc, dbb_win, dr2_win, dpick, cap, mp, mr, mi, out, nil))
+  if match ~= nil then return self:match_tables(match, out, B, rows, prefix) end   -- match_batch: read-back 2 is the match tables
   local h = ffi.new('double[?]', 16 * B * (rows + 1))
   check(C.frcnn_memcpy_d2h(h, out, 128 * B * (rows + 1), nil))           -- ---- read-back 2 of 2: every frame's winner table
   check(C.frcnn_stream_sync(nil))

@@ -8,9 +8,9 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unuse
 X3FLAGS="-fno-slp-vectorize -save-temps=obj"
 mkdir -p ../build
 pids=(); names=()
-for f in conv.hip elem.hip gemm.hip roi.hip roi_align.hip rpn.hip nms.hip cnet.hip image.hip convx.hip wgradx.hip gemmx.hip detect.hip heads.hip topk.hip soft_nms.hip box_vote.hip proposal_targets.hip roi_hard.hip cnet_loss.hip box_head.hip class_boxes.hip api.cpp net.cpp anchors.cpp comm.cpp; do
+for f in conv.hip elem.hip gemm.hip roi.hip roi_align.hip rpn.hip nms.hip cnet.hip image.hip convx.hip wgradx.hip gemmx.hip detect.hip heads.hip topk.hip soft_nms.hip box_vote.hip proposal_targets.hip roi_hard.hip cnet_loss.hip box_head.hip class_boxes.hip eval_match.hip api.cpp net.cpp anchors.cpp comm.cpp; do
   o=../build/${f%.*}.o
-  if [ "$FORCE" = "1" ] || [ ! -f $o ] || [ $f -nt $o ] || [ kernels.h -nt $o ] || [ common.h -nt $o ] || [ own.h -nt $o ] || [ linear.h -nt $o ] || [ amax.h -nt $o ] || [ roi_fix.h -nt $o ] || [ box_iou.h -nt $o ] || [ box_row.h -nt $o ] || [ anchor_decode.h -nt $o ] || [ ../../include/frcnn_hip.h -nt $o ] || [ ../../include/frcnn_hip_hard.h -nt $o ] || [ ../../include/frcnn_hip_loss.h -nt $o ] || [ ../../include/frcnn_hip_box.h -nt $o ] || [ ../../include/frcnn_hip_classbox.h -nt $o ] || [ ../../include/frcnn_hip_heads.h -nt $o ]; then
+  if [ "$FORCE" = "1" ] || [ ! -f $o ] || [ $f -nt $o ] || [ kernels.h -nt $o ] || [ common.h -nt $o ] || [ own.h -nt $o ] || [ linear.h -nt $o ] || [ amax.h -nt $o ] || [ roi_fix.h -nt $o ] || [ box_iou.h -nt $o ] || [ box_row.h -nt $o ] || [ anchor_decode.h -nt $o ] || [ ../../include/frcnn_hip.h -nt $o ] || [ ../../include/frcnn_hip_hard.h -nt $o ] || [ ../../include/frcnn_hip_loss.h -nt $o ] || [ ../../include/frcnn_hip_box.h -nt $o ] || [ ../../include/frcnn_hip_classbox.h -nt $o ] || [ ../../include/frcnn_hip_eval.h -nt $o ] || [ ../../include/frcnn_hip_heads.h -nt $o ]; then
     case $f in *.cpp) X="-x hip";; convx.hip|wgradx.hip) X="$X3FLAGS";; *) X="";; esac
     hipcc $FLAGS $X -c $f -o $o 2> >(grep -v "argument unused during compilation" >&2) &
     pids+=($!); names+=($f)
@@ -29,6 +29,6 @@ for b in convx wgradx; do
 done
 python3 ../../tools/x3_isa_check.py ../build/isa/convx.s ../build/isa/wgradx.s \
   || { echo "build_lib.sh: error: the split kernels' ISA check failed" >&2; exit 1; }
-OBJS=""; for f in conv elem gemm roi roi_align rpn nms cnet image convx wgradx gemmx detect heads topk soft_nms box_vote proposal_targets roi_hard cnet_loss box_head class_boxes api net anchors comm; do OBJS="$OBJS ../build/$f.o"; done
+OBJS=""; for f in conv elem gemm roi roi_align rpn nms cnet image convx wgradx gemmx detect heads topk soft_nms box_vote proposal_targets roi_hard cnet_loss box_head class_boxes eval_match api net anchors comm; do OBJS="$OBJS ../build/$f.o"; done
 hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -o $OUT || { echo "build_lib.sh: error: link failed" >&2; exit 1; }
 echo "built $OUT"

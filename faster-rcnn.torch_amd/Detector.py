@@ -49,7 +49,12 @@ are the SEGMENTS of the chunk: steps 1-4 run on them as they run on frames.  Beh
 launch turns the survivors of a frame's views into one segment in the frame's coordinates, on which the per-class pass (hard,
 soft, voting) and the gather run unchanged: winners compete, and vote, across views.  A detection gains `view`; its r2 is in the
 frame's coordinates, its p, r and a describe the anchor in the VIEW's coordinates, its candidate indexes the concatenation of the
-views' classification-net outputs."""
+views' classification-net outputs.
+
+Nor is match_batch(frames, ground_truth, iou_thresholds): detect_batch's pipeline up to and including the gather, then the winners
+matched to the frames' ground truth on the device for mean average precision (max_detections by frcnn_eval_conf_rows +
+frcnn_topk_select, ONE frcnn_eval_match_batch), and read-back 2 of 16 bytes a row -- class, confidence, a true-positive bit per
+threshold, matched box -- in place of the 128-byte records.  detect_batch itself launches, allocates and returns what it did."""
 import collections
 import ctypes as C
 import math
@@ -296,6 +301,36 @@ def keep_best(conf, M):
     """max_detections: the rows (ascending) of the M highest values of conf, compared as fp32 values, ties to the earlier row."""
     c = np.asarray(conf).astype(np.float32)
     return np.sort(np.argsort(-c, kind="stable")[:M])
+
+
+MATCH_MAX_THRESHOLDS = 16    # IoU thresholds of one match_batch call (a bit each of the tp mask)
+MATCH_MAX_BOXES = 1024       # ground-truth boxes a frame (frcnn_eval_match_batch)
+
+
+def _gt_arrays(boxes):
+    """A frame's ground truth -- (class_index, Rect) pairs, or objects with .class_index and .rect (what nextValidation hands out)
+    -> (classes int32[G], rects float64[G][4]), in the given order."""
+    cls, rects = [], []
+    for g in boxes:
+        c, r = (g.class_index, g.rect) if hasattr(g, "rect") else (g[0], g[1])
+        cls.append(int(c))
+        rects.append((r.minX, r.minY, r.maxX, r.maxY) if hasattr(r, "minX") else tuple(float(v) for v in r))
+    return np.array(cls, np.int32), np.array(rects, np.float64).reshape(-1, 4)
+
+
+def _match_result(table, iou, with_iou):
+    """One frame's result of match_batch from its table of frcnn_eval_match_batch ((rows + 2) x 4 int32; None: a frame without
+    detections): dict(cls, confidence (float32), tp (uint32: bit t = a true positive at threshold t), gt (1-based, 0: none)[, iou])
+    in the order of detect_batch's list -- classes ascending (a stable sort), the table's order within a class."""
+    n = 0 if table is None else int(table[1, 0])
+    rows = np.zeros((0, 4), np.int32) if table is None else table[2:2 + n]
+    order = np.argsort(rows[:, 0], kind="stable")
+    rows = np.ascontiguousarray(rows[order])
+    out = dict(cls=rows[:, 0].copy(), confidence=rows[:, 1].copy().view(np.float32), tp=rows[:, 2].copy().view(np.uint32),
+               gt=rows[:, 3].copy())
+    if with_iou:
+        out["iou"] = (np.zeros(0, np.float64) if iou is None else iou[:n][order]).copy()
+    return out
 
 
 class _Detections(object):
@@ -817,6 +852,89 @@ class Detector(object, metaclass=_DetectorType):
         self.last_batch = records
         return results
 
+    def match_batch(self, frames, ground_truth, iou_thresholds=(0.5,), mixed_sizes=False, shared_cnet=False, with_iou=False):
+        """detect_batch(frames) matched to the frames' ground truth ON THE DEVICE, for mean average precision: per frame a dict
+        of arrays cls, confidence (float32), tp (uint32), gt (and iou, float64, with_iou=True) whose row k describes
+        detect_batch(frames)[f][k] -- bit t of tp[k] says that the detection is a true positive at iou_thresholds[t] by
+        evaluation.mean_average_precision's rule (it reaches the box of its class it overlaps most, Rect.IoU >= the threshold, and
+        no detection of higher confidence -- fp32 values, ties to the earlier one -- reaches that box at that threshold), gt[k] is
+        that box (1-based in ground_truth[f], 0: the frame has no box of the class), iou[k] the overlap (-1 without a box).
+        ground_truth[f]: the frame's boxes, (class_index, Rect) pairs or objects with .class_index and .rect (what nextValidation
+        hands out), at most 1024; up to 16 thresholds.  evaluation.average_precision_from_matches turns the results into AP / mAP.
+        The pipeline is detect_batch's, unchanged, up to and including the gather; behind it cfg.scoring's max_detections is
+        applied by frcnn_eval_conf_rows + frcnn_topk_select (keep_best's rule) and ONE frcnn_eval_match_batch matches the chunk.
+        Read-back 2 brings the match tables -- 16 bytes a row -- INSTEAD of the 128-byte winner records: the host still waits
+        twice per chunk.  Every Detector setting applies as in detect_batch (under cfg.tta: one result per original frame);
+        last_batch is filled as detect_batch fills it.  Bad arguments are refused (ValueError) before anything is queued."""
+        frames = list(frames)
+        gts = [_gt_arrays(g) for g in ground_truth]
+        if len(gts) != len(frames):
+            raise ValueError("match_batch: %d frames, ground truth for %d" % (len(frames), len(gts)))
+        thr = [float(t) for t in iou_thresholds]
+        if not 1 <= len(thr) <= MATCH_MAX_THRESHOLDS or any(t != t for t in thr):
+            raise ValueError("match_batch: 1 ... %d IoU thresholds, none of them NaN (got %r)" % (MATCH_MAX_THRESHOLDS, thr))
+        if any(len(c) > MATCH_MAX_BOXES for c, _ in gts):
+            raise ValueError("match_batch: a frame with %d ground-truth boxes (at most %d)"
+                             % (max(len(c) for c, _ in gts), MATCH_MAX_BOXES))
+        shapes = [_frame_shape(f) for f in frames]
+        if not mixed_sizes and any(shp != shapes[0] for shp in shapes):
+            raise ValueError("match_batch: frames of different sizes in one call: %s" % sorted(set(shapes)))
+        results, records = [], []
+        step = max(int(self.BATCH), 1)
+        views = self._view_lists(shapes)     # (cfg.tta: refused before anything is queued)
+        if views is not None:
+            step = max(1, step // len(views[0])) if views else step
+        for lo in range(0, len(frames), step):
+            for r in records:
+                r.detach()
+            res, rec = self._detect_chunk(frames[lo:lo + step], bool(shared_cnet), "b_",
+                                          dict(gt=gts[lo:lo + step], thr=thr, with_iou=bool(with_iou)))
+            results += res
+            records += rec
+        self.last_batch = records
+        return results
+
+    def _match_tables(self, match, out, B, rows, pre):
+        """The chunk's winner tables `out` (B x (rows + 1) x 16 float64, just queued) against match["gt"], queued on the caller's
+        stream: the ground truth's upload, under max_detections frcnn_eval_conf_rows + frcnn_topk_select, ONE
+        frcnn_eval_match_batch.  -> a function that reads the tables back in ONE copy and wait: (int32[B][rows + 2][4], float64[B][rows]
+        or None)."""
+        i32 = np.int32
+        s = stream_ptr()
+        gts = match["gt"]
+        row0 = np.concatenate([[0], np.cumsum([len(c) for c, _ in gts])]).astype(np.int64)
+        G = int(row0[-1])
+        gt_rect = self._buf(pre + "gt_rect", (max(G, 1), 4), np.float64)
+        gt_class = self._buf(pre + "gt_class", (max(G, 1),), i32)
+        host = None
+        if G:
+            host = (np.ascontiguousarray(np.concatenate([r for _, r in gts])), np.ascontiguousarray(np.concatenate([c for c, _ in gts])))
+            _lib.call("frcnn_memcpy_h2d", ptr(gt_rect), host[0].ctypes.data_as(C.c_void_p), host[0].nbytes, s)
+            _lib.call("frcnn_memcpy_h2d", ptr(gt_class), host[1].ctypes.data_as(C.c_void_p), host[1].nbytes, s)
+        sel, kcap, kd = None, 0, None
+        M = self.scoring[2] if self.scoring else None
+        if M is not None and rows:
+            kcap = min(rows, int(M))
+            conf = self._buf(pre + "eval_conf", (B, rows)); cnt = self._buf(pre + "eval_count", (B,), i32)
+            sel = self._buf(pre + "eval_sel", (B, kcap), i32); kd = self._buf(pre + "eval_k", (B,), i32)
+            wsb = _lib.load().frcnn_topk_select_workspace_bytes(B, rows)
+            ws = self._buf(pre + "eval_sel_ws", (wsb,), np.uint8)
+            _lib.call("frcnn_eval_conf_rows", ptr(out), B, rows, ptr(conf), ptr(cnt), s)
+            _lib.call("frcnn_topk_select", ptr(conf), B, rows, rows, ptr(cnt), int(M), ptr(sel), kcap, ptr(kd), ptr(ws), wsb, s)
+        tbytes = B * (rows + 2) * 16
+        nbytes = tbytes + (B * rows * 8 if match["with_iou"] else 0)
+        buf = self._buf(pre + "eval_match", (nbytes,), np.uint8)
+        thr = match["thr"]
+        _lib.call("frcnn_eval_match_batch", ptr(out), B, rows, ptr(sel), kcap, ptr(kd), ptr(gt_rect), ptr(gt_class),
+                  (C.c_longlong * (B + 1))(*[int(v) for v in row0]), (C.c_double * len(thr))(*thr), len(thr), ptr(buf),
+                  C.c_void_p(buf.ptr + tbytes) if match["with_iou"] else None, s)
+
+        def read(_alive=host):      # (the uploaded host arrays live as long as this function: until the read-back)
+            raw = self._read(buf.ptr, nbytes, np.uint8)
+            mt = raw[:tbytes].view(i32).reshape(B, rows + 2, 4)
+            return mt, (raw[tbytes:].view(np.float64).reshape(B, rows) if match["with_iou"] else None)
+        return read
+
     def _layout_of(self, H, W):
         """_layout of an H x W frame under this Detector's model, worked out once per size."""
         t = self._layouts.get((H, W))
@@ -952,10 +1070,13 @@ class Detector(object, metaclass=_DetectorType):
             records.append(_BatchRecord(n, R, dev, matches[b] if matches is not None else None))
         return records
 
-    def _detect_chunk(self, frames, shared, pre):
+    def _detect_chunk(self, frames, shared, pre, match=None):
         """detect() of a chunk of frames -> (one result per frame, their records): _first_stage, then -- unless no frame has a match
         -- per frame the pooling, the classification net and the class test, ONE segmented per-class NMS, ONE gather and
         read-back 2 of 2.
+        match (match_batch; None: nothing below is launched, allocated or read differently): dict(gt: per frame (classes, rects),
+        thr, with_iou).  Behind the gather the winners are matched to the ground truth on the device (_match_tables) and read-back
+        2 brings the match tables in place of the winner tables; a frame's result is then a _match_result.
         Under cfg["tta"] the SEGMENTS of the chunk are the frames' views (frame f's V views at segments f * V ... f * V + V - 1,
         made by _make_views): _first_stage and step 4 run on them as on frames, ONE frcnn_detect_merge_views launch then makes one
         segment per frame of them, and step 5 runs on those -- B frames, V times the rows."""
@@ -981,9 +1102,10 @@ class Detector(object, metaclass=_DetectorType):
         c_K, c_W = counts.segment(2), ptr(counts.segment(3))
         Rmax = max([Rs[b] for b in range(B) if ns[b] > 0] + [0])
         if Rmax == 0:   # no frame has a match (:71)
+            none = (lambda: []) if match is None else (lambda: _match_result(None, None, match["with_iou"]))
             if view_lists:
-                return [[] for _ in range(B // V)], self._frame_records(self._records(st), V, {})
-            return [[] for _ in range(B)], self._records(st)
+                return [none() for _ in range(B // V)], self._frame_records(self._records(st), V, {})
+            return [none() for _ in range(B)], self._records(st)
         # ---- 4. per frame with candidates: REGION CLASSIFICATION (:90-101) into the frame's rows.  These launches come first:
         #         the device has been idle since read-back 1, and whatever else the host prepares it prepares while they run
         cnet.evaluate()
@@ -1130,14 +1252,19 @@ class Detector(object, metaclass=_DetectorType):
         out = self._buf(pre + "winners", (B, rows + 1, 16), np.float64)
         _lib.call("frcnn_detect_gather_batch", ptr(wpick), ptr(counts), B, rows, ptr(keep_row), ptr(kc), ptr(bb_win), ptr(r2_win),
                   ptr(pick), cap, ptr(mp), ptr(mr), ptr(mi), ptr(out), s)
+        if match is not None:     # match_batch: the winners against the ground truth, queued behind the gather
+            tables = self._match_tables(match, out, B, rows, pre)
         records = self._records(st, more)
         if view_lists:    # one record per frame over its views' records
             records = self._frame_records(records, V, dict((f, dict(pick=pick.segment(f, int(roffs[f][-1])))) for f in range(B)),
                                           roffs)
-        raw = self._read(out.ptr, out.nbytes, np.float64).reshape(out.shape)   # ---- read-back 2 of 2
+        if match is None:
+            raw = self._read(out.ptr, out.nbytes, np.float64).reshape(out.shape)   # ---- read-back 2 of 2
+        else:
+            mt, iou = tables()                                                      # ---- read-back 2 of 2: 16 bytes a row
         results = []
         for b in range(B):
-            hdr = raw[b, 0].view(i32)
+            hdr = raw[b, 0].view(i32) if match is None else mt[b, 0]
             K = int(hdr[2])
             # (soft, voting: the class test's survivors as the pass read them, views of the chunk's buffers until detach();
             # cfg.tta: always, and all of them -- the merged survivors exist nowhere else)
@@ -1147,6 +1274,9 @@ class Detector(object, metaclass=_DetectorType):
             if voting:
                 extra.update(votes=votes.segment(b, K))
             records[b].finish(K, **extra)
+            if match is not None:
+                results.append(_match_result(mt[b], None if iou is None else iou[b], match["with_iou"]))
+                continue
             if records[b]["n"] == 0:
                 results.append([])
                 continue

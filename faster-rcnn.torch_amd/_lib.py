@@ -227,6 +227,12 @@ CLASSBOX_SIGS = {
                                        C.c_int),
 }
 
+# the entry points of include/frcnn_hip_eval.h (Detector.match_batch: detections matched to ground truth on the device)
+EVAL_SIGS = {
+    "frcnn_eval_match_batch": ([vp, C.c_int, C.c_int, vp, C.c_longlong, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp], C.c_int),
+    "frcnn_eval_conf_rows": ([vp, C.c_int, C.c_int, vp, vp, vp], C.c_int),
+}
+
 
 class GemmJob(C.Structure):
     """frcnn_gemm_job of include/frcnn_hip_heads.h"""
@@ -259,7 +265,8 @@ _lib = None
 
 def exported_symbols():
     """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS; of
-    frcnn_hip_box.h: BOX_SIGS; of frcnn_hip_classbox.h: CLASSBOX_SIGS; of frcnn_hip_heads.h: HEADS_SIGS)"""
+    frcnn_hip_box.h: BOX_SIGS; of frcnn_hip_classbox.h: CLASSBOX_SIGS; of frcnn_hip_eval.h: EVAL_SIGS; of frcnn_hip_heads.h:
+    HEADS_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -282,7 +289,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()) + list(HEADS_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()) + list(EVAL_SIGS.items()) + list(HEADS_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

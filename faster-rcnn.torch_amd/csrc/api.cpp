@@ -242,6 +242,15 @@ int frcnn_detect_class_boxes_batch(const float* feat, int nf, const long long* r
   return detect_class_boxes_batch(feat, nf, row0_host, B, W, b, C, rect, pick, match_stride, kc, keep_row, K_dev, row_stride, bb, r2,
                                   S(stream));
 }
+int frcnn_eval_match_batch(const double* rec, int B, int row_stride, const int* sel_row, long long sel_stride, const int* k_dev,
+                           const double* gt_rect, const int* gt_class, const long long* gt_row0_host, const double* thr_host, int T,
+                           int* match, double* iou, void* stream) {
+  return eval_match_batch(rec, B, row_stride, sel_row, sel_stride, k_dev, gt_rect, gt_class, gt_row0_host, thr_host, T, match, iou,
+                          S(stream));
+}
+int frcnn_eval_conf_rows(const double* rec, int B, int row_stride, float* conf, int* count, void* stream) {
+  return eval_conf_rows(rec, B, row_stride, conf, count, S(stream));
+}
 int frcnn_detect_gather_batch(const long long* wpick, const int* counts, int B, int row_stride, const int* keep_row, const int* kc,
                               const float* bb, const double* r2, const long long* pick, long long match_stride,
                               const float* match_p, const double* match_rect, const int* match_idx, double* rec, void* stream) {

@@ -356,6 +356,12 @@ int box_head_backward(const float* g, const float* x, const int* sel, int R, int
 int detect_class_boxes_batch(const float* feat, int nf, const long long* row0, int B, const float* W, const float* b, int C,
                              const double* rect, const long long* pick, long long match_stride, const int* kc, const int* keep_row,
                              const int* K_dev, int row_stride, float* bb, double* r2, hipStream_t s);
+// ---- detections matched to ground truth for mean average precision (eval_match.hip; semantics: include/frcnn_hip_eval.h).
+// gt_row0 (B + 1) and thr (T): host values.
+int eval_match_batch(const double* rec, int B, int row_stride, const int* sel_row, long long sel_stride, const int* k_dev,
+                     const double* gt_rect, const int* gt_class, const long long* gt_row0, const double* thr, int T, int* match,
+                     double* iou, hipStream_t s);
+int eval_conf_rows(const double* rec, int B, int row_stride, float* conf, int* count, hipStream_t s);
 // ---- Detector:detect glue that stays on the device (detect.hip)
 int roi_windows(const double* rect, const long long* pick, int k, const int* layers, int nlayers, int fmH, int fmW, int* wins,
                 hipStream_t s);

@@ -13,6 +13,9 @@ PASCAL-VOC style mean average precision over `BatchIterator:nextValidation` (Bat
       its Rect.IoU (Rect.lua:138-141) with a not yet matched ground-truth box of class c in the same image is >= iou_threshold
       (0.5); detections are taken in order of decreasing confidence; AP is the area under the monotone precision envelope
       (VOC2010+) or the 11-point average (use_07_metric=True); mAP averages the classes that have ground truth.
+      match="device": the matching itself runs on the device between the two read-backs of a chunk (Detector.match_batch,
+      frcnn_eval_match_batch) at all thresholds at once, and average_precision_from_matches(matches, ground_truth, thresholds)
+      turns the true-positive masks into the same dict.
   proposal_recall(detector, batch_iterator, count) -> {recall, ground_truth, proposals_per_image}: the share of ground-truth
       boxes that some candidate of the first NMS (Detector.proposals: no classification net) covers with Rect.IoU >=
       iou_threshold -- the figure by which the proposal settings (order, pre_nms_top_n, post_nms_top_n) are chosen.
@@ -202,8 +205,86 @@ def mean_average_precision_range(detections, ground_truth, iou_thresholds=IOU_RA
     return dict(mAP=float(np.mean([by_iou[t]["mAP"] for t in ts])), by_iou=by_iou)
 
 
-def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False, batch=1, mixed_sizes=False):
+def average_precision_from_matches(matches, ground_truth, iou_thresholds=0.5, use_07_metric=False):
+    """mean_average_precision / mean_average_precision_range from what Detector.match_batch returns: matches[f] the dict of frame
+    f (cls, confidence, tp: bit t = a true positive at threshold t), ground_truth[f] its boxes ((class_index, Rect) pairs or
+    objects with .class_index and .rect), iou_thresholds the thresholds match_batch was called with -- a number (one threshold,
+    bit 0) -> the dict of mean_average_precision; a sequence -> the dict of mean_average_precision_range, threshold t from bit t.
+    The matching is done: what is left is, per class, the stable sort by decreasing confidence across the frames in their order,
+    the cumulative sums and voc_ap, on arrays.  Equal key by key to the host functions on the same detections."""
+    single = not isinstance(iou_thresholds, (tuple, list, np.ndarray))
+    ts = [float(iou_thresholds)] if single else [float(t) for t in iou_thresholds]
+    if not ts:
+        raise ValueError("average_precision_from_matches: no IoU threshold")
+    if len(matches) != len(ground_truth):
+        raise ValueError("average_precision_from_matches: %d frames, ground truth for %d" % (len(matches), len(ground_truth)))
+    npos_of = {}
+    for boxes in ground_truth:
+        for g in boxes:
+            c = int(g.class_index if hasattr(g, "rect") else g[0])
+            npos_of[c] = npos_of.get(c, 0) + 1
+    cls = np.concatenate([np.asarray(m["cls"], np.int64) for m in matches] + [np.zeros(0, np.int64)])
+    conf = np.concatenate([np.asarray(m["confidence"], np.float32) for m in matches] + [np.zeros(0, np.float32)]).astype(np.float64)
+    mask = np.concatenate([np.asarray(m["tp"], np.uint32) for m in matches] + [np.zeros(0, np.uint32)])
+    per_class = {}
+    for c in sorted(npos_of):
+        rows = np.nonzero(cls == c)[0]
+        per_class[c] = mask[rows[np.argsort(-conf[rows], kind="stable")]]     # equal confidences keep their detection order
+    by_iou = {}
+    for bit, t in enumerate(ts):
+        ap = {}
+        tp_total = fp_total = 0
+        for c in sorted(npos_of):
+            tp = ((per_class[c] >> np.uint32(bit)) & np.uint32(1)).astype(np.float64)
+            fp = 1.0 - tp
+            ctp, cfp = np.cumsum(tp), np.cumsum(fp)
+            recall = ctp / float(npos_of[c])
+            precision = ctp / np.maximum(ctp + cfp, np.finfo(np.float64).eps)
+            ap[c] = voc_ap(recall, precision, use_07_metric) if len(tp) else 0.0
+            tp_total += int(tp.sum()); fp_total += int(fp.sum())
+        by_iou[t] = dict(mAP=float(np.mean(list(ap.values()))) if ap else float("nan"), ap=ap, npos=dict(npos_of), tp=tp_total,
+                         fp=fp_total)
+    if single:
+        return by_iou[ts[0]]
+    return dict(mAP=float(np.mean([by_iou[t]["mAP"] for t in ts])), by_iou=by_iou)
+
+
+def _evaluate_on_device(detector, batch_iterator, count, iou_threshold, use_07_metric, batch, mixed_sizes):
+    """evaluate_detections(match="device"): the same chunks through Detector.match_batch, then average_precision_from_matches."""
+    single = not isinstance(iou_threshold, (tuple, list, np.ndarray))
+    thr = [float(iou_threshold)] if single else [float(t) for t in iou_threshold]
+    if not thr:
+        raise ValueError("mean_average_precision_range: no IoU threshold")
+    matches, ground_truth = [], []
+    pending = []     # frames -- of one size unless mixed_sizes -- waiting for match_batch; their boxes are the tail of ground_truth
+    images = 0
+
+    def flush():
+        matches.extend(detector.match_batch(pending, ground_truth[len(matches):], thr, mixed_sizes=bool(mixed_sizes) and batch > 1))
+        del pending[:]
+    while images < count:
+        for x in batch_iterator.nextValidation(1):
+            images += 1
+            if batch > 1 and not mixed_sizes and pending and tuple(pending[0].shape) != tuple(x["img"].shape):
+                flush()
+            ground_truth.append([(int(roi.class_index), roi.rect) for roi in x["rois"]])
+            pending.append(x["img"])
+            if len(pending) >= max(batch, 1):
+                flush()
+    if pending:
+        flush()
+    res = average_precision_from_matches(matches, ground_truth, thr[0] if single else thr, use_07_metric)
+    res.update(images=images, detections=sum(len(m["cls"]) for m in matches), ground_truth=sum(len(g) for g in ground_truth))
+    return res
+
+
+def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_07_metric=False, batch=1, mixed_sizes=False,
+                        match="host"):
     """Detector:detect on `count` validation images (main.lua:198-206) scored against their ground truth.
+    match = "host" (default): the detections are read back and matched here (mean_average_precision).  "device": every chunk goes
+    through Detector.match_batch -- the matching runs on the device at all thresholds at once, 16 bytes a detection come back
+    instead of a 128-byte record, and average_precision_from_matches does the rest; batch=1 is a chunk of one frame.  The same
+    dict either way; anything else is a ValueError before the device is touched.
     iou_threshold: a number, or a sequence of them -> the dict of mean_average_precision_range (mAP, by_iou).
     batch > 1: up to that many consecutive frames of one size go through Detector.detect_batch in one call (same detections,
     two host waits per chunk instead of two per frame); 1 is the frame-by-frame loop of the reference.
@@ -214,6 +295,10 @@ def evaluate_detections(detector, batch_iterator, count, iou_threshold=0.5, use_
     region under every class over the threshold; the reference's class test (arg-max only, p > 0.2) cuts the low-confidence
     tail off every curve.  A model with a per-class box head (cfg["box_head"]) is evaluated that way with boxes = "class" in the
     same table (Detector.scoring_boxes): every (region, class) row is then scored with the box of its own class."""
+    if match not in ("host", "device"):
+        raise ValueError("evaluate_detections: match = %r (\"host\" or \"device\")" % (match,))
+    if match == "device":
+        return _evaluate_on_device(detector, batch_iterator, count, iou_threshold, use_07_metric, batch, mixed_sizes)
     detections, ground_truth = [], []
     images = 0
     pending = []     # (image id, frame) -- of one size unless mixed_sizes -- waiting for detect_batch

@@ -13,7 +13,10 @@ voting (frcnn_box_vote_batch) and the proposal-target layer of training on sampl
 roi_hard_select(roi, crout, crtarget, ccout, cctarget, nfg, ...) -- online hard example mining of the classification net's rows:
 frcnn_roi_hard_keys_batch, the NMS keyed by the loss, frcnn_roi_hard_gather_batch.
 
-cnet_loss(crout, crtarget, ccout, cctarget, npos, settings, ...) -- the losses of cfg["cnet_loss"] row by row: frcnn_cnet_loss_rows."""
+cnet_loss(crout, crtarget, ccout, cctarget, npos, settings, ...) -- the losses of cfg["cnet_loss"] row by row: frcnn_cnet_loss_rows.
+
+eval_match(rects, classes, confidences, gt_rects, gt_classes, iou_thresholds, ...) -- one frame's detections matched to its ground
+truth at several IoU thresholds at once, for mean average precision: frcnn_eval_match_batch."""
 import ctypes as C
 import math
 import numbers
@@ -435,3 +438,87 @@ def class_boxes(feat, row0, W, b, rect, pick, kc, keep_row, K, bb, r2, overrides
     out_bb = d_bb.numpy().reshape(-1)[:bb.size].reshape(bb.shape).copy()
     out_r2 = d_r2.numpy().reshape(-1)[:r2.size].reshape(r2.shape).copy()
     return dict(code=int(code), bb=out_bb, r2=out_r2)
+
+
+def winner_table(rects, classes, confidences, row_stride=None):
+    """One frame's winner table as frcnn_detect_gather_batch lays it out ((row_stride + 1) x 16 float64: a 128-byte header whose
+    int 3 is the winner count, then a record per winner with its class in column 0, its confidence in column 2 and its box r2 in
+    columns 8-11; everything else zero) from host arrays: what eval_match() and the tests feed frcnn_eval_match_batch with."""
+    rects = np.ascontiguousarray(rects, dtype=np.float64).reshape(-1, 4)
+    n = int(rects.shape[0])
+    classes = np.ascontiguousarray(classes).reshape(-1)
+    confidences = np.ascontiguousarray(confidences, dtype=np.float32).reshape(-1)
+    if classes.shape[0] != n or confidences.shape[0] != n:
+        raise ValueError("winner_table: %d rects, %d classes, %d confidences" % (n, classes.shape[0], confidences.shape[0]))
+    stride = n if row_stride is None else int(row_stride)
+    if stride < n:
+        raise ValueError("winner_table: row_stride %d below the %d winners" % (stride, n))
+    tab = np.zeros((stride + 1, 16), np.float64)
+    tab[0].view(np.int32)[:4] = (n, n, n, n)
+    tab[1:n + 1, 0] = classes
+    tab[1:n + 1, 2] = confidences
+    tab[1:n + 1, 8:12] = rects
+    return tab
+
+
+def unpack_match(table, iou=None):
+    """One frame's table of frcnn_eval_match_batch ((row_stride + 2) x 4 int32) -> dict(counts: the frame's four counts, n, G, T,
+    winners, cls int32[n], confidence float32[n], tp uint32[n], gt int32[n]) and, with the frame's iou row given, iou float64[n]."""
+    table = np.asarray(table).reshape(-1, 4)
+    n = int(table[1, 0])
+    rows = table[2:2 + n]
+    out = dict(counts=tuple(int(v) for v in table[0]), n=n, G=int(table[1, 1]), T=int(table[1, 2]), winners=int(table[1, 3]),
+               cls=rows[:, 0].astype(np.int32), confidence=np.ascontiguousarray(rows[:, 1]).view(np.float32).copy(),
+               tp=np.ascontiguousarray(rows[:, 2]).view(np.uint32).copy(), gt=rows[:, 3].astype(np.int32))
+    if iou is not None:
+        out["iou"] = np.asarray(iou, dtype=np.float64).reshape(-1)[:n].copy()
+    return out
+
+
+def eval_match(rects, classes, confidences, gt_rects, gt_classes, iou_thresholds, max_detections=None):
+    """frcnn_eval_match_batch (not in the reference) on host arrays, one frame: the detections (rects n x 4 float64, classes,
+    confidences: in the order Detector.detect_batch lists them, or any other) matched to the frame's ground truth (gt_rects G x 4
+    float64, gt_classes, 1-based; G <= 1024) at up to 16 IoU thresholds at once, by evaluation.mean_average_precision's rule: a
+    detection looks at the box of its class it overlaps most (Rect.IoU, the first maximum), and at a threshold that box goes to the
+    first detection, by decreasing fp32 confidence and then by row, that reaches it.
+    max_detections = M: the M most confident detections only (frcnn_eval_conf_rows + frcnn_topk_select: Detector.keep_best's rule).
+    -> dict(rows: the 0-based rows matched, ascending; cls, confidence (float32), tp (uint32: bit t set for a true positive at
+    iou_thresholds[t]), gt (1-based box, 0: none), iou (float64: the best overlap, -1 without a box of the class)), one entry per
+    matched row.  Runs on the device: there is no host twin (semantics: include/frcnn_hip_eval.h); a refused setting raises
+    FrcnnError before anything is launched."""
+    tab = winner_table(rects, classes, confidences)
+    n = tab.shape[0] - 1
+    gt_rects = np.ascontiguousarray(gt_rects, dtype=np.float64).reshape(-1, 4)
+    gt_classes = np.ascontiguousarray(gt_classes, dtype=np.int32).reshape(-1)
+    G = int(gt_rects.shape[0])
+    if gt_classes.shape[0] != G:
+        raise ValueError("eval_match: %d ground-truth boxes, %d classes" % (G, gt_classes.shape[0]))
+    thr = [float(t) for t in iou_thresholds]
+    if max_detections is not None and int(max_detections) < 1:
+        raise ValueError("eval_match: max_detections = %r (at least 1)" % (max_detections,))
+    s = stream_ptr()
+    rec = DeviceTensor.from_numpy(tab)
+    d_gt = DeviceTensor.from_numpy(gt_rects if G else np.zeros((1, 4)))
+    d_gc = DeviceTensor.from_numpy(gt_classes if G else np.zeros(1, np.int32))
+    match = DeviceTensor.empty((n + 2, 4), np.int32)
+    iou = DeviceTensor.empty((max(n, 1),), np.float64)
+    sel = cnt = None
+    rows = np.arange(n, dtype=np.int64)
+    if max_detections is not None and n:
+        M = int(max_detections)
+        conf = DeviceTensor.empty((n,), np.float32)
+        cnt = DeviceTensor.empty((1,), np.int32)
+        sel = DeviceTensor.empty((n,), np.int32)
+        kd = DeviceTensor.empty((1,), np.int32)
+        wsb = _lib.load().frcnn_topk_select_workspace_bytes(1, n)
+        ws = DeviceTensor.empty((max(wsb, 1),), np.uint8)
+        _lib.call("frcnn_eval_conf_rows", ptr(rec), 1, n, ptr(conf), ptr(cnt), s)
+        _lib.call("frcnn_topk_select", ptr(conf), 1, n, n, ptr(cnt), M, ptr(sel), n, ptr(kd), ptr(ws), wsb, s)
+    _lib.call("frcnn_eval_match_batch", ptr(rec), 1, n, ptr(sel) if sel is not None else None, n if sel is not None else 0,
+              ptr(kd) if sel is not None else None, ptr(d_gt), ptr(d_gc), (C.c_longlong * 2)(0, G),
+              (C.c_double * max(len(thr), 1))(*thr), len(thr), ptr(match), ptr(iou), s)
+    out = unpack_match(match.numpy(), iou.numpy())
+    if sel is not None:
+        rows = sel.numpy()[:out["n"]].astype(np.int64)
+    out["rows"] = rows
+    return out

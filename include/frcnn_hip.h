@@ -983,6 +983,8 @@ int frcnn_broadcast_f32(frcnn_comm *, float *buf, long long n, int root, void *s
 #include "frcnn_hip_box.h"
 /* The box of its own class for every row of the all-class class test (cfg.scoring.boxes = "class"): two entry points, likewise. */
 #include "frcnn_hip_classbox.h"
+/* Detections matched to ground truth on the device, for mean average precision (Detector:match_batch): two entry points, likewise. */
+#include "frcnn_hip_eval.h"
 /* The anchor nets' sparse training chain, its grouped product and position helpers without a model: test-facing, likewise. */
 #include "frcnn_hip_heads.h"
 #endif /* FRCNN_HIP_H */
