@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "own.h"
 #include "linear.h"
+#include "pack_tables.h"
 
 namespace frcnn {
 
@@ -136,14 +137,13 @@ struct frcnn_model {
   DevBuf delta_last;           // delta_outputs[nheads+1]
   DevBuf zero_arena;           // delta_outputs[1..n+1] followed by the pooled-map gradients: zeroed by ONE memset each
   size_t delta_bytes = 0, gpool_bytes = 0;
-  DevBuf pack_jobs;            // device table of PackJob (fwd packs first, then dgrad packs)
-  DevBuf x3_jobs;              // device table of PackXJob, same arrangement
+  PackTables packs;            // the device job tables of the weight packs and their named parts (pack_tables.h)
   // Two-plane fp16 form of the split launches (option x3_f16): every tensor such a launch reads is scaled by a power of two that
   // puts its largest magnitude just below the end of the fp16 range, so the magnitudes travel with the tensors -- one record
   // (amax.h: a maximum per block of the launch that wrote the tensor) per convolution output, output gradient, weight tensor and
   // pooled map; amax_ws[c.am] = the weight tensor's largest magnitude as a scalar (published by the pack).
-  DevBuf amax, amax_ws, amax_jobs;   // the records; the weight scalars; AmaxJob table of the weight tensors
-  int n_amax = 0, n_amax_jobs = 0, amax_grid = 0;
+  DevBuf amax, amax_ws;        // the records; the weight scalars
+  int n_amax = 0;
   float* rec(int id) const { return (float*)amax.p + (size_t)id * AMAX_REC; }
   // am_live[id]: record id was handed to the launch that writes it in the last pass (forward pass: outputs, pooled maps, weights;
   // backward pass: output gradients) -- what frcnn_model_debug_buffer's record kinds may show.  rec_w: rec for a producer.
@@ -151,21 +151,12 @@ struct frcnn_model {
   float* rec_w(int id) { am_live[id] = 1; return rec(id); }
   // the weight records a tensor_absmax_multi launch of the forward pass writes: every owner's, or the backbone's only
   void weights_live(bool heads_too) {
-    for (auto& c : convs) if (c.x_f || c.x_d) am_live[c.am + 2] = 1;
-    for (auto& hd : heads) if (heads_too && (hd.c3.x_f || hd.c3.x_d)) am_live[hd.c3.am + 2] = 1;
+    for (auto& t : packs.tensors) if (t.has_record() && (heads_too || !t.head())) am_live[t.am + 2] = 1;
   }
   bool f16_packed = false;     // the current packs are in the fp16 form
   long eval_packs_gen = -1;    // option static_weights: generation (g_static_gen) the evaluate-mode packs were made in, -1 = none
   const float* eval_packs_w = nullptr;
-  int n_x3_all = 0, n_x3_fwd = 0, x3_grid_all = 0, x3_grid_fwd = 0;
-  int n_pack_fwd = 0, n_pack_all = 0, n_pack_heads = 0, pack_grid_fwd = 0, pack_grid_all = 0, pack_grid_heads = 0;
   bool head_packs_fresh = false;   // head input-gradient packs match the weights of the last forward
-  // Packs by owner (round 6, the update that runs beside the backward pass): group b < nblocks = backbone block b, group nblocks =
-  // the anchor nets.  Each group has sub-tables of its own behind the model-wide ones in pack_jobs / amax_jobs / x3_jobs, so that
-  // frcnn_pnet_refresh_packs can renew one owner's packs as soon as ITS slice of the weight vector has been updated; a training
-  // forward whose groups are all fresh for the weight vector it is given skips the three model-wide launches.
-  struct PackGroup { int pk_off = 0, pk_n = 0, pk_grid = 0, am_off = 0, am_n = 0, am_grid = 0, x3_off = 0, x3_off16 = 0, x3_n = 0, x3_grid = 0; };
-  std::vector<PackGroup> groups;
   unsigned fresh_mask = 0;         // bit g: group g's training packs were renewed by frcnn_pnet_refresh_packs since the last forward
   const float* fresh_w = nullptr;  // ... from this weight vector
   bool fresh_f16 = false;          // ... in this form
@@ -174,8 +165,6 @@ struct frcnn_model {
   static const int DC_RING = 4;
   PinBuf dc_pin; DevBuf dc_dev; size_t dc_slot_bytes = 0, dc_idx_off = 0; unsigned dc_step = 0;
   Event dc_ev[DC_RING];                       // slot s's copy to the device has run (a host that queues more than DC_RING passes ahead waits here)
-  std::vector<PackXJob> x3_host, x3_host16;   // the model's training pack jobs as built by ensure_shapes (plain | fp16 form), host copies
-  std::vector<int> x3_conv;                   // ... the convolution each job belongs to (index into convs, -1: an anchor net)
   DevBuf dbg_expand;                          // frcnn_model_debug_buffer: a compact tensor laid out dense
   std::vector<Event> block_rd_ev;   // block b's weights and packs have been read for the last time (caller's stream, frcnn_pnet_backward)
   hipStream_t side = nullptr;      // accGradParameters stream (runs beside the updateGradInput chain)
@@ -190,8 +179,6 @@ struct frcnn_model {
   Event bwd_ev;                    // the backbone's backward pass has begun on the caller's stream (anchor nets joined)
   Event upd_ev, upd_join_ev;       // fork / join points of the update stream (frcnn_model_update_*)
   bool head_x3_fresh = true;       // the anchor nets' split-operand packs and weight magnitudes match the last forward pass's weights
-  int am_bb_off = 0, am_bb_n = 0, am_bb_grid = 0;   // AmaxJob sub-table: the backbone's weight tensors only
-  int pk_bb_off = 0, pk_bb_n = 0, pk_bb_grid = 0;   // PackJob sub-table: the backbone's training packs only
   bool heads_deferred = false;     // training pass: the anchor nets' forward part has not been launched yet (frcnn_pnet_forward_async_heads
                                    // leaves it to the call that knows the sampled positions: heads.hip)
   bool heads_sparse_fwd = false;   // ... and was then computed at the sampled positions only
@@ -224,6 +211,11 @@ struct frcnn_model {
   int box_kind = 0, box_n = 0;
   std::vector<std::array<long long, 4>> table;
 };
+
+// one launch per job kind from a named part of its table (an empty span queues nothing)
+static int run_packs(const frcnn_model* m, const float* w, const Span& sp, hipStream_t s) { return conv_pack_weights_multi(w, m->packs.pack.at(sp), sp.n, sp.grid, s); }
+static int run_amax(const frcnn_model* m, const float* w, const Span& sp, hipStream_t s) { return tensor_absmax_multi(w, m->packs.amax.at(sp), sp.n, sp.grid, s); }
+static int run_x3_packs(const frcnn_model* m, const float* w, const Span& sp, hipStream_t s) { return conv_x3_pack_multi(w, m->packs.x3.at(sp), sp.n, sp.grid, s); }
 
 static int pool_out(int n) { return (n - 2 + 1) / 2 + 1; }
 static int refresh_group(frcnn_model* m, const float* w, int group, hipStream_t s);
@@ -344,6 +336,16 @@ static int ensure_conv(Conv& c, int H, int W, bool need_dgrad) {
   return FRCNN_OK;
 }
 
+// a convolution's entry in the enumeration the pack-job tables are built from (pack_tables.h)
+static PackTensor pack_tensor(const Conv& c, PackTensor::Kind kind, int group, int conv) {
+  PackTensor t;
+  t.kind = kind; t.group = group; t.conv = conv; t.first = c.block == 0 && c.step == 0;
+  t.x_f = c.x_f; t.x_d = c.x_d; t.am = c.am;
+  t.w_off = c.w_off; t.Cout = c.Cout; t.Cin = c.Cin; t.k = c.k; t.H = c.H; t.W = c.W; t.Ho = c.Ho; t.Wo = c.Wo;
+  t.wf = c.wf.f(); t.wd = c.wd.f(); t.wx = c.wx.p; t.wxd = c.wxd.p;
+  return t;
+}
+
 static int ensure_shapes(frcnn_model* m, int H, int W) {
   int h = H, w = W;
   for (size_t b = 0; b < m->blocks.size(); ++b) {
@@ -392,185 +394,42 @@ static int ensure_shapes(frcnn_model* m, int H, int W) {
   }
   FR_TRY(m->wg_ws.ensure(wsb));
   { const Conv& c0 = m->convs[0]; FR_TRY(m->wg_ws_first.ensure(conv_wgrad_workspace_bytes(c0.Cin, c0.H, c0.W, c0.Cout, c0.k, c0.pad))); }
-  {  // pack-job table (buffers may have been re-allocated above)
-    std::vector<PackJob> jobs;
-    for (auto& c : m->convs)
-      if (!c.x_f) jobs.push_back(conv_pack_job(c.w_off, c.Cout, c.Cin, c.k, 0, c.wf.f()));
-    for (auto& hd : m->heads) {
-      if (!hd.c3.x_f) jobs.push_back(conv_pack_job(hd.c3.w_off, hd.c3.Cout, hd.c3.Cin, hd.c3.k, 0, hd.c3.wf.f()));
-      jobs.push_back(conv_pack_job(hd.c1.w_off, hd.c1.Cout, hd.c1.Cin, hd.c1.k, 0, hd.c1.wf.f()));
-    }
-    m->n_pack_fwd = (int)jobs.size();
-    for (auto& c : m->convs)
-      if (!(c.block == 0 && c.step == 0) && !c.x_d) jobs.push_back(conv_pack_job(c.w_off, c.Cout, c.Cin, c.k, 1, c.wd.f()));
-    m->n_pack_all = (int)jobs.size();
-    // the heads' input-gradient packs are only needed by the dense head backward (more than SPARSE_MAX_POS
-    // examples on a head); they are refreshed lazily by frcnn_pnet_backward
-    std::vector<PackJob> hd_jobs;
-    for (auto& hd : m->heads) {
-      hd_jobs.push_back(conv_pack_job(hd.c3.w_off, hd.c3.Cout, hd.c3.Cin, hd.c3.k, 1, hd.c3.wd.f()));
-      hd_jobs.push_back(conv_pack_job(hd.c1.w_off, hd.c1.Cout, hd.c1.Cin, hd.c1.k, 1, hd.c1.wd.f()));
-    }
-    m->n_pack_heads = (int)hd_jobs.size();
-    // three tables: [training jobs, blocks dealt over all] [forward jobs only] [head input-gradient jobs]
-    std::vector<PackJob> both = jobs;
-    m->pack_grid_all = conv_pack_assign_blocks(both.data(), m->n_pack_all, 2048);
-    std::vector<PackJob> fwd(jobs.begin(), jobs.begin() + m->n_pack_fwd);
-    m->pack_grid_fwd = conv_pack_assign_blocks(fwd.data(), m->n_pack_fwd, 2048);
-    m->pack_grid_heads = hd_jobs.empty() ? 0 : conv_pack_assign_blocks(hd_jobs.data(), m->n_pack_heads, 2048);
-    both.insert(both.end(), fwd.begin(), fwd.end());
-    both.insert(both.end(), hd_jobs.begin(), hd_jobs.end());
-    // per-owner sub-tables (training packs: forward and input-gradient images of the owner's convolutions)
-    m->groups.assign(m->blocks.size() + 1, frcnn_model::PackGroup());
-    for (size_t g = 0; g <= m->blocks.size(); ++g) {
-      std::vector<PackJob> gj;
-      if (g < m->blocks.size()) {
-        for (auto& c : m->convs) {
-          if (c.block != (int)g) continue;
-          if (!c.x_f) gj.push_back(conv_pack_job(c.w_off, c.Cout, c.Cin, c.k, 0, c.wf.f()));
-          if (!(c.block == 0 && c.step == 0) && !c.x_d) gj.push_back(conv_pack_job(c.w_off, c.Cout, c.Cin, c.k, 1, c.wd.f()));
-        }
-      } else {
-        for (auto& hd : m->heads) {
-          if (!hd.c3.x_f) gj.push_back(conv_pack_job(hd.c3.w_off, hd.c3.Cout, hd.c3.Cin, hd.c3.k, 0, hd.c3.wf.f()));
-          gj.push_back(conv_pack_job(hd.c1.w_off, hd.c1.Cout, hd.c1.Cin, hd.c1.k, 0, hd.c1.wf.f()));
-        }
-      }
-      auto& G = m->groups[g];
-      G.pk_off = (int)both.size(); G.pk_n = (int)gj.size();
-      G.pk_grid = gj.empty() ? 0 : conv_pack_assign_blocks(gj.data(), G.pk_n, 512);
-      both.insert(both.end(), gj.begin(), gj.end());
-    }
-    {   // the backbone's training packs only (a pass that runs the anchor nets sparse: frcnn_model::head_x3_fresh)
-      std::vector<PackJob> gj;
-      for (auto& c : m->convs) {
-        if (!c.x_f) gj.push_back(conv_pack_job(c.w_off, c.Cout, c.Cin, c.k, 0, c.wf.f()));
-        if (!(c.block == 0 && c.step == 0) && !c.x_d) gj.push_back(conv_pack_job(c.w_off, c.Cout, c.Cin, c.k, 1, c.wd.f()));
-      }
-      m->pk_bb_off = (int)both.size(); m->pk_bb_n = (int)gj.size();
-      m->pk_bb_grid = gj.empty() ? 0 : conv_pack_assign_blocks(gj.data(), m->pk_bb_n, 512);
-      both.insert(both.end(), gj.begin(), gj.end());
-    }
-    FR_TRY(m->pack_jobs.ensure(both.size() * sizeof(PackJob)));
-    FR_HIP(hipMemcpy(m->pack_jobs.p, both.data(), both.size() * sizeof(PackJob), hipMemcpyHostToDevice));
+  {  // magnitude records of the two-plane fp16 form (see frcnn_model::amax)
+    int n = 0;
+    for (auto& c : m->convs) { c.am = n; n += 3; }
+    for (auto& hd : m->heads) { hd.c3.am = n; n += 3; }
+    for (auto& b : m->blocks) b.am = n++;
+    m->n_amax = n;
+    m->am_live.assign((size_t)n, 0);
+    FR_TRY(m->amax.ensure((size_t)n * AMAX_REC * 4));
+    FR_TRY(m->amax_ws.ensure((size_t)n * 4));
   }
-  {  // split-bf16 pack jobs
-    // magnitude scalars of the two-plane fp16 form (see frcnn_model::amax) and the table of the weight tensors' segments
-    {
-      int n = 0;
-      for (auto& c : m->convs) { c.am = n; n += 3; }
-      for (auto& hd : m->heads) { hd.c3.am = n; n += 3; }
-      for (auto& b : m->blocks) b.am = n++;
-      m->n_amax = n;
-      m->am_live.assign((size_t)n, 0);
-      FR_TRY(m->amax.ensure((size_t)n * AMAX_REC * 4));
-      FR_TRY(m->amax_ws.ensure((size_t)n * 4));
-      std::vector<AmaxJob> aj;
-      auto addw = [&](Conv& c) {
-        if (c.x_f || c.x_d) aj.push_back(AmaxJob{c.w_off, (long)c.Cout * c.Cin * c.k * c.k, m->rec(c.am + 2), 0});
-      };
-      for (auto& c : m->convs) addw(c);
-      for (auto& hd : m->heads) addw(hd.c3);
-      m->n_amax_jobs = (int)aj.size();
-      m->amax_grid = tensor_absmax_assign_blocks(aj.data(), m->n_amax_jobs);
-      FR_CHECK(m->amax_grid >= 0, "ensure_shapes: a weight tensor is too large for its magnitude record");
-      {   // the backbone's tensors only (a training pass that leaves the anchor nets to the sparse path, heads.hip)
-        std::vector<AmaxJob> gj;
-        for (auto& c : m->convs)
-          if (c.x_f || c.x_d) gj.push_back(AmaxJob{c.w_off, (long)c.Cout * c.Cin * c.k * c.k, m->rec(c.am + 2), 0});
-        m->am_bb_off = (int)aj.size(); m->am_bb_n = (int)gj.size();
-        m->am_bb_grid = gj.empty() ? 0 : tensor_absmax_assign_blocks(gj.data(), m->am_bb_n);
-        aj.insert(aj.end(), gj.begin(), gj.end());
-      }
-      for (size_t g = 0; g <= m->blocks.size(); ++g) {   // per-owner sub-tables (see frcnn_model::groups)
-        std::vector<AmaxJob> gj;
-        auto addg = [&](Conv& c) {
-          if (c.x_f || c.x_d) gj.push_back(AmaxJob{c.w_off, (long)c.Cout * c.Cin * c.k * c.k, m->rec(c.am + 2), 0});
-        };
-        if (g < m->blocks.size()) { for (auto& c : m->convs) if (c.block == (int)g) addg(c); }
-        else for (auto& hd : m->heads) addg(hd.c3);
-        auto& G = m->groups[g];
-        G.am_off = (int)aj.size(); G.am_n = (int)gj.size();
-        G.am_grid = gj.empty() ? 0 : tensor_absmax_assign_blocks(gj.data(), G.am_n);
-        FR_CHECK(G.am_grid >= 0, "ensure_shapes: a weight tensor is too large for its magnitude record");
-        aj.insert(aj.end(), gj.begin(), gj.end());
-      }
-      if (!aj.empty()) {
-        FR_TRY(m->amax_jobs.ensure(aj.size() * sizeof(AmaxJob)));
-        FR_HIP(hipMemcpy(m->amax_jobs.p, aj.data(), aj.size() * sizeof(AmaxJob), hipMemcpyHostToDevice));
-      }
+  {  // the pack-job tables (buffers may have been re-allocated above)
+    const int nb = (int)m->blocks.size();
+    std::vector<PackTensor> ts;
+    for (size_t i = 0; i < m->convs.size(); ++i) ts.push_back(pack_tensor(m->convs[i], PackTensor::BACKBONE, m->convs[i].block, (int)i));
+    for (auto& hd : m->heads) {
+      ts.push_back(pack_tensor(hd.c3, PackTensor::HEAD_C3, nb, -1));
+      ts.push_back(pack_tensor(hd.c1, PackTensor::HEAD_C1, nb, -1));
     }
-    // four tables: [training jobs] [forward jobs], then the same two with the weight magnitude attached (fp16 form)
-    std::vector<PackXJob> all, fwd, all16, fwd16;
-    auto add = [&](Conv& c) {
-      if (c.x_f) {
-        all.push_back(conv_x3_pack_job(c.w_off, c.Cout, c.Cin, c.k, 0, c.wx.p, c.Ho, c.Wo)); fwd.push_back(all.back());
-        PackXJob j = all.back(); j.amax = m->rec(c.am + 2); j.amax_w = m->amax_ws.f() + c.am;
-        all16.push_back(j); fwd16.push_back(j);
-      }
-      if (c.x_d) {
-        all.push_back(conv_x3_pack_job(c.w_off, c.Cout, c.Cin, c.k, 1, c.wxd.p, c.H, c.W));
-        PackXJob j = all.back(); j.amax = m->rec(c.am + 2); j.amax_w = m->amax_ws.f() + c.am;
-        all16.push_back(j);
-      }
-    };
-    m->x3_conv.clear();
-    for (size_t ci = 0; ci < m->convs.size(); ++ci) {
-      const size_t n0 = all.size();
-      add(m->convs[ci]);
-      m->x3_conv.insert(m->x3_conv.end(), all.size() - n0, (int)ci);
+    FR_TRY(m->packs.build(std::move(ts), nb, m->amax.f(), m->amax_ws.f()));
+    FR_TRY(m->packs.upload());
+  }
+  {  // ring of per-step tables: [PackXJob x jobs][int x channels of every block], see frcnn_model::dc_pin
+    size_t chans = 0;
+    for (size_t b = 0; b < m->blocks.size(); ++b) chans += (size_t)m->d.filters[b];
+    m->dc_idx_off = (m->packs.x3_train[0].n * sizeof(PackXJob) + 255) / 256 * 256;
+    const size_t slot = (m->dc_idx_off + chans * 4 + 255) / 256 * 256;
+    if (slot != m->dc_slot_bytes) {   // a new ring: no slot has a copy in flight, the first pass takes slot 0
+      for (auto& e : m->dc_ev) e.reset();
+      m->dc_step = 0;
+      FR_TRY(m->dc_pin.alloc(slot * frcnn_model::DC_RING));
+      m->dc_dev.release();
+      FR_TRY(m->dc_dev.ensure(slot * frcnn_model::DC_RING));
+      m->dc_slot_bytes = slot;
     }
-    for (auto& hd : m->heads) { const size_t n0 = all.size(); add(hd.c3); m->x3_conv.insert(m->x3_conv.end(), all.size() - n0, -1); }
-    m->x3_host = all; m->x3_host16 = all16;   // (host copies for the per-step tables of the compact blocks)
-    {  // ring of per-step tables: [PackXJob x jobs][int x channels of every block], see frcnn_model::dc_pin
-      size_t chans = 0;
-      for (size_t b = 0; b < m->blocks.size(); ++b) chans += (size_t)m->d.filters[b];
-      m->dc_idx_off = (all.size() * sizeof(PackXJob) + 255) / 256 * 256;
-      const size_t slot = (m->dc_idx_off + chans * 4 + 255) / 256 * 256;
-      if (slot != m->dc_slot_bytes) {   // a new ring: no slot has a copy in flight, the first pass takes slot 0
-        for (auto& e : m->dc_ev) e.reset();
-        m->dc_step = 0;
-        FR_TRY(m->dc_pin.alloc(slot * frcnn_model::DC_RING));
-        m->dc_dev.release();
-        FR_TRY(m->dc_dev.ensure(slot * frcnn_model::DC_RING));
-        m->dc_slot_bytes = slot;
-      }
-      for (size_t b = 0; b < m->blocks.size(); ++b)
-        if (m->blocks[b].has_drop) FR_TRY(m->blocks[b].dc_bias.ensure((size_t)m->d.filters[b] * 4));
-    }
-    m->n_x3_all = (int)all.size(); m->n_x3_fwd = (int)fwd.size();
-    m->x3_grid_all = conv_x3_pack_assign_blocks(all.data(), m->n_x3_all);
-    m->x3_grid_fwd = conv_x3_pack_assign_blocks(fwd.data(), m->n_x3_fwd);
-    conv_x3_pack_assign_blocks(all16.data(), m->n_x3_all);
-    conv_x3_pack_assign_blocks(fwd16.data(), m->n_x3_fwd);
-    all.insert(all.end(), fwd.begin(), fwd.end());
-    all.insert(all.end(), all16.begin(), all16.end());
-    all.insert(all.end(), fwd16.begin(), fwd16.end());
-    for (size_t g = 0; g <= m->blocks.size(); ++g) {   // per-owner sub-tables: [plain jobs][the same with the weight magnitude attached]
-      std::vector<PackXJob> gp, g16;
-      auto addg = [&](Conv& c) {
-        if (c.x_f) {
-          gp.push_back(conv_x3_pack_job(c.w_off, c.Cout, c.Cin, c.k, 0, c.wx.p, c.Ho, c.Wo));
-          PackXJob j = gp.back(); j.amax = m->rec(c.am + 2); j.amax_w = m->amax_ws.f() + c.am; g16.push_back(j);
-        }
-        if (c.x_d) {
-          gp.push_back(conv_x3_pack_job(c.w_off, c.Cout, c.Cin, c.k, 1, c.wxd.p, c.H, c.W));
-          PackXJob j = gp.back(); j.amax = m->rec(c.am + 2); j.amax_w = m->amax_ws.f() + c.am; g16.push_back(j);
-        }
-      };
-      if (g < m->blocks.size()) { for (auto& c : m->convs) if (c.block == (int)g) addg(c); }
-      else for (auto& hd : m->heads) addg(hd.c3);
-      auto& G = m->groups[g];
-      G.x3_n = (int)gp.size();
-      G.x3_grid = gp.empty() ? 0 : conv_x3_pack_assign_blocks(gp.data(), G.x3_n);
-      if (!g16.empty()) conv_x3_pack_assign_blocks(g16.data(), G.x3_n);
-      G.x3_off = (int)all.size(); all.insert(all.end(), gp.begin(), gp.end());
-      G.x3_off16 = (int)all.size(); all.insert(all.end(), g16.begin(), g16.end());
-    }
-    if (!all.empty()) {
-      FR_TRY(m->x3_jobs.ensure(all.size() * sizeof(PackXJob)));
-      FR_HIP(hipMemcpy(m->x3_jobs.p, all.data(), all.size() * sizeof(PackXJob), hipMemcpyHostToDevice));
-    }
+    for (size_t b = 0; b < m->blocks.size(); ++b)
+      if (m->blocks[b].has_drop) FR_TRY(m->blocks[b].dc_bias.ensure((size_t)m->d.filters[b] * 4));
   }
   m->H = H; m->W = W;
   m->eval_packs_gen = -1;   // (pack buffers and job tables were rebuilt)
@@ -884,12 +743,13 @@ static int pack_compact(frcnn_model* m, const float* w, bool f16, hipStream_t s)
   ++m->dc_step;
   char* hslot = m->dc_pin.p + (size_t)slot * m->dc_slot_bytes;
   char* dslot = (char*)m->dc_dev.p + (size_t)slot * m->dc_slot_bytes;
-  const std::vector<PackXJob>& src = f16 ? m->x3_host16 : m->x3_host;
+  const Span& train = m->packs.x3_train[f16];
+  const PackXJob* src = m->packs.x3.host_at(train);   // the model's training pack jobs (plain | fp16 form)
   PackXJob* jobs = (PackXJob*)hslot;
   int n = 0;
-  for (int i = 0; i < (int)src.size(); ++i) {
+  for (int i = 0; i < train.n; ++i) {
     PackXJob j = src[i];
-    const int ci = m->x3_conv[i];
+    const int ci = m->packs.x3_conv[i];
     if (ci < 0 && !m->head_x3_fresh) continue;   // an anchor net's pack in a pass that runs the anchor nets sparse
     if (ci >= 0) {
       const Conv& c = m->convs[ci];
@@ -958,37 +818,29 @@ static int pnet_forward_impl(frcnn_model* m, const float* w, const float* img, i
   // it has not written the weights in between (a training-mode pass, a shape change and every frcnn_set_option("static_weights", v)
   // call drop them).
   m->head_packs_fresh = false;
-  const bool f16 = get_x3_f16() && m->n_amax_jobs > 0;
+  const bool f16 = m->packs.f16();
   const bool reuse = !training && g_static_weights && m->eval_packs_gen == g_static_gen && m->eval_packs_w == w && m->f16_packed == f16;
   m->f16_packed = f16;
   std::fill(m->am_live.begin(), m->am_live.end(), 0);
   // ... or every owner's packs were renewed from this weight vector since the last pass (frcnn_pnet_refresh_packs: the update
   // ran beside the previous backward pass).  One-shot: the promise covers the pass that consumes it.
-  const bool fresh = training && !m->groups.empty() && m->fresh_mask == (1u << m->groups.size()) - 1 && m->fresh_w == w && m->fresh_f16 == f16 &&
-                     !any_compact(m);   // (a compact block's packs depend on the step's keep vector)
+  const bool fresh = training && !m->packs.groups.empty() && m->fresh_mask == (1u << m->packs.groups.size()) - 1 && m->fresh_w == w &&
+                     m->fresh_f16 == f16 && !any_compact(m);   // (a compact block's packs depend on the step's keep vector)
   m->fresh_mask = 0;
   if (!reuse && !fresh) {
     // (a training pass that leaves the anchor nets to the sparse path packs nothing of theirs: frcnn_model::head_x3_fresh)
-    const bool skip_heads = training && m->heads_deferred && any_compact(m) && m->am_bb_n > 0;
+    const PackTables& pt = m->packs;
+    const bool skip_heads = training && m->heads_deferred && any_compact(m) && pt.am_bb.n > 0;
     m->head_x3_fresh = !skip_heads;
-    if (training && skip_heads) {
-      if (m->pk_bb_n) FR_TRY(conv_pack_weights_multi(w, (const PackJob*)m->pack_jobs.p + m->pk_bb_off, m->pk_bb_n, m->pk_bb_grid, s));
-    } else if (training)
-      FR_TRY(conv_pack_weights_multi(w, (const PackJob*)m->pack_jobs.p, m->n_pack_all, m->pack_grid_all, s));
-    else
-      FR_TRY(conv_pack_weights_multi(w, (const PackJob*)m->pack_jobs.p + m->n_pack_all, m->n_pack_fwd, m->pack_grid_fwd, s));
-    const PackXJob* xjobs = (const PackXJob*)m->x3_jobs.p + (f16 ? m->n_x3_all + m->n_x3_fwd : 0);
-    if (f16 && skip_heads)
-      FR_TRY(tensor_absmax_multi(w, (const AmaxJob*)m->amax_jobs.p + m->am_bb_off, m->am_bb_n, m->am_bb_grid, s));
-    else if (f16)   // the weight tensors' magnitudes first: their packs are scaled by them
-      FR_TRY(tensor_absmax_multi(w, (const AmaxJob*)m->amax_jobs.p, m->n_amax_jobs, m->amax_grid, s));
-    if (f16) m->weights_live(!skip_heads);
+    FR_TRY(run_packs(m, w, skip_heads ? pt.pk_bb : training ? pt.pk_train : pt.pk_fwd, s));
+    if (f16) {   // the weight tensors' magnitudes first: their packs are scaled by them
+      FR_TRY(run_amax(m, w, skip_heads ? pt.am_bb : pt.am_all, s));
+      m->weights_live(!skip_heads);
+    }
     if (training && any_compact(m))
       FR_TRY(pack_compact(m, w, f16, s));   // the step's own table: the compact blocks' jobs gather the kept filters / channels
-    else if (training)
-      FR_TRY(conv_x3_pack_multi(w, xjobs, m->n_x3_all, m->x3_grid_all, s));
     else
-      FR_TRY(conv_x3_pack_multi(w, xjobs + m->n_x3_all, m->n_x3_fwd, m->x3_grid_fwd, s));
+      FR_TRY(run_x3_packs(m, w, training ? pt.x3_train[f16] : pt.x3_fwd[f16], s));
   }
   m->eval_packs_gen = training ? -1 : g_static_gen;
   m->eval_packs_w = w;
@@ -1245,8 +1097,7 @@ static int backward_head(frcnn_model* m, Head& h, const float* w, float* grad, h
   }
   h.sp_count = -1; h.sp_pos = nullptr;
   if (!m->head_packs_fresh) {   // dense fallback: bring the heads' input-gradient packs up to date
-    FR_TRY(conv_pack_weights_multi(w, (const PackJob*)m->pack_jobs.p + m->n_pack_all + m->n_pack_fwd, m->n_pack_heads,
-                                   m->pack_grid_heads, s));
+    FR_TRY(run_packs(m, w, m->packs.pk_heads, s));
     m->head_packs_fresh = true;
   }
   // 1x1 conv: accGradParameters + updateGradInput
@@ -1498,17 +1349,16 @@ int frcnn_pnet_wait_block_done(frcnn_model* m, int block, void* stream) {
 // given, that forward skips its prologue.  The caller promises that nothing writes w between this call and that forward except
 // updates followed by their own refresh; frcnn_pnet_invalidate_packs withdraws the promise.
 static int refresh_group(frcnn_model* m, const float* w, int group, hipStream_t s) {
-  const bool f16 = get_x3_f16() && m->n_amax_jobs > 0;
-  const frcnn_model::PackGroup& G = m->groups[group];
-  if (G.pk_n) FR_TRY(conv_pack_weights_multi(w, (const PackJob*)m->pack_jobs.p + G.pk_off, G.pk_n, G.pk_grid, s));
-  if (f16 && G.am_n) FR_TRY(tensor_absmax_multi(w, (const AmaxJob*)m->amax_jobs.p + G.am_off, G.am_n, G.am_grid, s));
-  if (G.x3_n) FR_TRY(conv_x3_pack_multi(w, (const PackXJob*)m->x3_jobs.p + (f16 ? G.x3_off16 : G.x3_off), G.x3_n, G.x3_grid, s));
-  return FRCNN_OK;
+  const bool f16 = m->packs.f16();
+  const PackTables::Group& G = m->packs.groups[group];
+  FR_TRY(run_packs(m, w, G.pk, s));
+  if (f16) FR_TRY(run_amax(m, w, G.am, s));
+  return run_x3_packs(m, w, G.x3[f16], s);
 }
 int frcnn_pnet_refresh_packs(frcnn_model* m, const float* w, int group, void* stream) {
   FR_CHECK(m->H > 0, "pnet_refresh_packs: call frcnn_pnet_forward first");
-  FR_CHECK(group >= 0 && group < (int)m->groups.size(), "pnet_refresh_packs: group %d out of range", group);
-  const bool f16 = get_x3_f16() && m->n_amax_jobs > 0;
+  FR_CHECK(group >= 0 && group < (int)m->packs.groups.size(), "pnet_refresh_packs: group %d out of range", group);
+  const bool f16 = m->packs.f16();
   if (m->fresh_mask && (m->fresh_w != w || m->fresh_f16 != f16)) m->fresh_mask = 0;
   FR_TRY(refresh_group(m, w, group, S(stream)));
   if (group == (int)m->blocks.size()) m->head_x3_fresh = true;
