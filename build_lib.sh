@@ -10,7 +10,7 @@ mkdir -p ../build
 pids=(); names=()
 for f in conv.hip elem.hip gemm.hip roi.hip roi_align.hip rpn.hip nms.hip cnet.hip image.hip convx.hip wgradx.hip gemmx.hip detect.hip heads.hip topk.hip soft_nms.hip box_vote.hip proposal_targets.hip roi_hard.hip cnet_loss.hip box_head.hip class_boxes.hip eval_match.hip api.cpp net.cpp anchors.cpp comm.cpp; do
   o=../build/${f%.*}.o
-  if [ "$FORCE" = "1" ] || [ ! -f $o ] || [ $f -nt $o ] || [ kernels.h -nt $o ] || [ common.h -nt $o ] || [ own.h -nt $o ] || [ linear.h -nt $o ] || [ pack_tables.h -nt $o ] || [ amax.h -nt $o ] || [ roi_fix.h -nt $o ] || [ box_iou.h -nt $o ] || [ box_row.h -nt $o ] || [ anchor_decode.h -nt $o ] || [ ../../include/frcnn_hip.h -nt $o ] || [ ../../include/frcnn_hip_hard.h -nt $o ] || [ ../../include/frcnn_hip_loss.h -nt $o ] || [ ../../include/frcnn_hip_box.h -nt $o ] || [ ../../include/frcnn_hip_classbox.h -nt $o ] || [ ../../include/frcnn_hip_eval.h -nt $o ] || [ ../../include/frcnn_hip_heads.h -nt $o ]; then
+  if [ "$FORCE" = "1" ] || [ ! -f $o ] || [ $f -nt $o ] || [ kernels.h -nt $o ] || [ common.h -nt $o ] || [ own.h -nt $o ] || [ linear.h -nt $o ] || [ pack_tables.h -nt $o ] || [ amax.h -nt $o ] || [ roi_fix.h -nt $o ] || [ box_iou.h -nt $o ] || [ box_row.h -nt $o ] || [ anchor_decode.h -nt $o ] || [ ../../include/frcnn_hip.h -nt $o ] || [ ../../include/frcnn_hip_hard.h -nt $o ] || [ ../../include/frcnn_hip_loss.h -nt $o ] || [ ../../include/frcnn_hip_box.h -nt $o ] || [ ../../include/frcnn_hip_classbox.h -nt $o ] || [ ../../include/frcnn_hip_eval.h -nt $o ] || [ ../../include/frcnn_hip_heads.h -nt $o ] || [ ../../include/frcnn_hip_compact.h -nt $o ]; then
     case $f in *.cpp) X="-x hip";; convx.hip|wgradx.hip) X="$X3FLAGS";; *) X="";; esac
     hipcc $FLAGS $X -c $f -o $o 2> >(grep -v "argument unused during compilation" >&2) &
     pids+=($!); names+=($f)

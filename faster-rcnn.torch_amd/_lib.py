@@ -260,13 +260,23 @@ HEADS_SIGS = {
     "frcnn_col2im_positions_add": ([vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp], C.c_int),
 }
 
+# the test-facing entry points of include/frcnn_hip_compact.h (the launches of a channel-compact dropout block without a model)
+COMPACT_SIGS = {
+    "frcnn_conv2d_forward_gathered": ([vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp,
+                                       vp, vp], C.c_int),
+    "frcnn_conv2d_backward_input_gathered": ([vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int,
+                                              vp, vp, vp, vp, vp, vp, vp], C.c_int),
+    "frcnn_conv2d_backward_weight_mapped": ([vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp,
+                                             vp], C.c_int),
+}
+
 _lib = None
 
 
 def exported_symbols():
     """the entry points of include/frcnn_hip.h itself (those of frcnn_hip_hard.h: HARD_SIGS; of frcnn_hip_loss.h: LOSS_SIGS; of
     frcnn_hip_box.h: BOX_SIGS; of frcnn_hip_classbox.h: CLASSBOX_SIGS; of frcnn_hip_eval.h: EVAL_SIGS; of frcnn_hip_heads.h:
-    HEADS_SIGS)"""
+    HEADS_SIGS; of frcnn_hip_compact.h: COMPACT_SIGS)"""
     return sorted(_SIGS.keys())
 
 
@@ -289,7 +299,7 @@ def load():
     except ImportError:
         pass
     L = C.CDLL(SO_PATH)
-    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()) + list(EVAL_SIGS.items()) + list(HEADS_SIGS.items()):
+    for name, (args, res) in list(_SIGS.items()) + list(HARD_SIGS.items()) + list(LOSS_SIGS.items()) + list(BOX_SIGS.items()) + list(CLASSBOX_SIGS.items()) + list(EVAL_SIGS.items()) + list(HEADS_SIGS.items()) + list(COMPACT_SIGS.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

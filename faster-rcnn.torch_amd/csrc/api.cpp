@@ -578,6 +578,130 @@ int frcnn_col2im_positions_add(const float* col, int C, int H, int W, int k, int
   return col2im_positions_add(col, C, H, W, k, Wo, pos, P, gX, S(stream));
 }
 
+// ---- test entry points (include/frcnn_hip_compact.h): the launches of a channel-compact dropout block (net.cpp plan_compact,
+// pack_compact, wgrad_args) on tensors of the caller -- a gathered pack through the multi-job pack launch + conv_x3, and
+// conv_wgrad through a WgradMap
+// a gather / scatter table, read back: null = the identity (n entries must exist), negative = padding, every entry below `full`
+static int compact_table(const char* who, const char* name, const int* tab, int n, int full, hipStream_t s) {
+  if (!tab) {
+    FR_CHECK(n <= full, "%s: %s is NULL (the identity) but the launch has %d entries and the tensor %d", who, name, n, full);
+    return FRCNN_OK;
+  }
+  std::vector<int> h((size_t)n);
+  FR_HIP(hipMemcpyAsync(h.data(), tab, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  FR_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) FR_CHECK(h[i] < full, "%s: %s[%d] = %d, the tensor has %d", who, name, i, h[i], full);
+  return FRCNN_OK;
+}
+
+// mode 0: forward (K = nC channels, M = nO filters); mode 1: input gradient (K = nO, M = nC).  Hin x Win: the map the launch
+// reads, cpad: conv_x3's padding.
+static int conv2d_gathered(const char* who, int mode, const float* in, int Hin, int Win, const float* in_slope, const float* in_scale,
+                           const float* weight, const float* bias, int O_full, int C_full, const int* oidx, int nO, const int* cidx,
+                           int nC, int cpad, float* out, int out_mode, const float* rec_in, float* rec_out, const X3PostAct* post,
+                           hipStream_t s) {
+  const int Kc = mode == 0 ? nC : nO, M = mode == 0 ? nO : nC;
+  const int Ho = Hin + 2 * cpad - 2, Wo = Win + 2 * cpad - 2;
+  FR_CHECK(in && weight && out, "%s: NULL argument", who);
+  FR_CHECK(O_full >= 1 && C_full >= 1 && nO >= 1 && nC >= 1 && Hin >= 1 && Win >= 1 && cpad >= 0 && Ho >= 1 && Wo >= 1,
+           "%s: %d of %d filters, %d of %d channels, map %d x %d -> %d x %d", who, nO, O_full, nC, C_full, Hin, Win, Ho, Wo);
+  FR_CHECK(conv_x3_eligible(Kc, M, 3), "%s: %d channels -> %d filters does not take the split form", who, Kc, M);
+  bool f16 = get_x3_f16() != 0;
+  if (f16 && in_scale) FR_TRY(scale_fits_f16_form(in_scale, Kc, s, &f16));
+  FR_CHECK(f16 || (!rec_in && !rec_out), "%s: magnitude records belong to the fp16 form (option x3_f16, scale entries <= 1)", who);
+  FR_TRY(compact_table(who, "oidx", oidx, nO, O_full, s));
+  FR_TRY(compact_table(who, "cidx", cidx, nC, C_full, s));
+  // the flat vector the pack reads: the full weight tensor, the full bias behind it (PackXJob::bias_off)
+  const long nw = (long)O_full * C_full * 9;
+  DevBuf flat, wp, bg, am, jobs, ident;
+  // pack_x_job reads the source row pitch Cs only in its gathered branch: two NULL tables over a tensor with more channels than
+  // the launch take that branch through an identity channel table
+  if (!oidx && !cidx && C_full != nC) {
+    std::vector<int> h((size_t)nC);
+    for (int i = 0; i < nC; ++i) h[i] = i;
+    FR_TRY(ident.ensure((size_t)nC * 4));
+    FR_HIP(hipMemcpy(ident.p, h.data(), (size_t)nC * 4, hipMemcpyHostToDevice));
+    cidx = (const int*)ident.p;
+  }
+  const float* base = weight;
+  if (bias) {
+    FR_TRY(flat.ensure((size_t)(nw + O_full) * 4));
+    FR_HIP(hipMemcpyAsync(flat.p, weight, (size_t)nw * 4, hipMemcpyDeviceToDevice, s));
+    FR_HIP(hipMemcpyAsync(flat.f() + nw, bias, (size_t)O_full * 4, hipMemcpyDeviceToDevice, s));
+    FR_TRY(bg.ensure((size_t)nO * 4));
+    base = flat.f();
+  }
+  FR_TRY(wp.ensure(conv_x3_pack_bytes(Kc, M, 3)));
+  FR_TRY(jobs.ensure(sizeof(PackXJob)));
+  if (f16) FR_TRY(am.ensure(X3_REC_BYTES));
+  float* const amw = f16 ? am.f() + AMAX_REC : nullptr;       // the weights' record: of the FULL tensor, as pack_compact has it
+  float* const aws = f16 ? am.f() + 2 * AMAX_REC : nullptr;   // their largest magnitude
+  if (f16) {
+    if (!rec_in) FR_TRY(tensor_absmax(in, (long)Kc * Hin * Win, am.f(), s));
+    FR_TRY(tensor_absmax(base, nw, amw, s));
+  }
+  PackXJob g = conv_x3_pack_job(0, nO, nC, 3, mode, wp.p, Ho, Wo);
+  g.oidx = oidx; g.cidx = cidx; g.Cs = C_full;
+  if (bias) { g.bias_off = nw; g.bias_dst = bg.f(); }
+  g.amax = amw; g.amax_w = aws;
+  const int grid = conv_x3_pack_assign_blocks(&g, 1);
+  FR_HIP(hipMemcpy(jobs.p, &g, sizeof(PackXJob), hipMemcpyHostToDevice));
+  int rc = conv_x3_pack_multi(base, (const PackXJob*)jobs.p, 1, grid, s);
+  if (rc == FRCNN_OK)
+    rc = conv_x3(in, Kc, Hin, Win, in_slope, in_scale, wp.p, bias ? bg.f() : nullptr, M, 3, cpad, out, out_mode, 0, s, 0, post,
+                 f16 ? (rec_in ? rec_in : am.f()) : nullptr, aws, rec_out);
+  (void)hipStreamSynchronize(s);
+  return rc;
+}
+int frcnn_conv2d_forward_gathered(const float* in, int H, int W, const float* in_slope, const float* in_scale, const float* weight,
+                                  const float* bias, int O_full, int C_full, const int* oidx, int nO, const int* cidx, int nC,
+                                  int pad, float* out, const float* rec_in, float* rec_out, void* stream) {
+  return conv2d_gathered("frcnn_conv2d_forward_gathered", 0, in, H, W, in_slope, in_scale, weight, bias, O_full, C_full, oidx, nO,
+                         cidx, nC, pad, out, OUT_STORE, rec_in, rec_out, nullptr, S(stream));
+}
+int frcnn_conv2d_backward_input_gathered(const float* gout, int Ho, int Wo, const float* weight, int O_full, int C_full,
+                                         const int* oidx, int nO, const int* cidx, int nC, int pad, float* gin, int accumulate,
+                                         const float* rec_g, float* rec_out, const float* post_x, const float* post_slope,
+                                         const float* post_scale, float* gslope, void* stream) {
+  const char* who = "frcnn_conv2d_backward_input_gathered";
+  FR_CHECK(pad >= 0 && pad <= 2, "%s: padding %d", who, pad);
+  FR_CHECK(post_x || (!post_slope && !post_scale && !gslope), "%s: a fused activation backward needs post_x", who);
+  FR_CHECK(!post_x || (post_slope && !accumulate), "%s: the fused activation backward belongs to a storing launch with a slope", who);
+  const X3PostAct post{post_x, post_slope, post_scale, gslope};
+  return conv2d_gathered(who, 1, gout, Ho, Wo, nullptr, nullptr, weight, nullptr, O_full, C_full, oidx, nO, cidx, nC, 2 - pad, gin,
+                         accumulate ? OUT_ADD : OUT_STORE, rec_g, rec_out, post_x ? &post : nullptr, S(stream));
+}
+int frcnn_conv2d_backward_weight_mapped(const float* in, int Cin, int H, int W, const float* in_slope, const float* in_scale,
+                                        const float* gout, int O, int pad, float* gweight, float* gbias, int O_full, int Cfull,
+                                        const int* omap, const int* cmap, void* stream) {
+  const char* who = "frcnn_conv2d_backward_weight_mapped";
+  hipStream_t s = S(stream);
+  const int Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
+  FR_CHECK(in && gout && gweight, "%s: NULL argument", who);
+  FR_CHECK(Cin >= 1 && O >= 1 && O_full >= 1 && Cfull >= 1 && H >= 1 && W >= 1 && pad >= 0 && Ho >= 1 && Wo >= 1,
+           "%s: %d of %d filters, %d of %d channels, map %d x %d -> %d x %d", who, O, O_full, Cin, Cfull, H, W, Ho, Wo);
+  FR_CHECK(conv_wgradx_eligible(Cin, O, 3), "%s: a gathered weight gradient needs a conv_wgradx shape, not %d channels x %d filters",
+           who, Cin, O);
+  FR_CHECK(omap || cmap || Cfull == Cin, "%s: no table, but the tensor has %d channels and the launch %d", who, Cfull, Cin);
+  FR_TRY(compact_table(who, "omap", omap, O, O_full, s));
+  FR_TRY(compact_table(who, "cmap", cmap, Cin, Cfull, s));
+  bool unit = true;
+  FR_TRY(scale_fits_f16_form(in_scale, Cin, s, &unit));
+  DevBuf ws, am;
+  FR_TRY(ws.ensure(conv_wgrad_workspace_bytes(Cin, H, W, O, 3, pad)));
+  const bool f16 = unit && get_x3_f16();
+  if (f16) {   // (the records of both tensors, as frcnn_conv2d_backward_weight takes them)
+    FR_TRY(am.ensure(X3_REC_BYTES));
+    FR_TRY(tensor_absmax(in, (long)Cin * H * W, am.f(), s));
+    FR_TRY(tensor_absmax(gout, (long)O * Ho * Wo, am.f() + AMAX_REC, s));
+  }
+  const WgradMap map{omap, cmap, Cfull};
+  const int rc = conv_wgrad(in, Cin, H, W, in_slope, in_scale, gout, O, 3, pad, gweight, ws.p, ws.bytes, s, gbias,
+                            f16 ? am.f() : nullptr, f16 ? am.f() + AMAX_REC : nullptr, &map);
+  (void)hipStreamSynchronize(s);
+  return rc;
+}
+
 int frcnn_roi_pool_forward(const float* fmap, int C, int H, int W, const int* wins, int R, int kh, int kw,
                            float* out, int* idx, void* stream) {
   return roi_pool_forward(fmap, C, H, W, wins, R, kh, kw, out, idx, S(stream));

@@ -987,4 +987,6 @@ int frcnn_broadcast_f32(frcnn_comm *, float *buf, long long n, int root, void *s
 #include "frcnn_hip_eval.h"
 /* The anchor nets' sparse training chain, its grouped product and position helpers without a model: test-facing, likewise. */
 #include "frcnn_hip_heads.h"
+/* The launches of a channel-compact dropout block without a model (gathered packs, mapped folds): test-facing, likewise. */
+#include "frcnn_hip_compact.h"
 #endif /* FRCNN_HIP_H */

@@ -498,3 +498,14 @@ def emulate_split(op, a, b, f16, amax_a=None, amax_b=None, top_a=14, top_b=14):
     ha, ma, la = planes_bf16(a)
     hb, mb, lb = planes_bf16(b)
     return op(ha + ma + la, hb + mb + lb) - op(ma + la, lb) - op(la, mb)
+
+
+def representation_share(op, a, b, f16, what, amax_a=None, amax_b=None, top_a=14):
+    """asserts that the emulated split misses op(a, b) by no more than representation_bound; -> the largest distance / share"""
+    want = op(np.asarray(a, np.float64), np.asarray(b, np.float64))
+    got = emulate_split(op, a, b, f16, amax_a=amax_a, amax_b=amax_b, top_a=top_a)
+    rep = representation_bound(op, a, b, f16, amax_a=amax_a, amax_b=amax_b)
+    err = np.abs(got - want)
+    worst = float((err / np.maximum(rep, 1e-300)).max())
+    assert np.all(err <= rep), "%s: the kept plane products miss the product by %.3f times the representation share" % (what, worst)
+    return worst

@@ -25,6 +25,17 @@ def test_ctypes_table_matches_header(F):
     assert sorted(F._lib.exported_symbols()) == _header_symbols()
 
 
+def test_library_exports_the_test_facing_entry_points(F):
+    """the entry points of include/frcnn_hip_heads.h and include/frcnn_hip_compact.h (_lib.HEADS_SIGS, _lib.COMPACT_SIGS): exported
+    by the library, and no part of frcnn_hip.h's own list"""
+    lib = ctypes.CDLL(F._lib.SO_PATH)
+    for table in (F._lib.HEADS_SIGS, F._lib.COMPACT_SIGS):
+        assert table and not [n for n in table if not hasattr(lib, n)]
+        assert not set(table) & set(_header_symbols())
+    assert sorted(F._lib.COMPACT_SIGS) == ["frcnn_conv2d_backward_input_gathered", "frcnn_conv2d_backward_weight_mapped",
+                                           "frcnn_conv2d_forward_gathered"]
+
+
 def test_host_only_entry_points(F):
     lib = F._lib.load()
     assert lib.frcnn_version() >= 100

@@ -150,12 +150,15 @@ def _amax_of_activated(x, slope):
 
 
 class Gate(object):
-    """squared errors of the split form and of the fp32 kernel, pooled over the repetitions of one case"""
+    """squared errors of the split form and of the fp32 kernel, pooled over the repetitions of one case.  ratios / worst: the
+    lists the ratio is recorded in (this file's; another file that uses the class passes its own)"""
 
-    def __init__(self):
+    def __init__(self, ratios=None, worst=None):
         self.s = self.d = 0.0
         self.n = 0
         self.differ = False
+        self.ratios = RATIOS if ratios is None else ratios
+        self.worst = GATE_WORST if worst is None else worst
 
     def add(self, split, direct, want):
         self.s += float(((split.astype(np.float64) - want) ** 2).sum())
@@ -168,10 +171,10 @@ class Gate(object):
         assert self.n >= POOL and self.differ, "%s %s: the option did not switch the kernel" % (role, what)
         es, ed = np.sqrt(self.s / self.n), np.sqrt(self.d / self.n)
         r = es / max(ed, 1e-30)
-        RATIOS.append(r)
+        self.ratios.append(r)
         key = (role, FORMS[form])
-        if r > GATE_WORST.get(key, (0.0, ""))[0]:
-            GATE_WORST[key] = (r, what)
+        if r > self.worst.get(key, (0.0, ""))[0]:
+            self.worst[key] = (r, what)
         print("%s %s %s: rms error split / fp32 kernel = %.3f over %d outputs" % (role, FORMS[form], what, r, self.n))
         return r, es <= RMS_GATE * ed + 1e-9
 
@@ -183,15 +186,15 @@ def _gates(role, what, gates):
     assert not bad, "%s %s: rms error above %.2f times the fp32 kernel's: %r" % (role, what, RMS_GATE, bad)
 
 
-def _check(role, form, what, got, want64, bound):
-    """all finite, the bar, the worst-case bound"""
+def _check(role, form, what, got, want64, bound, worst=WORST):
+    """all finite, the bar, the worst-case bound; worst: where the largest ratio per role and form is recorded"""
     assert got.shape == want64.shape and got.dtype == np.float32
     assert np.isfinite(got).all(), "%s %s: not finite (an element was left out?)" % (role, what)
     err = np.abs(got.astype(np.float64) - want64)
     ratio = float((err / np.maximum(bound, 1e-300)).max())
     key = (role, FORMS[form])
-    if ratio > WORST.get(key, (0.0, ""))[0]:
-        WORST[key] = (ratio, what)
+    if ratio > worst.get(key, (0.0, ""))[0]:
+        worst[key] = (ratio, what)
     print("%s %s %s: max error / bound = %.4f" % (role, FORMS[form], what, ratio))
     assert_close(got, want64, 1e-4, "%s %s %s" % (role, FORMS[form], what))
     assert ratio <= 1.0, "%s %s %s: error %.3f times the bound" % (role, FORMS[form], what, ratio)

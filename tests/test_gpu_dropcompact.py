@@ -2,7 +2,9 @@
 (models/model_utilities.lua:10-12 behind the first convolution of a block) computes what the dense pass computes -- the
 products it skips are products with exact zeros.  Loss, every gradient tensor and the zero pattern of the dropped filters /
 channels are compared between the two ways; the oracle-backed parity tests (test_gpu_model, test_gpu_fullsize, bench.py's
-parity object) run with the option on, its default."""
+parity object) run with the option on, its default, and tests/test_gpu_compact_ops.py holds each of a compact block's six
+launches by itself -- the gathered packs and the mapped folds -- to the fp64 reference, the derived bound and the bits of the
+dense entry points."""
 import ctypes as C
 
 import numpy as np
